@@ -13,9 +13,14 @@ Workloads (``--workload``, default ``auto``):
   dp64  BASELINE.json configs[2] (reference: evaluate.py:202-210, 346).  One step = the whole job of 64 seeded images:
         contiguous shards of 64 / N per rank, ``evaluate_batch`` with up to 16 images per call (--dp-per-call), ONE all-gather -> [64, 6890],
         rank-0 D2H.  Strong scaling; ``value`` = 64 * K / time.
-  auto  N == 1: b1 (the headline, with a dp64 pass reported under ``dp64_one_gpu``: the strong-scaling baseline);
-        N > 1: dp64 (with the same 64 images on rank 0 alone measured after the timed region: ``one_gpu_same_workload``).
+  auto  N == 1: b1 (the headline; with --full, a dp64 pass reported under ``dp64_one_gpu``: the strong-scaling baseline);
+        N > 1: dp64 (with --full, the same 64 images on rank 0 alone measured after the timed region: ``one_gpu_same_workload``).
 Inputs are resident in HBM when the timed region starts.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly K steps and prints the line (``value``, ``ms_per_step``); the other fields are null.
+``--full`` adds every other leg: the variants, the roofline passes, the parity legs against the fp32 CPU oracle and the CPU
+baseline (``--no-cpu-baseline`` / ``--no-roofline`` / ``--no-variants`` leave parts of it out).  ``--dump-outputs DIR`` writes
+what the timed path returned in its last step as DIR/<name>.npy (seeded inputs: two builds compare output for output).
 """
 from __future__ import annotations
 
@@ -32,6 +37,25 @@ sys.path.insert(0, REPO)
 
 PEAK_BF16_TFLOPS = 2500.0  # dense MFMA bf16 (MI355X_MICROARCH.md: ~2.5 PF dense; 5 PF figure is 2:1 sparse)
 PEAK_HBM_GBPS = 8000.0     # HBM3E spec peak (6.3 TB/s achievable by a float4 copy)
+DUMP_LIMIT_BYTES = 60_000_000  # array bytes of --dump-outputs: under 64 MB (either meaning) with the .npy headers
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each tensor as <path>/<name>.npy, floating point as float32, integers as float64 (exact for int32 ids).  Past
+    `limit` bytes in all, every array is cut to the same fraction of its elements, chosen with a fixed seed (flattened order)."""
+    import numpy as np
+
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        out[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    total = sum(a.nbytes for a in out.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        if total > limit:
+            k = a.size * limit // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def flops_per_image(cfg, T0, n_new, V):
@@ -399,10 +423,15 @@ def main():
     ap.add_argument("--dp-images", type=int, default=64, help="images of the dp64 job (64 = BASELINE configs[2]; tests use fewer)")
     ap.add_argument("--dp-per-call", type=int, default=16, help="images per evaluate_batch call of the dp64 job (<= 16: the batched "
                     "decode step streams the weights once for all of them - 24.3 images/s on one GPU against 21.8 with 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the cached-SAM and dp64 variant legs (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every leg beyond the headline figure "
+                    "(variants, roofline passes, parity against the fp32 CPU oracle, CPU baseline, the one-GPU denominator at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU oracle legs")
+    ap.add_argument("--no-roofline", action="store_true", help="(with --full) skip the roofline passes")
+    ap.add_argument("--no-variants", action="store_true", help="(with --full) skip the cached-SAM and dp64 variant legs (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the outputs and the result line - nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_variants = True
 
     import torch.distributed as dist
 
@@ -453,10 +482,12 @@ def main():
     T0 = ids.shape[1] + cfg.img_emb_len
 
     guard = {"recomputed": 0}  # calls that left fp16's exponent range and were recomputed with bf16 operands (a parity failure)
+    last = {}  # evaluate()'s result of the latest b1 step (--dump-outputs)
 
     def step_b1():
         out = model.evaluate(images_clip, images, ids, cams, [(S, S)], [(S, S)], contact_type="hcontact",
                              forced_new_tokens=forced)
+        last["out"] = out
         if out.get("recomputed_in_bf16"):
             guard["recomputed"] += 1
         allc = gather_contacts(out["pred_contact_3d"])  # ONE all-gather of [1,6890] fp32 per rank
@@ -501,10 +532,18 @@ def main():
     dt, res = timed_steps(step, args.warmup, args.steps, world, dev)
     items_per_step = world if workload == "b1" else N_IMG
     assert res.shape == (items_per_step, 6890)
+    if args.dump_outputs and rank == 0:  # before any other leg can run the model again
+        arrays = {"pred_contact_3d": res}  # the gathered contacts: [world, 6890] (b1) or [images, 6890] (dp64)
+        if workload == "b1":  # ... and the rest of rank 0's evaluate() result
+            o = last["out"]
+            arrays.update(pred_masks=o["pred_masks"][0], output_ids=o["output_ids"])
+            if "uncertainty_maps" in o:
+                arrays["uncertainty_maps"] = o["uncertainty_maps"][0]
+        dump_outputs(args.dump_outputs, arrays)
 
     # ---- dp64 at N > 1: the SAME 64 images on rank 0 alone (the strong-scaling denominator, measured in the same run)
     one_gpu = None
-    if workload == "dp64" and world > 1:
+    if workload == "dp64" and world > 1 and args.full:
         one_gpu = one_gpu_same_workload(N_IMG, PER_CALL, dp_chunk, rank, world, dev, res, dt, args.steps, prefetch=dp_image)
 
     # ---- weight residency of the mode `value` is quoted on and the free-running greedy loop (item 4): the
@@ -515,11 +554,13 @@ def main():
         return {"llama_bf16": round(rb_["bf16"] / 1e9, 2), "llama_f16": round(rb_["f16"] / 1e9, 2),
                 "llama_bf12_planes": round(rb_["bf12"] / 1e9, 2), "llama_total": round(sum(rb_.values()) / 1e9, 2)}
 
-    hbm_resident = {"default": resident_gb(), "torch_allocated_total": round(torch.cuda.memory_allocated(dev) / 1e9, 2),
-                    "note": "language-model weight bytes held by the model, by form (embed_tokens + lm_head + norms stay bf16; the "
-                            "default mode holds fp16 prefill copies + lossless 12-bit decode planes and NO bf16 original of a packed "
-                            "matrix - a switch to 'bf16' / 'parity' rebuilds them bit for bit from the planes); torch_allocated_total "
-                            "also counts this script's own bf16 state dict (kept for the CPU-oracle leg), CLIP, SAM, KV caches"}
+    hbm_resident = None
+    if args.full:
+        hbm_resident = {"default": resident_gb(), "torch_allocated_total": round(torch.cuda.memory_allocated(dev) / 1e9, 2),
+                        "note": "language-model weight bytes held by the model, by form (embed_tokens + lm_head + norms stay bf16; the "
+                                "default mode holds fp16 prefill copies + lossless 12-bit decode planes and NO bf16 original of a packed "
+                                "matrix - a switch to 'bf16' / 'parity' rebuilds them bit for bit from the planes); torch_allocated_total "
+                                "also counts this script's own bf16 state dict (kept for the CPU-oracle leg), CLIP, SAM, KV caches"}
     free_running = None
     if workload == "b1" and world == 1 and not args.no_variants:
         n_tok = len(forced)

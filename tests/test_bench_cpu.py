@@ -53,3 +53,20 @@ def test_set_equality_fields_of_the_bench_line():
     assert b._exact_sets_rate(pf) is None
     # no parity leg (e.g. --no-cpu-baseline): the fields are null, not false
     assert b._sets_exact(None, "default") is None and b._sets_detail(None, "default") is None and b._exact_sets_rate(None) is None
+
+
+def test_dump_outputs_dtypes_and_size_limit(tmp_path):
+    """--dump-outputs: float tensors as float32, integer ids as float64; past the byte limit a seeded, fixed sample of every array."""
+    b = _bench()
+    masks = torch.randn(4, 8, 8, dtype=torch.float16)
+    ids = torch.tensor([[1, 32000, 7]])
+    b.dump_outputs(str(tmp_path / "a"), {"pred_masks": masks, "output_ids": ids})
+    m, i = np.load(tmp_path / "a" / "pred_masks.npy"), np.load(tmp_path / "a" / "output_ids.npy")
+    assert m.dtype == np.float32 and np.array_equal(m, masks.float().numpy())
+    assert i.dtype == np.float64 and np.array_equal(i, ids.numpy())
+    big = {"x": torch.arange(1000, dtype=torch.float32), "y": torch.arange(500)}  # 4000 + 4000 bytes as dumped
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), big, limit=1200)
+    x, y = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert x.nbytes + y.nbytes <= 1200 and len(x) == 150 and len(y) == 75
+    assert np.all(np.diff(x) > 0) and np.array_equal(x, np.load(tmp_path / "c" / "x.npy"))  # sorted, and the same sample every run
