@@ -11,16 +11,20 @@ MI355X-first differences (same numbers, less work):
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, graphs, ops
 from .sam import _LN, _Lin, _dev
 from .weights import CLIP_PREFIX, ClipCfg, LlamaCfg
 
 BF16 = torch.bfloat16
 F32 = torch.float32
+
+# a captured decode step (Llama._graphs): batched (decode_graph_batch) or not, sequences per step, and what selects its launches
+_GraphKey = collections.namedtuple("_GraphKey", "batched B precision packed fp8 fused")
 
 
 class ClipTower:
@@ -28,7 +32,7 @@ class ClipTower:
 
     def __init__(self, w, cfg: ClipCfg, device, prefix=CLIP_PREFIX):
         self.cfg, self.device = cfg, device
-        self._graphs = {}
+        self._graphs = graphs.Cache()
         self._patch_rows = {}
         e = prefix + ".embeddings"
         K = 3 * cfg.patch * cfg.patch
@@ -50,30 +54,13 @@ class ClipTower:
                 qkv_w=_dev(qkv_w, device), qkv_b=_dev(qkv_b, device), out=_Lin(w, p + ".self_attn.out_proj", device),
                 fc1=_Lin(w, p + ".mlp.fc1", device), fc2=_Lin(w, p + ".mlp.fc2", device)))
 
-    use_graph = True  # replay the tower as one HIP graph (it is ~250 launches of 5-15 us kernels: launch-bound)
+    use_graph = graphs.ON  # replay the tower as one HIP graph (it is ~250 launches of 5-15 us kernels: launch-bound)
 
     def __call__(self, images):
         """images [B,3,S,S] bf16 -> patch features [B, T-1, hidden]."""
-        if not (self.use_graph and images.is_cuda) or torch.cuda.is_current_stream_capturing() or ops.TIMER.enabled:
+        if not graphs.enabled(self.use_graph, images):
             return self._forward(images)
-        B = images.shape[0]
-        gkey = (B, self.precision, self.fp8)
-        ent = self._graphs.get(gkey)
-        if ent is None:
-            static_in = images.to(BF16).contiguous().clone()
-            side = torch.cuda.Stream(device=images.device)
-            side.wait_stream(torch.cuda.current_stream(images.device))
-            with torch.cuda.stream(side):  # warm-up outside capture (first-use attribute calls, allocator pools)
-                self._forward(static_in)
-            torch.cuda.current_stream(images.device).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):  # (an RCCL watchdog thread may be polling events)
-                static_out = self._forward(static_in)
-            ent = self._graphs[gkey] = (g, static_in, static_out)
-        g, static_in, static_out = ent
-        static_in.copy_(images)
-        g.replay()
-        return static_out.clone()
+        return self._graphs.run((images.shape[0], self.precision, self.fp8), self._forward, [images], BF16)
 
     # "parity": fp32-activation arithmetic (hi + lo bf16 operands), see SamImageEncoder.precision; "f16": every MFMA operand as
     # IEEE fp16 (one pass, an eighth of the bf16 operand rounding; fp16 copies of the weights made on first use)
@@ -217,8 +204,7 @@ class Llama:
         self.precision = "default"
         self.decode_splitkv = False  # split-KV decode attention (long prompts): see _attn_scratch
         self.kcache_lo = self.vcache_lo = None  # "parity" precision: lo planes of the cache (allocated on first use)
-        self._dgraphs = {}
-        self._dgraph = None
+        self._graphs = {}  # _GraphKey -> captured decode step (decode_graph / decode_graph_batch); entries leave by _drop_graphs
         self._fused = None
         # attention + o_proj in ONE launch (o_proj blocks wait on device counters): saved a launch per layer when the o_proj
         # GEMV was the persistent kernel; with gemv1_kernel the separate launches are as fast (2.67 vs 2.68 ms/token, same
@@ -228,28 +214,9 @@ class Llama:
         # reconstructed bit for bit, dots on the matrix cores: ivlm_gemv1_bf12m; copies made on the first decode step, +10 GB for
         # 7B): 2.69 -> 2.34 ms per token.  Matrices whose shape the fragment layout does not take (rows % 16, columns % 64) stay
         # on the bf16 kernel (the lm_head's rows are padded with zeros).  IVLM_DECODE_PACKED=0 / decode_packed = False: bf16 weights everywhere.
-        self._decode_packed = os.environ.get("IVLM_DECODE_PACKED", "1") != "0"
+        self.decode_packed = os.environ.get("IVLM_DECODE_PACKED", "1") != "0"
         self.decode_attn_parts = os.environ.get("IVLM_DECODE_ATTN_PARTS", "1") != "0"  # (with decode_packed: see _decode_step)
         self.decode_packed_batch = os.environ.get("IVLM_DECODE_PACKED_BATCH", "1") != "0"  # (the batched step: ivlm_gemv16_bf12m)
-
-    # captured decode graphs are kept per (precision, packed decode weights or not): their launches bake in the weight pointers
-    def _gkey(self):
-        return (self.precision, bool(self._decode_packed))
-
-    @property
-    def decode_packed(self):
-        return self._decode_packed
-
-    @decode_packed.setter
-    def decode_packed(self, flag):
-        flag = bool(flag)
-        if flag == self._decode_packed:
-            return
-        self._dgraphs[self._gkey()] = self._dgraph
-        self._decode_packed = flag
-        self._dgraph = self._dgraphs.get(self._gkey())
-        if hasattr(self, "_bgraphs"):
-            self._bgraphs = {}
 
     # ---- which copies of the layer matrices are resident -----------------------------------------
     # Three forms exist: the checkpoint's bf16 matrices (prefill of the bf16 / parity modes, bf16 decode), IEEE fp16 copies (prefill
@@ -262,7 +229,7 @@ class Llama:
         if self.fp8 or self._calibrating:
             return
         for L in self.layers:
-            if self._decode_packed:
+            if self.decode_packed:
                 for n in _LayerW.MATS:
                     if n + "_p" not in L:
                         L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
@@ -271,7 +238,7 @@ class Llama:
             else:  # bf16 / parity prefill reads the bf16 matrices (rebuilt from the planes if the default mode had released them)
                 for n in _LayerW.MATS:
                     L[n]
-        if self._decode_packed and ops.PackedBf12.takes(16, self.cfg.hidden) and getattr(self, "lm_head_p", None) is None:
+        if self.decode_packed and ops.PackedBf12.takes(16, self.cfg.hidden) and getattr(self, "lm_head_p", None) is None:
             self.lm_head_p = ops.PackedBf12(self.lm_head, pad_rows=True)
 
     def release_unused(self):
@@ -283,7 +250,7 @@ class Llama:
                 if self.precision == "f16":
                     wp = L.get(n + "_p")
                     have16 = n + "_h" in L or n + "_hp" in L
-                    if self._decode_packed and wp is not None and wp.frag and dict.__contains__(L, n) and have16:
+                    if self.decode_packed and wp is not None and wp.frag and dict.__contains__(L, n) and have16:
                         del L[n]
                         dropped = True
                     if n + "_hp" in L and L.pop(n + "_h", None) is not None:  # (the panels replace the row-major copy)
@@ -292,12 +259,8 @@ class Llama:
                     for k in (n + "_h", n + "_hp"):
                         if L.pop(k, None) is not None:
                             dropped = True
-        if dropped:  # graphs of the bf16-weight decode step hold pointers into what was just released
-            self._dgraphs = {k: g for k, g in self._dgraphs.items() if k[1]}
-            if not self._decode_packed:
-                self._dgraph = None
-            if hasattr(self, "_bgraphs"):
-                self._bgraphs = {}
+        if dropped:  # graphs that read the bf16 matrices (unpacked steps, the fused attention + o_proj) hold pointers into them
+            self._drop_graphs(lambda k: not k.packed or k.fused)
 
     def resident_bytes(self):
         """{form: bytes} of the language model's weights currently in HBM."""
@@ -325,11 +288,7 @@ class Llama:
         assert mode in ("default", "parity", "f16")
         if mode == self.precision:
             return
-        self._dgraphs[self._gkey()] = self._dgraph
         self.precision = mode
-        self._dgraph = self._dgraphs.get(self._gkey())
-        if hasattr(self, "_bgraphs"):
-            self._bgraphs = {}
         if mode == "parity" and self.kcache_lo is None:
             self.kcache_lo, self.vcache_lo = torch.zeros_like(self.kcache), torch.zeros_like(self.vcache)
 
@@ -357,13 +316,11 @@ class Llama:
         for L in self.layers:
             L["s"] = {k: (v / 448.0).clamp_(min=1e-12) for k, v in L["amax"].items()}
         self.fp8 = True
-        self._dgraph = None
-        self._dgraphs = {}
+        self._drop_graphs(lambda k: True)
 
     def disable_fp8(self):
         self.fp8 = False
-        self._dgraph = None
-        self._dgraphs = {}
+        self._drop_graphs(lambda k: True)
 
     def _lo(self, li):
         return (self.kcache_lo[li], self.vcache_lo[li]) if self.precision == "parity" else None
@@ -417,6 +374,7 @@ class Llama:
         if bc is None or bc[0].shape[1] < B:
             kc, vc = self.batch_cache(B)
             bc = self._bcache_lo = (torch.zeros_like(self._bcache[0]), torch.zeros_like(self._bcache[1]))
+            self._drop_graphs(lambda k: k.batched and k.precision == "parity")
         return bc[0][:, :B], bc[1][:, :B]
 
     def _layer_parity(self, L, x, T, pos0, kc, vc, kcl, vcl):
@@ -562,50 +520,59 @@ class Llama:
     # ---- one decode step as a replayable HIP graph ------------------------------------------------------------------
     # Static buffers: token id in, position (device int32, read by the attention kernel), hidden out, argmax out.
     # Per generated token the host then issues 1 graph launch instead of ~165 kernel launches (2.4 ms of Python).
+    # The graphs are cached per _GraphKey: switching precision or `decode_packed` selects another entry, and whatever frees or
+    # replaces a buffer that a captured step reads (weights, cache slabs) drops the entries that read it (_drop_graphs).
+    def _graph_key(self, B, batched):
+        if batched:
+            return _GraphKey(True, B, self.precision, self.decode_packed and self.decode_packed_batch and B > 1, self.fp8, False)
+        c = self.cfg
+        # (every block of the fused launch must be resident at once: one 1024-thread block per CU)
+        fused = bool(self.fuse_attn_oproj and c.hidden in (512, 1024, 4096, 5120)
+                     and c.heads + c.hidden // 32 <= torch.cuda.get_device_properties(self.device).multi_processor_count)
+        return _GraphKey(False, 1, self.precision, bool(self.decode_packed), self.fp8, fused)
+
+    def _drop_graphs(self, pred):
+        """the only way a captured decode step leaves the cache: called where a buffer it may have baked in is freed or replaced"""
+        self._graphs = {k: st for k, st in self._graphs.items() if not pred(k)}
+
+    def _capture_decode(self, key, st, body, caches, counters):
+        """capture body (one decode step) into st["graph"] and cache st under key.  The warm-up run writes KV row 0 of every cache
+        plane and advances the counters (positions, fused-launch counters): both are put back."""
+        saved = [t[..., :1, :, :].clone() for t in caches]  # (fp16 mode: the same bytes)
+        st["graph"], _ = graphs.capture(body, self.device)
+        for t in counters:
+            t.zero_()
+        for t, sv in zip(caches, saved):
+            t[..., :1, :, :].copy_(sv)
+        self._graphs[key] = st
+
     def decode_graph(self):
-        if self._dgraph is None:
-            dev = self.device
+        key = self._graph_key(1, batched=False)
+        st = self._graphs.get(key)
+        if st is None:
+            dev, c = self.device, self.cfg
             st = dict(tok=torch.zeros(1, dtype=torch.int32, device=dev), pos=torch.zeros(1, dtype=torch.int32, device=dev),
                       pos64=torch.zeros(1, dtype=torch.int64, device=dev))
-            c = self.cfg
-            n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-            # (every block of the fused launch must be resident at once: one 1024-thread block per CU)
-            if self.fuse_attn_oproj and c.hidden in (512, 1024, 4096, 5120) and c.heads + c.hidden // 32 <= n_cu:
+            if key.fused:
                 # fused attention + o_proj launches: per-layer arrival counters, tokens-decoded counter, status word
                 st["fused"] = dict(step=torch.zeros(1, dtype=torch.int32, device=dev),
                                    counters=torch.zeros(c.layers, 32, dtype=torch.int32, device=dev),  # 128-B apart
                                    status=torch.zeros(1, dtype=torch.int32, device=dev),
                                    scratch=torch.zeros(c.layers, c.hidden, dtype=F32, device=dev))
-            self._fused = st.get("fused")
+            fz = self._fused = st.get("fused")
 
             def body():
                 e = self.embed_ids(st["tok"])
                 h = self._decode_step(e, st["pos"])
                 st["hidden"] = h
                 st["nxt"] = ops.argmax(self.logits(h), bump=st["pos"])  # (+ position += 1 in the same launch)
-                if self._fused is not None:
-                    self._fused["step"].add_(1)
+                if fz is not None:
+                    fz["step"].add_(1)
 
             caches = [self.kcache, self.vcache] + ([self.kcache_lo, self.vcache_lo] if self.precision == "parity" else [])
-            saved = [t[:, :1].clone() for t in caches]  # the warm-up / capture runs write row 0 (fp16 mode: the same bytes)
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            st["pos"].zero_()
-            st["pos64"].zero_()
-            if self._fused is not None:
-                self._fused["step"].zero_()
-                self._fused["counters"].zero_()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                body()
-            for t, sv in zip(caches, saved):
-                t[:, :1].copy_(sv)
-            st["graph"] = g
-            self._dgraph = st
-        return self._dgraph
+            counters = [st["pos"], st["pos64"]] + ([fz["step"], fz["counters"]] if fz is not None else [])
+            self._capture_decode(key, st, body, caches, counters)
+        return st
 
     # ---- B sequences per decode step (configs[2]: 8 images per GPU) ---------------------------------------------------
     # The weights are streamed once per step for all B tokens (GEMV rows M = B <= 8 share every weight load), so a step of
@@ -617,7 +584,7 @@ class Llama:
             H, hd = c.heads, c.hidden // c.heads
             bc = self._bcache = tuple(torch.zeros(c.layers, B, self.max_len, H, hd, dtype=BF16, device=self.device)
                                       for _ in range(2))
-            self._bgraphs = {}
+            self._drop_graphs(lambda k: k.batched)
         if self.precision == "f16":  # the same slabs, seen as fp16
             return bc[0].view(torch.float16)[:, :B], bc[1].view(torch.float16)[:, :B]
         return bc[0][:, :B], bc[1][:, :B]
@@ -653,7 +620,8 @@ class Llama:
         """One batched decode step (embed -> layers -> norm -> lm_head -> argmax, positions += 1) as a HIP graph."""
         kc, vc = self.batch_cache(B)
         lo = self.batch_cache_lo(B) if self.precision == "parity" else None
-        st = self._bgraphs.get(B)
+        key = self._graph_key(B, batched=True)
+        st = self._graphs.get(key)
         if st is None:
             dev = self.device
             st = dict(tok=torch.zeros(B, dtype=torch.int32, device=dev), pos=torch.zeros(B, dtype=torch.int32, device=dev))
@@ -663,22 +631,7 @@ class Llama:
                 st["hidden"] = h
                 st["nxt"] = ops.argmax(self.logits(h), bump=st["pos"])  # (+ positions += 1 in the same launch)
 
-            caches = [kc, vc] + (list(lo) if lo is not None else [])
-            saved = [t[:, :, :1].clone() for t in caches]  # the warm-up / capture runs write row 0 of every slab
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            st["pos"].zero_()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                body()
-            for t, sv in zip(caches, saved):
-                t[:, :, :1].copy_(sv)
-            st["pos"].zero_()
-            st["graph"] = g
-            self._bgraphs[B] = st
+            self._capture_decode(key, st, body, [kc, vc] + list(lo or ()), [st["pos"]])
         return st
 
     def _attn_scratch(self):
@@ -708,7 +661,7 @@ class Llama:
                 x = ops.linear_fp8w(h, L["down_q"], L["down_s"], residual=x)
             return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
         kc_, vc_ = self._caches()
-        if self._decode_packed and fz is None:
+        if self.decode_packed and fz is None:
             def lin(x_, L, n, **kw):  # (packed where the fragment layout takes the matrix, bf16 otherwise)
                 if n + "_p" not in L:
                     N_, K_ = L[n].shape

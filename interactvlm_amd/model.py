@@ -19,7 +19,7 @@ from typing import List, Optional
 
 import torch
 
-from . import ops
+from . import graphs, ops
 from .components import HumanContact3DPredictor, ObjectMeshContact3DPredictor, ObjectPCAfford3DPredictor
 from .constants import IGNORE_LABEL, IMAGE_TOKEN_INDEX
 from .heads import SamFusionHead, UncertaintyHead
@@ -84,9 +84,7 @@ class InteractVLMForCausalLM:
         self.use_fusion, self.use_uncertainty = bool(c.use_fusion), bool(c.use_uncertainty)
         self.debug_taps = None  # set to a dict to record intermediate tensors (tests / diagnostics only)
         self.overlap_sam_encoder = True
-        # HIP-graph replay of the decode step / CLIP tower (launch-bound on the host otherwise); IVLM_NO_GRAPHS=1 turns both
-        # off (rocprofv3 --pmc passes crash on replayed graphs)
-        self.graph_decode = not os.environ.get("IVLM_NO_GRAPHS")
+        self.graph_decode = graphs.ON  # HIP-graph replay of the decode step (launch-bound on the host otherwise)
         self.sam_after_prefill = bool(os.environ.get("IVLM_SAM_AFTER_PREFILL"))  # measured: 107.6 vs 106.6 ms - overlapping the decode instead of the prefill is not better
         self.packed_prefill = True  # generate_batch: prefill all prompts of a batch as one packed pass (rows independent)
         self.fused_lowres_lift = False  # measured slower than lifting the (cache-resident) full-res masks
@@ -95,17 +93,12 @@ class InteractVLMForCausalLM:
         self.prioritise_llm = False  # measured: no gain (the two streams time-share the CUs either way)
 
         self.vision_tower = ClipTower(w, c.clip, dev)
-        if os.environ.get("IVLM_NO_GRAPHS"):
-            self.vision_tower.use_graph = False
         self.mm_projector = _Lin(w, "model.mm_projector", dev)
         self.llm = Llama(w, c.llama, dev, max_len=max_len)
         self.text_hidden_fcs = (_Lin(w, "model.text_hidden_fcs.0.0", dev), _Lin(w, "model.text_hidden_fcs.0.2", dev))
         vm = SimpleNamespace()
         vm.image_encoder = SamImageEncoder(w, c.sam, dev)
         vm.mask_decoder = SamMaskDecoder(w, dev, grid=c.sam.grid)
-        if os.environ.get("IVLM_NO_GRAPHS"):
-            vm.mask_decoder.use_graph = False
-            vm.image_encoder.use_graph = False
         vm.prompt_encoder = vm.mask_decoder  # text path of the prompt encoder is folded into the decoder object
         self.use_diff_decoder = "DifDe" in c.token_type
         if self.use_diff_decoder:  # separately trained decoder copies, picked per sample by dataset name (InteractVLM.py:46-52)
@@ -113,13 +106,9 @@ class InteractVLMForCausalLM:
             if c.difde_load == "reference":  # the reference's load-into-aliases-then-deepcopy: all three = the key set loaded last
                 vm.mask_decoder = SamMaskDecoder(w, dev, grid=c.sam.grid, decoder="object_mask_decoder")
                 vm.prompt_encoder = vm.mask_decoder
-                if os.environ.get("IVLM_NO_GRAPHS"):
-                    vm.mask_decoder.use_graph = False
             names = ("object_mask_decoder",) * 2 if c.difde_load == "reference" else ("human_mask_decoder", "object_mask_decoder")
             vm.human_mask_decoder = SamMaskDecoder(w, dev, grid=c.sam.grid, decoder=names[0])
             vm.object_mask_decoder = SamMaskDecoder(w, dev, grid=c.sam.grid, decoder=names[1])
-            if os.environ.get("IVLM_NO_GRAPHS"):
-                vm.human_mask_decoder.use_graph = vm.object_mask_decoder.use_graph = False
         if self.use_fusion:
             vm.fusion = SamFusionHead(w, dev)
         if self.use_uncertainty:
@@ -546,7 +535,7 @@ class InteractVLMForCausalLM:
         if forced_new_tokens is not None:
             forced_dev = torch.tensor([int(t) for t in forced_new_tokens], dtype=torch.int32, device=self.device)
         self.last_argmax = []
-        use_graph = self.graph_decode and not ops.TIMER.enabled and not torch.cuda.is_current_stream_capturing()
+        use_graph = graphs.enabled(self.graph_decode)
         if use_graph:
             # one decode step = one replay of a captured HIP graph (embed -> 32 layers -> norm -> lm_head -> argmax, position
             # read from device memory); the host issues 3 launches per token instead of ~165
@@ -613,7 +602,7 @@ class InteractVLMForCausalLM:
                 # a bounded device-side wait of the fused attention + o_proj launch expired (its blocks were not co-resident,
                 # e.g. a third stream holding the CUs): drop to the two-launch path for good and redo this generation
                 self.llm.fuse_attn_oproj = False
-                self.llm._dgraph = None
+                self.llm._drop_graphs(lambda k: k.fused)
                 return self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, forced_new_tokens, None)
             out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
             return out_ids, hidden_all[:pos]
@@ -679,7 +668,7 @@ class InteractVLMForCausalLM:
         if forced_new_tokens is not None:
             pad = [list(map(int, f[:n])) + [eos_token_id] * (n_max - n) for f, n in zip(forced_new_tokens, n_seq)]
             forced_dev = torch.tensor(pad, dtype=torch.int32, device=dev).t().contiguous()  # [n_max, B]
-        use_graph = self.graph_decode and not ops.TIMER.enabled and not torch.cuda.is_current_stream_capturing()
+        use_graph = graphs.enabled(self.graph_decode)
         pos_t = torch.tensor(T0, dtype=torch.int32, device=dev)
         if use_graph:
             dg = self.llm.decode_graph_batch(B)

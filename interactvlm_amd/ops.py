@@ -325,7 +325,7 @@ SPLITK = os.environ.get("IVLM_SPLITK", "1") != "0"  # small-M GEMMs (prefill, CL
 # launch it saves.  Opt-in, kept for the record and for single-XCD parts.
 SPLITK_FUSED = os.environ.get("IVLM_SPLITK_FUSED", "0") == "1"
 _SPLITK_CNT = {}
-_SPLITK_CNT_CAPTURE = {}
+_SPLITK_CNT_CAPTURE = None  # the arrays of the capture in progress: opened and closed by graphs.capture
 
 
 def _splitk_counters(device):
@@ -334,18 +334,15 @@ def _splitk_counters(device):
     captured the array is created INSIDE the capture (memory of the graph's own pool, one array per capture, its zero fill is
     a node of the graph): two graphs - which may be replayed on different streams at the same time - never share counters, and
     the launches inside one captured stream are ordered."""
+    cnts = _SPLITK_CNT
     if torch.cuda.is_current_stream_capturing():
-        key = (device.index, _stream())
-        c = _SPLITK_CNT_CAPTURE.get(key)
-        if c is None:
-            c = _SPLITK_CNT_CAPTURE[key] = torch.zeros(4096, dtype=torch.int32, device=device)
-        return c
-    if _SPLITK_CNT_CAPTURE:
-        _SPLITK_CNT_CAPTURE.clear()  # (no capture in progress: the next capture gets arrays of its own)
+        if _SPLITK_CNT_CAPTURE is None:
+            raise IvlmError("fused split-K GEMM captured outside graphs.capture (its counters need a capture scope)")
+        cnts = _SPLITK_CNT_CAPTURE
     key = (device.index, _stream())
-    c = _SPLITK_CNT.get(key)
+    c = cnts.get(key)
     if c is None:
-        c = _SPLITK_CNT[key] = torch.zeros(4096, dtype=torch.int32, device=device)
+        c = cnts[key] = torch.zeros(4096, dtype=torch.int32, device=device)
     return c
 
 

@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from . import ops
+from . import graphs, ops
 from .weights import SAM_PREFIX, SamEncCfg
 
 BF16 = torch.bfloat16
@@ -64,6 +64,7 @@ class SamImageEncoder:
 
     def __init__(self, w, cfg: SamEncCfg, device, prefix=SAM_PREFIX + ".image_encoder"):
         self.cfg, self.device = cfg, device
+        self._graphs = graphs.Cache()
         p = prefix
         D = cfg.embed_dim
         self.patch = _Lin(w, p + ".patch_embed.proj", device)
@@ -136,8 +137,7 @@ class SamImageEncoder:
         for blk in self.blocks:
             blk["s"] = {k: (v / 448.0).clamp_(min=1e-12) for k, v in blk["amax"].items()}
         self.fp8 = True
-        if hasattr(self, "_graphs"):
-            self._graphs.clear()
+        self._graphs.clear()
 
     _calibrating = False
 
@@ -208,31 +208,13 @@ class SamImageEncoder:
     # The encoder is ~320 launches (ViT-H, 4 views).  Issued one by one they cost the host ~22 ms - during which the language
     # path, launched after it by the same thread, has not even started (measured: the first 21.9 ms of evaluate() had an idle
     # main stream).  Replayed as ONE HIP graph per input shape the host is free after ~20 us.  Same kernels, same order.
-    use_graph = True
+    use_graph = graphs.ON
 
     def __call__(self, images):
-        if not (self.use_graph and images.is_cuda) or torch.cuda.is_current_stream_capturing() or ops.TIMER.enabled:
+        if not graphs.enabled(self.use_graph, images):
             return self._forward(images)
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
         key = tuple(images.shape) + (self.fp8, self.precision, self.parity_sites, self.q_lo_level)
-        ent = self._graphs.get(key)
-        dev = images.device
-        if ent is None:
-            static_in = images.to(BF16).contiguous().clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # warm-up outside capture (window maps, allocator pools)
-                self._forward(static_in)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                static_out = self._forward(static_in)
-            ent = self._graphs[key] = (g, static_in, static_out)
-        g, static_in, static_out = ent
-        static_in.copy_(images)
-        g.replay()
-        return static_out.clone()
+        return self._graphs.run(key, self._forward, [images], BF16)
 
     # ---- "parity" precision (opt-in): fp32-activation arithmetic on the bf16 matrix cores --------------------------------------
     # Every activation that the default mode rounds to a bf16 MFMA operand (normed rows, q / k / v, softmax weights, attention
@@ -478,6 +460,7 @@ class SamMaskDecoder:
         """decoder: the attribute name of the decoder module to load ('-DifDe' checkpoints also carry 'human_mask_decoder' and
         'object_mask_decoder', separately trained copies: InteractVLM.py:114-121); the prompt encoder is shared."""
         self.device, self.grid = device, grid
+        self._graphs = graphs.Cache()
         pe, md = prefix + ".prompt_encoder", prefix + "." + decoder
         self.C = C = w[md + ".iou_token.weight"].shape[1]
         f32 = lambda t: t.to(device=device, dtype=BF16).to(F32).contiguous()  # the checkpoint's bf16 values, held as fp32
@@ -534,33 +517,13 @@ class SamMaskDecoder:
     # The decoder chain (prompt tokens -> two-way transformer -> upscaler -> hypernetwork dot -> IoU head) is ~200 launches of
     # 3-30 us kernels with no host decision inside: replayed as ONE HIP graph per (views, tokens) shape (BASELINE.json
     # configs[4]: "fused SAM decoder in one hipGraph").  Same kernels, same order: bit-identical to the eager chain.
-    use_graph = True
+    use_graph = graphs.ON
 
     def __call__(self, image_embeddings, text_embeds):
-        if (not (self.use_graph and image_embeddings.is_cuda) or torch.cuda.is_current_stream_capturing()
-                or ops.TIMER.enabled):
+        if not graphs.enabled(self.use_graph, image_embeddings):
             return self._forward(image_embeddings, text_embeds)
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
         key = (tuple(image_embeddings.shape), image_embeddings.dtype, tuple(text_embeds.shape), text_embeds.dtype)
-        ent = self._graphs.get(key)
-        dev = image_embeddings.device
-        if ent is None:
-            s_emb, s_txt = image_embeddings.contiguous().clone(), text_embeds.contiguous().clone()
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):  # warm-up outside capture (allocator pools, lazy module loads)
-                self._forward(s_emb, s_txt)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                s_out = self._forward(s_emb, s_txt)
-            ent = self._graphs[key] = (g, s_emb, s_txt, s_out)
-        g, s_emb, s_txt, s_out = ent
-        s_emb.copy_(image_embeddings)
-        s_txt.copy_(text_embeds)
-        g.replay()
-        return s_out[0].clone(), s_out[1].clone()
+        return self._graphs.run(key, self._forward, [image_embeddings, text_embeds])
 
     def _forward(self, image_embeddings, text_embeds):
         """image_embeddings [V, g*g, C] fp32 or bf16 (channels last); text_embeds [1, T, C] (the views as TOKENS)

@@ -237,6 +237,91 @@ def test_graph_decode_with_fused_attn_oproj_matches_eager(hip_lib, cuda, hidden,
         assert (torch.tensor(arg_b)[clear] == lg.argmax(-1)[clear]).all()
 
 
+def test_decode_graph_cache_through_the_invalidation_events(hip_lib, cuda):
+    """The captured decode steps are cached per (batched, B, precision, packed, fp8, fused); every event that frees or replaces a
+    buffer a captured step reads drops the entries that read it.  Walked in order - a capture in the default mode, the bf16-weight
+    path and back with release, decode_packed off and on, batched steps at B = 2 then B = 5 (slab growth) and B = 2 again, parity
+    (lo planes), back to the default mode - after each event one replayed step equals the eager step bit for bit."""
+    import torch
+
+    from interactvlm_amd import llava, ops
+    from interactvlm_amd import weights as Wt
+
+    lc = Wt.LlamaCfg(hidden=512, layers=3, heads=4, inter=1024, vocab=1003)
+    w = _bf16_weights(Wt.llama_spec(lc))
+    g = torch.Generator().manual_seed(23)
+    T0 = 21
+    emb = (torch.randn(5, T0, 512, generator=g) * 0.5).to(torch.bfloat16).float().to(cuda)
+    toks = torch.randint(3, 1000, (5,), generator=g).to(torch.int32).to(cuda)
+    llm = llava.Llama(w, lc, cuda, max_len=64)
+
+    def mode(precision, packed=True, release=False):  # (what InteractVLMForCausalLM.set_precision does to the language model)
+        llm.decode_packed = packed
+        llm.set_precision(precision)
+        llm.prepare()
+        if release:
+            llm.release_unused()
+
+    def step1():  # a fresh prefill, then one step at position T0: eager, then replayed (which rewrites the same KV row)
+        llm.forward(emb[0], 0)
+        pos = torch.full((1,), T0, dtype=torch.int32, device=cuda)
+        h = llm._decode_step(llm.embed_ids(toks[:1]), pos)
+        nxt = ops.argmax(llm.logits(h))
+        dg = llm.decode_graph()
+        dg["pos"].fill_(T0)
+        dg["tok"].copy_(toks[:1])
+        dg["graph"].replay()
+        assert torch.equal(dg["hidden"], h) and torch.equal(dg["nxt"], nxt) and int(dg["pos"][0]) == T0 + 1
+
+    def step_batch(B):
+        kc, vc = llm.batch_cache(B)
+        lo = llm.batch_cache_lo(B) if llm.precision == "parity" else None
+        for b in range(B):
+            llm.forward(emb[b], 0, cache=(kc[:, b], vc[:, b]) + ((lo[0][:, b], lo[1][:, b]) if lo else ()))
+        pos = torch.full((B,), T0, dtype=torch.int32, device=cuda)
+        h = llm.decode_step_batch(llm.embed_ids(toks[:B]), pos, kc, vc, lo)
+        nxt = ops.argmax(llm.logits(h))
+        dg = llm.decode_graph_batch(B)
+        dg["pos"].copy_(pos)
+        dg["tok"].copy_(toks[:B])
+        dg["graph"].replay()
+        assert torch.equal(dg["hidden"], h) and torch.equal(dg["nxt"], nxt) and torch.equal(dg["pos"], pos + 1)
+        return dg
+
+    keys = lambda: set(llm._graphs)
+    K = llava._GraphKey
+    mode("f16", release=True)  # 1. the default mode (fp16 prefill, packed decode planes, bf16 matrices released)
+    step1()
+    assert keys() == {K(False, 1, "f16", True, False, False)}
+    mode("default", packed=False)  # 2. the bf16-weight path (matrices rebuilt from the planes) ...
+    step1()
+    assert K(False, 1, "default", False, False, False) in keys()
+    mode("f16", release=True)  # ... and back: the release drops the graph that read the rebuilt matrices
+    assert keys() == {K(False, 1, "f16", True, False, False)}
+    step1()
+    mode("default", packed=False)  # (a new capture on the matrices rebuilt once more)
+    step1()
+    mode("f16", release=True)
+    llm.decode_packed = False  # 3. decode_packed off (bf16 matrices rebuilt on first use) and on
+    step1()
+    llm.decode_packed = True
+    step1()
+    assert keys() == {K(False, 1, "f16", True, False, False), K(False, 1, "f16", False, False, False)}
+    dg2 = step_batch(2)  # 4. batched: B = 2, then B = 5 grows the slabs and drops every batched entry, B = 2 recaptured
+    step_batch(5)
+    assert {k for k in keys() if k.batched} == {K(True, 5, "f16", True, False, False)}
+    assert step_batch(2) is not dg2
+    mode("parity")  # 5. parity: K / V as hi + lo planes (batch-1 and slab lo planes)
+    step1()
+    step_batch(2)
+    step_batch(5)
+    mode("f16", release=True)  # back: every surviving entry reads only live buffers (the release dropped the bf16-weight ones)
+    assert all(k.packed for k in keys())
+    dg2 = llm._graphs[K(True, 2, "f16", True, False, False)]
+    assert step_batch(2) is dg2
+    step1()
+
+
 def _toy(golden_dir):
     import torch
 
