@@ -400,6 +400,24 @@ int ivlm_llama_decode_attn_batch(const void *qkv, int io_dtype, int64_t ldq, voi
                                  int tmax, void *o, int64_t ldo, int B, int H, int D, const int32_t *pos_dev, float theta,
                                  float scale, const float *cos_tab, const float *sin_tab, ivlm_stream_t stream);
 
+/* Verify pass of speculative greedy decoding (one sequence): rows i = 0 .. k-1 (k <= 16) of qkv fp32 [k, 3*H*D] are new tokens at
+ * positions pos_dev[0] + i (device memory: graph-capturable).  RoPE of q and k, append of the k key / value rows to kcache / vcache
+ * [tmax, H, D] (bf16; the _f16 twin: IEEE fp16, as ivlm_llama_decode_attn_f16), causal attention - query i sees keys 0 .. pos+i -
+ * into o fp32 [k, H*D].  One block per head streams the cached rows once for all k queries; per row the arithmetic of
+ * ivlm_llama_decode_attn with fp32 I/O (fp32 q and softmax, query i sees new rows < i as cached and its own row unrounded).  Rows
+ * whose position is >= tmax are not appended and their output rows are zeros.  D <= 128, D % 16 == 0. */
+int ivlm_llama_verify_attn(const float *qkv, int k, void *kcache, void *vcache, int tmax, float *o, int H, int D,
+                           const int32_t *pos_dev, float theta, float scale, const float *cos_tab, const float *sin_tab,
+                           ivlm_stream_t stream);
+int ivlm_llama_verify_attn_f16(const float *qkv, int k, void *kcache, void *vcache, int tmax, float *o, int H, int D,
+                               const int32_t *pos_dev, float theta, float scale, const float *cos_tab, const float *sin_tab,
+                               ivlm_stream_t stream);
+/* Accept step of a verify pass (one thread, graph-capturable): amax i32 [k] = argmax of the k verified rows, fed i32 [k] = the ids fed
+ * (fed[0] the last emitted token, fed[1 .. n] the draft, n = *n_draft <= k - 1).  Writes *n_acc = the number of leading draft ids with
+ * fed[j + 1] == amax[j], *tok = amax[*n_acc] (the next token) and *pos += *n_acc + 1. */
+int ivlm_spec_accept(const int32_t *amax, const int32_t *fed, const int32_t *n_draft, int k, int32_t *n_acc, int32_t *tok, int32_t *pos,
+                     ivlm_stream_t stream);
+
 /* "Parity" precision of the two kernels above: fp32 qkv / o, and the cache holds K / V as hi + lo bf16 planes (kcache_lo /
  * vcache_lo: the layout of the hi caches) - the appended rows are not rounded to bf16, the cached ones are read as hi + lo. */
 int ivlm_llama_decode_attn_split(const void *qkv, void *kcache, void *kcache_lo, void *vcache, void *vcache_lo, int tmax, void *o,

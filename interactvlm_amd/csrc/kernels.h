@@ -191,6 +191,13 @@ int llama_decode_attn_parts(const float* qkv, bf16_t* kcache, bf16_t* vcache, in
                             float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
                             int cache_f16);
 
+// speculative decoding of one sequence (verify.hip): k <= 16 new tokens at positions pos_dev[0] .. +k-1 in one attention launch
+// (fp32 qkv [k, 3*H*D] / o [k, H*D]; bf16 or fp16 cache), and the accept step of a verify pass
+int llama_verify_attn(const float* qkv, int k, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, const int32_t* pos_dev,
+                      float theta, float scale, const float* cos_tab, const float* sin_tab, int cache_f16, hipStream_t st);
+int spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* nd_dev, int k, int32_t* n_acc, int32_t* tok, int32_t* pos,
+                hipStream_t st);
+
 // fused decode attention + o_proj (decode_fused.hip)
 int llama_attn_oproj(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* attn_scratch, const bf16_t* wo,
                      const float* x, float* x_out, int H, int D, float theta, float scale, const float* cos_tab,

@@ -51,6 +51,47 @@ def tokenizer_image_token(prompt: str, tokenizer, image_token_index: int = IMAGE
     return torch.tensor(ids, dtype=torch.long)
 
 
+# the answer formats of the released checkpoints (FIX.md "Updated DAMON numbers": the `simple` and the `parts` template)
+ANSWER_TEMPLATES = ("Sure, [SEG].", "The contacting body parts are {body_parts}, and the contact region is [SEG].")
+
+
+def answer_templates(tokenizer, contact_type="hcontact", seg_token_idx=None):
+    """Token-id templates of the released answer formats for ``speculative.Drafter``: each text is tokenised (no BOS), a ``{...}``
+    slot becomes ``speculative.SLOT`` (free text: drafting resumes on the fragment after it), the literal "[SEG]" is the model's
+    [SEG] id (``seg_token_idx``, default: the tokenizer's own id for "[SEG]", else 32000) and the tokenizer's EOS id, if it has
+    one, ends every template.  contact_type selects nothing yet: both formats answer every contact type of the released models."""
+    import re
+
+    from .speculative import SLOT
+
+    del contact_type
+    if seg_token_idx is None:
+        conv = getattr(tokenizer, "convert_tokens_to_ids", None)
+        seg_token_idx = conv("[SEG]") if conv is not None else 32000
+    bos = getattr(tokenizer, "bos_token_id", None)
+    eos = getattr(tokenizer, "eos_token_id", None)
+
+    def tok(text):
+        ids = list(tokenizer(text).input_ids)
+        return ids[1:] if ids and bos is not None and ids[0] == bos else ids
+
+    out = []
+    for text in ANSWER_TEMPLATES:
+        t = []
+        for i, part in enumerate(re.split(r"\{[^}]*\}", text)):
+            if i:
+                t.append(SLOT)
+            for j, piece in enumerate(part.split("[SEG]")):
+                if j:
+                    t.append(int(seg_token_idx))
+                if piece.strip():
+                    t.extend(tok(piece.strip()))
+        if eos is not None:
+            t.append(int(eos))
+        out.append(t)
+    return out
+
+
 def cam_params_for(contact_type: str, view_type: str) -> torch.Tensor:
     """[1, V, 5] normalised camera parameters in view order (run_demo.py:276-278, 205-210)."""
     table = HUMAN_VIEW_DICT if "hcontact" in contact_type else OBJS_VIEW_DICT

@@ -23,8 +23,9 @@ from .weights import CLIP_PREFIX, ClipCfg, LlamaCfg
 BF16 = torch.bfloat16
 F32 = torch.float32
 
-# a captured decode step (Llama._graphs): batched (decode_graph_batch) or not, sequences per step, and what selects its launches
-_GraphKey = collections.namedtuple("_GraphKey", "batched B precision packed fp8 fused")
+# a captured decode step (Llama._graphs): batched (decode_graph_batch) or not, sequences per step, and what selects its launches;
+# verify: a speculative verify pass of this instance's sequence (verify_graph, B = rows per pass)
+_GraphKey = collections.namedtuple("_GraphKey", "batched B precision packed fp8 fused verify", defaults=(False,))
 
 
 class ClipTower:
@@ -535,15 +536,15 @@ class Llama:
         """the only way a captured decode step leaves the cache: called where a buffer it may have baked in is freed or replaced"""
         self._graphs = {k: st for k, st in self._graphs.items() if not pred(k)}
 
-    def _capture_decode(self, key, st, body, caches, counters):
-        """capture body (one decode step) into st["graph"] and cache st under key.  The warm-up run writes KV row 0 of every cache
-        plane and advances the counters (positions, fused-launch counters): both are put back."""
-        saved = [t[..., :1, :, :].clone() for t in caches]  # (fp16 mode: the same bytes)
+    def _capture_decode(self, key, st, body, caches, counters, rows=1):
+        """capture body (one decode step) into st["graph"] and cache st under key.  The warm-up run writes KV rows 0 .. rows-1 of
+        every cache plane and advances the counters (positions, fused-launch counters): both are put back."""
+        saved = [t[..., :rows, :, :].clone() for t in caches]  # (fp16 mode: the same bytes)
         st["graph"], _ = graphs.capture(body, self.device)
         for t in counters:
             t.zero_()
         for t, sv in zip(caches, saved):
-            t[..., :1, :, :].copy_(sv)
+            t[..., :rows, :, :].copy_(sv)
         self._graphs[key] = st
 
     def decode_graph(self):
@@ -597,16 +598,7 @@ class Llama:
         H, hd = c.heads, c.hidden // c.heads
         if x.shape[0] > 16:
             raise ops.IvlmError("decode_step_batch: at most 16 sequences per step (weight-streaming kernels)")
-        packed = self.decode_packed and self.decode_packed_batch and x.shape[0] > 1
-
-        def lin(x_, L, n, **kw):  # (the packed planes of the batch-1 step where the fragment layout takes the matrix, bf16 otherwise)
-            if packed:
-                if n + "_p" not in L:
-                    L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
-                if L[n + "_p"] is not None and L[n + "_p"].frag:
-                    return ops.linear_bf12(x_, L[n + "_p"], **kw)
-            return ops.linear(x_, L[n], out_f32=True, **kw)
-
+        lin = self._rows_linear(self.decode_packed and self.decode_packed_batch and x.shape[0] > 1)
         for li, L in enumerate(self.layers):
             qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
             a = ops.llama_decode_attn_batch(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope,
@@ -615,6 +607,73 @@ class Llama:
             h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
             x = lin(h, L, "down", residual=x)
         return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+
+    @staticmethod
+    def _rows_linear(packed):
+        """the linears of the multi-row steps (decode_step_batch, verify_step): the packed planes of the batch-1 step where the
+        fragment layout takes the matrix (the weights streamed once for all rows), bf16 otherwise"""
+        def lin(x_, L, n, **kw):
+            if packed:
+                if n + "_p" not in L:
+                    L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
+                if L[n + "_p"] is not None and L[n + "_p"].frag:
+                    return ops.linear_bf12(x_, L[n + "_p"], **kw)
+            return ops.linear(x_, L[n], out_f32=True, **kw)
+        return lin
+
+    # ---- speculative greedy decoding: k <= 16 new tokens of THIS instance's sequence in one pass over the weights -----------------
+    # The rows [t0, d1 .. d_{k-1}] (last emitted token + a draft) sit at positions pos .. pos+k-1 of the single-sequence cache; one
+    # pass costs about what a batched step of k sequences costs (the linears of decode_step_batch), and an accepted draft token saves a
+    # whole decode step.  Not in the "parity" mode (hi + lo cache planes) or with fp8 weights: the generation loop runs the plain
+    # step there (InteractVLMForCausalLM.generate).
+    VERIFY_BUCKETS = (4, 8, 16)  # rows per captured verify pass (a shorter draft is padded; padded rows are never accepted)
+
+    def verify_supported(self):
+        return self.precision != "parity" and not self.fp8
+
+    def verify_step(self, x, pos_dev):
+        """x fp32 [k, hidden] (k <= 16 new tokens), pos_dev int32 [1] = position of row 0 on the device -> final-norm hidden fp32
+        [k, hidden]; appends k rows to the cache (rows at or past max_len are not appended).  Row i equals the i-th of k sequential
+        ``_decode_step`` calls to the batch-vs-single tolerance of decode_step_batch (the same linears), the cache rows bit for bit."""
+        c = self.cfg
+        H, hd = c.heads, c.hidden // c.heads
+        if not 1 <= x.shape[0] <= 16:
+            raise ops.IvlmError("verify_step: 1 .. 16 rows per pass (weight-streaming kernels)")
+        if not self.verify_supported():
+            raise ops.IvlmError(f"verify_step: not in precision {self.precision!r} / fp8 (no multi-token attention on hi + lo planes)")
+        kc, vc = self._caches()
+        lin = self._rows_linear(self.decode_packed and self.decode_packed_batch)
+        for li, L in enumerate(self.layers):
+            qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
+            a = ops.llama_verify_attn(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope)
+            x = lin(a, L, "o", residual=x)
+            h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
+            x = lin(h, L, "down", residual=x)
+        return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+
+    def verify_pass(self, st):
+        """embed st["ids"] -> verify_step -> lm_head -> argmax -> accept (st: the static buffers of verify_graph)"""
+        h = self.verify_step(self.embed_ids(st["ids"]), st["pos"])
+        st["hidden"] = h
+        st["amax"] = ops.argmax(self.logits(h))
+        ops.spec_accept(st["amax"], st["ids"], st["nd"], st["n_acc"], st["tok"], st["pos"])
+        return st
+
+    def verify_state(self, kb):
+        """fresh static buffers of a verify pass of kb rows: ids fed, draft length, position (advanced by the accept step), accepted
+        count, next token"""
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=self.device)
+        return dict(ids=i32(kb), nd=i32(1), pos=i32(1), n_acc=i32(1), tok=i32(1))
+
+    def verify_graph(self, kb):
+        """the verify pass of kb rows (one of VERIFY_BUCKETS) as a HIP graph; cached and dropped with the decode steps (_drop_graphs)"""
+        key = _GraphKey(False, kb, self.precision, bool(self.decode_packed and self.decode_packed_batch), self.fp8, False, True)
+        st = self._graphs.get(key)
+        if st is None:
+            st = self.verify_state(kb)
+            caches = [self.kcache, self.vcache]
+            self._capture_decode(key, st, lambda: self.verify_pass(st), caches, [st["pos"], st["n_acc"], st["tok"]], rows=kb)
+        return st
 
     def decode_graph_batch(self, B):
         """One batched decode step (embed -> layers -> norm -> lm_head -> argmax, positions += 1) as a HIP graph."""

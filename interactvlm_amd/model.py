@@ -507,10 +507,13 @@ class InteractVLMForCausalLM:
 
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, forced_new_tokens=None,
-                 after_prefill=None):
+                 after_prefill=None, draft=None):
         """Greedy search with a KV cache for ONE sequence.  Returns (output_ids [1, L+n], hidden [L+n-1+255, H]).
         forced_new_tokens (extension for weight-free benchmarking): feed these ids instead of the argmax (the
-        argmax/lm_head work is still done every step), like the reference's inference_type='forward'."""
+        argmax/lm_head work is still done every step), like the reference's inference_type='forward'.
+        draft (opt-in, free-running search only): a ``speculative.Drafter`` - or any object with ``propose(ids, k)`` (and optionally
+        ``observe(n_proposed, n_accepted)``) - whose proposals are verified k rows per pass over the weights (``_generate_speculative``):
+        the same ids as without it.  Ignored with forced_new_tokens; in the "parity" modes and with fp8 the plain loop runs."""
         feats = self.encode_images(images_clip)[0]
         ids = input_ids[0]
         x = self._input_embeds(ids, feats)
@@ -528,6 +531,12 @@ class InteractVLMForCausalLM:
         hidden_all[:T0].copy_(h)
         if after_prefill is not None:
             after_prefill()  # evaluate(): the SAM encoder is enqueued here, between the prefill and the decode loop
+        if draft is not None and forced_new_tokens is None and self.llm.verify_supported():
+            out = self._generate_speculative(ids, h[T0 - 1: T0], T0, n_max, eos_token_id, hidden_all, draft)
+            if out is not None:
+                return out
+            return self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, None, None, draft)
+        self.last_spec = None
         new_ids = []
         last = h[T0 - 1: T0]
         pos = T0
@@ -624,6 +633,91 @@ class InteractVLMForCausalLM:
             pos += 1
         out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
         return out_ids, hidden_all[:pos]
+
+    def _generate_speculative(self, ids, last, T0, n_max, eos_token_id, hidden_all, draft):
+        """The free-running greedy loop with verify passes (generate(draft=...)).  Per round the host knows every id so far and asks
+        the drafter for up to 15 ids to follow; with a proposal d1 .. dm the rows [t, d1 .. dm] (t = last id, padded to a bucket of
+        VERIFY_BUCKETS) run through ONE Llama.verify_step at positions pos .. pos+m, the accept step finds n_acc (leading d_j equal to
+        the argmax of row j-1), and d1 .. d_n_acc + argmax(row n_acc) are emitted, hidden rows 0 .. n_acc kept; the host reads n_acc and
+        the next id once per pass.  Without a proposal the plain decode step runs (its pos / tok words copied from the accept step's).
+        Stops exactly at EOS or n_max (rows past the stop are dropped, as the plain loop drops its one speculative step); no row is
+        written past max_len (n_max already keeps every fed position below it).  -> (output_ids, hidden) or None when a fused
+        attention + o_proj launch timed out (the caller redoes the generation on the two-launch path)."""
+        llm, dev = self.llm, self.device
+        use_graph = graphs.enabled(self.graph_decode)
+        kmax = max(llm.VERIFY_BUCKETS)
+        nxt = ops.argmax(llm.logits(last))
+        new_ids = [int(nxt.item())]
+        self.last_argmax = [nxt]
+        stats = self.last_spec = dict(passes=0, plain_steps=0, proposed=0, accepted=0, pattern=[])
+        pos = T0  # position at which new_ids[-1] is fed
+        dg = fz = None
+        if use_graph:
+            dg = llm.decode_graph()
+            dg["pos"].fill_(T0)
+            dg["pos64"].fill_(T0)
+            fz = dg.get("fused")
+            if fz is not None:
+                fz["step"].zero_()
+                fz["counters"].zero_()
+                fz["status"].zero_()
+        observe = getattr(draft, "observe", None)
+        while new_ids[-1] != eos_token_id and len(new_ids) < n_max:
+            rem = n_max - len(new_ids)  # ids still to emit; the fed rows stay below T0 + n_max - 1 <= max_len - 1
+            prop = [int(t) for t in draft.propose(list(new_ids), kmax)][: min(kmax - 1, rem - 1)]
+            m = len(prop)
+            if m == 0:  # the plain step (graph replay or eager), then one read-back
+                stats["plain_steps"] += 1
+                if use_graph:
+                    dg["tok"].fill_(new_ids[-1])
+                    dg["graph"].replay()
+                    hidden_all[pos: pos + 1].copy_(dg["hidden"])
+                    nxt = dg["nxt"].clone()
+                else:
+                    h = llm.forward(llm.embed_ids(torch.tensor([new_ids[-1]], dtype=torch.int32, device=dev)), pos)
+                    hidden_all[pos: pos + 1].copy_(h)
+                    nxt = ops.argmax(llm.logits(h))
+                self.last_argmax.append(nxt)
+                new_ids.append(int(nxt.item()))
+                pos += 1
+                continue
+            kb = next(b for b in llm.VERIFY_BUCKETS if b >= m + 1)
+            fed = torch.tensor([new_ids[-1]] + prop + [new_ids[-1]] * (kb - 1 - m), dtype=torch.int32)
+            st = llm.verify_graph(kb) if use_graph else llm.verify_state(kb)
+            st["pos"].fill_(pos)
+            st["ids"].copy_(fed)
+            st["nd"].fill_(m)
+            if use_graph:
+                st["graph"].replay()
+            else:
+                llm.verify_pass(st)
+            n_acc, tok = torch.cat([st["n_acc"], st["tok"]]).tolist()  # (the one read-back of the pass)
+            stats["passes"] += 1
+            stats["proposed"] += m
+            stats["accepted"] += n_acc
+            stats["pattern"].append((m, n_acc))
+            if observe is not None:
+                observe(m, n_acc)
+            amax = st["amax"][: n_acc + 1].clone()
+            emitted = prop[:n_acc] + [tok]
+            keep = 0
+            for e in emitted:  # stop exactly at EOS / n_max, even inside an accepted draft
+                new_ids.append(e)
+                keep += 1
+                if e == eos_token_id or len(new_ids) >= n_max:
+                    break
+            hidden_all[pos: pos + keep].copy_(st["hidden"][:keep])
+            self.last_argmax.extend(amax[j: j + 1] for j in range(keep))
+            pos += keep
+            if use_graph:  # the plain step continues from the accept step's position and token
+                dg["pos"].copy_(st["pos"])
+                dg["tok"].copy_(st["tok"])
+        if fz is not None and int(fz["status"].item()) != 0:
+            llm.fuse_attn_oproj = False
+            llm._drop_graphs(lambda k: k.fused)
+            return None
+        out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
+        return out_ids, hidden_all[: T0 + len(new_ids) - 1]
 
     @torch.no_grad()
     # ---- B images per call (BASELINE.json configs[2]: 8 images per GPU) -----------------------------------------------
@@ -875,8 +969,10 @@ class InteractVLMForCausalLM:
 
     def evaluate(self, images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                  lift2d_dict_path=None, contact_type="hcontact", max_new_tokens=32, tokenizer=None,
-                 forced_new_tokens=None, eos_token_id=2, image_embeddings=None):
+                 forced_new_tokens=None, eos_token_id=2, image_embeddings=None, draft=None):
         """Generate -> [SEG] hidden state -> SAM decode -> lift (InteractVLM.py:510-638).
+
+        draft (opt-in): speculative greedy decoding with these proposals (``generate``, ``speculative.Drafter``); same ids.
 
         image_embeddings (extension): pre-computed SAM embeddings [V, g*g, 256] of ``images``
         (``precompute_visual_embs``).  For hcontact the SAM inputs are the SAME four canonical body renders for
@@ -885,7 +981,8 @@ class InteractVLMForCausalLM:
         if self._guard_applies():
             return self._guarded(self.evaluate, (images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                                                  lift2d_dict_path, contact_type, max_new_tokens, tokenizer, forced_new_tokens,
-                                                 eos_token_id, image_embeddings), {}, supplied_embeddings=image_embeddings)
+                                                 eos_token_id, image_embeddings), {"draft": draft},
+                                 supplied_embeddings=image_embeddings)
         # The SAM ViT-H encoder (MFMA-bound, ~60 ms) does not depend on the language model (CLIP -> prefill -> decode:
         # HBM-bound weight streaming that leaves the matrix cores idle): run it on a second HIP stream and join
         # before the mask decoder.  The reference runs them back to back (InteractVLM.py:524-531, 578).
@@ -915,7 +1012,7 @@ class InteractVLMForCausalLM:
             with torch.cuda.stream(hi):
                 out = self._evaluate_tail(images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                                           lift2d_dict_path, contact_type, max_new_tokens, forced_new_tokens,
-                                          eos_token_id, box, side, after_prefill)
+                                          eos_token_id, box, side, after_prefill, draft)
             main.wait_stream(hi)
             for tns in list(out["pred_masks"]) + [out["pred_contact_3d"]]:
                 if tns is not None:
@@ -923,13 +1020,13 @@ class InteractVLMForCausalLM:
             return out
         return self._evaluate_tail(images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                                    lift2d_dict_path, contact_type, max_new_tokens, forced_new_tokens, eos_token_id,
-                                   box, side, after_prefill)
+                                   box, side, after_prefill, draft)
 
     def _evaluate_tail(self, images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                        lift2d_dict_path, contact_type, max_new_tokens, forced_new_tokens, eos_token_id,
-                       box, side, after_prefill):
+                       box, side, after_prefill, draft=None):
         output_ids, hidden = self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, forced_new_tokens,
-                                           after_prefill=after_prefill)
+                                           after_prefill=after_prefill, draft=draft)
         rows = self._seg_rows(output_ids[0], extra_false_col=False)
         image_embeddings = box["emb"]
         if side is not None:

@@ -1224,6 +1224,39 @@ def llama_decode_attn_batch(qkv, kcache, vcache, H, D, pos_dev, theta, scale, ta
     return out
 
 
+def llama_verify_attn(qkv, kcache, vcache, H, D, pos_dev, theta, scale, table=None, out=None):
+    """Verify pass of speculative decoding, one sequence: qkv fp32 [k, 3*H*D] (k <= 16 new tokens at positions pos_dev[0] ..
+    pos_dev[0] + k - 1), kcache / vcache bf16 | fp16 [Tmax, H, D] -> o fp32 [k, H*D]; RoPE + append of the k rows + causal
+    attention in one launch.  Rows whose position reaches Tmax are not appended; their output rows are zero."""
+    lib = _lib.load()
+    k = qkv.shape[0]
+    assert qkv.dtype == F32 and qkv.is_contiguous() and qkv.shape[1] == 3 * H * D and 1 <= k <= 16
+    assert kcache.is_contiguous() and vcache.is_contiguous() and kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
+    assert kcache.shape == vcache.shape and tuple(kcache.shape[1:]) == (H, D)
+    assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() >= 1
+    if table is not None:  # (the kernel reads the cos / sin rows of every position it appends)
+        assert table[0].shape[0] >= kcache.shape[0] and table[0].shape[1] == D // 2
+    if out is None:
+        out = torch.empty(k, H * D, dtype=F32, device=qkv.device)
+    fn = lib.ivlm_llama_verify_attn_f16 if kcache.dtype == F16 else lib.ivlm_llama_verify_attn
+    check(fn(qkv.data_ptr(), k, kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(), H, D, pos_dev.data_ptr(),
+             float(theta), float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()), "llama_verify_attn")
+    return out
+
+
+def spec_accept(amax, fed, n_draft, n_acc, tok, pos):
+    """Accept step of a verify pass (all int32 on the device): amax [k] argmax ids of the verified rows, fed [k] the ids fed
+    (fed[0] = last emitted token, fed[1 .. n_draft[0]] = the draft) -> n_acc[0] = accepted draft ids, tok[0] = the next token
+    (amax[n_acc]), pos[0] += n_acc + 1."""
+    lib = _lib.load()
+    k = amax.numel()
+    for t in (amax, fed, n_draft, n_acc, tok, pos):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    assert fed.numel() == k
+    check(lib.ivlm_spec_accept(amax.data_ptr(), fed.data_ptr(), n_draft.data_ptr(), k, n_acc.data_ptr(), tok.data_ptr(), pos.data_ptr(),
+                               _stream()), "spec_accept")
+
+
 def llama_attn_oproj(qkv, kcache, vcache, wo, x, H, D, pos_dev, step_dev, counter, status, theta, scale, table, scratch):
     """One launch: single-token attention of every head + o_proj GEMV + residual -> x_out fp32 [1, H*D] (qkv, x fp32)."""
     lib = _lib.load()
