@@ -232,8 +232,7 @@ class Llama:
         for L in self.layers:
             if self.decode_packed:
                 for n in _LayerW.MATS:
-                    if n + "_p" not in L:
-                        L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
+                    self._planes(L, n)
             if self.precision == "f16":
                 self._f16w(L)
             else:  # bf16 / parity prefill reads the bf16 matrices (rebuilt from the planes if the default mode had released them)
@@ -536,6 +535,17 @@ class Llama:
         """the only way a captured decode step leaves the cache: called where a buffer it may have baked in is freed or replaced"""
         self._graphs = {k: st for k, st in self._graphs.items() if not pred(k)}
 
+    def fused_wait_expired(self, st):
+        """after the replays of decode_graph state st: did a bounded device-side wait of the fused attention + o_proj launch expire
+        (its blocks were not co-resident, e.g. a third stream holding the CUs)?  Then the fused steps are dropped and the two-launch
+        path is used for good: the caller redoes the generation."""
+        fz = st.get("fused")
+        if fz is None or int(fz["status"].item()) == 0:
+            return False
+        self.fuse_attn_oproj = False
+        self._drop_graphs(lambda k: k.fused)
+        return True
+
     def _capture_decode(self, key, st, body, caches, counters, rows=1):
         """capture body (one decode step) into st["graph"] and cache st under key.  The warm-up run writes KV rows 0 .. rows-1 of
         every cache plane and advances the counters (positions, fused-launch counters): both are put back."""
@@ -547,7 +557,8 @@ class Llama:
             t[..., :rows, :, :].copy_(sv)
         self._graphs[key] = st
 
-    def decode_graph(self):
+    def decode_graph(self, pos=None):
+        """the captured batch-1 step; pos: a generation starts at this position (resets the position and the fused-launch counters)"""
         key = self._graph_key(1, batched=False)
         st = self._graphs.get(key)
         if st is None:
@@ -573,6 +584,12 @@ class Llama:
             caches = [self.kcache, self.vcache] + ([self.kcache_lo, self.vcache_lo] if self.precision == "parity" else [])
             counters = [st["pos"], st["pos64"]] + ([fz["step"], fz["counters"]] if fz is not None else [])
             self._capture_decode(key, st, body, caches, counters)
+        if pos is not None:
+            st["pos"].fill_(pos)
+            st["pos64"].fill_(pos)
+            if "fused" in st:
+                for k in ("step", "counters", "status"):
+                    st["fused"][k].zero_()
         return st
 
     # ---- B sequences per decode step (configs[2]: 8 images per GPU) ---------------------------------------------------
@@ -598,28 +615,36 @@ class Llama:
         H, hd = c.heads, c.hidden // c.heads
         if x.shape[0] > 16:
             raise ops.IvlmError("decode_step_batch: at most 16 sequences per step (weight-streaming kernels)")
-        lin = self._rows_linear(self.decode_packed and self.decode_packed_batch and x.shape[0] > 1)
+        return self._rows_step(x, self.decode_packed and self.decode_packed_batch and x.shape[0] > 1, lambda qkv, li: (
+            ops.llama_decode_attn_batch(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope,
+                                        lo=(lo[0][li], lo[1][li]) if lo is not None else None)))
+
+    @staticmethod
+    def _planes(L, n):
+        """the lossless 12-bit decode planes of matrix n of layer L (ops.PackedBf12), made on first use; None where the fragment
+        layout does not take the matrix's shape"""
+        if n + "_p" not in L:
+            L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
+        return L[n + "_p"]
+
+    def _rows_step(self, x, packed, attn):
+        """the layers of the multi-row steps (decode_step_batch, verify_step): x fp32 [rows, hidden] -> final-norm hidden fp32;
+        attn(qkv, li) -> the attention rows of layer li.  packed: the planes of the batch-1 step where the fragment layout takes the
+        matrix (the weights streamed once for all rows), bf16 otherwise"""
+        c = self.cfg
+
+        def lin(x_, L, n, **kw):
+            wp = self._planes(L, n) if packed else None
+            if wp is not None and wp.frag:
+                return ops.linear_bf12(x_, wp, **kw)
+            return ops.linear(x_, L[n], out_f32=True, **kw)
+
         for li, L in enumerate(self.layers):
             qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
-            a = ops.llama_decode_attn_batch(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope,
-                                            lo=(lo[0][li], lo[1][li]) if lo is not None else None)
-            x = lin(a, L, "o", residual=x)
+            x = lin(attn(qkv, li), L, "o", residual=x)
             h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
             x = lin(h, L, "down", residual=x)
         return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-
-    @staticmethod
-    def _rows_linear(packed):
-        """the linears of the multi-row steps (decode_step_batch, verify_step): the packed planes of the batch-1 step where the
-        fragment layout takes the matrix (the weights streamed once for all rows), bf16 otherwise"""
-        def lin(x_, L, n, **kw):
-            if packed:
-                if n + "_p" not in L:
-                    L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
-                if L[n + "_p"] is not None and L[n + "_p"].frag:
-                    return ops.linear_bf12(x_, L[n + "_p"], **kw)
-            return ops.linear(x_, L[n], out_f32=True, **kw)
-        return lin
 
     # ---- speculative greedy decoding: k <= 16 new tokens of THIS instance's sequence in one pass over the weights -----------------
     # The rows [t0, d1 .. d_{k-1}] (last emitted token + a draft) sit at positions pos .. pos+k-1 of the single-sequence cache; one
@@ -642,14 +667,8 @@ class Llama:
         if not self.verify_supported():
             raise ops.IvlmError(f"verify_step: not in precision {self.precision!r} / fp8 (no multi-token attention on hi + lo planes)")
         kc, vc = self._caches()
-        lin = self._rows_linear(self.decode_packed and self.decode_packed_batch)
-        for li, L in enumerate(self.layers):
-            qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
-            a = ops.llama_verify_attn(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope)
-            x = lin(a, L, "o", residual=x)
-            h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
-            x = lin(h, L, "down", residual=x)
-        return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+        return self._rows_step(x, self.decode_packed and self.decode_packed_batch, lambda qkv, li: (
+            ops.llama_verify_attn(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope)))
 
     def verify_pass(self, st):
         """embed st["ids"] -> verify_step -> lm_head -> argmax -> accept (st: the static buffers of verify_graph)"""
@@ -675,8 +694,9 @@ class Llama:
             self._capture_decode(key, st, lambda: self.verify_pass(st), caches, [st["pos"], st["n_acc"], st["tok"]], rows=kb)
         return st
 
-    def decode_graph_batch(self, B):
-        """One batched decode step (embed -> layers -> norm -> lm_head -> argmax, positions += 1) as a HIP graph."""
+    def decode_graph_batch(self, B, pos=None):
+        """One batched decode step (embed -> layers -> norm -> lm_head -> argmax, positions += 1) as a HIP graph; pos (int32 [B] on
+        the device): a generation starts at these positions"""
         kc, vc = self.batch_cache(B)
         lo = self.batch_cache_lo(B) if self.precision == "parity" else None
         key = self._graph_key(B, batched=True)
@@ -691,6 +711,8 @@ class Llama:
                 st["nxt"] = ops.argmax(self.logits(h), bump=st["pos"])  # (+ positions += 1 in the same launch)
 
             self._capture_decode(key, st, body, [kc, vc] + list(lo or ()), [st["pos"]])
+        if pos is not None:
+            st["pos"].copy_(pos)
         return st
 
     def _attn_scratch(self):
@@ -722,10 +744,7 @@ class Llama:
         kc_, vc_ = self._caches()
         if self.decode_packed and fz is None:
             def lin(x_, L, n, **kw):  # (packed where the fragment layout takes the matrix, bf16 otherwise)
-                if n + "_p" not in L:
-                    N_, K_ = L[n].shape
-                    L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(N_, K_) else None
-                wp = L[n + "_p"]
+                wp = self._planes(L, n)
                 return ops.linear_bf12(x_, wp, **kw) if wp is not None else ops.linear(x_, L[n], out_f32=True, **kw)
 
             # attention as 4 key ranges per head whose (o, max, sum) partials the o_proj merges in its prologue (128 blocks instead of
@@ -735,11 +754,10 @@ class Llama:
                 self._parts = torch.zeros(H * 4 * (hd + 4), dtype=F32, device=self.norm.device)
             for li, L in enumerate(self.layers):
                 qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
-                if "o_p" not in L:
-                    L["o_p"] = ops.PackedBf12(L["o"]) if ops.PackedBf12.takes(*L["o"].shape) else None
-                if split and L["o_p"] is not None:
+                wo = self._planes(L, "o")
+                if split and wo is not None:
                     ops.llama_decode_attn_parts(qkv, kc_[li], vc_[li], H, hd, pos, c.theta, hd ** -0.5, self._parts, table=self.rope)
-                    x = ops.linear_bf12(None, L["o_p"], residual=x, parts=(self._parts, hd))
+                    x = ops.linear_bf12(None, wo, residual=x, parts=(self._parts, hd))
                 else:
                     a = ops.llama_decode_attn(qkv, kc_[li], vc_[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope,
                                               lo=self._lo(li), scratch=self._attn_scratch())

@@ -19,7 +19,7 @@ from typing import List, Optional
 
 import torch
 
-from . import graphs, ops
+from . import decoding, graphs, ops
 from .components import HumanContact3DPredictor, ObjectMeshContact3DPredictor, ObjectPCAfford3DPredictor
 from .constants import IGNORE_LABEL, IMAGE_TOKEN_INDEX
 from .heads import SamFusionHead, UncertaintyHead
@@ -498,13 +498,6 @@ class InteractVLMForCausalLM:
             result["pred_object_3d_afford"] = self.object_3d_afford_predictor(pred_masks, ds_name_list, mask_paths_list)
         return result
 
-    def _id_ring(self, n):
-        """pinned host int32 array of >= n generated ids (written by asynchronous device-to-host copies, read one step late)"""
-        r = getattr(self, "_ring", None)
-        if r is None or r.numel() < n:
-            r = self._ring = torch.empty(max(n, 64), dtype=torch.int32).pin_memory()
-        return r
-
     @torch.no_grad()
     def generate(self, images_clip, input_ids, max_new_tokens=32, eos_token_id=2, forced_new_tokens=None,
                  after_prefill=None, draft=None):
@@ -512,7 +505,7 @@ class InteractVLMForCausalLM:
         forced_new_tokens (extension for weight-free benchmarking): feed these ids instead of the argmax (the
         argmax/lm_head work is still done every step), like the reference's inference_type='forward'.
         draft (opt-in, free-running search only): a ``speculative.Drafter`` - or any object with ``propose(ids, k)`` (and optionally
-        ``observe(n_proposed, n_accepted)``) - whose proposals are verified k rows per pass over the weights (``_generate_speculative``):
+        ``observe(n_proposed, n_accepted)``) - whose proposals are verified k rows per pass over the weights (``decoding.speculative``):
         the same ids as without it.  Ignored with forced_new_tokens; in the "parity" modes and with fp8 the plain loop runs."""
         feats = self.encode_images(images_clip)[0]
         ids = input_ids[0]
@@ -524,200 +517,49 @@ class InteractVLMForCausalLM:
         n_max = min(n_max, self.llm.max_len - T0)
         if n_max <= 0:
             raise ops.IvlmError(f"prompt of {T0} positions does not fit the KV cache (max_len={self.llm.max_len})")
-        if forced_new_tokens is not None:
-            forced_new_tokens = list(forced_new_tokens)[:n_max]
         hidden_all = torch.empty(T0 + n_max, self.config.llama.hidden, dtype=F32, device=self.device)
         h = self.llm.forward(x, 0)
         hidden_all[:T0].copy_(h)
         if after_prefill is not None:
             after_prefill()  # evaluate(): the SAM encoder is enqueued here, between the prefill and the decode loop
-        if draft is not None and forced_new_tokens is None and self.llm.verify_supported():
-            out = self._generate_speculative(ids, h[T0 - 1: T0], T0, n_max, eos_token_id, hidden_all, draft)
-            if out is not None:
-                return out
-            return self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, None, None, draft)
-        self.last_spec = None
-        new_ids = []
         last = h[T0 - 1: T0]
-        pos = T0
-        forced_dev = None
+        if draft is not None and forced_new_tokens is None and self.llm.verify_supported():
+            out = self._generate_speculative(ids, last, T0, n_max, eos_token_id, hidden_all, draft)
+        else:
+            out = self._generate_greedy(ids, last, T0, n_max, eos_token_id, hidden_all, forced_new_tokens)
+        if out is None:  # a fused attention + o_proj wait expired (Llama.fused_wait_expired): redo it on the two-launch path
+            return self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, forced_new_tokens, None, draft)
+        return out
+
+    def _generate_greedy(self, ids, last, T0, n_max, eos_token_id, hidden_all, forced_new_tokens=None):
+        """generate() after the prefill (last = the prompt's last hidden row, hidden_all[:T0] its rows): decoding.greedy"""
+        forced = None
         if forced_new_tokens is not None:
-            forced_dev = torch.tensor([int(t) for t in forced_new_tokens], dtype=torch.int32, device=self.device)
-        self.last_argmax = []
-        use_graph = graphs.enabled(self.graph_decode)
-        if use_graph:
-            # one decode step = one replay of a captured HIP graph (embed -> 32 layers -> norm -> lm_head -> argmax, position
-            # read from device memory); the host issues 3 launches per token instead of ~165
-            dg = self.llm.decode_graph()
-            dg["pos"].fill_(T0)
-            dg["pos64"].fill_(T0)
-            fz = dg.get("fused")
-            if fz is not None:
-                fz["step"].zero_()
-                fz["counters"].zero_()
-                fz["status"].zero_()
-            nxt = ops.argmax(self.llm.logits(last))
-            if forced_new_tokens is not None:
-                for step in range(n_max):
-                    self.last_argmax.append(nxt)
-                    new_ids.append(int(forced_new_tokens[step]))
-                    if new_ids[-1] == eos_token_id or step == n_max - 1:
-                        break
-                    dg["tok"].copy_(forced_dev[step: step + 1])
-                    dg["graph"].replay()
-                    hidden_all[pos: pos + 1].copy_(dg["hidden"])
-                    nxt = dg["nxt"].clone()
-                    pos += 1
-            else:
-                # Free-running greedy search WITHOUT a host round trip per token (reference loop: InteractVLM.py:524-531,
-                # stop on EOS or max_new_tokens).  The argmax of step s stays on the device and is the token of step s + 1
-                # (`tok.copy_(nxt)`: device to device); every id is also copied - asynchronously - into a pinned host array.  The host
-                # keeps ONE replay queued ahead of the one it is waiting for: before it enqueues step s + 1 it waits for the event of
-                # step s - 1 and reads id s - 1 from the pinned array - so the GPU never idles between replays, and when id k turns
-                # out to be EOS exactly one speculative step (the one that consumed EOS) has been enqueued: its hidden row and KV
-                # row lie beyond the returned length and are dropped.
-                ring = self._id_ring(n_max)
-                evs = [torch.cuda.Event() for _ in range(n_max)]
-                cur = torch.cuda.current_stream(self.device)
-                ids_dev = torch.empty(n_max, dtype=torch.int32, device=self.device)
-                ids_dev[0:1].copy_(nxt)
-                ring[0:1].copy_(nxt, non_blocking=True)
-                evs[0].record(cur)
-                n_tok, enq = None, 0  # n_tok: number of new ids once known; enq: decode steps enqueued
-                for step in range(n_max):
-                    # (a) id `step - 1` (one step late): stop at EOS
-                    if step >= 1:
-                        evs[step - 1].synchronize()
-                        if int(ring[step - 1]) == eos_token_id:
-                            n_tok = step
-                            break
-                    if step == n_max - 1:
-                        break
-                    # (b) enqueue the decode step that consumes id `step` and produces id `step + 1`
-                    dg["tok"].copy_(ids_dev[step: step + 1])
-                    dg["graph"].replay()
-                    hidden_all[pos + enq: pos + enq + 1].copy_(dg["hidden"])
-                    ids_dev[step + 1: step + 2].copy_(dg["nxt"])
-                    ring[step + 1: step + 2].copy_(dg["nxt"], non_blocking=True)
-                    evs[step + 1].record(cur)
-                    enq += 1
-                if n_tok is None:  # no EOS among ids 0 .. n_max - 2: the last id decides nothing (max_new_tokens reached)
-                    evs[n_max - 1].synchronize()
-                    n_tok = n_max
-                new_ids = [int(t) for t in ring[:n_tok].tolist()]
-                self.last_argmax = [ids_dev[i: i + 1] for i in range(n_tok)]
-                pos += n_tok - 1  # decode steps whose hidden rows count (a speculative step past EOS is dropped)
-            if fz is not None and int(fz["status"].item()) != 0:
-                # a bounded device-side wait of the fused attention + o_proj launch expired (its blocks were not co-resident,
-                # e.g. a third stream holding the CUs): drop to the two-launch path for good and redo this generation
-                self.llm.fuse_attn_oproj = False
-                self.llm._drop_graphs(lambda k: k.fused)
-                return self.generate(images_clip, input_ids, max_new_tokens, eos_token_id, forced_new_tokens, None)
-            out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
-            return out_ids, hidden_all[:pos]
-        for step in range(n_max):
-            nxt = ops.argmax(self.llm.logits(last))  # int32 [1] on device
-            self.last_argmax.append(nxt)
-            if forced_new_tokens is not None:
-                tok = int(forced_new_tokens[step])
-                tok_t = forced_dev[step: step + 1]
-            else:
-                tok = int(nxt.item())
-                tok_t = nxt
-            new_ids.append(tok)
-            if tok == eos_token_id or step == n_max - 1:
-                break
-            e = self.llm.embed_ids(tok_t)
-            last = self.llm.forward(e, pos)
-            hidden_all[pos: pos + 1].copy_(last)
-            pos += 1
-        out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
-        return out_ids, hidden_all[:pos]
+            host = [int(t) for t in list(forced_new_tokens)[:n_max]]
+            forced = ([host], torch.tensor(host, dtype=torch.int32, device=self.device)[:, None])
+        step = self._single_step(hidden_all, T0)
+        self.last_spec = None
+        (new_ids,), self.last_argmax = decoding.greedy(step, ops.argmax(self.llm.logits(last)), [n_max], eos_token_id, forced)
+        return self._generated(ids, step, T0, new_ids)
 
     def _generate_speculative(self, ids, last, T0, n_max, eos_token_id, hidden_all, draft):
-        """The free-running greedy loop with verify passes (generate(draft=...)).  Per round the host knows every id so far and asks
-        the drafter for up to 15 ids to follow; with a proposal d1 .. dm the rows [t, d1 .. dm] (t = last id, padded to a bucket of
-        VERIFY_BUCKETS) run through ONE Llama.verify_step at positions pos .. pos+m, the accept step finds n_acc (leading d_j equal to
-        the argmax of row j-1), and d1 .. d_n_acc + argmax(row n_acc) are emitted, hidden rows 0 .. n_acc kept; the host reads n_acc and
-        the next id once per pass.  Without a proposal the plain decode step runs (its pos / tok words copied from the accept step's).
-        Stops exactly at EOS or n_max (rows past the stop are dropped, as the plain loop drops its one speculative step); no row is
-        written past max_len (n_max already keeps every fed position below it).  -> (output_ids, hidden) or None when a fused
-        attention + o_proj launch timed out (the caller redoes the generation on the two-launch path)."""
-        llm, dev = self.llm, self.device
-        use_graph = graphs.enabled(self.graph_decode)
-        kmax = max(llm.VERIFY_BUCKETS)
-        nxt = ops.argmax(llm.logits(last))
-        new_ids = [int(nxt.item())]
-        self.last_argmax = [nxt]
-        stats = self.last_spec = dict(passes=0, plain_steps=0, proposed=0, accepted=0, pattern=[])
-        pos = T0  # position at which new_ids[-1] is fed
-        dg = fz = None
-        if use_graph:
-            dg = llm.decode_graph()
-            dg["pos"].fill_(T0)
-            dg["pos64"].fill_(T0)
-            fz = dg.get("fused")
-            if fz is not None:
-                fz["step"].zero_()
-                fz["counters"].zero_()
-                fz["status"].zero_()
-        observe = getattr(draft, "observe", None)
-        while new_ids[-1] != eos_token_id and len(new_ids) < n_max:
-            rem = n_max - len(new_ids)  # ids still to emit; the fed rows stay below T0 + n_max - 1 <= max_len - 1
-            prop = [int(t) for t in draft.propose(list(new_ids), kmax)][: min(kmax - 1, rem - 1)]
-            m = len(prop)
-            if m == 0:  # the plain step (graph replay or eager), then one read-back
-                stats["plain_steps"] += 1
-                if use_graph:
-                    dg["tok"].fill_(new_ids[-1])
-                    dg["graph"].replay()
-                    hidden_all[pos: pos + 1].copy_(dg["hidden"])
-                    nxt = dg["nxt"].clone()
-                else:
-                    h = llm.forward(llm.embed_ids(torch.tensor([new_ids[-1]], dtype=torch.int32, device=dev)), pos)
-                    hidden_all[pos: pos + 1].copy_(h)
-                    nxt = ops.argmax(llm.logits(h))
-                self.last_argmax.append(nxt)
-                new_ids.append(int(nxt.item()))
-                pos += 1
-                continue
-            kb = next(b for b in llm.VERIFY_BUCKETS if b >= m + 1)
-            fed = torch.tensor([new_ids[-1]] + prop + [new_ids[-1]] * (kb - 1 - m), dtype=torch.int32)
-            st = llm.verify_graph(kb) if use_graph else llm.verify_state(kb)
-            st["pos"].fill_(pos)
-            st["ids"].copy_(fed)
-            st["nd"].fill_(m)
-            if use_graph:
-                st["graph"].replay()
-            else:
-                llm.verify_pass(st)
-            n_acc, tok = torch.cat([st["n_acc"], st["tok"]]).tolist()  # (the one read-back of the pass)
-            stats["passes"] += 1
-            stats["proposed"] += m
-            stats["accepted"] += n_acc
-            stats["pattern"].append((m, n_acc))
-            if observe is not None:
-                observe(m, n_acc)
-            amax = st["amax"][: n_acc + 1].clone()
-            emitted = prop[:n_acc] + [tok]
-            keep = 0
-            for e in emitted:  # stop exactly at EOS / n_max, even inside an accepted draft
-                new_ids.append(e)
-                keep += 1
-                if e == eos_token_id or len(new_ids) >= n_max:
-                    break
-            hidden_all[pos: pos + keep].copy_(st["hidden"][:keep])
-            self.last_argmax.extend(amax[j: j + 1] for j in range(keep))
-            pos += keep
-            if use_graph:  # the plain step continues from the accept step's position and token
-                dg["pos"].copy_(st["pos"])
-                dg["tok"].copy_(st["tok"])
-        if fz is not None and int(fz["status"].item()) != 0:
-            llm.fuse_attn_oproj = False
-            llm._drop_graphs(lambda k: k.fused)
+        """generate(draft=...) after the prefill: decoding.speculative"""
+        step = self._single_step(hidden_all, T0)
+        new_ids, self.last_argmax, self.last_spec = decoding.speculative(step, ops.argmax(self.llm.logits(last)), n_max,
+                                                                         eos_token_id, draft)
+        return self._generated(ids, step, T0, new_ids)
+
+    def _single_step(self, hidden_all, T0):
+        # graph: one decode step = one replay of a captured HIP graph (embed -> 32 layers -> norm -> lm_head -> argmax, position
+        # read from device memory); the host issues 3 launches per token instead of ~165
+        return (decoding.SingleGraph if graphs.enabled(self.graph_decode) else decoding.SingleEager)(self.llm, hidden_all, T0)
+
+    def _generated(self, ids, step, T0, new_ids):
+        """-> (output_ids, hidden rows that count), or None when the generation has to be redone (Llama.fused_wait_expired)"""
+        if step.st is not None and self.llm.fused_wait_expired(step.st):
             return None
         out_ids = torch.cat([ids.cpu(), torch.tensor(new_ids, dtype=ids.dtype)])[None]
-        return out_ids, hidden_all[: T0 + len(new_ids) - 1]
+        return out_ids, step.hidden[: T0 + len(new_ids) - 1]
 
     @torch.no_grad()
     # ---- B images per call (BASELINE.json configs[2]: 8 images per GPU) -----------------------------------------------
@@ -758,84 +600,16 @@ class InteractVLMForCausalLM:
         for b, h in enumerate(hs):
             hidden_all[b, : T0[b]].copy_(h)
             last[b].copy_(h[T0[b] - 1])
-        forced_dev = None
+        forced = None
         if forced_new_tokens is not None:
             pad = [list(map(int, f[:n])) + [eos_token_id] * (n_max - n) for f, n in zip(forced_new_tokens, n_seq)]
-            forced_dev = torch.tensor(pad, dtype=torch.int32, device=dev).t().contiguous()  # [n_max, B]
-        use_graph = graphs.enabled(self.graph_decode)
-        pos_t = torch.tensor(T0, dtype=torch.int32, device=dev)
-        if use_graph:
-            dg = self.llm.decode_graph_batch(B)
-            dg["pos"].copy_(pos_t)
-        rows = torch.arange(B, device=dev)
-        nxt = ops.argmax(self.llm.logits(last))
-        new_ids = [[] for _ in range(B)]
-        done = [False] * B
-
-        def absorb(toks):  # the ids of one step, in order: append to the sequences still running, mark those that stop
-            for b in range(B):
-                if not done[b]:
-                    new_ids[b].append(int(toks[b]))
-                    if toks[b] == eos_token_id or len(new_ids[b]) >= n_seq[b]:
-                        done[b] = True
-
-        if use_graph and forced_dev is None:
-            # free-running: no host round trip per token (see generate): ids stay on the device, a pinned host copy is read one
-            # step late, one speculative step at most is enqueued after the last sequence has stopped
-            ring = self._id_ring(n_max * B)[: n_max * B].view(n_max, B)
-            evs = [torch.cuda.Event() for _ in range(n_max)]
-            cur = torch.cuda.current_stream(dev)
-            ids_dev = torch.empty(n_max, B, dtype=torch.int32, device=dev)
-            ids_dev[0].copy_(nxt)
-            ring[0].copy_(nxt, non_blocking=True)
-            evs[0].record(cur)
-            absorbed = 0
-            for step in range(n_max):
-                if step >= 1:
-                    evs[step - 1].synchronize()
-                    absorb(ring[step - 1].tolist())
-                    absorbed = step
-                    if all(done):
-                        break
-                if step == n_max - 1:
-                    break
-                dg["tok"].copy_(ids_dev[step])
-                idx = dg["pos"].to(torch.int64)  # positions BEFORE the step's += 1
-                dg["graph"].replay()
-                hidden_all[rows, idx] = dg["hidden"]
-                ids_dev[step + 1].copy_(dg["nxt"])
-                ring[step + 1].copy_(dg["nxt"], non_blocking=True)
-                evs[step + 1].record(cur)
-            if not all(done):
-                evs[n_max - 1].synchronize()
-                for st_ in range(absorbed, n_max):
-                    absorb(ring[st_].tolist())
-            n_steps = 0  # (the stepping loop below is skipped)
+            forced = (pad, torch.tensor(pad, dtype=torch.int32, device=dev).t().contiguous())  # [n_max, B]
+        pos = torch.tensor(T0, dtype=torch.int32, device=dev)
+        if graphs.enabled(self.graph_decode):
+            step = decoding.BatchGraph(self.llm, hidden_all, pos)
         else:
-            n_steps = n_max
-        for step in range(n_steps):
-            if forced_dev is not None:
-                tok_t = forced_dev[step]
-                toks = [pad[b][step] for b in range(B)]
-            else:
-                tok_t = nxt
-                toks = nxt.tolist()  # (eager launches: the host is the bottleneck anyway)
-            absorb(toks)
-            if all(done):
-                break
-            # (finished sequences keep stepping - their rows are ignored; a sequence whose position has reached the end of its
-            #  cache slab is skipped by the attention kernel: nothing is appended past Tmax)
-            if use_graph:
-                dg["tok"].copy_(tok_t)
-                idx = dg["pos"].to(torch.int64)  # positions BEFORE the step's += 1
-                dg["graph"].replay()
-                h, nxt = dg["hidden"], dg["nxt"].clone()
-            else:
-                h = self.llm.decode_step_batch(self.llm.embed_ids(tok_t.contiguous()), pos_t, kc, vc, lo)
-                idx = pos_t.to(torch.int64)
-                nxt = ops.argmax(self.llm.logits(h))
-                pos_t = pos_t + 1
-            hidden_all[rows, idx] = h
+            step = decoding.BatchEager(self.llm, hidden_all, pos, (kc, vc, lo))
+        new_ids, _ = decoding.greedy(step, ops.argmax(self.llm.logits(last)), n_seq, eos_token_id, forced)
         out = []
         for b in range(B):
             ids = input_ids_list[b].reshape(-1).cpu()
