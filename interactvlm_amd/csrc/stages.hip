@@ -220,9 +220,9 @@ extern "C" int ivlm_llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_laye
                          workspace_bytes, stream, 0);
 }
 
-// The default precision of the host model (interactvlm_amd/llava.py Llama._layer_f16): IEEE fp16 MFMA operands in one pass - the
-// qkv / o / gu / down pointers of layers16_host are fp16 copies of the bf16 weights (ivlm_bf16_to_f16: exact inside the fp16
-// range; ln1 / ln2 stay the bf16 norm weights), RMSNorm / q|k|v / SwiGLU outputs and the KV cache are fp16.  Needs T > 16.
+// The default precision of the host model (interactvlm_amd/llava.py Llama._prefill_layer, "f16"): IEEE fp16 MFMA operands in one
+// pass - the qkv / o / gu / down pointers of layers16_host are fp16 copies of the bf16 weights (ivlm_bf16_to_f16: exact inside the
+// fp16 range; ln1 / ln2 stay the bf16 norm weights), RMSNorm / q|k|v / SwiGLU outputs and the KV cache are fp16.  Needs T > 16.
 extern "C" int ivlm_llama_prefill_f16(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers16_host, const void* final_norm,
                                       void* kcache16, void* vcache16, const float* cos_tab, const float* sin_tab, const float* x_in,
                                       int T, int pos0, float* hidden_out, void* workspace, size_t workspace_bytes,

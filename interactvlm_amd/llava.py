@@ -354,21 +354,6 @@ class Llama:
                 L[n + "_hp"] = ops.panel_weight(h)  # (the row-major copy is not kept: _f16 rebuilds it for the C sequencers)
         return {n: L[n + "_hp"] for n in _LayerW.MATS}
 
-    def _layer_f16(self, L, x, T, pos0, kc, vc, a_out=None):
-        """one prefill layer on fp16 operands: x fp32 [T, hidden] -> fp32 [T, hidden]; kc / vc = this layer's fp16 cache planes"""
-        c = self.cfg
-        H, hd = c.heads, c.hidden // c.heads
-        W = self._f16w(L)
-        qkv = ops.linear(ops.rmsnorm(x, L["ln1"], c.eps, out_f16=True), W["qkv"], out_f16=True)
-        ops.rope_kv(qkv, H, hd, pos0, c.theta, kc, vc, table=self.rope)
-        q = qkv.view(T, 3, H, hd)[:, 0].permute(1, 0, 2).unsqueeze(0)
-        k = kc[: pos0 + T].permute(1, 0, 2).unsqueeze(0)
-        v = vc[: pos0 + T].permute(1, 0, 2).unsqueeze(0)
-        a = ops.attention(q, k, v, hd ** -0.5, causal=True, q_pos0=pos0).permute(0, 2, 1, 3).reshape(T, c.hidden)
-        x = ops.linear(a, W["o"], residual=x, out_f32=True)
-        h = ops.linear(ops.rmsnorm(x, L["ln2"], c.eps, out_f16=True), W["gu"], act="swiglu", out_f16=True)
-        return ops.linear(h, W["down"], residual=x, out_f32=True)
-
     def batch_cache_lo(self, B):
         bc = getattr(self, "_bcache_lo", None)
         if bc is None or bc[0].shape[1] < B:
@@ -377,33 +362,15 @@ class Llama:
             self._drop_graphs(lambda k: k.batched and k.precision == "parity")
         return bc[0][:, :B], bc[1][:, :B]
 
-    def _layer_parity(self, L, x, T, pos0, kc, vc, kcl, vcl):
-        """one prefill layer on fp32-activation arithmetic: x fp32 [T, hidden] -> fp32 [T, hidden]; kc.. = this layer's cache planes"""
-        c = self.cfg
-        H, hd = c.heads, c.hidden // c.heads
-        qkv = ops.linear(ops.rmsnorm(x, L["ln1"], c.eps, out_split=True), L["qkv"], a_split=True, out_split=True)  # [T, 6*hidden]
-        ops.rope_kv_split(qkv, H, hd, pos0, (kc, kcl, vc, vcl), self.rope)
-        q6 = qkv.view(T, 2, 3, H, hd)
-        qh, ql = (q6[:, i, 0].permute(1, 0, 2).unsqueeze(0) for i in range(2))
-        kv = [t[: pos0 + T].permute(1, 0, 2).unsqueeze(0) for t in (kc, kcl, vc, vcl)]
-        a = ops.attention_split(qh, ql, kv[0], kv[1], kv[2], kv[3], hd ** -0.5, causal=True, q_pos0=pos0)  # [T, 2*hidden]
-        x = ops.linear(a, L["o"], residual=x, out_f32=True, a_split=True)
-        h = ops.linear(ops.rmsnorm(x, L["ln2"], c.eps, out_split=True), L["gu"], act="swiglu", a_split=True, out_split=True)
-        return ops.linear(h, L["down"], residual=x, out_f32=True, a_split=True)
-
     def embed_ids(self, ids_i32, out=None):
         """embed_tokens gather: ids int32 [n] -> fp32 [n, hidden] (the start of the fp32 residual stream)."""
         return ops.gather_rows(self.embed, ids_i32, out=out, out_kind="f32")
 
     def forward(self, x, pos0, cache=None):
         """x fp32 [T, hidden] input embeddings at positions pos0..pos0+T-1 -> final-norm hidden fp32 [T, hidden];
-        appends to the KV cache (prefill: T = prompt, decode: T = 1).  cache = (k, v) [layers, Tmax, H, hd] views of
-        another sequence's slab (batched generation); default: this instance's single-sequence cache.
-        Precision: the residual stream is fp32 (GEMM residual epilogues write fp32, RMSNorm reads it); the MFMA operands
-        (normed rows, attention output, SwiGLU product) are bf16."""
-        c = self.cfg
+        appends to the KV cache (prefill: T = prompt, decode: T = 1).  cache = (k, v[, k_lo, v_lo]) [layers, Tmax, H, hd] views
+        of another sequence's slab (batched generation); default: this instance's single-sequence cache."""
         T = x.shape[0]
-        H, hd = c.heads, c.hidden // c.heads
         assert pos0 + T <= self.max_len and x.dtype == F32
         if T == 1 and cache is None:
             return self._decode_step(x, pos0)
@@ -411,111 +378,85 @@ class Llama:
             # (the fp16 / split tile GEMMs need M > 16: a short chunk goes token by token through the fp32-activation decode
             #  kernels, which are exact on the bf16 weights)
             return torch.cat([self._decode_step(x[t: t + 1], pos0 + t) for t in range(T)], 0)
-        kc, vc = cache[:2] if cache is not None else self._caches()
-        if self.precision == "f16":
-            for li, L in enumerate(self.layers):
-                x = self._layer_f16(L, x, T, pos0, kc[li], vc[li])
-            return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-        if self.precision == "parity":
-            kcl, vcl = cache[2:] if cache is not None else (self.kcache_lo, self.vcache_lo)
-            for li, L in enumerate(self.layers):
-                x = self._layer_parity(L, x, T, pos0, kc[li], vc[li], kcl[li], vcl[li])
-            return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-        fp8 = self.fp8 and T > 16 and not self._calibrating
-        for li, L in enumerate(self.layers):
-            cal = L.get("amax") if self._calibrating else None
-            sc = L["s"] if fp8 else None
-            if fp8:
-                qkv = ops.linear_fp8(ops.rmsnorm(x, L["ln1"], c.eps, fp8_scale=sc["y1"]), L["qkv_q"], sc["y1"], L["qkv_s"])
-            else:
-                y = ops.rmsnorm(x, L["ln1"], c.eps)
-                qkv = ops.linear(y, L["qkv"])  # [T, 3*hidden] == [T, 3, H, hd]
-            ops.rope_kv(qkv, H, hd, pos0, c.theta, kc[li], vc[li], table=self.rope)
-            q = qkv.view(T, 3, H, hd)[:, 0].permute(1, 0, 2).unsqueeze(0)  # [1,H,T,hd]
-            k = kc[li, : pos0 + T].permute(1, 0, 2).unsqueeze(0)
-            v = vc[li, : pos0 + T].permute(1, 0, 2).unsqueeze(0)
-            a = ops.attention(q, k, v, hd ** -0.5, causal=True, q_pos0=pos0).permute(0, 2, 1, 3).reshape(T, c.hidden)
-            if fp8:
-                x = ops.linear_fp8(ops.gather_rows(a, out_kind="fp8", scale=sc["a"]), L["o_q"], sc["a"], L["o_s"], residual=x,
-                                   out_kind="f32")
-                h8 = ops.linear_fp8(ops.rmsnorm(x, L["ln2"], c.eps, fp8_scale=sc["y2"]), L["gu_q"], sc["y2"], L["gu_s"],
-                                    act="swiglu", out_kind="fp8", scale_out=sc["h"])
-                x = ops.linear_fp8(h8, L["down_q"], sc["h"], L["down_s"], residual=x, out_kind="f32")
-                continue
-            x = ops.linear(a, L["o"], residual=x, out_f32=True)
-            y2 = ops.rmsnorm(x, L["ln2"], c.eps)
-            h = ops.linear(y2, L["gu"], act="swiglu")
-            if cal:
-                for k_, t_ in (("y1", y), ("a", a), ("y2", y2), ("h", h)):
-                    ops.amax(t_, cal[k_])
-            x = ops.linear(h, L["down"], residual=x, out_f32=True)
-        return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+        if cache is None:
+            cache = self._caches() + ((self.kcache_lo, self.vcache_lo) if self.precision == "parity" else ())
+        return self._prefill(x, [(0, T, pos0, cache)])[0]
 
     def forward_packed(self, xs, kc, vc, lo=None):
         """Prefill of B sequences in ONE pass over the weights: xs = [x_b fp32 [T_b, hidden]] (lengths may differ), kc / vc
-        [layers, B, Tmax, H, hd] cache slabs -> [final-norm hidden fp32 [T_b, hidden]].  The four projections of a layer run
-        on the packed rows (M = sum T_b: one efficient GEMM instead of B skinny ones, weights streamed once); RoPE + cache
-        append and the causal attention stay per sequence.  Row-wise identical arithmetic to ``forward``."""
+        [layers, B, Tmax, H, hd] cache slabs (lo = their (k_lo, v_lo) slabs in "parity") -> [final-norm hidden fp32 [T_b, hidden]].
+        Row-wise identical arithmetic to ``forward``: B = 1 is forward(xs[0], 0, cache=slab 0)."""
+        assert max(int(x.shape[0]) for x in xs) <= self.max_len
+        segs, r0 = [], 0
+        for b, x in enumerate(xs):
+            segs.append((r0, r0 + x.shape[0], 0, (kc[:, b], vc[:, b]) + ((lo[0][:, b], lo[1][:, b]) if lo is not None else ())))
+            r0 += x.shape[0]
+        return self._prefill(torch.cat(xs, 0) if len(xs) > 1 else xs[0], segs)  # (one sequence: its rows as they are, no copy)
+
+    def _prefill(self, x, segs):
+        """The prefill layers on the packed rows x fp32 [rows, hidden] of one or more sequences; segs = [(r0, r1, pos0, cache)]: a
+        sequence's rows, the position of its first row and its cache planes (k, v[, k_lo, v_lo]) [layers, Tmax, H, hd]
+        -> [final-norm hidden fp32 [r1 - r0, hidden]] per sequence.  The four projections of a layer run on all rows (M = sum of
+        the lengths: one efficient GEMM instead of B skinny ones, weights streamed once); RoPE + cache append and the causal
+        attention run per sequence.  The residual stream is fp32 (GEMM residual epilogues write fp32, RMSNorm reads it).
+        fp8 operands (enable_fp8) for one sequence of more than 16 rows only, never while calibrating."""
+        fp8 = self.fp8 and not self._calibrating and len(segs) == 1 and x.shape[0] > 16
+        for li in range(len(self.layers)):
+            x = self._prefill_layer(li, x, segs, fp8)
+        x = ops.rmsnorm(x, self.norm, self.cfg.eps, out_f32=True)
+        return [x[r0: r1] for r0, r1, _, _ in segs]
+
+    # the MFMA operands of a prefill layer per precision mode: the rmsnorm flags, the flags of the q|k|v and gate|up GEMMs (whose
+    # outputs are operands again) and those of the o and down GEMMs (fp32 residual out).  "default": bf16; "f16": IEEE fp16 (the
+    # _f16w copies of the weights); "parity": [hi | lo] bf16 rows (fp32 activations) on the bf16 weights
+    _PREFILL_FLAGS = {"default": ({}, {}, {}),
+                      "f16": (dict(out_f16=True), dict(out_f16=True), {}),
+                      "parity": (dict(out_split=True), dict(a_split=True, out_split=True), dict(a_split=True))}
+
+    def _prefill_layer(self, li, x, segs, fp8=False):
+        """prefill layer li on the packed rows x fp32 [rows, hidden] of segs (see _prefill) -> fp32 [rows, hidden]"""
+        c, L = self.cfg, self.layers[li]
+        if fp8:  # e4m3 operands with the calibrated per-tensor scales; attention stays bf16
+            sc = L["s"]
+            qkv = ops.linear_fp8(ops.rmsnorm(x, L["ln1"], c.eps, fp8_scale=sc["y1"]), L["qkv_q"], sc["y1"], L["qkv_s"])
+            a8 = ops.gather_rows(self._prefill_attn(qkv, li, segs), out_kind="fp8", scale=sc["a"])
+            x = ops.linear_fp8(a8, L["o_q"], sc["a"], L["o_s"], residual=x, out_kind="f32")
+            h8 = ops.linear_fp8(ops.rmsnorm(x, L["ln2"], c.eps, fp8_scale=sc["y2"]), L["gu_q"], sc["y2"], L["gu_s"], act="swiglu",
+                                out_kind="fp8", scale_out=sc["h"])
+            return ops.linear_fp8(h8, L["down_q"], sc["h"], L["down_s"], residual=x, out_kind="f32")
+        norm, lin_in, lin_out = self._PREFILL_FLAGS[self.precision]
+        W = self._f16w(L) if self.precision == "f16" else L
+        y = ops.rmsnorm(x, L["ln1"], c.eps, **norm)
+        a = self._prefill_attn(ops.linear(y, W["qkv"], **lin_in), li, segs)
+        x = ops.linear(a, W["o"], residual=x, out_f32=True, **lin_out)
+        y2 = ops.rmsnorm(x, L["ln2"], c.eps, **norm)
+        h = ops.linear(y2, W["gu"], act="swiglu", **lin_in)
+        if self._calibrating and self.precision == "default":  # the activation ranges of the fp8 operands (enable_fp8)
+            for k, t in (("y1", y), ("a", a), ("y2", y2), ("h", h)):
+                ops.amax(t, L["amax"][k])
+        return ops.linear(h, W["down"], residual=x, out_f32=True, **lin_out)
+
+    def _prefill_attn(self, qkv, li, segs):
+        """RoPE + cache append + causal attention of layer li, sequence by sequence: qkv [rows, 3*hidden] ("parity": [hi | lo]
+        rows [rows, 6*hidden]) -> the attention rows [rows, hidden] in qkv's dtype ("parity": [rows, 2*hidden] = [hi | lo])"""
         c = self.cfg
         H, hd = c.heads, c.hidden // c.heads
-        lens = [int(x.shape[0]) for x in xs]
-        assert max(lens) <= self.max_len
-        offs = [0]
-        for n in lens:
-            offs.append(offs[-1] + n)
-        x = torch.cat(xs, 0)
-        if self.precision == "f16":  # fp16 operands (see _layer_f16); kc / vc are fp16 views of the slabs
-            for li, L in enumerate(self.layers):
-                W = self._f16w(L)
-                qkv = ops.linear(ops.rmsnorm(x, L["ln1"], c.eps, out_f16=True), W["qkv"], out_f16=True)
-                a = torch.empty(offs[-1], c.hidden, dtype=torch.float16, device=x.device)
-                for b, T in enumerate(lens):
-                    qb = qkv[offs[b]: offs[b + 1]]
-                    ops.rope_kv(qb, H, hd, 0, c.theta, kc[li, b], vc[li, b], table=self.rope)
-                    q = qb.view(T, 3, H, hd)[:, 0].permute(1, 0, 2).unsqueeze(0)
-                    k = kc[li, b, :T].permute(1, 0, 2).unsqueeze(0)
-                    v = vc[li, b, :T].permute(1, 0, 2).unsqueeze(0)
-                    ops.attention(q, k, v, hd ** -0.5, causal=True, q_pos0=0,
-                                  out=a[offs[b]: offs[b + 1]].view(1, T, H, hd).permute(0, 2, 1, 3))
-                x = ops.linear(a, W["o"], residual=x, out_f32=True)
-                h = ops.linear(ops.rmsnorm(x, L["ln2"], c.eps, out_f16=True), W["gu"], act="swiglu", out_f16=True)
-                x = ops.linear(h, W["down"], residual=x, out_f32=True)
-            x = ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-            return [x[offs[b]: offs[b + 1]] for b in range(len(lens))]
-        if self.precision == "parity":  # fp32-activation arithmetic (see _layer_parity), lo = (kc_lo, vc_lo) slabs
-            kcl, vcl = lo
-            for li, L in enumerate(self.layers):
-                qkv = ops.linear(ops.rmsnorm(x, L["ln1"], c.eps, out_split=True), L["qkv"], a_split=True, out_split=True)
-                a = torch.empty(offs[-1], 2 * c.hidden, dtype=BF16, device=x.device)
-                for b, T in enumerate(lens):
-                    qb = qkv[offs[b]: offs[b + 1]]
-                    ops.rope_kv_split(qb, H, hd, 0, (kc[li, b], kcl[li, b], vc[li, b], vcl[li, b]), self.rope)
-                    q6 = qb.view(T, 2, 3, H, hd)
-                    qh, ql = (q6[:, i, 0].permute(1, 0, 2).unsqueeze(0) for i in range(2))
-                    kv = [t[li, b, :T].permute(1, 0, 2).unsqueeze(0) for t in (kc, kcl, vc, vcl)]
-                    ops.attention_split(qh, ql, kv[0], kv[1], kv[2], kv[3], hd ** -0.5, causal=True, q_pos0=0,
-                                        out=a[offs[b]: offs[b + 1]].view(1, T, 2, H, hd))
-                x = ops.linear(a, L["o"], residual=x, out_f32=True, a_split=True)
-                h = ops.linear(ops.rmsnorm(x, L["ln2"], c.eps, out_split=True), L["gu"], act="swiglu", a_split=True, out_split=True)
-                x = ops.linear(h, L["down"], residual=x, out_f32=True, a_split=True)
-            x = ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-            return [x[offs[b]: offs[b + 1]] for b in range(len(lens))]
-        for li, L in enumerate(self.layers):
-            qkv = ops.linear(ops.rmsnorm(x, L["ln1"], c.eps), L["qkv"])
-            a = torch.empty(offs[-1], c.hidden, dtype=BF16, device=x.device)
-            for b, T in enumerate(lens):
-                qb = qkv[offs[b]: offs[b + 1]]
-                ops.rope_kv(qb, H, hd, 0, c.theta, kc[li, b], vc[li, b], table=self.rope)
-                q = qb.view(T, 3, H, hd)[:, 0].permute(1, 0, 2).unsqueeze(0)
-                k = kc[li, b, :T].permute(1, 0, 2).unsqueeze(0)
-                v = vc[li, b, :T].permute(1, 0, 2).unsqueeze(0)
-                ops.attention(q, k, v, hd ** -0.5, causal=True, q_pos0=0,
-                              out=a[offs[b]: offs[b + 1]].view(1, T, H, hd).permute(0, 2, 1, 3))
-            x = ops.linear(a, L["o"], residual=x, out_f32=True)
-            h = ops.linear(ops.rmsnorm(x, L["ln2"], c.eps), L["gu"], act="swiglu")
-            x = ops.linear(h, L["down"], residual=x, out_f32=True)
-        x = ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-        return [x[offs[b]: offs[b + 1]] for b in range(len(lens))]
+        a = torch.empty(qkv.shape[0], qkv.shape[1] // 3, dtype=qkv.dtype, device=qkv.device)
+        for r0, r1, pos0, cache in segs:
+            T, qs, out = r1 - r0, qkv[r0: r1], a[r0: r1]
+            if self.precision == "parity":
+                kc, vc, kcl, vcl = (t[li] for t in cache)
+                ops.rope_kv_split(qs, H, hd, pos0, (kc, kcl, vc, vcl), self.rope)
+                qh, ql = (qs.view(T, 2, 3, H, hd)[:, i, 0].permute(1, 0, 2).unsqueeze(0) for i in range(2))
+                kv = [t[: pos0 + T].permute(1, 0, 2).unsqueeze(0) for t in (kc, kcl, vc, vcl)]
+                ops.attention_split(qh, ql, *kv, hd ** -0.5, causal=True, q_pos0=pos0, out=out.view(1, T, 2, H, hd))
+            else:
+                kc, vc = cache[0][li], cache[1][li]
+                ops.rope_kv(qs, H, hd, pos0, c.theta, kc, vc, table=self.rope)
+                q = qs.view(T, 3, H, hd)[:, 0].permute(1, 0, 2).unsqueeze(0)  # [1, H, T, hd]
+                k, v = (t[: pos0 + T].permute(1, 0, 2).unsqueeze(0) for t in (kc, vc))
+                ops.attention(q, k, v, hd ** -0.5, causal=True, q_pos0=pos0, out=out.view(1, T, H, hd).permute(0, 2, 1, 3))
+        return a
 
     # ---- one decode step as a replayable HIP graph ------------------------------------------------------------------
     # Static buffers: token id in, position (device int32, read by the attention kernel), hidden out, argmax out.
@@ -615,9 +556,10 @@ class Llama:
         H, hd = c.heads, c.hidden // c.heads
         if x.shape[0] > 16:
             raise ops.IvlmError("decode_step_batch: at most 16 sequences per step (weight-streaming kernels)")
-        return self._rows_step(x, self.decode_packed and self.decode_packed_batch and x.shape[0] > 1, lambda qkv, li: (
+        lin = self._lin("frag" if self.decode_packed and self.decode_packed_batch and x.shape[0] > 1 else None)
+        return self._decode_layers(x, lin, self._attn_then_o(lin, lambda qkv, li: (
             ops.llama_decode_attn_batch(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope,
-                                        lo=(lo[0][li], lo[1][li]) if lo is not None else None)))
+                                        lo=(lo[0][li], lo[1][li]) if lo is not None else None))))
 
     @staticmethod
     def _planes(L, n):
@@ -627,24 +569,33 @@ class Llama:
             L[n + "_p"] = ops.PackedBf12(L[n]) if ops.PackedBf12.takes(*L[n].shape) else None
         return L[n + "_p"]
 
-    def _rows_step(self, x, packed, attn):
-        """the layers of the multi-row steps (decode_step_batch, verify_step): x fp32 [rows, hidden] -> final-norm hidden fp32;
-        attn(qkv, li) -> the attention rows of layer li.  packed: the planes of the batch-1 step where the fragment layout takes the
-        matrix (the weights streamed once for all rows), bf16 otherwise"""
+    def _decode_layers(self, x, lin, attn_o):
+        """the layers of every decode step (_decode_step, decode_step_batch, verify_step): x fp32 [rows, hidden] -> final-norm
+        hidden fp32.  lin(x, L, name, **kw): the linear of matrix name of layer L on fp32 rows (which weights, which kernel);
+        attn_o(qkv, li, L, x) -> the residual stream after the attention and o_proj of layer li (separate or merged launches)"""
         c = self.cfg
-
-        def lin(x_, L, n, **kw):
-            wp = self._planes(L, n) if packed else None
-            if wp is not None and wp.frag:
-                return ops.linear_bf12(x_, wp, **kw)
-            return ops.linear(x_, L[n], out_f32=True, **kw)
-
         for li, L in enumerate(self.layers):
             qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
-            x = lin(attn(qkv, li), L, "o", residual=x)
+            x = attn_o(qkv, li, L, x)
             h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
             x = lin(h, L, "down", residual=x)
         return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+
+    @staticmethod
+    def _attn_then_o(lin, attn):
+        """the attn_o of _decode_layers from attn(qkv, li) -> the attention rows of layer li: then o_proj + residual through lin"""
+        return lambda qkv, li, L, x: lin(attn(qkv, li), L, "o", residual=x)
+
+    def _lin(self, planes=None):
+        """a lin of _decode_layers on the bf16 weights: the 12-bit planes (_planes) where planes = "any" (batch 1: every matrix that
+        has them) or "frag" (several rows: the fragment layout only; the weights streamed once for all rows), the bf16 matrix
+        otherwise"""
+        def lin(x, L, n, **kw):
+            wp = self._planes(L, n) if planes else None
+            if wp is not None and (planes == "any" or wp.frag):
+                return ops.linear_bf12(x, wp, **kw)
+            return ops.linear(x, L[n], out_f32=True, **kw)
+        return lin
 
     # ---- speculative greedy decoding: k <= 16 new tokens of THIS instance's sequence in one pass over the weights -----------------
     # The rows [t0, d1 .. d_{k-1}] (last emitted token + a draft) sit at positions pos .. pos+k-1 of the single-sequence cache; one
@@ -667,8 +618,9 @@ class Llama:
         if not self.verify_supported():
             raise ops.IvlmError(f"verify_step: not in precision {self.precision!r} / fp8 (no multi-token attention on hi + lo planes)")
         kc, vc = self._caches()
-        return self._rows_step(x, self.decode_packed and self.decode_packed_batch, lambda qkv, li: (
-            ops.llama_verify_attn(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope)))
+        lin = self._lin("frag" if self.decode_packed and self.decode_packed_batch else None)
+        return self._decode_layers(x, lin, self._attn_then_o(lin, lambda qkv, li: (
+            ops.llama_verify_attn(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope))))
 
     def verify_pass(self, st):
         """embed st["ids"] -> verify_step -> lm_head -> argmax -> accept (st: the static buffers of verify_graph)"""
@@ -733,50 +685,33 @@ class Llama:
         c = self.cfg
         H, hd = c.heads, c.hidden // c.heads
         fz = self._fused if isinstance(pos, torch.Tensor) else None
-        if self.fp8:  # e4m3 weights, fp32 activations: half the bytes per token
-            for li, L in enumerate(self.layers):
-                qkv = ops.linear_fp8w(x, L["qkv_q"], L["qkv_s"], rms=(L["ln1"], c.eps))
-                a = ops.llama_decode_attn(qkv, self.kcache[li], self.vcache[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope)
-                x = ops.linear_fp8w(a, L["o_q"], L["o_s"], residual=x)
-                h = ops.linear_fp8w(x, L["gu_q"], L["gu_s"], act="swiglu", rms=(L["ln2"], c.eps))
-                x = ops.linear_fp8w(h, L["down_q"], L["down_s"], residual=x)
-            return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-        kc_, vc_ = self._caches()
-        if self.decode_packed and fz is None:
-            def lin(x_, L, n, **kw):  # (packed where the fragment layout takes the matrix, bf16 otherwise)
-                wp = self._planes(L, n)
-                return ops.linear_bf12(x_, wp, **kw) if wp is not None else ops.linear(x_, L[n], out_f32=True, **kw)
-
+        if self.fp8:  # e4m3 weights, fp32 activations: half the bytes per token (on the bf16 cache)
+            lin = lambda x_, L, n, **kw: ops.linear_fp8w(x_, L[n + "_q"], L[n + "_s"], **kw)
+            return self._decode_layers(x, lin, self._attn_then_o(lin, lambda qkv, li: ops.llama_decode_attn(
+                qkv, self.kcache[li], self.vcache[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope)))
+        kc, vc = self._caches()
+        packed = self.decode_packed and fz is None  # (a fused step streams the bf16 weights)
+        lin = self._lin("any" if packed else None)
+        attn_o = plain = self._attn_then_o(lin, lambda qkv, li: ops.llama_decode_attn(
+            qkv, kc[li], vc[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope, lo=self._lo(li), scratch=self._attn_scratch()))
+        if packed:
             # attention as 4 key ranges per head whose (o, max, sum) partials the o_proj merges in its prologue (128 blocks instead of
             # 32, no merge launch): when o_proj is packed and K / V are single planes (not the hi + lo planes of "parity")
             split = self.decode_attn_parts and self._lo(0) is None
             if split and getattr(self, "_parts", None) is None:
                 self._parts = torch.zeros(H * 4 * (hd + 4), dtype=F32, device=self.norm.device)
-            for li, L in enumerate(self.layers):
-                qkv = lin(x, L, "qkv", rms=(L["ln1"], c.eps))
+
+            def attn_o(qkv, li, L, x):
                 wo = self._planes(L, "o")
-                if split and wo is not None:
-                    ops.llama_decode_attn_parts(qkv, kc_[li], vc_[li], H, hd, pos, c.theta, hd ** -0.5, self._parts, table=self.rope)
-                    x = ops.linear_bf12(None, wo, residual=x, parts=(self._parts, hd))
-                else:
-                    a = ops.llama_decode_attn(qkv, kc_[li], vc_[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope,
-                                              lo=self._lo(li), scratch=self._attn_scratch())
-                    x = lin(a, L, "o", residual=x)
-                h = lin(x, L, "gu", act="swiglu", rms=(L["ln2"], c.eps))
-                x = lin(h, L, "down", residual=x)
-            return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
-        for li, L in enumerate(self.layers):
-            qkv = ops.linear(x, L["qkv"], rms=(L["ln1"], c.eps), out_f32=True)
-            if fz is not None and self.precision == "default":  # attention + o_proj + residual in one launch (W_o streams while the attention runs)
-                x = ops.llama_attn_oproj(qkv, self.kcache[li], self.vcache[li], L["o"], x, H, hd, pos, fz["step"],
-                                         fz["counters"][li], fz["status"], c.theta, hd ** -0.5, self.rope, fz["scratch"][li])
-            else:
-                a = ops.llama_decode_attn(qkv, kc_[li], vc_[li], H, hd, pos, c.theta, hd ** -0.5, table=self.rope, lo=self._lo(li),
-                                          scratch=self._attn_scratch())
-                x = ops.linear(a, L["o"], residual=x, out_f32=True)
-            h = ops.linear(x, L["gu"], act="swiglu", rms=(L["ln2"], c.eps), out_f32=True)
-            x = ops.linear(h, L["down"], residual=x, out_f32=True)
-        return ops.rmsnorm(x, self.norm, c.eps, out_f32=True)
+                if not split or wo is None:
+                    return plain(qkv, li, L, x)
+                ops.llama_decode_attn_parts(qkv, kc[li], vc[li], H, hd, pos, c.theta, hd ** -0.5, self._parts, table=self.rope)
+                return ops.linear_bf12(None, wo, residual=x, parts=(self._parts, hd))
+        elif fz is not None and self.precision == "default":  # attention + o_proj + residual in one launch (W_o streams while the attention runs)
+            attn_o = lambda qkv, li, L, x: ops.llama_attn_oproj(
+                qkv, self.kcache[li], self.vcache[li], L["o"], x, H, hd, pos, fz["step"], fz["counters"][li], fz["status"], c.theta,
+                hd ** -0.5, self.rope, fz["scratch"][li])
+        return self._decode_layers(x, lin, attn_o)
 
     def logits(self, hidden_rows):
         """lm_head on fp32 [n, hidden] -> f32 [n, vocab].  n <= 16: exact fp32 activations on the weight-streaming kernels; more rows:

@@ -86,7 +86,6 @@ class InteractVLMForCausalLM:
         self.overlap_sam_encoder = True
         self.graph_decode = graphs.ON  # HIP-graph replay of the decode step (launch-bound on the host otherwise)
         self.sam_after_prefill = bool(os.environ.get("IVLM_SAM_AFTER_PREFILL"))  # measured: 107.6 vs 106.6 ms - overlapping the decode instead of the prefill is not better
-        self.packed_prefill = True  # generate_batch: prefill all prompts of a batch as one packed pass (rows independent)
         self.fused_lowres_lift = False  # measured slower than lifting the (cache-resident) full-res masks
         self._side_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self._hi_stream = torch.cuda.Stream(device=dev, priority=-1) if dev.type == "cuda" else None
@@ -565,8 +564,8 @@ class InteractVLMForCausalLM:
     # ---- B images per call (BASELINE.json configs[2]: 8 images per GPU) -----------------------------------------------
     def generate_batch(self, images_clip, input_ids_list, max_new_tokens=32, eos_token_id=2, forced_new_tokens=None):
         """Greedy search for B sequences at once (extension: the reference's evaluate() is batch 1, evaluate.py:479).
-        The prompts are prefilled one by one into their own KV-cache slab, then every decode step streams the weights ONCE
-        for all B new tokens.  Per sequence the arithmetic is that of ``generate`` (same kernels, row-independent), so the
+        The prompts are prefilled in one packed pass, each into its own KV-cache slab, then every decode step streams the weights
+        ONCE for all B new tokens.  Per sequence the arithmetic is that of ``generate`` (same kernels, row-independent), so the
         outputs equal B separate calls.  forced_new_tokens: one list per sequence (or one shared list).
         -> [(output_ids [1, L+n], hidden [L+n-1+255, H])] * B."""
         B = len(input_ids_list)
@@ -592,12 +591,7 @@ class InteractVLMForCausalLM:
         n_max = max(n_seq)
         hidden_all = torch.empty(B, max(T0) + n_max, self.config.llama.hidden, dtype=F32, device=dev)
         last = torch.empty(B, self.config.llama.hidden, dtype=F32, device=dev)
-        if self.packed_prefill and B > 1:  # the B prompts in one pass over the weights
-            hs = self.llm.forward_packed(xs, kc, vc, lo)
-        else:
-            hs = [self.llm.forward(xs[b], 0, cache=(kc[:, b], vc[:, b]) + ((lo[0][:, b], lo[1][:, b]) if lo else ()))
-                  for b in range(B)]
-        for b, h in enumerate(hs):
+        for b, h in enumerate(self.llm.forward_packed(xs, kc, vc, lo)):  # the B prompts in one pass over the weights
             hidden_all[b, : T0[b]].copy_(h)
             last[b].copy_(h[T0[b] - 1])
         forced = None

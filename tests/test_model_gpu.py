@@ -322,6 +322,35 @@ def test_decode_graph_cache_through_the_invalidation_events(hip_lib, cuda):
     step1()
 
 
+@pytest.mark.parametrize("precision", ["default", "f16", "parity"])
+def test_packed_prefill_equals_per_sequence_prefill(hip_lib, cuda, precision):
+    """forward_packed of three prompts of different lengths (one pass over the weights, one cache slab each) against
+    forward(x_b, 0, cache=slab b) per prompt into a second slab: the hidden rows and every written cache row, bit for bit."""
+    import torch
+
+    from interactvlm_amd import llava
+    from interactvlm_amd import weights as Wt
+
+    lc = Wt.LlamaCfg(hidden=512, layers=3, heads=4, inter=1024, vocab=1003)
+    w = _bf16_weights(Wt.llama_spec(lc))
+    g = torch.Generator().manual_seed(31)
+    lens = (21, 40, 33)
+    xs = [(torch.randn(T, 512, generator=g) * 0.5).to(torch.bfloat16).float().to(cuda) for T in lens]
+    llm = llava.Llama(w, lc, cuda, max_len=64)
+    llm.set_precision(precision)
+    # cache planes (k, v[, k_lo, v_lo]) [layers, B, Tmax, H, hd]: fp16 K / V in "f16", hi + lo bf16 planes in "parity"
+    dts = [torch.float16 if precision == "f16" else torch.bfloat16] * 2 + [torch.bfloat16] * (2 if precision == "parity" else 0)
+    slab_p, slab_s = ([torch.zeros(lc.layers, len(lens), 64, 4, 128, dtype=dt, device=cuda) for dt in dts] for _ in range(2))
+    hp = llm.forward_packed(xs, slab_p[0], slab_p[1], tuple(slab_p[2:]) or None)
+    hs = [llm.forward(x, 0, cache=tuple(t[:, b] for t in slab_s)) for b, x in enumerate(xs)]
+    for b, T in enumerate(lens):
+        print(f"[{precision}] prompt {b} (T = {T}): max|dh| = {float((hp[b] - hs[b]).abs().max()):.3e}")
+        assert hp[b].shape == (T, 512) and torch.equal(hp[b], hs[b])
+        for tp, ts in zip(slab_p, slab_s):
+            assert torch.equal(tp[:, b, :T], ts[:, b, :T])
+    assert all(bool(t.any()) for t in slab_p)  # (the packed pass wrote every plane)
+
+
 def _toy(golden_dir):
     import torch
 

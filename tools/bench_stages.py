@@ -34,7 +34,7 @@ def main():
     # [r6] finer events on the language stream (is the first language kernel late under the overlap?):
     # after the CLIP tower + projector, after LLaMA layers 0 / 7 / 15 / 23 of the prefill - no profiler attached.
     marks = {}
-    orig_enc, orig_layer = m.encode_images, m.llm._layer_f16
+    orig_enc, orig_layer = m.encode_images, m.llm._prefill_layer
     state = {"layer": 0, "after_clip": None}
 
     def enc(*a, **k):
@@ -52,7 +52,7 @@ def main():
         state["layer"] = i + 1
         return r
 
-    m.encode_images, m.llm._layer_f16 = enc, layer
+    m.encode_images, m.llm._prefill_layer = enc, layer
     names = ["clip", "L0", "L7", "L15", "L23"]
 
     def one(mode):
