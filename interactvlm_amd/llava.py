@@ -95,69 +95,61 @@ class ClipTower:
         self.fp8 = True
         self._graphs.clear()
 
+    def _attention(self, qkv, B, split=False):
+        """softmax(q k^T * scale) v of B images on their q|k|v rows [B*T, 3*hidden] -> the attention rows [B*T, hidden] in qkv's
+        dtype; split: [hi | lo] rows [B*T, 6*hidden] -> [B*T, 2*hidden] (fp32-activation attention, ops.attention_split)"""
+        c = self.cfg
+        T, H, hd = c.tokens, c.heads, c.hidden // c.heads
+        if split:
+            q6 = qkv.view(B, T, 2, 3, H, hd)
+            (q, k, v), (q_lo, k_lo, v_lo) = ([q6[:, :, j, i].permute(0, 2, 1, 3) for i in range(3)] for j in range(2))
+            return ops.attention_split(q, q_lo, k, k_lo, v, v_lo, hd ** -0.5, prescale_q=True)
+        q, k, v = (qkv.view(B, T, 3, H, hd)[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        return ops.attention(q, k, v, hd ** -0.5, prescale_q=True).permute(0, 2, 1, 3).reshape(B * T, c.hidden)
+
     def _forward(self, images):
-        """-> penultimate-layer patch features, bf16 [B, T-1, hidden] (the mm_projector's MFMA operand; "parity" precision:
-        [B, T-1, 2*hidden] = [hi | lo] rows).  The residual stream is fp32 between the GEMMs (residual epilogues write fp32,
-        the LayerNorms read it)."""
-        par = self.precision == "parity"
+        """-> penultimate-layer patch features, bf16 [B, T-1, hidden] (the mm_projector's MFMA operand; "parity" and "f16"
+        precision: [B, T-1, 2*hidden] = [hi | lo] rows).  The residual stream is fp32 between the GEMMs (residual epilogues write
+        fp32, the LayerNorms read it)."""
         c = self.cfg
         B = images.shape[0]
-        T, Hh, hd = c.tokens, c.heads, c.hidden // c.heads
+        T = c.tokens
         cols = ops.im2col_nchw(images.to(BF16).contiguous(), c.patch, c.patch, self.kpad)  # [B*(T-1), kpad]
         x = torch.empty(B, T, c.hidden, dtype=F32, device=images.device)
         for b in range(B):  # patch GEMM writes rows 1..T-1 and adds their position embeddings in the epilogue
             ops.linear(cols[b * (T - 1): (b + 1) * (T - 1)], self.patch_w, residual=self.pos[1:], out=x[b, 1:])
             ops.gather_rows(self.cls_row, out=x[b, 0:1])  # class_embedding + position_embedding[0] (precomputed constant)
         x = self.pre_ln(x.view(B * T, c.hidden), out_f32=True)
+        norm, lin_in, lin_out = Llama._PREFILL_FLAGS[self.precision]  # (the operands of a LLaMA prefill layer in the same mode)
+        split = self.precision == "parity"
         for L in self.layers:
             if self.fp8:  # e4m3 operands for qkv / out / fc1 / fc2 (attention stays bf16, the residual stream fp32)
                 sc = L["s"]
-                qkv = ops.linear_fp8(L["ln1"](x, fp8_scale=sc["y1"]), L["qkv_q"], sc["y1"], L["qkv_s"], L["qkv_b"]).view(B, T, 3, Hh, hd)
-                q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-                a = ops.attention(q, k, v, hd ** -0.5, prescale_q=True).permute(0, 2, 1, 3).reshape(B * T, c.hidden)
+                a = self._attention(ops.linear_fp8(L["ln1"](x, fp8_scale=sc["y1"]), L["qkv_q"], sc["y1"], L["qkv_s"], L["qkv_b"]), B)
                 aq = ops.gather_rows(a, out_kind="fp8", scale=sc["a"])
                 x = ops.linear_fp8(aq, L["out_q"], sc["a"], L["out_s"], L["out"].b, residual=x, out_kind="f32")
                 h8 = ops.linear_fp8(L["ln2"](x, fp8_scale=sc["y2"]), L["fc1_q"], sc["y2"], L["fc1_s"], L["fc1"].b, act="quick_gelu",
                                     out_kind="fp8", scale_out=sc["h"])
                 x = ops.linear_fp8(h8, L["fc2_q"], sc["h"], L["fc2_s"], L["fc2"].b, residual=x, out_kind="f32")
                 continue
-            if par:  # every MFMA operand as hi + lo halves; q * scale, softmax in fp32
-                qkv = ops.linear(L["ln1"](x, out_split=True), L["qkv_w"], L["qkv_b"], a_split=True, out_split=True)
-                q6 = qkv.view(B, T, 2, 3, Hh, hd)
-                hi = [q6[:, :, 0, i].permute(0, 2, 1, 3) for i in range(3)]
-                lo = [q6[:, :, 1, i].permute(0, 2, 1, 3) for i in range(3)]
-                a = ops.attention_split(hi[0], lo[0], hi[1], lo[1], hi[2], lo[2], hd ** -0.5, prescale_q=True)
-                x = L["out"](a, residual=x, out_f32=True, a_split=True)
-                h = L["fc1"](L["ln2"](x, out_split=True), act="quick_gelu", a_split=True, out_split=True)
-                x = L["fc2"](h, residual=x, out_f32=True, a_split=True)
-                continue
-            if self.precision == "f16":
-                L = self._f16(L)
-                qkv = ops.linear(L["ln1"](x, out_f16=True), L["qkv_h"], L["qkv_b"], out_f16=True).view(B, T, 3, Hh, hd)
-                q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-                a = ops.attention(q, k, v, hd ** -0.5, prescale_q=True).permute(0, 2, 1, 3).reshape(B * T, c.hidden)
-                x = ops.linear(a, L["out_h"], L["out"].b, residual=x, out_f32=True)
-                h = ops.linear(L["ln2"](x, out_f16=True), L["fc1_h"], L["fc1"].b, act="quick_gelu", out_f16=True)
-                x = ops.linear(h, L["fc2_h"], L["fc2"].b, residual=x, out_f32=True)
-                continue
-            cal = L.get("amax") if self._calibrating else None
-            y = L["ln1"](x)
-            qkv = ops.linear(y, L["qkv_w"], L["qkv_b"]).view(B, T, 3, Hh, hd)
-            q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-            a = ops.attention(q, k, v, hd ** -0.5, prescale_q=True).permute(0, 2, 1, 3).reshape(B * T, c.hidden)
-            x = L["out"](a, residual=x, out_f32=True)
-            y2 = L["ln2"](x)
-            h = L["fc1"](y2, act="quick_gelu")
+            wq, wo, w1, w2 = (tuple(self._f16(L)[n + "_h"] for n in ("qkv", "out", "fc1", "fc2")) if self.precision == "f16"
+                              else (L["qkv_w"], L["out"].w, L["fc1"].w, L["fc2"].w))
+            y = L["ln1"](x, **norm)
+            a = self._attention(ops.linear(y, wq, L["qkv_b"], **lin_in), B, split)
+            x = ops.linear(a, wo, L["out"].b, residual=x, out_f32=True, **lin_out)
+            y2 = L["ln2"](x, **norm)
+            h = ops.linear(y2, w1, L["fc1"].b, act="quick_gelu", **lin_in)
+            cal = L.get("amax") if self._calibrating and self.precision == "default" else None  # (enable_fp8)
             if cal:
                 for k_, t_ in (("y1", y), ("a", a), ("y2", y2), ("h", h)):
                     ops.amax(t_, cal[k_])
-            x = L["fc2"](h, residual=x, out_f32=True)
+            x = ops.linear(h, w2, L["fc2"].b, residual=x, out_f32=True, **lin_out)
         if B not in self._patch_rows:  # drop the CLS row of every image
             r = torch.arange(B * T, dtype=torch.int32).view(B, T)[:, 1:].reshape(-1)
             self._patch_rows[B] = r.to(images.device)
-        if par or self.precision == "f16":  # (the mm_projector takes hi + lo rows in both: 0.03 % of the image's FLOPs)
-            return ops.gather_rows(x, self._patch_rows[B], out_kind="split").view(B, T - 1, 2 * c.hidden)
-        return ops.gather_rows(x, self._patch_rows[B], out_kind="bf16").view(B, T - 1, c.hidden)
+        # (the mm_projector takes hi + lo rows in the "parity" and "f16" modes: 0.03 % of the image's FLOPs)
+        kind = "bf16" if self.precision == "default" else "split"
+        return ops.gather_rows(x, self._patch_rows[B], out_kind=kind).view(B, T - 1, -1)
 
 
 class _LayerW(dict):

@@ -154,16 +154,17 @@ class InteractVLMForCausalLM:
     # ("f16": the default without the exact q path - 8 - 9e-4, i.e. inside 1e-3 without margin; kept for diagnostics, not listed.)
     precision_modes = ("default", "bf16", "parity-fast", "parity")
     precision = "default"
+    # model mode -> the modes of the (CLIP tower, LLaMA, SAM encoder); at tower level "default" means bf16 operands
+    _TOWER_MODES = {"default": ("f16", "f16", "f16q"), "f16": ("f16", "f16", "f16"), "bf16": ("default", "default", "default"),
+                    "parity-fast": ("parity", "parity", "parity-fast"), "parity": ("parity", "parity", "parity")}
 
     def set_precision(self, mode):
-        assert mode in self.precision_modes + ("f16",), mode
+        assert mode in self._TOWER_MODES, mode
         self.precision = mode
-        lang = {"parity": "parity", "parity-fast": "parity", "bf16": "default"}.get(mode, "f16")  # (tower-level names)
-        self.vision_tower.precision = lang
-        self.llm.set_precision(lang)
-        enc = self.model.visual_model.image_encoder
-        enc.precision = "default" if mode == "bf16" else "parity"  # ("parity" = the site-driven forward of the encoder)
-        enc.parity_sites = {"parity": enc.PARITY_SITES, "f16": enc.SITES_F16, "default": enc.SITES_F16Q}.get(mode, enc.PARITY_SITES_FAST)
+        clip, llm, enc = self._TOWER_MODES[mode]
+        self.vision_tower.precision = clip
+        self.llm.set_precision(llm)
+        self.model.visual_model.image_encoder.precision = enc
         # the weight copies this mode reads are built NOW (a failure - memory, a weight outside fp16's range - surfaces here, not in
         # the first forward), the ones it does not read are released (default mode: the bf16 originals of the LLaMA matrices, which
         # the fp16 prefill copies + the lossless 12-bit decode planes replace: 36 -> 23 GB of language-model weights for 7B)

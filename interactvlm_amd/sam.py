@@ -8,6 +8,8 @@ NCHW<->NHWC permutes the reference performs (transformer.py:82-84, mask_decoder.
 """
 from __future__ import annotations
 
+import collections
+import functools
 import math
 
 import torch
@@ -59,6 +61,49 @@ class _LN:
 # ================================================================================================
 # image encoder
 # ================================================================================================
+_F16, _F16_SPLIT = dict(out_f16=True), dict(out_f16=True, out_split=True)
+_SPLIT, _SPLIT_A, _SPLIT_AO = dict(out_split=True), dict(a_split=True), dict(a_split=True, out_split=True)
+
+# The MFMA operands of an encoder block per precision mode (SamImageEncoder.precision): the flags of norm1's output, of the q|k|v
+# GEMM ("f16q": of its q part), the attention kind, the flags of the proj GEMM, of norm2's output and of the two MLP GEMMs, and
+# whether the neck takes [hi | lo] operands.  A GEMM on fp16 operands reads the fp16 copy of its weight (_Block.weight).
+_Mode = collections.namedtuple("_Mode", "n1 qkv attn proj n2 lin1 lin2 split_neck")
+_MODES = {"default": _Mode({}, {}, "bf16", {}, {}, {}, {}, False),
+          "f16": _Mode(_F16, _F16, "f16", {}, _F16, _F16, {}, True),
+          "f16q": _Mode(_F16_SPLIT, dict(_F16_SPLIT, a_split=True), "f16q", {}, _F16, _F16, {}, True),
+          "parity-fast": _Mode(_SPLIT, _SPLIT_AO, "split", _SPLIT_A, _F16, _F16, {}, True),
+          "parity": _Mode(_SPLIT, _SPLIT_AO, "split", _SPLIT_A, _SPLIT, _SPLIT_AO, _SPLIT_A, True)}
+
+
+class _Block(dict):
+    """One encoder block's tensors.  The derived ones are built on first access, i.e. only in a mode that reads them: ``rel_cat``
+    ([rel_pos_h ; rel_pos_w], ops.relpos_tables_cat), the fp16 copies ``rel_cat_h``, ``qkv_b_h`` and ``<gemm>_h`` (ops.f16_weight:
+    a bf16 weight inside the fp16 normal range converts exactly, one outside it raises), and the rows that fill the padded window
+    positions of the split and exact-q q|k|v buffers (``qkv_b_split``, ``q_b_split_h``, ``kv_b_h``)."""
+
+    def __missing__(self, k):
+        if k == "rel_cat":
+            t = ops.relpos_tables_cat(self["rel_h"], self["rel_w"])
+        elif k in ("rel_cat_h", "qkv_b_h"):
+            t = ops.bf16_to_f16(self["rel_cat"] if k == "rel_cat_h" else self["qkv"].b)
+        elif k in ("qkv_h", "proj_h", "lin1_h", "lin2_h"):
+            t = ops.f16_weight(self[k[:-2]].w, k[:-2])
+        elif k == "qkv_b_split":
+            t = torch.cat([self["qkv"].b, torch.zeros_like(self["qkv"].b)]).contiguous()
+        elif k in ("q_b_split_h", "kv_b_h"):
+            b = self["qkv_b_h"]
+            D = b.numel() // 3
+            t = torch.cat([b[:D], torch.zeros_like(b[:D])]).contiguous() if k == "q_b_split_h" else b[D:].contiguous()
+        else:
+            raise KeyError(k)
+        self[k] = t
+        return t
+
+    def weight(self, n, a):
+        """GEMM n's weight for the A operand a: its fp16 copy for fp16 operands (ops.linear takes both in one type)"""
+        return self[n + "_h"] if a.dtype == torch.float16 else self[n].w
+
+
 class SamImageEncoder:
     """ImageEncoderViT.forward (image_encoder.py:110-125): [V,3,S,S] bf16 -> [V, g*g, 256] bf16 (channels last)."""
 
@@ -72,7 +117,7 @@ class SamImageEncoder:
         self.blocks = []
         for i in range(cfg.depth):
             bp = f"{p}.blocks.{i}"
-            self.blocks.append(dict(
+            self.blocks.append(_Block(
                 glob=i in cfg.global_attn_indexes,
                 norm1=_LN(w, bp + ".norm1", device, 1e-6), norm2=_LN(w, bp + ".norm2", device, 1e-6),
                 qkv=_Lin(w, bp + ".attn.qkv", device), proj=_Lin(w, bp + ".attn.proj", device),
@@ -85,7 +130,7 @@ class SamImageEncoder:
         self.neck2_w = _dev(w2.permute(0, 2, 3, 1).reshape(w2.shape[0], -1), device)
         self.neck3 = _LN(w, p + ".neck.3", device, 1e-6)
         self._maps = {}
-        self._xw = {}  # per view count: the window-ordered q|k|v buffer of the windowed blocks
+        self._xw = {}  # per (attention kind, view count): the window-ordered q|k|v buffers of the windowed blocks
 
     def _window_maps(self, V):
         """Row maps of window_partition / window_unpartition (image_encoder.py:263-318) incl. zero padding."""
@@ -110,16 +155,23 @@ class SamImageEncoder:
                              nw, gp, pad.to(torch.int32).to(self.device))
         return self._maps[V]
 
-    # ---- fp8 (OCP e4m3) operands for the four big GEMMs of every block (BASELINE.json configs[4]; opt-in) -------------------
+    def _qkv_buffers(self, kind, V, nwin, device):
+        """The q|k|v output of the windowed blocks in window order, one set shared by all of them: [rows, 3D] bf16 / fp16,
+        [q hi | q lo] and [k | v] fp16 ("f16q"), [rows, 6D] bf16 = [hi | lo] ("split")."""
+        if (kind, V) not in self._xw:
+            rows, D = nwin * self.cfg.window ** 2, self.cfg.embed_dim
+            shapes = {"bf16": [(3, BF16)], "f16": [(3, torch.float16)], "f16q": [(2, torch.float16)] * 2, "split": [(6, BF16)]}[kind]
+            self._xw[(kind, V)] = [torch.empty(rows, n * D, dtype=dt, device=device) for n, dt in shapes]
+        return self._xw[(kind, V)]
+
+    # ---- fp8 (OCP e4m3) operands for the four big GEMMs of every block (BASELINE.json configs[4]; opt-in, on top of "default") ----
     # Per-tensor scales: the weights are quantised once (amax / 448); the activation scales (norm1 / attention / norm2 / GELU
     # outputs of every block) are calibrated on one bf16 pass over sample images and then FIXED (values beyond them saturate).
     # The quantisation is fused into the producers: the LayerNorms and the mlp1 GEMM's GELU epilogue write e4m3 directly; only
     # the attention output (bf16 kernel) takes one conversion pass.  Patch embedding, attention and neck stay bf16; the residual
     # stream stays fp32.
     fp8 = False
-    rel_in_kernel = True  # window attention computes its rel-pos terms itself (ops.attention rel_tab=...); False: relpos kernel
-    rel_in_kernel_global = True  # ... and so does the global 64 x 64 attention (bf16 / fp16 operands; the split kernels take arrays)
-    parity_window_arrays = True
+    _calibrating = False
 
     def enable_fp8(self, calib_images):
         """calib_images [V,3,S,S]: one bf16 pass records the activation ranges, then the fp8 path is switched on."""
@@ -139,72 +191,6 @@ class SamImageEncoder:
         self.fp8 = True
         self._graphs.clear()
 
-    _calibrating = False
-
-    def _attention(self, blk, xn, V, side, nwin, win=None):
-        """Attention.forward (image_encoder.py:235-260) on rows laid out [nwin, side*side, D].  win = (unpart, pad, buffer):
-        xn is in IMAGE order and the block is windowed - the q|k|v GEMM runs on the real rows only and scatters them to their
-        window positions (window_partition folded into its epilogue); the rows of the padded window positions, whose input is
-        zero, are the bias: filled, not computed (16 % of the rows at 64x64 / 14)."""
-        c = self.cfg
-        H, hd = c.num_heads, c.embed_dim // c.num_heads
-        S = side * side
-        if win is None:
-            qkv = blk["qkv"](xn)  # [nwin*S, 3*D] == [nwin, S, 3, H, hd]
-        else:
-            unpart, pad, qkv = win
-            blk["qkv"](xn, out=qkv, out_rows=unpart)
-            ops.fill_rows(qkv, pad, blk["qkv"].b)
-        qkv5 = qkv.view(nwin, S, 3, H, hd)
-        q, k, v = (qkv5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-        if self.rel_in_kernel and (2 * side <= 32 or (side == 64 and self.rel_in_kernel_global)) and hd == 80:
-            # windows: the decomposed rel-pos terms are computed inside the attention kernel (one small MFMA product per query
-            # tile against the [rel_pos_h ; rel_pos_w] table) - no relpos pass, no [B*H, S, 2 side] fp32 arrays
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-            o = ops.attention(q, k, v, hd ** -0.5, rel_tab=(blk["rel_cat"], side))
-            return o.permute(0, 2, 1, 3).reshape(nwin * S, H * hd)
-        if "rel_cat" not in blk:
-            blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-        rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=blk["rel_cat"])
-        o = ops.attention(q, k, v, hd ** -0.5, rel=rel)  # view of a [nwin, S, H, hd] buffer
-        return o.permute(0, 2, 1, 3).reshape(nwin * S, H * hd)
-
-    def _block_fp8(self, blk, x, V, nwin, unpart, pad):
-        """One block with e4m3 operands for qkv / proj / mlp1 / mlp2 (same dataflow as the bf16 block)."""
-        c = self.cfg
-        H, hd = c.num_heads, c.embed_dim // c.num_heads
-        sc = blk["s"]
-        xq = blk["norm1"](x, fp8_scale=sc["n1"])
-        glob = blk["glob"]
-        side = c.grid if glob else c.window
-        S = side * side
-        nw_ = V if glob else nwin
-        if glob:
-            qkv = ops.linear_fp8(xq, blk["qkv_q"], sc["n1"], blk["qkv_s"], blk["qkv"].b)
-        else:
-            qkv = self._xw[V]
-            ops.linear_fp8(xq, blk["qkv_q"], sc["n1"], blk["qkv_s"], blk["qkv"].b, out=qkv, out_rows=unpart)
-            ops.fill_rows(qkv, pad, blk["qkv"].b)
-        qkv5 = qkv.view(nw_, S, 3, H, hd)
-        q, k, v = (qkv5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-        if self.rel_in_kernel and (2 * side <= 32 or (side == 64 and self.rel_in_kernel_global)) and hd == 80:
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-            a = ops.attention(q, k, v, hd ** -0.5, rel_tab=(blk["rel_cat"], side)).permute(0, 2, 1, 3).reshape(nw_ * S, H * hd)
-        else:
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-            rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=blk["rel_cat"])
-            a = ops.attention(q, k, v, hd ** -0.5, rel=rel).permute(0, 2, 1, 3).reshape(nw_ * S, H * hd)
-        aq = ops.gather_rows(a, out_kind="fp8", scale=sc["att"])
-        x = ops.linear_fp8(aq, blk["proj_q"], sc["att"], blk["proj_s"], blk["proj"].b, residual=x, out=x,
-                           a_rows=None if glob else unpart)
-        hq = blk["norm2"](x, fp8_scale=sc["n2"])
-        h8 = ops.linear_fp8(hq, blk["lin1_q"], sc["n2"], blk["lin1_s"], blk["lin1"].b, act="gelu", out_kind="fp8",
-                            scale_out=sc["h"])
-        return ops.linear_fp8(h8, blk["lin2_q"], sc["h"], blk["lin2_s"], blk["lin2"].b, residual=x, out=x)
-
     # The encoder is ~320 launches (ViT-H, 4 views).  Issued one by one they cost the host ~22 ms - during which the language
     # path, launched after it by the same thread, has not even started (measured: the first 21.9 ms of evaluate() had an idle
     # main stream).  Replayed as ONE HIP graph per input shape the host is free after ~20 us.  Same kernels, same order.
@@ -213,234 +199,144 @@ class SamImageEncoder:
     def __call__(self, images):
         if not graphs.enabled(self.use_graph, images):
             return self._forward(images)
-        key = tuple(images.shape) + (self.fp8, self.precision, self.parity_sites, self.q_lo_level)
+        key = (tuple(images.shape), self.fp8, self.precision, self.q_lo_level)
         return self._graphs.run(key, self._forward, [images], BF16)
 
-    # ---- "parity" precision (opt-in): fp32-activation arithmetic on the bf16 matrix cores --------------------------------------
-    # Every activation that the default mode rounds to a bf16 MFMA operand (normed rows, q / k / v, softmax weights, attention
-    # output, MLP hidden) is carried as hi + lo bf16 halves (x = hi + lo to 2^-17): the four GEMMs of a block take [hi | lo]
-    # rows against the plain weight (each W tile used twice: 2 x the MFMA work), the attention runs three MFMAs per fragment,
-    # rel-pos terms / q scaling / softmax stay fp32.  The bf16 weights are exact in both modes.  Measured on the headline
-    # configuration (ViT-H depth 32, 7B): default mode max |dp| 5.8e-3 against the fp32 oracle, this mode < 1e-3 (bench.py).
+    # ---- precision modes (_MODES; model.InteractVLMForCausalLM.set_precision maps the model's modes onto them) -------------------
+    # "default": bf16 MFMA operands.
+    # "parity" (fp32-activation arithmetic on the bf16 matrix cores): every activation that "default" rounds to a bf16 MFMA operand
+    #   (normed rows, q / k / v, softmax weights, attention output, MLP hidden) is carried as hi + lo bf16 halves (x = hi + lo to
+    #   2^-17): the four GEMMs of a block take [hi | lo] rows against the plain weight (each W tile used twice: 2 x the MFMA work),
+    #   the attention runs three MFMAs per fragment, rel-pos terms / q scaling / softmax stay fp32.  The bf16 weights are exact in
+    #   every mode.  Measured on the headline configuration (ViT-H depth 32, 7B): "default" max |dp| 5.8e-3 against the fp32
+    #   oracle, this mode < 1e-3 (bench.py).
+    # "parity-fast": "parity" with the MLP's two GEMMs on IEEE fp16 operands - norm2 and the GELU epilogue write halves (11
+    #   significant bits: an eighth of the bf16 rounding error, ONE MFMA pass), the bf16 weights convert to fp16 exactly; measured
+    #   4.6e-4 end to end at depth 32 against 4.0e-4 with the "parity" encoder, 12 ms less per 4 views
+    #   (tools/experiments/diag_precision_modes.py).
+    # "f16": EVERY MFMA operand of a block as IEEE fp16 in one pass (norm1 output, q | k | v, softmax weights, attention output,
+    #   rel-pos table, norm2 output, GELU hidden) - the bf16 path's launches and FLOPs at an eighth of its operand rounding; the neck
+    #   (0.1 % of the FLOPs) takes hi + lo operands.
+    # "f16q": "f16" with the "exact q" path: norm1 writes [hi | lo] IEEE halves, q = W_q . (hi + lo) leaves its own GEMM as hi + lo
+    #   halves (k | v: a single-pass GEMM on the hi half), the attention takes q = hi + lo in the rel-pos table product (q_lo_level
+    #   2: in Q.K^T too, with the softmax weights split for P.V).  q's rounding is the one SAM's decomposed rel-pos terms amplify
+    #   (tools/emulate_f16_sites.py: 57 % of the fp16 mode's error variance comes through q), this path removes it for +1/3 of the
+    #   q|k|v GEMM's MFMA work.
     precision = "default"
-
-    # which operands travel as hi + lo halves in "parity" precision (diagnostics may switch sites off: tools/diag_precision_modes.py):
-    #   n1 / n2: the normed rows (q|k|v and mlp1 GEMM inputs), attn: q, k, v, softmax weights (split attention, fp32 rel-pos terms),
-    #   proj: the attention output (proj GEMM input), h: the GELU output (mlp2 GEMM input); rel32 (only without attn): fp32
-    #   rel-pos terms in the bf16 attention
-    #   f16mlp (instead of n2 / h): the MLP's two GEMMs take fp16 operands - norm2 and the GELU epilogue write IEEE halves (11
-    #   significant bits: an eighth of the bf16 rounding error, ONE MFMA pass), the bf16 weights convert to fp16 exactly
-    PARITY_SITES = frozenset(("n1", "attn", "proj", "n2", "h"))  # the "parity" mode: nothing below fp32-equivalent operands
-    # the encoder of the "parity-encoder" mode: measured 4.6e-4 end to end at depth 32 against 4.0e-4 for PARITY_SITES, 12 ms
-    # less per 4 views (tools/diag_precision_modes.py)
-    PARITY_SITES_FAST = frozenset(("n1", "attn", "proj", "f16mlp"))
-    # the "f16" mode: EVERY MFMA operand of a block as IEEE fp16 in one pass (f16attn: norm1 output, q | k | v, softmax weights,
-    # attention output, rel-pos table; f16mlp: norm2 output, GELU hidden) - the bf16 path's launches and FLOPs at an eighth of its
-    # operand rounding; the neck (0.1 % of the FLOPs) takes hi + lo operands
-    SITES_F16 = frozenset(("f16attn", "f16mlp"))
-    # ... with the "exact q" path (f16q): norm1 writes [hi | lo] IEEE halves, q = W_q . (hi + lo) leaves its own GEMM as hi + lo
-    # halves (k | v: a single-pass GEMM on the hi half), the attention takes q = hi + lo in the rel-pos table product and in Q.K^T and
-    # splits the softmax weights for P.V.  q's rounding is the one SAM's decomposed rel-pos terms amplify (tools/emulate_f16_sites.py:
-    # 57 % of the fp16 mode's error variance comes through q), this path removes it for +1/3 of the q|k|v GEMM's MFMA work
-    SITES_F16Q = frozenset(("f16attn", "f16q", "f16mlp"))
     q_lo_level = 1
-    parity_sites = PARITY_SITES
 
-    def _f16_weights(self, blk, names=("lin1", "lin2")):
-        """fp16 copies of a block's GEMM weights.  A bf16 value inside the fp16 NORMAL range (6.1e-5 .. 65504) converts exactly (8
-        significant bits into 11); smaller ones land on fp16 subnormals and move by at most 2^-25 = 3e-8 - checked here, and
-        irrelevant next to weights of typical size 1e-2."""
-        for n in names:
-            if n + "_h" not in blk:
-                blk[n + "_h"] = ops.f16_weight(blk[n].w, n)
-        return tuple(blk[n + "_h"] for n in names)
-
-    def _attention_f16(self, blk, xn, V, side, nwin, win=None, qx=False):
-        """_attention on fp16 operands: xn fp16 rows -> fp16 attention output [nwin*S, D].  qx ("exact q"): xn is [rows, 2D] =
-        [hi | lo] IEEE halves, win = (unpart, pad, q buffer [.., 2D], k|v buffer [.., 2D])."""
+    def _attention(self, blk, xn, side, nwin, win=None, fp8=False):
+        """Attention.forward (image_encoder.py:235-260) on rows laid out [nwin, side*side, D] -> the attention output [nwin*S, D]
+        ([nwin*S, 2D] = [hi | lo] rows for the "split" kind).  win = (unpart, pad, _qkv_buffers): xn is in IMAGE order and the
+        block is windowed - the q|k|v GEMM runs on the real rows only and scatters them to their window positions (window_partition
+        folded into its epilogue); the rows of the padded window positions, whose input is zero, are the bias: filled, not computed
+        (16 % of the rows at 64x64 / 14)."""
         c = self.cfg
         D = c.embed_dim
         H, hd = c.num_heads, D // c.num_heads
         S = side * side
-        (wq,) = self._f16_weights(blk, ("qkv",))
-        if "q_b_split_h" not in blk:
-            if "qkv_b_h" not in blk:
-                blk["qkv_b_h"] = ops.bf16_to_f16(blk["qkv"].b)
-            blk["q_b_split_h"] = torch.cat([blk["qkv_b_h"][:D], torch.zeros_like(blk["qkv_b_h"][:D])]).contiguous()
-            blk["kv_b_h"] = blk["qkv_b_h"][D:].contiguous()
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-            if "rel_cat_h" not in blk:
-                blk["rel_cat_h"] = ops.bf16_to_f16(blk["rel_cat"])
-        if qx:
-            bq, bkv = blk["qkv"].b[:D], blk["qkv"].b[D:]
-            if win is None:
-                q2 = ops.linear(xn, wq[:D], bq, a_split=True, out_split=True, out_f16=True)  # [rows, 2D] = [q hi | q lo]
-                kv = ops.linear(xn[:, :D], wq[D:], bkv, out_f16=True)                          # [rows, 2D] = [k | v]
-            else:
-                unpart, pad, q2, kv = win
-                ops.linear(xn, wq[:D], bq, out=q2, out_rows=unpart, a_split=True, out_split=True, out_f16=True)
-                ops.linear(xn[:, :D], wq[D:], bkv, out=kv, out_rows=unpart)
-                ops.fill_rows(q2, pad, blk["q_b_split_h"])
-                ops.fill_rows(kv, pad, blk["kv_b_h"])
-            q4, kv4 = q2.view(nwin, S, 2, H, hd), kv.view(nwin, S, 2, H, hd)
-            q, q_lo, k, v = (t.permute(0, 2, 1, 3) for t in (q4[:, :, 0], q4[:, :, 1], kv4[:, :, 0], kv4[:, :, 1]))
-            lv = self.q_lo_level  # 1: q's lo half in the rel-pos terms only (what amplifies its rounding); 2: in Q.K^T too, split P
-            # (level 2 on the 64 x 64 grid takes the terms as arrays: its kernel has no table mode)
-            if self.rel_in_kernel and (2 * side <= 32 or (side == 64 and self.rel_in_kernel_global and lv < 2)) and hd == 80:
-                o = ops.attention(q, k, v, hd ** -0.5, rel_tab=(blk["rel_cat_h"], side), q_lo=q_lo, q_lo_level=lv)
-            else:
-                rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=blk["rel_cat_h"], q_lo=q_lo)
-                o = ops.attention(q, k, v, hd ** -0.5, rel=rel, q_lo=q_lo if lv == 2 else None, q_lo_level=lv)
-            return o.permute(0, 2, 1, 3).reshape(nwin * S, H * hd)
+        m = _MODES[self.precision]
+        b = blk["qkv"].b
+        if fp8:
+            gemms = [(functools.partial(ops.linear_fp8, xn, blk["qkv_q"], blk["s"]["n1"], blk["qkv_s"], b), b)]
+        elif m.attn == "f16q":  # [q hi | q lo] from the [hi | lo] rows, [k | v] from a single-pass GEMM on the hi half
+            w = blk["qkv_h"]
+            gemms = [(functools.partial(ops.linear, xn, w[:D], b[:D], **m.qkv), blk["q_b_split_h"]),
+                     (functools.partial(ops.linear, xn[:, :D], w[D:], b[D:], out_f16=True), blk["kv_b_h"])]
+        else:
+            fill = blk["qkv_b_h"] if m.attn == "f16" else (blk["qkv_b_split"] if m.attn == "split" else b)
+            gemms = [(functools.partial(ops.linear, xn, blk.weight("qkv", xn), b, **m.qkv), fill)]
         if win is None:
-            qkv = ops.linear(xn, wq, blk["qkv"].b, out_f16=True)
+            outs = [gemm() for gemm, _ in gemms]
         else:
-            unpart, pad, qkv = win
-            ops.linear(xn, wq, blk["qkv"].b, out=qkv, out_rows=unpart)
-            ops.fill_rows(qkv, pad, blk["qkv_b_h"])
-        qkv5 = qkv.view(nwin, S, 3, H, hd)
-        q, k, v = (qkv5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-        if self.rel_in_kernel and (2 * side <= 32 or (side == 64 and self.rel_in_kernel_global)) and hd == 80:
-            o = ops.attention(q, k, v, hd ** -0.5, rel_tab=(blk["rel_cat_h"], side))
+            unpart, pad, outs = win
+            for (gemm, _), o in zip(gemms, outs):
+                gemm(out=o, out_rows=unpart)
+            for (_, fill), o in zip(gemms, outs):
+                ops.fill_rows(o, pad, fill)
+        if m.attn == "split":
+            # the fp32 rel-pos terms as arrays: the whole-window split kernel has no LDS left for the table product, and arrays
+            # measured faster than the generic split kernel in table mode
+            q6 = outs[0].view(nwin, S, 2, 3, H, hd)
+            (q, k, v), (q_lo, k_lo, v_lo) = ([q6[:, :, j, i].permute(0, 2, 1, 3) for i in range(3)] for j in range(2))
+            rel = ops.relpos_bias_split(q, q_lo, blk["rel_h"], blk["rel_w"], side, side)
+            return ops.attention_split(q, q_lo, k, k_lo, v, v_lo, hd ** -0.5, rel=rel)
+        if m.attn == "f16q":
+            q4, kv4 = (t.view(nwin, S, 2, H, hd) for t in outs)
+            q, q_lo, k, v = (t.permute(0, 2, 1, 3) for t in (q4[:, :, 0], q4[:, :, 1], kv4[:, :, 0], kv4[:, :, 1]))
+            lv = self.q_lo_level
         else:
-            rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=blk["rel_cat_h"])
-            o = ops.attention(q, k, v, hd ** -0.5, rel=rel)
+            qkv5 = outs[0].view(nwin, S, 3, H, hd)
+            q, k, v = (qkv5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+            q_lo, lv = None, 1
+        tab = blk["rel_cat_h"] if q.dtype == torch.float16 else blk["rel_cat"]
+        # table mode: the attention kernel computes the decomposed rel-pos terms itself (one small MFMA product per query tile
+        # against the [rel_pos_h ; rel_pos_w] table) - no relpos pass, no [B*H, S, 2 side] fp32 arrays.  Windows and the 64 x 64
+        # grid at head dim 80; level 2 of the exact q path has no table mode on the grid.
+        if hd == 80 and (2 * side <= 32 or (side == 64 and lv < 2)):
+            o = ops.attention(q, k, v, hd ** -0.5, rel_tab=(tab, side), q_lo=q_lo, q_lo_level=lv)
+        else:
+            rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=tab, q_lo=q_lo)
+            o = ops.attention(q, k, v, hd ** -0.5, rel=rel, q_lo=q_lo if lv == 2 else None, q_lo_level=lv)
         return o.permute(0, 2, 1, 3).reshape(nwin * S, H * hd)
 
-    def _attention_parity(self, blk, xn, V, side, nwin, win=None):
-        """_attention with split operands: xn [rows, D or 2D] -> attention output [nwin*S, 2D] ([hi | lo] rows), or
-        [nwin*S, D] bf16 when the 'attn' site is off."""
+    def _block(self, blk, x, V, nwin, win, fp8=False):
+        """Block.forward (image_encoder.py:177-193) on the fp32 residual stream x [V*g*g, D].  A windowed block runs both attention
+        GEMMs on the g*g real rows of every view only: window_partition is folded into the q|k|v GEMM's scatter epilogue (_attention)
+        and window_unpartition + shortcut into the proj GEMM's gather prologue, in place (its A rows are gathered from their window
+        positions; the rows of the padded window grid are never computed)."""
         c = self.cfg
-        D = c.embed_dim
-        H, hd = c.num_heads, D // c.num_heads
-        S = side * side
-        sites = self.parity_sites
-        sa, sn = "attn" in sites, "n1" in sites
-        if win is None:
-            qkv = blk["qkv"](xn, a_split=sn, out_split=sa)  # [nwin*S, (2 *) 3D]
-        else:
-            unpart, pad, qkv = win
-            blk["qkv"](xn, out=qkv, out_rows=unpart, a_split=sn, out_split=sa)
-            if sa and "qkv_b_split" not in blk:
-                blk["qkv_b_split"] = torch.cat([blk["qkv"].b, torch.zeros_like(blk["qkv"].b)]).contiguous()
-            ops.fill_rows(qkv, pad, blk["qkv_b_split"] if sa else blk["qkv"].b)
-        if not sa:
-            qkv5 = qkv.view(nwin, S, 3, H, hd)
-            q, k, v = (qkv5[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-            if "rel32" in sites:
-                rel = ops.relpos_bias_split(q, None, blk["rel_h"], blk["rel_w"], side, side)
-            else:
-                if "rel_cat" not in blk:
-                    blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-                rel = ops.relpos_bias(q, blk["rel_h"], blk["rel_w"], side, side, cat=blk["rel_cat"])
-            return ops.attention(q, k, v, hd ** -0.5, rel=rel).permute(0, 2, 1, 3).reshape(nwin * S, H * hd)
-        q6 = qkv.view(nwin, S, 2, 3, H, hd)
-        hi = [q6[:, :, 0, i].permute(0, 2, 1, 3) for i in range(3)]
-        lo = [q6[:, :, 1, i].permute(0, 2, 1, 3) for i in range(3)]
-        # windows: the whole-window split kernel has no LDS left for the table product, it takes the fp32 terms as arrays
-        # (parity_window_arrays; measured faster than the generic split kernel in table mode)
-        if self.rel_in_kernel and not self.parity_window_arrays and 2 * side <= 32 and hd == 80:
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
-            return ops.attention_split(hi[0], lo[0], hi[1], lo[1], hi[2], lo[2], hd ** -0.5, rel_tab=(blk["rel_cat"], side))
-        rel = ops.relpos_bias_split(hi[0], lo[0], blk["rel_h"], blk["rel_w"], side, side)
-        return ops.attention_split(hi[0], lo[0], hi[1], lo[1], hi[2], lo[2], hd ** -0.5, rel=rel)  # [nwin*S, 2D]
-
-    def _forward_parity(self, images):
-        c = self.cfg
-        V = images.shape[0]
-        g, D = c.grid, c.embed_dim
-        sites = self.parity_sites
-        sa = "attn" in sites
-        sp = sa and "proj" in sites
-        cols = ops.im2col_nchw(images.to(BF16).contiguous(), c.patch, c.patch)  # (bf16 pixels x bf16 weights: exact products)
-        x = self.patch(cols, residual=self.pos_embed, res_mod=g * g, out_f32=True)
-        part, unpart, nw, gp, pad = self._window_maps(V)
-        nwin = V * nw * nw
-        f16a = "f16attn" in sites
-        key = ("f16" if f16a else ("split" if sa else "bf16"), V)
-        if key not in self._xw:
-            self._xw[key] = torch.empty(nwin * c.window * c.window, (6 if sa else 3) * D, dtype=torch.float16 if f16a else BF16,
-                                        device=x.device)
-        qx = f16a and "f16q" in sites
-        if qx and ("f16q", V) not in self._xw:  # window-ordered [q hi | q lo] and [k | v] buffers
-            self._xw[("f16q", V)] = tuple(torch.empty(nwin * c.window * c.window, 2 * D, dtype=torch.float16, device=x.device)
-                                          for _ in range(2))
-        for blk in self.blocks:
-            if f16a:
-                xn = blk["norm1"](x, out_f16=True, out_split=qx)
-                (wp,) = self._f16_weights(blk, ("proj",))
-                if blk["glob"]:
-                    a = self._attention_f16(blk, xn, V, g, V, qx=qx)
-                    x = ops.linear(a, wp, blk["proj"].b, residual=x, out_f32=True)
-                else:
-                    a = self._attention_f16(blk, xn, V, c.window, nwin, qx=qx,
-                                            win=(unpart, pad) + (self._xw[("f16q", V)] if qx else (self._xw[key],)))
-                    x = ops.linear(a, wp, blk["proj"].b, residual=x, out=x, a_rows=unpart)
-            elif blk["glob"]:
-                a = self._attention_parity(blk, blk["norm1"](x, out_split="n1" in sites), V, g, V)
-                x = blk["proj"](a if (sp or not sa) else a[:, :D], residual=x, out_f32=True, a_split=sp)
-            else:
-                a = self._attention_parity(blk, blk["norm1"](x, out_split="n1" in sites), V, c.window, nwin,
-                                           win=(unpart, pad, self._xw[key]))
-                x = blk["proj"](a if (sp or not sa) else a[:, :D], residual=x, out=x, a_rows=unpart, a_split=sp)
-            if "f16mlp" in sites:
-                w1, w2 = self._f16_weights(blk)
-                h = ops.linear(blk["norm2"](x, out_f16=True), w1, blk["lin1"].b, act="gelu", out_f16=True)
-                x = ops.linear(h, w2, blk["lin2"].b, residual=x, out_f32=True)
-                continue
-            h = blk["lin1"](blk["norm2"](x, out_split="n2" in sites), act="gelu", a_split="n2" in sites, out_split="h" in sites)
-            x = blk["lin2"](h, residual=x, out_f32=True, a_split="h" in sites)
-        y = self.neck0(ops.gather_rows(x, out_kind="split"), out_f32=True, a_split=True)
-        y = self.neck1(y, out_split=True)  # [V*g*g, 2 * 256]
-        y = ops.linear(ops.im2col3x3_nhwc_split(y, V, g, g, c.out_chans), self.neck2_w, out_f32=True, a_split=True)
-        return self.neck3(y, out_f32=True).view(V, g * g, c.out_chans)
+        glob = blk["glob"]
+        side, nw_, win = (c.grid, V, None) if glob else (c.window, nwin, win)
+        a_rows = None if glob else win[0]
+        if fp8:  # e4m3 operands for qkv / proj / mlp1 / mlp2 (same dataflow as the bf16 block)
+            sc = blk["s"]
+            a = self._attention(blk, blk["norm1"](x, fp8_scale=sc["n1"]), side, nw_, win, fp8=True)
+            aq = ops.gather_rows(a, out_kind="fp8", scale=sc["att"])
+            x = ops.linear_fp8(aq, blk["proj_q"], sc["att"], blk["proj_s"], blk["proj"].b, residual=x, out=x, a_rows=a_rows)
+            hq = blk["norm2"](x, fp8_scale=sc["n2"])
+            h8 = ops.linear_fp8(hq, blk["lin1_q"], sc["n2"], blk["lin1_s"], blk["lin1"].b, act="gelu", out_kind="fp8",
+                                scale_out=sc["h"])
+            return ops.linear_fp8(h8, blk["lin2_q"], sc["h"], blk["lin2_s"], blk["lin2"].b, residual=x, out=x)
+        m = _MODES[self.precision]
+        cal = blk.get("amax") if self._calibrating and self.precision == "default" else None  # (enable_fp8)
+        xn = blk["norm1"](x, **m.n1)
+        if cal:
+            ops.amax(xn, cal["n1"])
+        a = self._attention(blk, xn, side, nw_, win)
+        if cal:
+            ops.amax(a, cal["att"])
+        x = ops.linear(a, blk.weight("proj", a), blk["proj"].b, residual=x, out_f32=True, out=None if glob else x, a_rows=a_rows,
+                       **m.proj)
+        xn2 = blk["norm2"](x, **m.n2)
+        h = ops.linear(xn2, blk.weight("lin1", xn2), blk["lin1"].b, act="gelu", **m.lin1)
+        if cal:
+            ops.amax(xn2, cal["n2"])
+            ops.amax(h, cal["h"])
+        return ops.linear(h, blk.weight("lin2", h), blk["lin2"].b, residual=x, out_f32=True, **m.lin2)
 
     def _forward(self, images):
-        """The residual stream x is fp32 (GEMM residual epilogues write it, the LayerNorms read it); MFMA operands are bf16.
-        window_partition is folded into the q|k|v GEMM's scatter epilogue and window_unpartition + shortcut into the proj GEMM's
-        gather prologue: both GEMMs of a windowed block run on the g*g real rows of every view only - no gather passes over the
-        activations, no work on the padded window positions (whose q|k|v rows are just the bias)."""
-        if self.precision == "parity":
-            return self._forward_parity(images)
+        """The residual stream x is fp32 (GEMM residual epilogues write it, the LayerNorms read it); the MFMA operands are those
+        of the precision mode, or e4m3 (fp8, on top of "default")."""
         c = self.cfg
         V = images.shape[0]
-        g, D = c.grid, c.embed_dim
-        cols = ops.im2col_nchw(images.to(BF16).contiguous(), c.patch, c.patch)
+        g = c.grid
+        m = _MODES[self.precision]
+        cols = ops.im2col_nchw(images.to(BF16).contiguous(), c.patch, c.patch)  # (bf16 pixels x bf16 weights: exact products)
         x = self.patch(cols, residual=self.pos_embed, res_mod=g * g, out_f32=True)  # + pos_embed broadcast over views
         part, unpart, nw, gp, pad = self._window_maps(V)
         nwin = V * nw * nw
-        if V not in self._xw:  # q|k|v in window order (one buffer for all windowed blocks of this view count)
-            self._xw[V] = torch.empty(nwin * c.window * c.window, 3 * D, dtype=BF16, device=x.device)
+        win = (unpart, pad, self._qkv_buffers(m.attn, V, nwin, x.device))
+        fp8 = self.fp8 and self.precision == "default"
         for blk in self.blocks:
-            if self.fp8:
-                x = self._block_fp8(blk, x, V, nwin, unpart, pad)
-                continue
-            cal = blk.get("amax") if self._calibrating else None
-            xn = blk["norm1"](x)
-            if cal:
-                ops.amax(xn, cal["n1"])
-            if blk["glob"]:
-                a = self._attention(blk, xn, V, g, V)
-                if cal:
-                    ops.amax(a, cal["att"])
-                x = blk["proj"](a, residual=x, out_f32=True)
-            else:
-                a = self._attention(blk, xn, V, c.window, nwin, win=(unpart, pad, self._xw[V]))
-                if cal:
-                    ops.amax(a.contiguous(), cal["att"])
-                # proj + window_unpartition + shortcut, in place: the GEMM runs on the g*g real rows of every view only (its A
-                # rows are gathered from their window positions; the rows of the padded window grid are never computed)
-                x = blk["proj"](a, residual=x, out=x, a_rows=unpart)
-            xn2 = blk["norm2"](x)
-            h = blk["lin1"](xn2, act="gelu")
-            if cal:
-                ops.amax(xn2, cal["n2"])
-                ops.amax(h, cal["h"])
-            x = blk["lin2"](h, residual=x, out_f32=True)
-        y = self.neck1(self.neck0(ops.gather_rows(x, out_kind="bf16")))
-        y = ops.linear(ops.im2col3x3_nhwc(y.view(V, g, g, c.out_chans)), self.neck2_w)
+            x = self._block(blk, x, V, nwin, win, fp8)
+        if m.split_neck:
+            y = self.neck0(ops.gather_rows(x, out_kind="split"), out_f32=True, a_split=True)
+            y = self.neck1(y, out_split=True)  # [V*g*g, 2 * 256]
+            y = ops.linear(ops.im2col3x3_nhwc_split(y, V, g, g, c.out_chans), self.neck2_w, out_f32=True, a_split=True)
+        else:
+            y = self.neck1(self.neck0(ops.gather_rows(x, out_kind="bf16")))
+            y = ops.linear(ops.im2col3x3_nhwc(y.view(V, g, g, c.out_chans)), self.neck2_w)
         return self.neck3(y, out_f32=True).view(V, g * g, c.out_chans)  # fp32: the mask decoder keeps fp32 activations
 
 

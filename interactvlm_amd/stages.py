@@ -217,11 +217,9 @@ class SamBlockF16C(C.Structure):
 
 
 class SamEncodeStages:
-    """``ivlm_sam_encode`` over the weights of a ``sam.SamImageEncoder`` (bf16 operands, fp32 residual stream)."""
+    """``ivlm_sam_encode*`` over the weights of a ``sam.SamImageEncoder`` (fp32 residual stream)."""
 
     def __init__(self, enc):
-        from . import ops
-
         self.e = enc
         c = enc.cfg
         self.cfg = SamCfgC(c.embed_dim, c.depth, c.num_heads, c.grid, c.window, c.patch, c.img_size, c.out_chans,
@@ -229,55 +227,40 @@ class SamEncodeStages:
         p = lambda t: t.data_ptr()
         self.head = SamHeadC(p(enc.patch.w), p(enc.patch.b), p(enc.pos_embed), p(enc.neck0.w), p(enc.neck1.w), p(enc.neck1.b),
                              p(enc.neck2_w), p(enc.neck3.w), p(enc.neck3.b))
-        for blk in enc.blocks:
-            if "rel_cat" not in blk:
-                blk["rel_cat"] = ops.relpos_tables_cat(blk["rel_h"], blk["rel_w"])
         self.blocks = (SamBlockC * c.depth)(*[
             SamBlockC(p(b["norm1"].w), p(b["norm1"].b), p(b["qkv"].w), p(b["qkv"].b), p(b["rel_h"]), p(b["rel_w"]), p(b["rel_cat"]),
                       p(b["proj"].w), p(b["proj"].b), p(b["norm2"].w), p(b["norm2"].b), p(b["lin1"].w), p(b["lin1"].b),
                       p(b["lin2"].w), p(b["lin2"].b), 1 if b["glob"] else 0) for b in enc.blocks])
 
     def __call__(self, images, precision="default"):
-        """precision 'parity': ``ivlm_sam_encode_parity`` (fp32-activation arithmetic, see SamImageEncoder.precision);
-        'parity-encoder': ``ivlm_sam_encode_parity_f16mlp`` (the same with the MLP GEMMs on fp16 operands)."""
+        """precision: the SamImageEncoder mode whose launches the C sequencer repeats - "default" (``ivlm_sam_encode``), "f16q"
+        (``ivlm_sam_encode_f16``: the host model's default), "parity-fast" (``ivlm_sam_encode_parity_f16mlp``) or "parity"
+        (``ivlm_sam_encode_parity``)."""
         lib = _lib.load()
         images = images.to(torch.bfloat16).contiguous()
         V = images.shape[0]
         c = self.e.cfg
         out = torch.empty(V, c.grid * c.grid, c.out_chans, dtype=torch.float32, device=images.device)
-        st = torch.cuda.current_stream().cuda_stream
-        if precision == "f16":  # the host model's default: fp16 operands, exact q path (ivlm_sam_encode_f16)
-            from . import ops
+        blocks = self.e.blocks
+        extra = ()  # the per-block fp16 tensors of the fp16-operand modes
+        if precision == "f16q":
             if not hasattr(self, "blocks16"):
-                rows = []
-                for b in self.e.blocks:
-                    w = self.e._f16_weights(b, ("qkv", "proj", "lin1", "lin2"))
-                    if "qkv_b_h" not in b:
-                        b["qkv_b_h"] = ops.bf16_to_f16(b["qkv"].b)
-                    if "rel_cat_h" not in b:
-                        b["rel_cat_h"] = ops.bf16_to_f16(b["rel_cat"])
-                    rows.append(SamBlockF16C(*[t.data_ptr() for t in w], b["qkv_b_h"].data_ptr(), b["rel_cat_h"].data_ptr()))
-                self.blocks16 = (SamBlockF16C * c.depth)(*rows)
-            nbytes = lib.ivlm_sam_encode_f16_workspace_bytes(C.byref(self.cfg), V)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
-            check(lib.ivlm_sam_encode_f16(C.byref(self.cfg), C.byref(self.head), self.blocks, self.blocks16, images.data_ptr(), V,
-                                          out.data_ptr(), ws.data_ptr(), nbytes, st), "sam_encode_f16")
-            return out
-        if precision == "parity-encoder":
+                self.blocks16 = (SamBlockF16C * c.depth)(*[SamBlockF16C(*[b[n].data_ptr() for n in (
+                    "qkv_h", "proj_h", "lin1_h", "lin2_h", "qkv_b_h", "rel_cat_h")]) for b in blocks])
+            size_fn, fn, extra = lib.ivlm_sam_encode_f16_workspace_bytes, lib.ivlm_sam_encode_f16, (self.blocks16,)
+        elif precision == "parity-fast":
             if not hasattr(self, "mlp16"):
-                w16 = [self.e._f16_weights(b) for b in self.e.blocks]
-                self.mlp16 = (SamMlpF16C * c.depth)(*[SamMlpF16C(a.data_ptr(), b.data_ptr()) for a, b in w16])
-            nbytes = lib.ivlm_sam_encode_parity_workspace_bytes(C.byref(self.cfg), V)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
-            check(lib.ivlm_sam_encode_parity_f16mlp(C.byref(self.cfg), C.byref(self.head), self.blocks, self.mlp16, images.data_ptr(),
-                                                    V, out.data_ptr(), ws.data_ptr(), nbytes, st), "sam_encode_parity_f16mlp")
-            return out
-        size_fn, fn = ((lib.ivlm_sam_encode_parity_workspace_bytes, lib.ivlm_sam_encode_parity) if precision == "parity"
-                       else (lib.ivlm_sam_encode_workspace_bytes, lib.ivlm_sam_encode))
+                self.mlp16 = (SamMlpF16C * c.depth)(*[SamMlpF16C(b["lin1_h"].data_ptr(), b["lin2_h"].data_ptr()) for b in blocks])
+            size_fn, fn, extra = lib.ivlm_sam_encode_parity_workspace_bytes, lib.ivlm_sam_encode_parity_f16mlp, (self.mlp16,)
+        elif precision == "parity":
+            size_fn, fn = lib.ivlm_sam_encode_parity_workspace_bytes, lib.ivlm_sam_encode_parity
+        else:
+            assert precision == "default", precision
+            size_fn, fn = lib.ivlm_sam_encode_workspace_bytes, lib.ivlm_sam_encode
         nbytes = size_fn(C.byref(self.cfg), V)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
-        check(fn(C.byref(self.cfg), C.byref(self.head), self.blocks, images.data_ptr(), V, out.data_ptr(), ws.data_ptr(), nbytes,
-                 st), "sam_encode")
+        check(fn(C.byref(self.cfg), C.byref(self.head), self.blocks, *extra, images.data_ptr(), V, out.data_ptr(), ws.data_ptr(),
+                 nbytes, torch.cuda.current_stream().cuda_stream), "sam_encode (" + precision + ")")
         return out
 
 

@@ -251,7 +251,7 @@ def test_rope_split_cache_and_decode_attention(hip_lib, cuda):
     assert float((ob.cpu().double() - ref).abs().max()) < 2e-5
 
 
-def test_towers_parity_mode_vs_oracle(hip_lib, cuda):
+def test_towers_precision_modes_vs_oracle(hip_lib, cuda):
     """SAM ViT (real width, 4 blocks incl. a global one), CLIP (4 layers) and LLaMA (3 layers, prefill + decode) in parity
     mode against the fp32 CPU oracle on identical bf16-valued weights: relative errors at the fp32 level (the default mode sits
     at 1e-2)."""
@@ -275,9 +275,9 @@ def test_towers_parity_mode_vs_oracle(hip_lib, cuda):
     e_par = rel(enc(x.to(cuda)), ref)
     e_par2 = rel(enc(x.to(cuda)), ref)  # graph replay
     # fp16 operands (the model's default mode): plain, and with the exact q path
-    enc.parity_sites = enc.SITES_F16
+    enc.precision = "f16"
     e_f16 = rel(enc(x.to(cuda)), ref)
-    enc.parity_sites = enc.SITES_F16Q
+    enc.precision = "f16q"
     e_f16q = rel(enc(x.to(cuda)), ref)
     enc.q_lo_level = 2
     e_f16q2 = rel(enc(x.to(cuda)), ref)
@@ -456,7 +456,7 @@ def test_full_depth_end_to_end_vs_oracle(hip_lib, cuda, seed, oracle):
 
 @pytest.mark.parametrize("M,N,K,act", [(16384, 5120, 1280, "gelu"), (16384, 1280, 5120, "none"), (300, 512, 256, "none")])
 def test_gemm_fp16_operands_and_output(hip_lib, cuda, M, N, K, act):
-    """IEEE-half operands on the tile GEMMs (the MLP of the SAM encoder in 'parity-encoder' precision): exact products of the fp16
+    """IEEE-half operands on the tile GEMMs (the MLP of the SAM encoder in 'parity-fast' precision): exact products of the fp16
     values, fp32 accumulation, fp16 / fp32 outputs, fp32 residual."""
     import torch
     import torch.nn.functional as F

@@ -106,7 +106,7 @@ def test_clip_encode_stage_equals_python_path(hip_lib, cuda):
 
 
 @pytest.mark.parametrize("V", [1, 4])
-def test_sam_encode_stage_equals_python_path(hip_lib, cuda, V):
+def test_sam_encode_stage_modes_equal_python_path(hip_lib, cuda, V):
     """ivlm_sam_encode (device-built window maps, scatter / gather row maps in the q|k|v and proj GEMMs, rel-pos through the
     batched GEMM for global blocks and the dot kernel for windows, neck) == SamImageEncoder._forward bit for bit, at the real
     ViT-H layer dimensions (2 windowed + 2 global blocks)."""
@@ -124,23 +124,23 @@ def test_sam_encode_stage_equals_python_path(hip_lib, cuda, V):
     got = stages.SamEncodeStages(enc)(x)
     assert got.shape == ref.shape and got.dtype == torch.float32
     assert torch.equal(got, ref), float((got - ref).abs().max())
-    # "parity" precision: ivlm_sam_encode_parity == SamImageEncoder._forward_parity bit for bit (and both differ from the default)
+    # "parity" precision: ivlm_sam_encode_parity == SamImageEncoder in "parity" bit for bit (and both differ from the default)
     enc.precision = "parity"
     ref_p = enc._forward(x)
     got_p = stages.SamEncodeStages(enc)(x, precision="parity")
     assert torch.equal(got_p, ref_p), float((got_p - ref_p).abs().max())
     assert not torch.equal(ref_p, ref)
-    # "parity-encoder": the MLP GEMMs on fp16 operands - ivlm_sam_encode_parity_f16mlp == the Python path with PARITY_SITES_FAST
-    enc.parity_sites = enc.PARITY_SITES_FAST
+    # "parity-fast": the MLP GEMMs on fp16 operands - ivlm_sam_encode_parity_f16mlp == the Python path in "parity-fast"
+    enc.precision = "parity-fast"
     ref_f = enc._forward(x)
-    got_f = stages.SamEncodeStages(enc)(x, precision="parity-encoder")
+    got_f = stages.SamEncodeStages(enc)(x, precision="parity-fast")
     assert torch.equal(got_f, ref_f), float((got_f - ref_f).abs().max())
     assert not torch.equal(ref_f, ref_p)
     assert float((ref_f - ref_p).abs().max()) < 0.25 * float((ref - ref_p).abs().max())  # (much closer to all-split than default is)
-    # the DEFAULT precision of the host model (fp16 operands, exact q path): ivlm_sam_encode_f16 == the Python path with SITES_F16Q
-    enc.parity_sites = enc.SITES_F16Q
+    # the DEFAULT precision of the host model (fp16 operands, exact q path): ivlm_sam_encode_f16 == the Python path in "f16q"
+    enc.precision = "f16q"
     ref_q = enc._forward(x)
-    got_q = stages.SamEncodeStages(enc)(x, precision="f16")
+    got_q = stages.SamEncodeStages(enc)(x, precision="f16q")
     assert torch.equal(got_q, ref_q), float((got_q - ref_q).abs().max())
     assert float((ref_q - ref_p).abs().max()) < 0.25 * float((ref - ref_p).abs().max())
 

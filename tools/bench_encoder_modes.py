@@ -26,16 +26,8 @@ def main():
     if os.environ.get("WIN_V2") is not None:
         from interactvlm_amd import _lib
         _lib.load().ivlm_attention_window_kernel(int(os.environ["WIN_V2"]))
-    for mode in (os.environ.get("MODES", "default,parity").split(",")):
-      for rik in ((True, False) if os.environ.get("AB_REL") else (True,)):
-        # modes: default | parity | f16 | f16q (the fp16-operand site sets of SamImageEncoder)
-        enc.precision = "default" if mode == "default" else "parity"
-        enc.parity_sites = {"f16": enc.SITES_F16, "f16q": enc.SITES_F16Q, "parity-fast": enc.PARITY_SITES_FAST}.get(mode, enc.PARITY_SITES)
-        enc.rel_in_kernel = rik
-        enc.rel_in_kernel_global = os.environ.get("GLOB_TAB", "1") == "1"  # REL 5: the global blocks' rel-pos terms in the kernel
-        enc.parity_window_arrays = os.environ.get("PWA", "1") == "1"
-        if hasattr(enc, "_graphs"):
-            enc._graphs.clear()
+    for mode in os.environ.get("MODES", "default,parity").split(","):  # SamImageEncoder.precision: default | f16 | f16q | parity-fast | parity
+        enc.precision = mode
         enc(im[0])
         enc(im[0])
         torch.cuda.synchronize()
@@ -43,7 +35,7 @@ def main():
         for _ in range(n):
             enc(im[0])
         torch.cuda.synchronize()
-        print(f"{mode} (rel-pos terms in the attention kernel: {rik}): {(time.perf_counter() - t0) / n * 1e3:.2f} ms per 4 views")
+        print(f"{mode}: {(time.perf_counter() - t0) / n * 1e3:.2f} ms per 4 views")
 
 
 if __name__ == "__main__":

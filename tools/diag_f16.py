@@ -52,13 +52,12 @@ def main():
                 enc = m.model.visual_model.image_encoder
                 line = f"{name} seed {seed} combos:"
                 for label, (e_, c_, l_) in (("enc-f16", ("f16", "parity", "parity")), ("clip-f16", ("parity", "f16", "parity")),
-                                            ("llm-f16", ("parity", "parity", "f16")), ("enc-f16attn", ("f16attn", "parity", "parity")),
-                                            ("enc-f16mlp", ("f16mlp", "parity", "parity")), ("lang-bf16", ("parity", "default", "default"))):
+                                            ("llm-f16", ("parity", "parity", "f16")), ("enc-f16mlp", ("parity-fast", "parity", "parity")),
+                                            ("lang-bf16", ("parity", "default", "default"))):
                     m.set_precision("parity")
                     m.vision_tower.precision = c_
                     m.llm.set_precision(l_)
-                    enc.parity_sites = {"f16": enc.SITES_F16, "parity": enc.PARITY_SITES,
-                                        "f16attn": frozenset(("f16attn", "n2", "h")), "f16mlp": enc.PARITY_SITES_FAST}[e_]
+                    enc.precision = e_
                     d = (ev() - ref).abs()
                     line += f"  {label} {float(d.max()):.2e}"
                 print(line, flush=True)

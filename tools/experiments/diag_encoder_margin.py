@@ -1,6 +1,7 @@
-"""How much margin does the "parity-encoder" mode keep under 1e-3?  Several weight / image seeds, two model shapes (the headline
+"""How much margin does a parity-mode encoder keep under 1e-3?  Several weight / image seeds, two model shapes (the headline
 7B one and tests/test_parity_mode_gpu.py's full-depth shape with a width-1024 LLaMA): max |dp| of evaluate() against the all-parity
-result (which sits < 1e-5 from the fp32 oracle) for the all-split encoder sites and for the fp16-MLP sites."""
+result (which sits < 1e-5 from the fp32 oracle) for the "parity" and the "parity-fast" (fp16 MLP) encoder next to the default
+language towers."""
 import os
 import sys
 
@@ -35,10 +36,9 @@ def main():
             ref = ev()
             m.set_precision("default")
             line = f"{name} seed {seed}: default {float((ev() - ref).abs().max()):.2e}"
-            m.set_precision("parity-encoder")
-            for label, sites in (("all-split", enc.PARITY_SITES), ("f16mlp", enc.PARITY_SITES_FAST)):
-                enc.parity_sites = sites
-                line += f"  encoder {label} {float((ev() - ref).abs().max()):.2e}"
+            for mode in ("parity", "parity-fast"):
+                enc.precision = mode
+                line += f"  encoder {mode} {float((ev() - ref).abs().max()):.2e}"
             m.set_precision("parity-fast")
             line += f"  parity-fast {float((ev() - ref).abs().max()):.2e}"
             for label, lang in (("clip", (1, 0)), ("llm", (0, 1))):  # all-split encoder + one language tower in parity precision

@@ -22,8 +22,7 @@ def main():
     w = synthetic.device_weights(cfg, dev, seed=0)
     encs = [sam.SamImageEncoder(w, cfg.sam, dev) for _ in range(4)]
     for e in encs:  # the default precision mode of the model (fp16 operands + exact q)
-        e.precision = "parity"
-        e.parity_sites = e.SITES_F16Q
+        e.precision = "f16q"
     _, im = synthetic.images(cfg, dev)
     views = im[0]
     streams = [torch.cuda.Stream(device=dev) for _ in range(4)]
