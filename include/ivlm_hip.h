@@ -400,6 +400,28 @@ int ivlm_llama_decode_attn_batch(const void *qkv, int io_dtype, int64_t ldq, voi
                                  int tmax, void *o, int64_t ldo, int B, int H, int D, const int32_t *pos_dev, float theta,
                                  float scale, const float *cos_tab, const float *sin_tab, ivlm_stream_t stream);
 
+/* The batched step for B <= 16 sequences whose first P = *prefix_len_dev cached positions hold the SAME rows (several questions about
+ * one picture: system text + image features; P in device memory like pos_dev, so one captured graph serves every call with the same
+ * B).  fp32 qkv / o (io_dtype must be IVLM_F32), bf16 cache; the _f16 twin: IEEE fp16 cache, as ivlm_llama_decode_attn_batch_f16.
+ * Keys / values [0, P) are read from slab 0 ONCE for all B queries (grid H x S key ranges, unnormalised (o, max, sum) per query into
+ * scratch); the next launch (grid H x B) does RoPE of q and k, appends sequence b's row at pos_dev[b] of ITS slab - bit-identical to
+ * the row ivlm_llama_decode_attn_batch appends -, attends over its own rows [P, pos_dev[b]] and merges the partials in a fixed order:
+ * the kernel boundary is the only synchronisation.  Every slab must hold the prefix rows (only slab 0's are read), so the plain
+ * kernel stays valid on the same state; the outputs differ from it by the fp32 summation order.  pos_dev[b] >= tmax: nothing
+ * appended, a zero output row.  pos_dev[b] < P (excluded by the caller): nothing appended, the output attends the prefix only.
+ * P is clamped to [0, tmax].  scratch: ivlm_llama_decode_attn_batch_prefix_scratch_bytes(B, H, D) bytes, 16-byte aligned, no state
+ * kept between calls, not shared by launches that can run concurrently.  D > 128, D % 16 != 0, B > 16 or another io_dtype:
+ * IVLM_ERR_UNSUPPORTED. */
+size_t ivlm_llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D);
+int ivlm_llama_decode_attn_batch_prefix(const void *qkv, int io_dtype, int64_t ldq, void *kcache, void *vcache, int64_t cache_stride,
+                                        int tmax, void *o, int64_t ldo, int B, int H, int D, const int32_t *pos_dev,
+                                        const int32_t *prefix_len_dev, float theta, float scale, const float *cos_tab,
+                                        const float *sin_tab, void *scratch, size_t scratch_bytes, ivlm_stream_t stream);
+int ivlm_llama_decode_attn_batch_prefix_f16(const void *qkv, int64_t ldq, void *kcache, void *vcache, int64_t cache_stride, int tmax,
+                                            void *o, int64_t ldo, int B, int H, int D, const int32_t *pos_dev,
+                                            const int32_t *prefix_len_dev, float theta, float scale, const float *cos_tab,
+                                            const float *sin_tab, void *scratch, size_t scratch_bytes, ivlm_stream_t stream);
+
 /* Verify pass of speculative greedy decoding (one sequence): rows i = 0 .. k-1 (k <= 16) of qkv fp32 [k, 3*H*D] are new tokens at
  * positions pos_dev[0] + i (device memory: graph-capturable).  RoPE of q and k, append of the k key / value rows to kcache / vcache
  * [tmax, H, D] (bf16; the _f16 twin: IEEE fp16, as ivlm_llama_decode_attn_f16), causal attention - query i sees keys 0 .. pos+i -

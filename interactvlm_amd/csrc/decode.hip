@@ -334,18 +334,20 @@ int llama_decode_attn_batch(const void* qkv, int io_f32, int64_t ldq, bf16_t* kc
     if (tmax <= 0 || (int64_t)tmax * H * D > cache_stride) return IVLM_ERR_INVALID_ARG;
     if ((kcache_lo != nullptr) != (vcache_lo != nullptr) || (kcache_lo && !io_f32)) return IVLM_ERR_INVALID_ARG;
     if (cache_f16 && (!io_f32 || kcache_lo)) return IVLM_ERR_INVALID_ARG;
+    // (ivlm_launch: a plain launch unless the caller armed ivlm_profile_launches - then the timing events ride on the kernel)
+    const dim3 grid(H, B);
     if (cache_f16)
-        llama_decode_attn_batch_kernel<true, false, true><<<dim3(H, B), kDecThreads, 0, st>>>(
-            qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, nullptr, nullptr);
+        ivlm_launch(llama_decode_attn_batch_kernel<true, false, true>, grid, dim3(kDecThreads), 0, st, qkv, ldq, kcache, vcache, cache_stride, o,
+                    ldo, H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, (bf16_t*)nullptr, (bf16_t*)nullptr);
     else if (kcache_lo)
-        llama_decode_attn_batch_kernel<true, true><<<dim3(H, B), kDecThreads, 0, st>>>(
-            qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, kcache_lo, vcache_lo);
+        ivlm_launch(llama_decode_attn_batch_kernel<true, true>, grid, dim3(kDecThreads), 0, st, qkv, ldq, kcache, vcache, cache_stride, o, ldo,
+                    H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, kcache_lo, vcache_lo);
     else if (io_f32)
-        llama_decode_attn_batch_kernel<true><<<dim3(H, B), kDecThreads, 0, st>>>(
-            qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, nullptr, nullptr);
+        ivlm_launch(llama_decode_attn_batch_kernel<true>, grid, dim3(kDecThreads), 0, st, qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D,
+                    theta, scale, cos_tab, sin_tab, pos_dev, tmax, (bf16_t*)nullptr, (bf16_t*)nullptr);
     else
-        llama_decode_attn_batch_kernel<false><<<dim3(H, B), kDecThreads, 0, st>>>(
-            qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D, theta, scale, cos_tab, sin_tab, pos_dev, tmax, nullptr, nullptr);
+        ivlm_launch(llama_decode_attn_batch_kernel<false>, grid, dim3(kDecThreads), 0, st, qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D,
+                    theta, scale, cos_tab, sin_tab, pos_dev, tmax, (bf16_t*)nullptr, (bf16_t*)nullptr);
     return ivlm_launch_status();
 }
 

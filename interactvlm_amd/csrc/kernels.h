@@ -193,6 +193,12 @@ int llama_decode_attn_parts(const float* qkv, bf16_t* kcache, bf16_t* vcache, in
 
 // speculative decoding of one sequence (verify.hip): k <= 16 new tokens at positions pos_dev[0] .. +k-1 in one attention launch
 // (fp32 qkv [k, 3*H*D] / o [k, H*D]; bf16 or fp16 cache), and the accept step of a verify pass
+// shared-prefix batched decode attention (decode_prefix.hip): keys [0, *prefix_len_dev) read from slab 0 once for all B <= 16 queries
+size_t llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D);
+int llama_decode_attn_batch_prefix(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,
+                                   int tmax, void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev,
+                                   const int32_t* prefix_len_dev, float theta, float scale, const float* cos_tab,
+                                   const float* sin_tab, int cache_f16, void* scratch, size_t scratch_bytes, hipStream_t st);
 int llama_verify_attn(const float* qkv, int k, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, const int32_t* pos_dev,
                       float theta, float scale, const float* cos_tab, const float* sin_tab, int cache_f16, hipStream_t st);
 int spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* nd_dev, int k, int32_t* n_acc, int32_t* tok, int32_t* pos,

@@ -11,8 +11,35 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .constants import IMAGE_TOKEN_INDEX
 
 _ring = None
+
+# the model precision modes (InteractVLMForCausalLM.set_precision) whose batched decode can share a prompt prefix: one K / V plane per
+# cache ("default": fp16 rows, "bf16"); the "parity" modes keep hi + lo planes and run the plain path, as speculative decoding does
+SHARED_PREFIX_MODES = ("default", "bf16")
+
+
+def shared_prefix_len(prompts, one_picture, mode="default", fp8=False, image_rows=256, image_id=IMAGE_TOKEN_INDEX):
+    """The number P of leading SPLICED positions that are identical in all B sequences, or 0 = take the plain batched path.
+    prompts: B id lists (the image id stands for its ``image_rows`` feature rows); one_picture: they refer to the same picture
+    (``images_clip.shape[0] == 1``), so equal ids mean equal rows.  P <= min(T0) - 1: every sequence keeps at least one prompt row of
+    its own (its last prompt row is what lm_head reads).  0 when: B == 1; several pictures (the text before the image alone is not
+    worth a second pass); P <= 16 or <= 16 suffix rows in all (both passes are tile GEMMs, M > 16); a mode outside
+    SHARED_PREFIX_MODES, or fp8.  Pure host code."""
+    prompts = [[int(t) for t in p] for p in prompts]
+    B = len(prompts)
+    if B < 2 or not one_picture or fp8 or mode not in SHARED_PREFIX_MODES:
+        return 0
+    n = 0  # common leading ids
+    while n < min(len(p) for p in prompts) and all(p[n] == prompts[0][n] for p in prompts):
+        n += 1
+    spliced = lambda ids: len(ids) + sum(image_rows - 1 for t in ids if t == image_id)
+    T0 = [spliced(p) for p in prompts]
+    P = min(spliced(prompts[0][:n]), min(T0) - 1)
+    if P <= 16 or sum(T0) - B * P <= 16:
+        return 0
+    return P
 
 
 def _id_ring(n):
@@ -87,9 +114,9 @@ class BatchGraph(_Step):
     """B sequences, one replay of Llama.decode_graph_batch per token; hidden [B, T, H]: the row of sequence b at position p goes to
     hidden[b, p] (positions read from the device before the replay advances them)"""
 
-    def __init__(self, llm, hidden, pos):
+    def __init__(self, llm, hidden, pos, prefix=None):
         super().__init__(llm, hidden)
-        self.st = llm.decode_graph_batch(pos.numel(), pos)
+        self.st = llm.decode_graph_batch(pos.numel(), pos, prefix)  # (prefix: the shared prefix length P on the host, or None)
         self.rows = torch.arange(pos.numel(), device=pos.device)
 
     def __call__(self, tok, out=None):
@@ -103,18 +130,20 @@ class BatchGraph(_Step):
 
 
 class BatchEager(_Step):
-    """B sequences, Llama.decode_step_batch as eager launches on the cache slabs (kc, vc, lo) at device positions pos"""
+    """B sequences, Llama.decode_step_batch as eager launches on the cache slabs (kc, vc, lo) at device positions pos; prefix: the
+    shared prefix length P on the host, or None"""
 
-    def __init__(self, llm, hidden, pos, caches):
+    def __init__(self, llm, hidden, pos, caches, prefix=None):
         super().__init__(llm, hidden)
         self.pos, self.caches = pos, caches
+        self.prefix = None if prefix is None else torch.tensor([int(prefix)], dtype=torch.int32, device=pos.device)
         self.rows = torch.arange(pos.numel(), device=pos.device)
 
     def __call__(self, tok, out=None):
         llm = self.llm
         # (finished sequences keep stepping - their rows are ignored; a sequence whose position has reached the end of its
         #  cache slab is skipped by the attention kernel: nothing is appended past Tmax)
-        h = llm.decode_step_batch(llm.embed_ids(tok.contiguous()), self.pos, *self.caches)
+        h = llm.decode_step_batch(llm.embed_ids(tok.contiguous()), self.pos, *self.caches, prefix=self.prefix)
         idx = self.pos.to(torch.int64)
         nxt = ops.argmax(llm.logits(h))
         self.pos = self.pos + 1

@@ -24,8 +24,9 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 
 # a captured decode step (Llama._graphs): batched (decode_graph_batch) or not, sequences per step, and what selects its launches;
-# verify: a speculative verify pass of this instance's sequence (verify_graph, B = rows per pass)
-_GraphKey = collections.namedtuple("_GraphKey", "batched B precision packed fp8 fused verify", defaults=(False,))
+# verify: a speculative verify pass of this instance's sequence (verify_graph, B = rows per pass); prefix: the batched step whose
+# attention reads a shared prompt prefix once for all sequences (decode_graph_batch(prefix=...))
+_GraphKey = collections.namedtuple("_GraphKey", "batched B precision packed fp8 fused verify prefix", defaults=(False, False))
 
 
 class ClipTower:
@@ -385,6 +386,32 @@ class Llama:
             r0 += x.shape[0]
         return self._prefill(torch.cat(xs, 0) if len(xs) > 1 else xs[0], segs)  # (one sequence: its rows as they are, no copy)
 
+    # ---- several prompts about ONE picture: the leading P spliced positions (system text + image features) are the same rows in
+    # every sequence.  They are prefilled ONCE (into slab 0) and copied to the other slabs - every slab ends up complete, so the
+    # plain batched decode kernel stays valid on the same state -, then the B suffixes run as packed segments that start at
+    # position P.  P comes from decoding.shared_prefix_len; not in the "parity" mode or with fp8 (as verify_step).
+    def prefix_supported(self):
+        return self.precision != "parity" and not self.fp8
+
+    def forward_shared_prefix(self, xs, P, kc, vc):
+        """forward_packed for B >= 2 sequences whose first P rows are identical: xs = [x_b fp32 [T_b, hidden]], P > 16 and
+        P < min(T_b), more than 16 suffix rows in all (the tile GEMMs need M > 16) -> [final-norm hidden fp32 [T_b, hidden]]."""
+        B = len(xs)
+        T = [int(x.shape[0]) for x in xs]
+        if not self.prefix_supported():
+            raise ops.IvlmError(f"forward_shared_prefix: not in precision {self.precision!r} / fp8")
+        if B < 2 or not 16 < P < min(T) or sum(T) - B * P <= 16 or max(T) > self.max_len:
+            raise ops.IvlmError(f"forward_shared_prefix: B={B}, P={P}, lengths {T}: need B >= 2, 16 < P < min length, > 16 suffix rows")
+        pre = self._prefill(xs[0][:P], [(0, P, 0, (kc[:, 0], vc[:, 0]))])[0]
+        for c in (kc, vc):  # one broadcast copy per cache: rows [0, P) of slab 0 -> slabs 1 .. B-1, every layer
+            c[:, 1:, :P].copy_(c[:, :1, :P])
+        segs, r0 = [], 0
+        for b in range(B):
+            segs.append((r0, r0 + T[b] - P, P, (kc[:, b], vc[:, b])))
+            r0 += T[b] - P
+        suf = self._prefill(torch.cat([x[P:] for x in xs], 0), segs)
+        return [torch.cat([pre, h], 0) for h in suf]
+
     def _prefill(self, x, segs):
         """The prefill layers on the packed rows x fp32 [rows, hidden] of one or more sequences; segs = [(r0, r1, pos0, cache)]: a
         sequence's rows, the position of its first row and its cache planes (k, v[, k_lo, v_lo]) [layers, Tmax, H, hd]
@@ -540,15 +567,25 @@ class Llama:
             return bc[0].view(torch.float16)[:, :B], bc[1].view(torch.float16)[:, :B]
         return bc[0][:, :B], bc[1][:, :B]
 
-    def decode_step_batch(self, x, pos_dev, kc, vc, lo=None):
+    def decode_step_batch(self, x, pos_dev, kc, vc, lo=None, prefix=None):
         """x fp32 [B, hidden] (one new token per sequence), pos_dev int32 [B], kc/vc [layers, B, Tmax, H, hd] ->
         final-norm hidden fp32 [B, hidden]; same arithmetic per row as ``_decode_step`` (fp32 activations: the skinny MFMA
-        kernel splits them into hi + lo bf16 operands, the batch-1 GEMV multiplies them exactly - equal to ~1e-5)."""
+        kernel splits them into hi + lo bf16 operands, the batch-1 GEMV multiplies them exactly - equal to ~1e-5).
+        prefix (int32 [1] on the device, or None): the first prefix[0] cached rows are the same in every slab
+        (forward_shared_prefix) and the attention reads them from slab 0 once for all sequences (ops.llama_decode_attn_batch_prefix)."""
         c = self.cfg
         H, hd = c.heads, c.hidden // c.heads
         if x.shape[0] > 16:
             raise ops.IvlmError("decode_step_batch: at most 16 sequences per step (weight-streaming kernels)")
         lin = self._lin("frag" if self.decode_packed and self.decode_packed_batch and x.shape[0] > 1 else None)
+        if prefix is not None:
+            if lo is not None or not self.prefix_supported():
+                raise ops.IvlmError(f"decode_step_batch(prefix=...): not in precision {self.precision!r} / fp8")
+            if getattr(self, "_prefix_scratch", None) is None:  # (sized for 16 sequences: one buffer for every B)
+                self._prefix_scratch = ops.decode_attn_prefix_scratch(16, H, hd, self.norm.device)
+            return self._decode_layers(x, lin, self._attn_then_o(lin, lambda qkv, li: (
+                ops.llama_decode_attn_batch_prefix(qkv, kc[li], vc[li], H, hd, pos_dev, prefix, c.theta, hd ** -0.5, table=self.rope,
+                                                   scratch=self._prefix_scratch))))
         return self._decode_layers(x, lin, self._attn_then_o(lin, lambda qkv, li: (
             ops.llama_decode_attn_batch(qkv, kc[li], vc[li], H, hd, pos_dev, c.theta, hd ** -0.5, table=self.rope,
                                         lo=(lo[0][li], lo[1][li]) if lo is not None else None))))
@@ -638,25 +675,32 @@ class Llama:
             self._capture_decode(key, st, lambda: self.verify_pass(st), caches, [st["pos"], st["n_acc"], st["tok"]], rows=kb)
         return st
 
-    def decode_graph_batch(self, B, pos=None):
+    def decode_graph_batch(self, B, pos=None, prefix=None):
         """One batched decode step (embed -> layers -> norm -> lm_head -> argmax, positions += 1) as a HIP graph; pos (int32 [B] on
-        the device): a generation starts at these positions"""
+        the device): a generation starts at these positions.  prefix (host int P, or None): the shared-prefix variant of the step
+        (decode_step_batch(prefix=...)), captured under its own key; P is written to device memory, so one graph serves every P."""
         kc, vc = self.batch_cache(B)
         lo = self.batch_cache_lo(B) if self.precision == "parity" else None
         key = self._graph_key(B, batched=True)
+        if prefix is not None:
+            key = key._replace(prefix=True)
         st = self._graphs.get(key)
         if st is None:
             dev = self.device
             st = dict(tok=torch.zeros(B, dtype=torch.int32, device=dev), pos=torch.zeros(B, dtype=torch.int32, device=dev))
+            if prefix is not None:
+                st["prefix"] = torch.zeros(1, dtype=torch.int32, device=dev)
 
             def body():
-                h = self.decode_step_batch(self.embed_ids(st["tok"]), st["pos"], kc, vc, lo)
+                h = self.decode_step_batch(self.embed_ids(st["tok"]), st["pos"], kc, vc, lo, st.get("prefix"))
                 st["hidden"] = h
                 st["nxt"] = ops.argmax(self.logits(h), bump=st["pos"])  # (+ positions += 1 in the same launch)
 
             self._capture_decode(key, st, body, [kc, vc] + list(lo or ()), [st["pos"]])
         if pos is not None:
             st["pos"].copy_(pos)
+        if prefix is not None:
+            st["prefix"].fill_(int(prefix))
         return st
 
     def _attn_scratch(self):

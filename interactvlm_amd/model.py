@@ -563,11 +563,17 @@ class InteractVLMForCausalLM:
 
     @torch.no_grad()
     # ---- B images per call (BASELINE.json configs[2]: 8 images per GPU) -----------------------------------------------
-    def generate_batch(self, images_clip, input_ids_list, max_new_tokens=32, eos_token_id=2, forced_new_tokens=None):
+    def generate_batch(self, images_clip, input_ids_list, max_new_tokens=32, eos_token_id=2, forced_new_tokens=None,
+                       share_prefix=False):
         """Greedy search for B sequences at once (extension: the reference's evaluate() is batch 1, evaluate.py:479).
         The prompts are prefilled in one packed pass, each into its own KV-cache slab, then every decode step streams the weights
         ONCE for all B new tokens.  Per sequence the arithmetic is that of ``generate`` (same kernels, row-independent), so the
         outputs equal B separate calls.  forced_new_tokens: one list per sequence (or one shared list).
+        share_prefix (opt-in): B questions about ONE picture share their leading spliced positions (system text + image features;
+        ``decoding.shared_prefix_len``): those rows are prefilled once and every decode step's attention reads them once for all
+        sequences (``Llama.forward_shared_prefix``, ``ops.llama_decode_attn_batch_prefix``).  Same ids; hidden rows equal to the
+        fp32 summation order of the attention.  Where nothing is shared (several pictures, B = 1, a "parity" mode, fp8, a prefix
+        or suffix of <= 16 rows) the plain path runs, unchanged.
         -> [(output_ids [1, L+n], hidden [L+n-1+255, H])] * B."""
         B = len(input_ids_list)
         if B > 16:  # (checked before any work: the weight-streaming decode kernels take at most 16 rows per step)
@@ -592,7 +598,15 @@ class InteractVLMForCausalLM:
         n_max = max(n_seq)
         hidden_all = torch.empty(B, max(T0) + n_max, self.config.llama.hidden, dtype=F32, device=dev)
         last = torch.empty(B, self.config.llama.hidden, dtype=F32, device=dev)
-        for b, h in enumerate(self.llm.forward_packed(xs, kc, vc, lo)):  # the B prompts in one pass over the weights
+        P = 0
+        if share_prefix:
+            P = decoding.shared_prefix_len([t.reshape(-1).tolist() for t in input_ids_list], images_clip.shape[0] == 1,
+                                           self.precision, self.fp8, image_rows=feats.shape[1])
+        prefix = P if P > 0 else None
+        assert P < min(T0)  # (no sequence sits inside the shared prefix: its last prompt row is its own)
+        # the B prompts in one pass over the weights (shared prefix: its rows once, then the B suffixes in one pass)
+        hs = self.llm.forward_shared_prefix(xs, P, kc, vc) if prefix else self.llm.forward_packed(xs, kc, vc, lo)
+        for b, h in enumerate(hs):
             hidden_all[b, : T0[b]].copy_(h)
             last[b].copy_(h[T0[b] - 1])
         forced = None
@@ -601,9 +615,9 @@ class InteractVLMForCausalLM:
             forced = (pad, torch.tensor(pad, dtype=torch.int32, device=dev).t().contiguous())  # [n_max, B]
         pos = torch.tensor(T0, dtype=torch.int32, device=dev)
         if graphs.enabled(self.graph_decode):
-            step = decoding.BatchGraph(self.llm, hidden_all, pos)
+            step = decoding.BatchGraph(self.llm, hidden_all, pos, prefix)
         else:
-            step = decoding.BatchEager(self.llm, hidden_all, pos, (kc, vc, lo))
+            step = decoding.BatchEager(self.llm, hidden_all, pos, (kc, vc, lo), prefix)
         new_ids, _ = decoding.greedy(step, ops.argmax(self.llm.logits(last)), n_seq, eos_token_id, forced)
         out = []
         for b in range(B):
@@ -614,7 +628,7 @@ class InteractVLMForCausalLM:
 
     def evaluate_batch(self, images_clip, images, input_ids_list, cam_params, resize_list, original_size_list,
                        contact_type="hcontact", max_new_tokens=32, forced_new_tokens=None, eos_token_id=2,
-                       lift2d_dict_path=None, image_embeddings=None, deferred=False):
+                       lift2d_dict_path=None, image_embeddings=None, deferred=False, share_prefix=False):
         """``evaluate`` for B images in one call: images_clip [B,3,h,w], images [B,V,3,S,S], one prompt per image.
         The SAM encoder of every image runs on the side stream while the B sequences decode together; the masks of all
         images are lifted in one launch.  -> [{'output_ids','pred_masks','pred_contact_3d'}] * B, each equal to what
@@ -623,7 +637,9 @@ class InteractVLMForCausalLM:
         prompt over the body renders and an object prompt over the object renders); contact_type and lift2d_dict_path
         may then be lists, one entry per prompt.
         image_embeddings: pre-computed SAM embeddings, one [V, g*g, 256] tensor for all samples (the four
-        canonical body renders of hcontact are the same for every image) or a list of B; ``images`` is then not encoded."""
+        canonical body renders of hcontact are the same for every image) or a list of B; ``images`` is then not encoded.
+        share_prefix (opt-in): B questions about one picture share the prompt prefix in the prefill and in every decode step
+        (``generate_batch``); the result dicts are the same."""
         # deferred=True: everything that does not depend on the encoder is ENQUEUED now (SAM encoder on the side stream, CLIP +
         # prefill + the batched decode loop on the caller's stream) and a function is returned that enqueues the tail (mask decoders,
         # lift) and returns the results.  A caller with several chunks begins chunk c + 1 before it finishes chunk c
@@ -650,7 +666,7 @@ class InteractVLMForCausalLM:
             def finish_all():
                 outs, pending = [], None
                 for sub in subs:
-                    nxt_ = self.evaluate_batch(*sub, deferred=True)
+                    nxt_ = self.evaluate_batch(*sub, deferred=True, share_prefix=share_prefix)
                     if pending is not None:
                         outs.extend(pending())
                     pending = nxt_
@@ -658,7 +674,7 @@ class InteractVLMForCausalLM:
                 return outs
             return finish_all if deferred else finish_all()
         guard = self._guard_applies()  # (fp16 exponent range: see _guarded)
-        st = self._evaluate_batch_begin(*args)
+        st = self._evaluate_batch_begin(*args, share_prefix=share_prefix)
 
         def finish():
             if not guard:
@@ -668,20 +684,21 @@ class InteractVLMForCausalLM:
             try:
                 outs = self._evaluate_batch_finish(st)
                 if not self._guard_ok(outs, image_embeddings):
-                    outs = self._recompute_bf16(lambda: self.evaluate_batch(*args))
+                    outs = self._recompute_bf16(lambda: self.evaluate_batch(*args, share_prefix=share_prefix))
                 return outs
             finally:
                 self._in_guard = False
         return finish if deferred else finish()
 
     def _evaluate_batch_begin(self, images_clip, images, input_ids_list, cam_params, resize_list, original_size_list,
-                              contact_type, max_new_tokens, forced_new_tokens, eos_token_id, lift2d_dict_path, image_embeddings):
+                              contact_type, max_new_tokens, forced_new_tokens, eos_token_id, lift2d_dict_path, image_embeddings,
+                              share_prefix=False):
         B = len(input_ids_list)
         main = torch.cuda.current_stream(self.device)
         ev = allv = None
         if image_embeddings is not None:
             embs = list(image_embeddings) if isinstance(image_embeddings, (list, tuple)) else [image_embeddings] * B
-            gens = self.generate_batch(images_clip, input_ids_list, max_new_tokens, eos_token_id, forced_new_tokens)
+            gens = self.generate_batch(images_clip, input_ids_list, max_new_tokens, eos_token_id, forced_new_tokens, share_prefix)
         else:
             side = self._side_stream if self.overlap_sam_encoder else main
             embs = []
@@ -698,7 +715,7 @@ class InteractVLMForCausalLM:
                 if side is not main:
                     ev = torch.cuda.Event()
                     ev.record(side)
-            gens = self.generate_batch(images_clip, input_ids_list, max_new_tokens, eos_token_id, forced_new_tokens)
+            gens = self.generate_batch(images_clip, input_ids_list, max_new_tokens, eos_token_id, forced_new_tokens, share_prefix)
         return dict(B=B, gens=gens, embs=embs, ev=ev, allv=allv, cam_params=cam_params, resize_list=resize_list,
                     original_size_list=original_size_list, contact_type=contact_type, lift2d_dict_path=lift2d_dict_path)
 

@@ -1224,6 +1224,44 @@ def llama_decode_attn_batch(qkv, kcache, vcache, H, D, pos_dev, theta, scale, ta
     return out
 
 
+def decode_attn_prefix_scratch(B, H, D, device):
+    """Scratch of llama_decode_attn_batch_prefix for B sequences (the shared phase's partials; no state between calls)."""
+    n = int(_lib.load().ivlm_llama_decode_attn_batch_prefix_scratch_bytes(B, H, D))
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def llama_decode_attn_batch_prefix(qkv, kcache, vcache, H, D, pos_dev, prefix_dev, theta, scale, table=None, out=None, scratch=None,
+                                   host_check=None):
+    """``llama_decode_attn_batch`` for B <= 16 sequences whose first P = prefix_dev[0] cached rows are the same in every slab: qkv fp32
+    [B, 3*H*D], kcache / vcache bf16 | fp16 [B, Tmax, H, D], pos_dev int32 [B] and prefix_dev int32 [1] on the device -> o fp32
+    [B, H*D].  Keys [0, P) are read from slab 0 once for all B queries, sequence b's own rows [P, pos_dev[b]] from its slab; its
+    new row is appended as the plain kernel appends it.  scratch: decode_attn_prefix_scratch(B, H, D) (made here when None; a
+    captured graph passes its own).  host_check = (positions, P) where the caller has the numbers on the host: P <= every position."""
+    lib = _lib.load()
+    B = qkv.shape[0]
+    if host_check is not None:
+        assert all(int(p) >= int(host_check[1]) for p in host_check[0]), "a sequence sits inside the shared prefix"
+    assert qkv.dtype == F32 and qkv.stride(1) == 1 and kcache.dim() == 4 and kcache.shape[0] == B
+    assert kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
+    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
+    assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() == B and pos_dev.is_contiguous()
+    assert prefix_dev.dtype == torch.int32 and prefix_dev.is_cuda and prefix_dev.numel() >= 1
+    if table is not None:  # (the kernels read the cos / sin row of every position below Tmax)
+        assert table[0].shape[0] >= kcache.shape[1] and table[0].shape[1] == D // 2
+    if out is None:
+        out = torch.empty(B, H * D, dtype=F32, device=qkv.device)
+    if scratch is None:
+        scratch = decode_attn_prefix_scratch(B, H, D, qkv.device)
+    args = (kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D,
+            pos_dev.data_ptr(), prefix_dev.data_ptr(), float(theta), float(scale), _p(table[0]) if table else 0,
+            _p(table[1]) if table else 0, scratch.data_ptr(), scratch.numel(), _stream())
+    if kcache.dtype == F16:
+        check(lib.ivlm_llama_decode_attn_batch_prefix_f16(qkv.data_ptr(), qkv.stride(0), *args), "llama_decode_attn_batch_prefix_f16")
+    else:
+        check(lib.ivlm_llama_decode_attn_batch_prefix(qkv.data_ptr(), IVLM_F32, qkv.stride(0), *args), "llama_decode_attn_batch_prefix")
+    return out
+
+
 def llama_verify_attn(qkv, kcache, vcache, H, D, pos_dev, theta, scale, table=None, out=None):
     """Verify pass of speculative decoding, one sequence: qkv fp32 [k, 3*H*D] (k <= 16 new tokens at positions pos_dev[0] ..
     pos_dev[0] + k - 1), kcache / vcache bf16 | fp16 [Tmax, H, D] -> o fp32 [k, H*D]; RoPE + append of the k rows + causal
