@@ -779,6 +779,31 @@ int ivlm_contact_prf(const float *gt, const float *pred, int B, int n, float thr
 int ivlm_spmv_csr(const int32_t *row_ptr, const int32_t *col, const float *val, const float *x, int B, int rows,
                   int cols, float *y, ivlm_stream_t stream);
 
+/* get_segmentation_metrics / intersectionAndUnionGPU with K = 2 (utils/eval_utils.py:27-61): pred f32 [V,H,W] = the mask values
+ * as evaluate returns them, class 1 where pred > 0 (on the 'oafford' 'HM' views the masks are probabilities, so that holds in the
+ * whole valid region, as in the reference); gt [V,H,W] of gt_dtype (IVLM_SEG_GT_*; f32 is truncated like .int()) -> out i32
+ * [V,3,2] = (intersection, output area, target area) of classes 0 and 1 per view.  A pixel whose gt equals ignore_label counts
+ * nowhere; a gt value outside {0, 1} is in no target or intersection bin (torch.histc with min 0, max 1).  Integer counts summed
+ * in a fixed order: the same bits every run.  H * W < 2^31.  workspace: ivlm_seg_iou_workspace_bytes(V) bytes, 16-byte aligned. */
+#define IVLM_SEG_GT_U8 0
+#define IVLM_SEG_GT_I32 1
+#define IVLM_SEG_GT_F32 2
+size_t ivlm_seg_iou_workspace_bytes(int V);
+int ivlm_seg_iou_counts(const float *pred, const void *gt, int gt_dtype, int V, int H, int W, int ignore_label, int32_t *out,
+                        void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+/* get_o_affordance_metrics (utils/eval_utils.py:153-213) per sample: gt, pred f32 [B,n], thresholds f32 [T] in DEVICE memory (the
+ * reference's np.linspace(0, 1, 20) rounded to fp32 by the host: torch compares an fp32 tensor with a scalar in fp32) -> out f32
+ * [B,4] = (SIM, MAE, ROC-AUC, aIoU), valid i32 [B].  SIM = sum min(gt / (sum gt + 1e-12), pred / (sum pred + 1e-12)) and MAE =
+ * sum |gt - pred| / mae_div (the reference divides by the literal 2048) are accumulated in fp64.  AUC = (#{pos > neg} + 0.5
+ * #{pos == neg}) / (P N) over the gt >= 0.5 split from integer counts = sklearn's roc_auc_score, ties included.  aIoU = mean over
+ * the thresholds of |pred >= t & gt >= 0.5| / |pred >= t | gt >= 0.5|.  A sample whose gt has a single class or whose pred holds
+ * a non-finite value is invalid: AUC and aIoU are NaN, valid is 0.  n <= IVLM_AFFORD_MAX_N and T <= IVLM_AFFORD_MAX_T, else
+ * IVLM_ERR_UNSUPPORTED before any launch. */
+#define IVLM_AFFORD_MAX_N 4096
+#define IVLM_AFFORD_MAX_T 64
+int ivlm_afford_metrics(const float *gt, const float *pred, int B, int n, const float *thresholds, int T, float mae_div,
+                        float *out, int32_t *valid, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

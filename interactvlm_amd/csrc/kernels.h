@@ -158,6 +158,13 @@ int contact_prf(const float* gt, const float* pred, int B, int n, float thr, flo
 int spmv_csr(const int32_t* row_ptr, const int32_t* col, const float* val, const float* x, int B, int rows, int cols,
              float* y, hipStream_t st);
 
+// ---- metrics of the validate() loop (validate_metrics.hip) ---------------------------------------------
+size_t seg_iou_workspace_bytes(int V);
+int seg_iou_counts(const float* pred, const void* gt, int gt_dtype, int V, int H, int W, int ignore_label, int32_t* out, void* ws,
+                   size_t ws_bytes, hipStream_t st);
+int afford_metrics(const float* gt, const float* pred, int B, int n, const float* thresholds, int T, float mae_div, float* out,
+                   int32_t* valid, hipStream_t st);
+
 // ---- rasterisation (raster.hip) -------------------------------------------------------------------
 size_t raster_workspace_bytes(int n_prims_verts, int H, int W);
 int rasterize_mesh(const float* verts, int nv, const int32_t* faces, int nf, const float* cam12_host, float fov_deg,

@@ -303,6 +303,8 @@ class InteractVLMForCausalLM:
             return self._causal_lm_forward(**kwargs)
         return self.model_forward(**kwargs)
 
+    __call__ = forward  # validate() calls model(**input_dict) like the reference's loop (evaluate.py:120)
+
     @torch.no_grad()
     def _causal_lm_forward(self, input_ids=None, attention_mask=None, past_key_values=None, inputs_embeds=None, labels=None,
                            use_cache=None, output_attentions=None, output_hidden_states=None, images=None, return_dict=None):

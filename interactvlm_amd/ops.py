@@ -1322,9 +1322,64 @@ def contact_prf(gt, pred, threshold=0.5):
     return out
 
 
-def h_geo_metric(pred, gt, dist):
-    """get_h_geo_metric (utils/eval_utils.py:129-151) on the device: pred / gt f32 [B,n], dist f32 [n,n] ->
-    (fp_dist_avg, fn_dist_avg) python floats (batch means) and the per-sample f32 [B,2] tensor."""
+o_contact_prf = contact_prf  # get_o_contact_metrics (utils/eval_utils.py:96-125): the same arithmetic under the object name
+
+
+_SEG_GT_CODE = {torch.uint8: 0, torch.int32: 1, torch.float32: 2}  # IVLM_SEG_GT_*
+_AFFORD_THRESHOLDS = {}
+
+
+def seg_iou_counts(pred, gt, ignore_label=255):
+    """intersectionAndUnionGPU with K = 2 per view (utils/eval_utils.py:27-61): pred f32 [V,H,W] (class 1 where pred > 0), gt
+    [V,H,W] u8 / i32 / f32 (f32 truncated like .int()) -> i32 [V,3,2] = (intersection, output area, target area) of classes
+    0 and 1.  area_union = output + target - intersection."""
+    lib = _lib.load()
+    pred = _req(pred, torch.float32, "pred")
+    gt = _req(gt, None, "gt")
+    if gt.dtype not in _SEG_GT_CODE:
+        raise IvlmError(f"gt: expected uint8, int32 or float32, got {gt.dtype}")
+    if pred.dim() != 3 or gt.shape != pred.shape:
+        raise IvlmError(f"seg_iou_counts: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must be the same [V,H,W]")
+    V, H, W = pred.shape
+    nbytes = lib.ivlm_seg_iou_workspace_bytes(V)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    out = torch.empty(V, 3, 2, dtype=torch.int32, device=pred.device)
+    check(lib.ivlm_seg_iou_counts(pred.data_ptr(), gt.data_ptr(), _SEG_GT_CODE[gt.dtype], V, H, W, int(ignore_label),
+                                  out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "seg_iou_counts")
+    return out
+
+
+def afford_thresholds(device):
+    """The reference's IOU_THRESHOLD = np.linspace(0, 1, 20), rounded to fp32 on the host (torch compares an fp32 tensor with
+    a scalar in fp32) and kept on the device: uploaded once per device."""
+    import numpy as np
+
+    key = str(device)
+    if key not in _AFFORD_THRESHOLDS:
+        _AFFORD_THRESHOLDS[key] = torch.from_numpy(np.linspace(0, 1, 20).astype(np.float32)).to(device)
+    return _AFFORD_THRESHOLDS[key]
+
+
+def affordance_metrics(gt, pred, thresholds=None):
+    """get_o_affordance_metrics (utils/eval_utils.py:153-213) per sample: gt, pred f32 [B,n] -> (f32 [B,4] = (sim, mae, auc,
+    aiou), i32 [B] valid flags); auc and aiou are NaN where valid is 0 (single-class gt or non-finite pred)."""
+    lib = _lib.load()
+    gt = _req(gt, torch.float32, "gt")
+    pred = _req(pred, torch.float32, "pred")
+    if pred.dim() != 2 or gt.shape != pred.shape:
+        raise IvlmError(f"affordance_metrics: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} must be the same [B,n]")
+    thr = afford_thresholds(pred.device) if thresholds is None else _req(thresholds, torch.float32, "thresholds")
+    B, n = pred.shape
+    out = torch.empty(B, 4, dtype=torch.float32, device=pred.device)
+    valid = torch.empty(B, dtype=torch.int32, device=pred.device)
+    check(lib.ivlm_afford_metrics(gt.data_ptr(), pred.data_ptr(), B, n, thr.data_ptr(), thr.numel(), 2048.0, out.data_ptr(),
+                                  valid.data_ptr(), _stream()), "afford_metrics")
+    return out, valid
+
+
+def h_geo_metric_per_sample(pred, gt, dist):
+    """get_h_geo_metric (utils/eval_utils.py:129-151) without its batch mean: -> f32 [B,2] = (fp, fn) distance per sample,
+    left on the device (no synchronisation)."""
     lib = _lib.load()
     pred = _req(pred, torch.float32, "pred")
     gt = _req(gt, torch.float32, "gt")
@@ -1336,6 +1391,13 @@ def h_geo_metric(pred, gt, dist):
     out = torch.empty(B, 2, dtype=torch.float32, device=pred.device)
     check(lib.ivlm_h_geo_metric(dist.data_ptr(), pred.data_ptr(), gt.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(), nbytes,
                                 _stream()), "h_geo_metric")
+    return out
+
+
+def h_geo_metric(pred, gt, dist):
+    """get_h_geo_metric (utils/eval_utils.py:129-151) on the device: pred / gt f32 [B,n], dist f32 [n,n] ->
+    (fp_dist_avg, fn_dist_avg) python floats (batch means) and the per-sample f32 [B,2] tensor."""
+    out = h_geo_metric_per_sample(pred, gt, dist)
     m = out.mean(0)
     return float(m[0]), float(m[1]), out
 
