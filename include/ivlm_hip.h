@@ -779,6 +779,22 @@ int ivlm_contact_prf(const float *gt, const float *pred, int B, int n, float thr
 int ivlm_spmv_csr(const int32_t *row_ptr, const int32_t *col, const float *val, const float *x, int B, int rows,
                   int cols, float *y, ivlm_stream_t stream);
 
+/* Band census of a contact map around its decision thresholds (census.hip): p f32 [B,Nv] with row stride ld (elements), thr f32 [J]
+ * ON THE DEVICE, 1 <= J <= 4 -> counts i32 [B,J+1]: counts[b,j] = number of finite p[b,:] with fabsf(p - thr[j]) <= margin (compared in
+ * fp32; margin 0 counts exact hits), counts[b,J] = number of non-finite p[b,:] (in no band); mindist f32 [B,J] = the smallest
+ * fabsf(p - thr[j]) over the finite values of the row, +inf if there is none.  One block per row, no atomics: bit-reproducible. */
+int ivlm_contact_band_census(const float *p, int64_t ld, int B, int Nv, const float *thr, int J, float margin, int32_t *counts,
+                             float *mindist, ivlm_stream_t stream);
+/* Band census of the pixels a thresholded lift (ivlm_lift_mesh_plan, mode 1) selects from: logits f32 [V,HW] of ONE call, ent_pix /
+ * row_ptr the CSR of ivlm_lift_plan_build (n_rows = V * Nv rows; row / Nv is the view).  counts i32 [2]: counts[0] = number of plan
+ * ENTRIES whose pixel has fabsf(sigmoid(logit) - thr_p) <= margin_p, counts[1] = number of entries with a non-finite logit (in no
+ * band).  A pixel inside a triangle has one entry per corner, so only zero against non-zero is meaningful.  The workspace holds the
+ * per-block partial counts, summed in block order by a second launch (no atomics: bit-reproducible). */
+size_t ivlm_mask_band_census_workspace_bytes(void);
+int ivlm_mask_band_census(const float *logits, int V, int64_t HW, const int32_t *ent_pix, const int32_t *row_ptr, int n_rows,
+                          float thr_p, float margin_p, int32_t *counts, void *workspace, size_t workspace_bytes,
+                          ivlm_stream_t stream);
+
 /* get_segmentation_metrics / intersectionAndUnionGPU with K = 2 (utils/eval_utils.py:27-61): pred f32 [V,H,W] = the mask values
  * as evaluate returns them, class 1 where pred > 0 (on the 'oafford' 'HM' views the masks are probabilities, so that holds in the
  * whole valid region, as in the reference); gt [V,H,W] of gt_dtype (IVLM_SEG_GT_*; f32 is truncated like .int()) -> out i32

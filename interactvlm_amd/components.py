@@ -103,6 +103,10 @@ class ObjectMeshContact3DPredictor(torch.nn.Module):
         self._plans = collections.OrderedDict()
         self._seen_once = collections.OrderedDict()
         self.max_plans = 8
+        # record_lift (set by the caller for the span of a call): last_lift = ("plan", plan, logits) or ("dense", None, None) says
+        # how the last lift ran, for the band census of the pixels it selected from (model.evaluate(exact_sets=...))
+        self.record_lift = False
+        self.last_lift = None
 
     # -- table sources ---------------------------------------------------------------------
     @staticmethod
@@ -148,6 +152,8 @@ class ObjectMeshContact3DPredictor(torch.nn.Module):
                     while len(self._seen_once) > 4096:
                         self._seen_once.popitem(last=False)
                 out = ops.lift_mesh_dense(logits, vid, bary, nv, mode=1, param=self.threshold)
+        if self.record_lift:
+            self.last_lift = ("plan", plan, logits) if plan is not None else ("dense", None, None)
         return out.to(dtype)
 
     def forward_inference(self, seg_maps, device, dtype, ds_names=None, lift2d_dict_path=None):

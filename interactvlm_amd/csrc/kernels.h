@@ -158,6 +158,13 @@ int contact_prf(const float* gt, const float* pred, int B, int n, float thr, flo
 int spmv_csr(const int32_t* row_ptr, const int32_t* col, const float* val, const float* x, int B, int rows, int cols,
              float* y, hipStream_t st);
 
+// ---- band census of a result around its decision thresholds (census.hip) ---------------------------------
+int contact_band_census(const float* p, int64_t ld, int B, int nv, const float* thr, int J, float margin, int32_t* counts,
+                        float* mindist, hipStream_t st);
+size_t mask_band_census_workspace_bytes();
+int mask_band_census(const float* logits, int V, int64_t HW, const int32_t* ent_pix, const int32_t* row_ptr, int n_rows,
+                     float thr_p, float margin_p, int32_t* counts, void* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- metrics of the validate() loop (validate_metrics.hip) ---------------------------------------------
 size_t seg_iou_workspace_bytes(int V);
 int seg_iou_counts(const float* pred, const void* gt, int gt_dtype, int V, int H, int W, int ignore_label, int32_t* out, void* ws,

@@ -20,6 +20,7 @@ from typing import List, Optional
 import torch
 
 from . import decoding, graphs, ops
+from . import exact_sets as _es
 from .components import HumanContact3DPredictor, ObjectMeshContact3DPredictor, ObjectPCAfford3DPredictor
 from .constants import IGNORE_LABEL, IMAGE_TOKEN_INDEX
 from .heads import SamFusionHead, UncertaintyHead
@@ -69,8 +70,12 @@ class _CamPoseEncoder:
 
 class InteractVLMForCausalLM:
     def __init__(self, config: IvlmCfg, weights: dict, device="cuda:0", lift_tables=None, metadata_root="./data",
-                 max_len=1024, precision=None):
+                 max_len=1024, precision=None, nonfinite_fallback=None):
         c = self.config = config
+        if nonfinite_fallback is not None:  # the mode a non-finite fp16-mode result is recomputed in: "bf16" (default) or "parity"
+            if nonfinite_fallback not in ("bf16", "parity"):
+                raise ValueError(f"nonfinite_fallback must be 'bf16' or 'parity', got {nonfinite_fallback!r}")
+            self.nonfinite_fallback = nonfinite_fallback
         self.device = dev = torch.device(device)
         w = weights
         self.hC_sam_view_type, self.oC_sam_view_type = c.hC_sam_view_type, c.oC_sam_view_type
@@ -203,6 +208,10 @@ class InteractVLMForCausalLM:
     fp8 = False
     # evaluate / evaluate_batch: recompute a non-finite result of an fp16-operand mode with bf16 operands (IVLM_NONFINITE_GUARD=0: off)
     nonfinite_guard = os.environ.get("IVLM_NONFINITE_GUARD", "1") != "0"
+    # ... or, opt-in (constructor keyword / attribute), in the "parity" mode: same exponent range, and the recomputed result is the
+    # set-exact one instead of the 8 x coarser bf16 one - at the parity mode's cost and residency (see _recompute_in)
+    nonfinite_fallback = "bf16"
+    recomputations = None  # {mode: number of calls recomputed in it} since construction (bookkeeping: tests, validate's re-run rate)
 
     def _guard_applies(self):
         return (self.nonfinite_guard and not self.fp8 and self.precision in ("default", "f16", "parity-fast")
@@ -220,7 +229,7 @@ class InteractVLMForCausalLM:
         try:
             out = fn(*args, **kwargs)
             if not self._guard_ok(out, supplied_embeddings):
-                out = self._recompute_bf16(lambda: fn(*args, **kwargs))
+                out = self._recompute_fallback(lambda: fn(*args, **kwargs))
             return out
         finally:
             self._in_guard = False
@@ -228,34 +237,71 @@ class InteractVLMForCausalLM:
     def _guard_ok(self, out, supplied_embeddings=None):
         """the one flag of a guarded call (tower outputs collected by _decode_sample + every contact tensor of the result finite);
         non-finite embeddings that the CALLER supplied raise"""
-        outs = out if isinstance(out, list) else [out]
-        flags = self._finite_flags + [torch.isfinite(o[k]).all() for o in outs
-                                      for k in ("pred_contact_3d", "pred_human_3d_contact", "pred_object_3d_contact",
-                                                "pred_object_3d_afford") if o.get(k) is not None]
+        flags = self._guard_flags(out)
         if not flags or bool(torch.stack(flags).all()):
             return True
+        self._check_supplied(supplied_embeddings)
+        return False
+
+    def _guard_flags(self, out):
+        outs = out if isinstance(out, list) else [out]
+        return self._finite_flags + [torch.isfinite(o[k]).all() for o in outs
+                                     for k in ("pred_contact_3d", "pred_human_3d_contact", "pred_object_3d_contact",
+                                               "pred_object_3d_afford") if o.get(k) is not None]
+
+    def _check_supplied(self, supplied_embeddings):
         if supplied_embeddings is not None:
             embs = supplied_embeddings if isinstance(supplied_embeddings, (list, tuple)) else [supplied_embeddings]
             if not all(bool(torch.isfinite(e).all()) for e in embs):
                 raise ops.IvlmError("image_embeddings passed by the caller are not finite (an fp16-mode encoder pass that "
                                     "overflowed?): re-encode them, e.g. model.precompute_visual_embs(views) - which checks")
-        return False
 
     def _recompute_bf16(self, fn):
         import warnings
 
         warnings.warn(f"non-finite contacts in precision mode {self.precision!r} (an activation left fp16's exponent "
                       "range): this call is recomputed with bf16 operands; consider model.set_precision('bf16')")
+        out = self._recompute_in("bf16", fn)
+        for o in (out if isinstance(out, list) else [out]):
+            o["recomputed_in_bf16"] = True
+        return out
+
+    def _recompute_fallback(self, fn):
+        """the non-finite guard's recomputation, in the mode `nonfinite_fallback` names"""
+        if self.nonfinite_fallback != "parity":
+            return self._recompute_bf16(fn)
+        import warnings
+
+        warnings.warn(f"non-finite contacts in precision mode {self.precision!r} (an activation left fp16's exponent "
+                      "range): this call is recomputed in the parity mode (nonfinite_fallback='parity')")
+        out = self._recompute_in("parity", fn)
+        for o in (out if isinstance(out, list) else [out]):
+            o["recomputed_in_parity"] = True
+        return out
+
+    def _recompute_in(self, target, fn, unpacked_decode=True):
+        """fn() under a TEMPORARY switch to the precision mode `target` ("bf16": the non-finite guard; "parity": the guard with
+        nonfinite_fallback="parity", and the exact_sets re-run).  unpacked_decode: the decode step on the bf16 weights, whose fp32
+        activations have the full fp32 range (the guard's reason to recompute); the exact_sets re-run has no range problem and
+        keeps the decode step of a plain call, so that its result IS that of set_precision("parity") + evaluate.  Residency: both targets read the bf16 originals of the LLaMA
+        matrices, which the default mode has released (36 -> 23 GB for 7B): the first recomputation rebuilds them from the packed
+        planes and they STAY resident (+13 GB for 7B) until the next explicit set_precision; "parity" also keeps its hi + lo KV
+        planes.  A deployment that cannot afford that leaves exact_sets off and nonfinite_fallback at its default, or calls
+        set_precision(model.precision) after a re-run to release them."""
         # The mode switch is TEMPORARY: nothing is released for it (the fp16 copies / packed planes of `mode` stay, the bf16
         # matrices are rebuilt from the planes and kept until the next explicit set_precision) - a fallback must not churn tens of GB
         # of weights, least of all under a pipelined evaluate_batch whose next chunk is already enqueued on the copies of `mode`
         # (ADVICE r5).  In that deferred mode a fallback also SERIALISES the pipeline: the recomputation is enqueued behind the
         # next chunk's work and that chunk's captured decode graphs are re-captured after the switch back.
         mode, packed, free = self.precision, self.llm.decode_packed, self.free_unused_weights
-        self.llm.decode_packed = False
+        if unpacked_decode:
+            self.llm.decode_packed = False
         self.free_unused_weights = False
+        if self.recomputations is None:
+            self.recomputations = {}
+        self.recomputations[target] = self.recomputations.get(target, 0) + 1
         try:
-            self.set_precision("bf16")
+            self.set_precision(target)
             out = fn()
         finally:
             self.llm.decode_packed = packed
@@ -263,9 +309,69 @@ class InteractVLMForCausalLM:
                 self.set_precision(mode)
             finally:
                 self.free_unused_weights = free
-        for o in (out if isinstance(out, list) else [out]):
-            o["recomputed_in_bf16"] = True
         return out
+
+    # ---- exact_sets (opt-in): certify the vertex-id sets of a call, or re-run it in the parity mode and say so ------------------
+    # After the pass in the model's mode the band census runs on the call's stream (ops.contact_band_census over pred_contact_3d;
+    # for a plan-backed object-mesh lift also ops.mask_band_census at the lift's own threshold) and its counts travel to the host
+    # TOGETHER with the non-finite flag of the guard: one read per call, where the guard alone reads one as well.  Band empty: the
+    # result of the pass, untouched, plus result["exact_sets"] (exact_sets.report).  Band not empty, a non-finite value, or a lift
+    # through single-use dense tables (no plan to census: "uncensused"): the images concerned are re-run in "parity" (the whole
+    # call: no partial re-run, so the result is bit for bit what set_precision("parity") + the same call returns) and carry
+    # "escalated": True with the parity pass's own census at exact_sets.PARITY_MARGIN.  A model that already runs in "parity" is
+    # censused at that margin and never re-run.  Residency of a re-run: _recompute_in.
+    # A NON-FINITE first pass under exact_sets is re-run in "parity" whatever `nonfinite_fallback` says (a bf16 recomputation could not
+    # be certified), without the guard's warning and without a recomputed_in_* flag: "reason": "nonfinite" in the report records it.
+    def _exact_sets_pass(self, cfg, produce, rerun, supplied_embeddings=None):
+        """produce() -> the results of the pass in the model's mode (a list, one per image); rerun(idx) -> the results of the images
+        idx, called under the parity mode."""
+        if self.fp8 or self.precision == "bf16":
+            raise ops.IvlmError(f"exact_sets: the margin is no error bound of the {'fp8' if self.fp8 else 'bf16'} mode "
+                                "(use the default mode, 'parity-fast' or 'parity')")
+        own_parity = self.precision == "parity"
+        margin = _es.PARITY_MARGIN if own_parity else cfg["margin"]
+        mask_margin = _es.PARITY_MARGIN if own_parity else cfg["mask_margin"]
+        thr, J = cfg["thresholds"], len(cfg["thresholds"])
+        guard = self._guard_applies()
+        mesh = self.object_3d_contact_predictor
+        mask_thr = mesh.threshold if mesh is not None else 0.3
+        self._in_guard = guard  # (the calls inside do not guard themselves; _decode_sample collects the tower flags)
+        self._finite_flags = []
+        self._lift_log = {}
+        if mesh is not None:
+            mesh.record_lift = True
+        try:
+            outs = produce()
+            parts, layout = _es.launch(outs, self._lift_log, thr, margin, mask_margin, mask_thr, ops)
+            ok, recs = _es.read(self._guard_flags(outs) if guard else [], parts, layout)
+            if not ok:
+                self._check_supplied(supplied_embeddings)
+            need = {} if own_parity else _es.select(ok, recs)
+            reports = [_es.report(r, margin, J) for r in recs]
+            if need:
+                idx = sorted(need)
+                self._lift_log = {}
+                # (a non-finite first pass is the guard's case: its re-run decodes on the bf16 weights, as the guard's does)
+                sub = self._recompute_in("parity", lambda: rerun(idx), unpacked_decode="nonfinite" in need.values())
+                parts, layout = _es.launch(sub, self._lift_log, thr, _es.PARITY_MARGIN, _es.PARITY_MARGIN, mask_thr, ops)
+                _, precs = _es.read([], parts, layout)
+                outs = _es.splice(outs, idx, sub)
+                for i, pr in zip(idx, precs):
+                    reports[i] = _es.report(recs[i], margin, J, parity_rec=pr, reason=need[i])
+            for o, rep in zip(outs, reports):
+                o["exact_sets"] = rep
+            return outs
+        finally:
+            self._in_guard = False
+            self._lift_log = None
+            if mesh is not None:
+                mesh.record_lift, mesh.last_lift = False, None
+
+    _lift_log = None  # {image index: how its object-mesh lift ran} while an exact_sets pass collects it
+
+    def _log_lift(self, b):
+        if self._lift_log is not None:
+            self._lift_log[b] = self.object_3d_contact_predictor.last_lift
 
     def _finite_or_bf16(self, fn):
         """tensor-returning encoder entry points under the fp16 exponent-range guard: a non-finite result is recomputed with bf16
@@ -630,7 +736,7 @@ class InteractVLMForCausalLM:
 
     def evaluate_batch(self, images_clip, images, input_ids_list, cam_params, resize_list, original_size_list,
                        contact_type="hcontact", max_new_tokens=32, forced_new_tokens=None, eos_token_id=2,
-                       lift2d_dict_path=None, image_embeddings=None, deferred=False, share_prefix=False):
+                       lift2d_dict_path=None, image_embeddings=None, deferred=False, share_prefix=False, exact_sets=None):
         """``evaluate`` for B images in one call: images_clip [B,3,h,w], images [B,V,3,S,S], one prompt per image.
         The SAM encoder of every image runs on the side stream while the B sequences decode together; the masks of all
         images are lifted in one launch.  -> [{'output_ids','pred_masks','pred_contact_3d'}] * B, each equal to what
@@ -641,7 +747,10 @@ class InteractVLMForCausalLM:
         image_embeddings: pre-computed SAM embeddings, one [V, g*g, 256] tensor for all samples (the four
         canonical body renders of hcontact are the same for every image) or a list of B; ``images`` is then not encoded.
         share_prefix (opt-in): B questions about one picture share the prompt prefix in the prefill and in every decode step
-        (``generate_batch``); the result dicts are the same."""
+        (``generate_batch``); the result dicts are the same.
+        exact_sets (opt-in, see ``evaluate``): the band census runs per image; only the images whose band is not empty are re-run,
+        in ONE parity evaluate_batch call over that subset, and spliced back - every result carries its own "exact_sets" report.
+        With deferred=True the census and a re-run happen in the finaliser."""
         # deferred=True: everything that does not depend on the encoder is ENQUEUED now (SAM encoder on the side stream, CLIP +
         # prefill + the batched decode loop on the caller's stream) and a function is returned that enqueues the tail (mask decoders,
         # lift) and returns the results.  A caller with several chunks begins chunk c + 1 before it finishes chunk c
@@ -668,7 +777,7 @@ class InteractVLMForCausalLM:
             def finish_all():
                 outs, pending = [], None
                 for sub in subs:
-                    nxt_ = self.evaluate_batch(*sub, deferred=True, share_prefix=share_prefix)
+                    nxt_ = self.evaluate_batch(*sub, deferred=True, share_prefix=share_prefix, exact_sets=exact_sets)
                     if pending is not None:
                         outs.extend(pending())
                     pending = nxt_
@@ -676,9 +785,15 @@ class InteractVLMForCausalLM:
                 return outs
             return finish_all if deferred else finish_all()
         guard = self._guard_applies()  # (fp16 exponent range: see _guarded)
+        es = _es.config(exact_sets)
         st = self._evaluate_batch_begin(*args, share_prefix=share_prefix)
 
         def finish():
+            if es is not None:
+                return self._exact_sets_pass(
+                    es, lambda: self._evaluate_batch_finish(st),
+                    lambda idx: self.evaluate_batch(*_es.subset_batch_args(args, idx), share_prefix=share_prefix),
+                    supplied_embeddings=image_embeddings)
             if not guard:
                 return self._evaluate_batch_finish(st)
             self._in_guard = True
@@ -686,7 +801,7 @@ class InteractVLMForCausalLM:
             try:
                 outs = self._evaluate_batch_finish(st)
                 if not self._guard_ok(outs, image_embeddings):
-                    outs = self._recompute_bf16(lambda: self.evaluate_batch(*args, share_prefix=share_prefix))
+                    outs = self._recompute_fallback(lambda: self.evaluate_batch(*args, share_prefix=share_prefix))
                 return outs
             finally:
                 self._in_guard = False
@@ -753,12 +868,29 @@ class InteractVLMForCausalLM:
                 # every object has its own mesh and tables (components.py:463: batch size 1): one lift per image
                 outs[b]["pred_contact_3d"] = self.object_3d_contact_predictor(
                     [lows[b]], ds_names=["ocontact"], lift2d_dict_path=paths[b])
+                self._log_lift(b)
         return outs
 
     def evaluate(self, images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                  lift2d_dict_path=None, contact_type="hcontact", max_new_tokens=32, tokenizer=None,
-                 forced_new_tokens=None, eos_token_id=2, image_embeddings=None, draft=None):
+                 forced_new_tokens=None, eos_token_id=2, image_embeddings=None, draft=None, exact_sets=None):
         """Generate -> [SEG] hidden state -> SAM decode -> lift (InteractVLM.py:510-638).
+
+        exact_sets (opt-in; None: this call and its result dict are exactly what they were): True or
+        dict(thresholds=(0.5, 0.3), margin=1e-3, mask_margin=None).  The vertex-id sets {p >= thr} / {p > thr} of a pass whose
+        per-vertex error is below `margin` (1e-3: the project's parity bar, which the default mode holds) can differ from the
+        fp32 oracle's only at vertices within `margin` of a threshold.  A device-side census counts those (and, for the
+        thresholded object-mesh lift, the plan pixels within `mask_margin` - None: `margin` - of the lift's 0.3); its counts are
+        read with the non-finite flag, one host read.  Band empty: the result of this pass plus result["exact_sets"] =
+        {"certified": True, "escalated": False, "in_band", "min_distance", "margin", "mask_band"}.  Otherwise the call is re-run
+        in the "parity" mode and that result is returned with "escalated": True, the "reason", and the parity pass's own census
+        at 1e-5 under "parity" ("certified" False: even the parity mode sits within its error of a threshold).  A lift through
+        single-use dense tables has no plan to census ("mask_band": "uncensused") and is always re-run.  A non-finite first pass
+        is re-run in "parity" too, whatever `nonfinite_fallback` is, silently: "reason": "nonfinite" records it (no warning, no
+        recomputed_in_* flag).  "certified" vouches for
+        the sets AS FAR AS `margin` bounds the pass's error: it is a check of the result against the bound, not a proof of the
+        bound.  Memory: a re-run rebuilds the bf16 originals of the LLaMA matrices that the default mode releases and keeps them
+        (+13 GB for 7B) until the next explicit set_precision (``_recompute_in``).
 
         draft (opt-in): speculative greedy decoding with these proposals (``generate``, ``speculative.Drafter``); same ids.
 
@@ -766,6 +898,12 @@ class InteractVLMForCausalLM:
         (``precompute_visual_embs``).  For hcontact the SAM inputs are the SAME four canonical body renders for
         every sample (run_demo.py:279-292, datasets/hcontact_3d.py:268-271), so they can be encoded once."""
         assert input_ids.shape[0] == 1, "the reference only ever calls evaluate with batch 1 (evaluate.py:479)"
+        es = _es.config(exact_sets)
+        if es is not None:
+            one = lambda: [self.evaluate(images_clip, images, input_ids, cam_params, resize_list, original_size_list,
+                                         lift2d_dict_path, contact_type, max_new_tokens, tokenizer, forced_new_tokens,
+                                         eos_token_id, image_embeddings, draft)]
+            return self._exact_sets_pass(es, one, lambda idx: one(), supplied_embeddings=image_embeddings)[0]
         if self._guard_applies():
             return self._guarded(self.evaluate, (images_clip, images, input_ids, cam_params, resize_list, original_size_list,
                                                  lift2d_dict_path, contact_type, max_new_tokens, tokenizer, forced_new_tokens,
@@ -839,6 +977,7 @@ class InteractVLMForCausalLM:
                 # same operator precedence as the reference (InteractVLM.py:626): 'oafford' always takes the mesh lift
                 pred_contact_3d = self.object_3d_contact_predictor(pred_masks, ds_names=["ocontact"],
                                                                    lift2d_dict_path=lift2d_dict_path)
+                self._log_lift(0)
         result = {"output_ids": output_ids, "pred_masks": pred_masks, "pred_contact_3d": pred_contact_3d}
         if self.use_uncertainty:
             result["uncertainty_maps"] = [self._eval_uncertainty(image_embeddings, original_size_list[0])]

@@ -1325,6 +1325,74 @@ def contact_prf(gt, pred, threshold=0.5):
 o_contact_prf = contact_prf  # get_o_contact_metrics (utils/eval_utils.py:96-125): the same arithmetic under the object name
 
 
+_BAND_THRESHOLDS = {}
+
+
+def band_thresholds(thresholds, device):
+    """The thresholds of a band census as an fp32 device tensor, uploaded once per (values, device)."""
+    key = (tuple(float(t) for t in thresholds), str(device))
+    if key not in _BAND_THRESHOLDS:
+        _BAND_THRESHOLDS[key] = torch.tensor(key[0], dtype=torch.float32).to(device)
+    return _BAND_THRESHOLDS[key]
+
+
+def contact_band_census(p, thresholds, margin):
+    """Which vertices could change side of a threshold under an error of ``margin``: p f32 [B,Nv] (rows may be strided: a
+    column slice of a wider buffer), thresholds an f32 [J] device tensor or 1 - 4 numbers -> (counts i32 [B,J+1], mindist f32
+    [B,J]) on the device, nothing is read back.  counts[b,j] = number of finite p[b] with |p - thr_j| <= margin in fp32,
+    counts[b,J] = number of non-finite p[b] (in no band), mindist[b,j] = smallest |p - thr_j| over the finite p[b] (+inf if
+    none)."""
+    lib = _lib.load()
+    if not isinstance(p, torch.Tensor) or not p.is_cuda:
+        raise IvlmError("p: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if p.dtype != torch.float32 or p.dim() != 2 or p.shape[0] < 1 or p.shape[1] < 1:
+        raise IvlmError(f"p: expected a non-empty f32 [B,Nv] tensor, got {p.dtype} {tuple(p.shape)}")
+    B, nv = p.shape
+    if nv > 1 and p.stride(1) != 1:
+        raise IvlmError("p: the vertices of a row must be contiguous")
+    ld = nv if B == 1 else p.stride(0)
+    if ld < nv:
+        raise IvlmError(f"p: row stride {ld} is smaller than the row length {nv}")
+    thr = thresholds if isinstance(thresholds, torch.Tensor) else band_thresholds(thresholds, p.device)
+    thr = _req(thr, torch.float32, "thresholds")
+    J = thr.numel()
+    if thr.dim() != 1 or not 1 <= J <= 4 or thr.device != p.device:
+        raise IvlmError("thresholds: expected 1 to 4 values on the device of p")
+    if not float(margin) >= 0.0:
+        raise IvlmError(f"margin must be >= 0, got {margin}")
+    counts = torch.empty(B, J + 1, dtype=torch.int32, device=p.device)
+    mindist = torch.empty(B, J, dtype=torch.float32, device=p.device)
+    check(lib.ivlm_contact_band_census(p.data_ptr(), ld, B, nv, thr.data_ptr(), J, float(margin), counts.data_ptr(),
+                                       mindist.data_ptr(), _stream()), "contact_band_census")
+    return counts, mindist
+
+
+def mask_band_census(logits, plan: LiftPlan, threshold=0.3, margin=1e-3):
+    """Which pixels a thresholded lift (``lift_mesh_plan(mode=1)``) could select differently under an error of ``margin`` on
+    sigmoid(logit): logits f32 [V,H,W] (or [1,V,H,W]) of one call -> counts i32 [2] on the device = (plan ENTRIES whose pixel has
+    |sigmoid(logit) - threshold| <= margin, entries with a non-finite logit).  A pixel has one entry per triangle corner it votes
+    for and pixels outside the plan have none: read it as zero / non-zero."""
+    lib = _lib.load()
+    logits = _req(logits, torch.float32, "logits")
+    if logits.dim() == 4 and logits.shape[0] == 1:
+        logits = logits[0]
+    if logits.dim() != 3 or logits.shape[0] != plan.V or logits[0].numel() != plan.HW:
+        raise IvlmError(f"logits {tuple(logits.shape)} do not match the lift plan (V={plan.V}, HW={plan.HW})")
+    if plan.row_ptr.device != logits.device:
+        raise IvlmError("logits and the lift plan are on different devices")
+    if not float(margin) >= 0.0:
+        raise IvlmError(f"margin must be >= 0, got {margin}")
+    counts = torch.zeros(2, dtype=torch.int32, device=logits.device)
+    if plan.nnz == 0:
+        return counts
+    nbytes = lib.ivlm_mask_band_census_workspace_bytes()
+    ws = _workspace(nbytes, logits.device)
+    check(lib.ivlm_mask_band_census(logits.data_ptr(), plan.V, plan.HW, plan.ent_pix.data_ptr(), plan.row_ptr.data_ptr(),
+                                    plan.V * plan.num_vertices, float(threshold), float(margin), counts.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream()), "mask_band_census")
+    return counts
+
+
 _SEG_GT_CODE = {torch.uint8: 0, torch.int32: 1, torch.float32: 2}  # IVLM_SEG_GT_*
 _AFFORD_THRESHOLDS = {}
 

@@ -134,16 +134,22 @@ def _to_device(input_dict, device):
     return out
 
 
-def validate(model, samples, ds_name, inference_type="generate", dist_matrix=None, group=None, evaluate_kwargs=None, metrics=None):
+def validate(model, samples, ds_name, inference_type="generate", dist_matrix=None, group=None, evaluate_kwargs=None, metrics=None,
+             exact_sets=None):
     """Score ``samples`` (an iterable of collate_fn-shaped dicts, batch 1 as in the reference's val loader) for dataset
     ``ds_name``.  -> {"giou", "ciou", "avg_*" of the task, "saved_results", "count", "task", "meters": the reduced sums and counts}.
 
     dist_matrix: the f32 [Nv,Nv] geodesic matrix on the device, required for 'hcontact' (the reference loads it from a data
     file at import time).  evaluate_kwargs: extra arguments of model.evaluate in 'generate' mode (e.g. forced_new_tokens for
     weights that never emit [SEG]).  metrics: the provider of seg_iou_counts / affordance_metrics / contact_prf /
-    o_contact_prf / h_geo_metric_per_sample; the HIP kernels of ``ops`` unless another is given."""
+    o_contact_prf / h_geo_metric_per_sample; the HIP kernels of ``ops`` unless another is given.
+    exact_sets ('generate' mode; None: off, nothing changes): forwarded to model.evaluate, which certifies each sample's
+    vertex-id sets or re-runs the sample in the parity mode; saved_results gains "escalated" (one bool per sample) and the
+    result "rerun_rate" (their mean).  No metric is added or changed."""
     if inference_type not in ("generate", "forward"):
         raise ValueError(f"inference_type must be 'generate' or 'forward', got {inference_type!r}")
+    if exact_sets is not None and inference_type != "generate":
+        raise ValueError("exact_sets is an option of model.evaluate: inference_type must be 'generate'")
     if metrics is None:
         from . import ops as metrics
     task = task_of(ds_name, model)
@@ -155,6 +161,7 @@ def validate(model, samples, ds_name, inference_type="generate", dist_matrix=Non
     saved = {"imgnames": [], "pred": [], "gt": []}
     if task == "hcontact":
         saved["objnames"] = []
+    escalated = []
     per_sample = []  # one fp64 [len(names)] device tensor per sample: what the reference appends to its lists
     one = torch.ones((), dtype=torch.float64, device=device)
 
@@ -170,11 +177,15 @@ def validate(model, samples, ds_name, inference_type="generate", dist_matrix=Non
             mask_path = input_dict["mask_paths_list"][0] if "mask_paths_list" in input_dict else None
             kw = dict(max_new_tokens=512)
             kw.update(evaluate_kwargs or {})
+            if exact_sets is not None:
+                kw["exact_sets"] = exact_sets
             ev = model.evaluate(images_clip=input_dict["images_clip"], images=input_dict["images"], input_ids=ids,
                                 cam_params=input_dict["cam_params"], resize_list=input_dict["resize_list"],
                                 original_size_list=input_dict["resize_list"], lift2d_dict_path=mask_path,
                                 contact_type=input_dict["ds_name_list"][0], **kw)
             output_dict = {"pred_masks": ev["pred_masks"], "gt_masks": input_dict["masks_list"]}
+            if exact_sets is not None:
+                escalated.append(bool(ev["exact_sets"]["escalated"]))
             pred3d = ev.get("pred_contact_3d", None)
             if task == "hcontact":
                 output_dict["pred_human_3d_contact"] = torch.zeros_like(gt3d) if pred3d is None else pred3d
@@ -253,5 +264,8 @@ def validate(model, samples, ds_name, inference_type="generate", dist_matrix=Non
     saved["gt"] = host[off + total * width: off + 2 * total * width].view(total, width).to(torch.float32).numpy() if total else []
     for name in names:
         saved["avg_" + name] = result["avg_" + name]
+    if exact_sets is not None:
+        saved["escalated"] = escalated
+        result["rerun_rate"] = sum(escalated) / len(escalated) if escalated else 0.0
     result["saved_results"] = saved
     return result
