@@ -557,12 +557,13 @@ int ivlm_sam_encode(const ivlm_sam_cfg *cfg, const ivlm_sam_head *head, const iv
                     float *embeddings_out, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 /* The same stage in "parity" precision (the mode that holds 1e-3 against the reference's fp32 path at the real depth): no
  * activation is rounded to bf16 - split LayerNorm outputs, split-operand / split-output GEMMs, split-operand attention with fp32
- * rel-pos terms.  Same structs, its own workspace size (head dim 80). */
+ * rel-pos terms.  Same structs, its own workspace size (head dim 80).  Python counterpart of every ivlm_sam_encode* entry point:
+ * SamImageEncoder._forward (interactvlm_amd/sam.py) in the mode of the same name - "default", "parity", "parity-fast", "f16q". */
 size_t ivlm_sam_encode_parity_workspace_bytes(const ivlm_sam_cfg *cfg, int V);
 int ivlm_sam_encode_parity(const ivlm_sam_cfg *cfg, const ivlm_sam_head *head, const ivlm_sam_block *blocks_host, const void *images,
                            int V, float *embeddings_out, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 /* ... with the two MLP GEMMs of every block on IEEE fp16 operands (norm2 and the GELU epilogue write halves: 11 significant bits, an
- * eighth of the bf16 rounding error, ONE MFMA pass instead of two): the encoder of the "parity-encoder" mode - measured 4.6e-4
+ * eighth of the bf16 rounding error, ONE MFMA pass instead of two): the encoder of the "parity-fast" mode - measured 4.6e-4
  * end to end at depth 32 (the all-split stage: 4.0e-4) for 12 ms less per 4 views.  mlp16_host[l] = fp16 copies of block l's
  * lin1_w / lin2_w (ivlm_bf16_to_f16; exact for |w| >= 2^-14, within 2^-25 below).  Workspace: the parity size. */
 typedef struct {
@@ -576,7 +577,8 @@ int ivlm_sam_encode_parity_f16mlp(const ivlm_sam_cfg *cfg, const ivlm_sam_head *
  * halves, its lo half in the rel-pos table products of the attention kernels (fp32 rel-pos terms), k | v / proj / mlp on single fp16
  * operands, the neck on hi + lo bf16 operands.  4 - 6e-4 end to end against the fp32 oracle at depth 32 (bf16 operands: 6e-3 .. 1e-2)
  * for ~10 % more encoder time.  blocks16_host[l] = fp16 copies (ivlm_bf16_to_f16) of block l's qkv_w / proj_w / lin1_w / lin2_w, of
- * its q|k|v bias and of rel_cat.  SAM ViT shapes (head dim 80, 64 x 64 grid, windows of 2 * side <= 32). */
+ * its q|k|v bias and of rel_cat.  SAM ViT shapes (head dim 80, 64 x 64 grid, windows of 2 * side <= 32), else IVLM_ERR_UNSUPPORTED.
+ * (SamImageEncoder mode "f16q".) */
 typedef struct {
     const void *qkv_w16, *proj_w16, *lin1_w16, *lin2_w16, *qkv_b16, *rel_cat16;
 } ivlm_sam_block_f16;

@@ -15,6 +15,7 @@
 // bit-identical to the Python-sequenced path (tests/test_stages_gpu.py).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -41,22 +42,33 @@ namespace {
 
 inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// Hands out 256-byte aligned regions of a caller workspace.  Every stage names its buffers ONCE, in a carve_*() function: its body
+// runs that on the real workspace, its *_workspace_bytes on a measuring carver (Carver{}: no base, no limit) and returns `used`,
+// so a size cannot disagree with the takes.
 struct Carver {
-    char* p;
-    size_t left;
+    char* base = nullptr;
+    size_t room = SIZE_MAX, used = 0;
     bool ok = true;
     void* take(size_t bytes) {
         bytes = al(bytes);
-        if (bytes > left) {
+        if (bytes > room - used) {
             ok = false;
             return nullptr;
         }
-        void* r = p;
-        p += bytes;
-        left -= bytes;
-        return r;
+        used += bytes;
+        return base ? base + (used - bytes) : nullptr;
+    }
+    template <class T>
+    T* get(size_t count) {
+        return static_cast<T*>(take(count * sizeof(T)));
     }
 };
+template <class Carve, class... Args>
+size_t carved_bytes(Carve carve, Args... args) {
+    Carver measure;
+    carve(args..., measure);
+    return measure.used;
+}
 
 // The fused split-K reduction (SplitKFused, kernels.h) is OPT-IN for the stage sequencers, as it is for the host model
 // (ops.SPLITK_FUSED): on MI355X it measured 2 - 3 x SLOWER than the two-launch form (down_proj 64 -> 192 us, prefill 12.0 -> 26.3 ms;
@@ -151,12 +163,20 @@ static bool cfg_ok(const ivlm_llama_cfg* c) {
            c->max_len <= 4096 && (c->hidden & 7) == 0 && (c->inter & 7) == 0;
 }
 
+namespace {
+
+// (xa / xb: the two fp32 residual streams; sk: split-K partials, <= 8 slices of [T, N <= max(hidden, inter)])
+struct PrefillBufs { bf16_t *y, *qkv, *att, *hh; float *xa, *xb, *sk; size_t skb; };
+PrefillBufs carve_prefill(const ivlm_llama_cfg* c, int T, Carver& cv) {
+    const size_t t = T, h = c->hidden, in = c->inter, skb = 8 * t * std::max(h, in) * 4;
+    return {cv.get<bf16_t>(t * h), cv.get<bf16_t>(t * 3 * h), cv.get<bf16_t>(t * h), cv.get<bf16_t>(t * in),
+            cv.get<float>(t * h),  cv.get<float>(t * h),      cv.get<float>(skb / 4), skb};
+}
+
+}  // namespace
+
 extern "C" size_t ivlm_llama_prefill_workspace_bytes(const ivlm_llama_cfg* c, int T) {
-    if (!cfg_ok(c) || T <= 0) return 0;
-    const size_t h = c->hidden, in = c->inter, t = T;
-    size_t b = al(t * h * 2) + al(t * 3 * h * 2) + al(t * h * 2) + al(t * in * 2) + 2 * al(t * h * 4);
-    b += al(8 * t * std::max(h, in) * 4);  // split-K partials (<= 8 slices of [T, N <= hidden])
-    return b + 256;
+    return cfg_ok(c) && T > 0 ? carved_bytes(carve_prefill, c, T) : 0;
 }
 
 static int llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers_host, const void* final_norm, void* kcache,
@@ -166,20 +186,12 @@ static int llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers
     if (!cfg_ok(c) || !layers_host || !final_norm || !kcache || !vcache || !x_in || !hidden_out || !workspace || T <= 0 || pos0 < 0 ||
         pos0 + T > c->max_len)
         return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_llama_prefill_workspace_bytes(c, T)) return IVLM_ERR_WORKSPACE;
+    Carver cv{static_cast<char*>(workspace), workspace_bytes};
+    auto [y, qkv, att, hh, xa, xb, sk, skb] = carve_prefill(c, T, cv);
+    if (!cv.ok) return IVLM_ERR_WORKSPACE;
     hipStream_t st = ivlm_stream(stream);
     const int Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter;
-    Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    bf16_t* y = static_cast<bf16_t*>(cv.take((size_t)T * Hd * 2));
-    bf16_t* qkv = static_cast<bf16_t*>(cv.take((size_t)T * 3 * Hd * 2));
-    bf16_t* att = static_cast<bf16_t*>(cv.take((size_t)T * Hd * 2));
-    bf16_t* hh = static_cast<bf16_t*>(cv.take((size_t)T * I * 2));
-    float* xa = static_cast<float*>(cv.take((size_t)T * Hd * 4));
-    float* xb = static_cast<float*>(cv.take((size_t)T * Hd * 4));
-    const size_t skb = (size_t)8 * T * std::max(Hd, I) * 4;
-    float* sk = static_cast<float*>(cv.take(skb));
     if (int rc0 = sk_counters_zero(sk, skb, st)) return rc0;
-    if (!cv.ok) return IVLM_ERR_WORKSPACE;
     const int64_t cache_layer = (int64_t)c->max_len * Hd;
     const float* x = x_in;
     int rc;
@@ -232,78 +244,112 @@ extern "C" int ivlm_llama_prefill_f16(const ivlm_llama_cfg* c, const ivlm_llama_
                          workspace_bytes, stream, 1);
 }
 
-extern "C" size_t ivlm_llama_decode_workspace_bytes(const ivlm_llama_cfg* c) {
-    if (!cfg_ok(c)) return 0;
-    const size_t h = c->hidden, in = c->inter, L = c->layers;
-    // activations | fused-launch state: per-layer arrival counters (128 B apart), status + step words, per-layer attention rows
-    // + the split-KV attention partials of the packed step [heads][4][head_dim + 4] fp32
-    return al(3 * h * 4) + al(in * 4) + 2 * al(h * 4) + al(h * 4) + al(L * 32 * 4) + 256 + al(L * h * 4) + 256 +
-           al((size_t)c->heads * 4 * (h / c->heads + 4) * 4);
+namespace {
+
+// One carve for every form of the decode step (the caller zeroes it at the start of a generation, whichever form it then calls):
+// activations | the fused launch's state: per-layer arrival counters (128 B apart), words [0] status, [1] tokens decoded so far,
+// per-layer attention rows | the split-KV attention partials of the packed step [heads][4][head_dim + 4]
+struct DecodeBufs { float *qkv, *hh, *xa, *xb, *att; int32_t *counters, *words; float *scratch, *parts; };
+DecodeBufs carve_decode(const ivlm_llama_cfg* c, Carver& cv) {
+    const size_t h = c->hidden, L = c->layers, H = c->heads;
+    return {cv.get<float>(3 * h), cv.get<float>(c->inter), cv.get<float>(h), cv.get<float>(h), cv.get<float>(h),
+            cv.get<int32_t>(L * 32), cv.get<int32_t>(64), cv.get<float>(L * h), cv.get<float>(H * 4 * (h / H + 4))};
 }
 
-static int llama_decode_step(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers_host, const void* final_norm, void* kcache,
-                             void* vcache, const float* cos_tab, const float* sin_tab, const float* x_in, int32_t* pos_dev, int advance,
-                             float* hidden_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream, const int cache_f16) {
+// The "linear" of a decode step, out = act(W . rmsnorm(x)) + res on fp32 activations with exact products (rms: the norm weight of the
+// RMSNorm prologue or null; SwiGLU: N = 2 * inter interleaved gate / up rows -> inter outputs): on a bf16 matrix ...
+int dec_linear(const ivlm_llama_cfg* c, const float* x, const void* W, float* out, const float* res, int N, int K, int act,
+               const void* rms, ivlm_stream_t stream) {
+    return lin(x, 1, K, W, K, out, 1, act == ACT_SWIGLU ? N / 2 : N, res, res ? 1 : 0, 1, N, K, act, rms, rms ? c->eps : 0.f, nullptr, 0,
+               ivlm_stream(stream));
+}
+// ... or on a losslessly packed one
+int dec_linear(const ivlm_llama_cfg* c, const float* x, const ivlm_bf12m& m, float* out, const float* res, int N, int K, int act,
+               const void* rms, ivlm_stream_t stream) {
+    return ivlm_gemv1_bf12m(x, m.Pf, m.Ef, m.ebase, m.patch_ptr, m.patch_col, m.patch_val, out, nullptr, res, N, K, act, 1, rms,
+                            rms ? c->eps : 0.0f, res ? IVLM_GEMM_RES_F32 : 0, stream);
+}
+
+// The decode step, written once for Layer = ivlm_llama_layer (bf16 weights) and ivlm_llama_layer_bf12 (packed weights).  Attention
+// and o_proj take one of three forms:
+//   fused      one launch, the o_proj blocks wait on device counters (bf16 weights and cache, fuse_attn_oproj, a grid that fits the CUs)
+//   one block  one attention block per head, then o_proj as a linear (bf16 weights otherwise; packed weights with fuse_attn_oproj)
+//   split KV   four key ranges per head, merged by the prologue of the packed o_proj (packed weights: the host model's default)
+template <class Layer>
+int decode_step(const ivlm_llama_cfg* c, const Layer* layers_host, const void* final_norm, void* kcache, void* vcache, int cache_f16,
+                const float* cos_tab, const float* sin_tab, const float* x_in, int32_t* pos_dev, int advance, float* hidden_out,
+                void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
+    constexpr bool packed = std::is_same<Layer, ivlm_llama_layer_bf12>::value;
     ivlm_enter();
     if (!cfg_ok(c) || !layers_host || !final_norm || !kcache || !vcache || !cos_tab || !sin_tab || !x_in || !pos_dev || !hidden_out ||
         !workspace)
         return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_llama_decode_workspace_bytes(c)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    const int Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter;
     Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    float* qkv = static_cast<float*>(cv.take((size_t)3 * Hd * 4));
-    float* hh = static_cast<float*>(cv.take((size_t)I * 4));
-    float* xa = static_cast<float*>(cv.take((size_t)Hd * 4));
-    float* xb = static_cast<float*>(cv.take((size_t)Hd * 4));
-    float* att = static_cast<float*>(cv.take((size_t)Hd * 4));
-    int32_t* counters = static_cast<int32_t*>(cv.take((size_t)c->layers * 32 * 4));
-    int32_t* words = static_cast<int32_t*>(cv.take(256));  // [0] status, [1] tokens decoded so far (the caller zeroes the
-    float* scratch = static_cast<float*>(cv.take((size_t)c->layers * Hd * 4));  // workspace at the start of a generation)
+    const DecodeBufs b = carve_decode(c, cv);
     if (!cv.ok) return IVLM_ERR_WORKSPACE;
+    const int Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter;
+    if (packed && ((Hd & 63) || (I & 63))) return IVLM_ERR_UNSUPPORTED;  // (every matrix must take the fragment layout)
+    hipStream_t st = ivlm_stream(stream);
     static int cus = 0;
-    if (cus == 0) {
+    if (!packed && cus == 0) {
         int dev = 0;
         IVLM_HIP_TRY(hipGetDevice(&dev));
         IVLM_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    const bool fuse = !cache_f16 && c->fuse_attn_oproj && (Hd == 512 || Hd == 1024 || Hd == 4096 || Hd == 5120) && H + Hd / 32 <= cus;
+    const bool fused = !packed && !cache_f16 && c->fuse_attn_oproj && (Hd == 512 || Hd == 1024 || Hd == 4096 || Hd == 5120) &&
+                       H + Hd / 32 <= cus;
+    const bool split_kv = packed && !c->fuse_attn_oproj;
     const int64_t cache_layer = (int64_t)c->max_len * Hd;
     const float scale = 1.0f / sqrtf((float)D);
     const float* x = x_in;
-    int rc;
+    int rc = 0;
     for (int l = 0; l < c->layers; ++l) {
-        const ivlm_llama_layer& L = layers_host[l];
+        const Layer& L = layers_host[l];
         bf16_t* kc = static_cast<bf16_t*>(kcache) + l * cache_layer;
         bf16_t* vc = static_cast<bf16_t*>(vcache) + l * cache_layer;
-        if ((rc = lin(x, 1, Hd, L.qkv, Hd, qkv, 1, 3 * Hd, nullptr, 0, 1, 3 * Hd, Hd, ACT_NONE, L.ln1, c->eps, nullptr, 0, st))) return rc;
-        float* x1 = (x == xa) ? xb : xa;
-        if (fuse) {
-            rc = llama_attn_oproj(qkv, kc, vc, c->max_len, scratch + (size_t)l * Hd, static_cast<const bf16_t*>(L.o), x, x1, H, D,
-                                  c->theta, scale, cos_tab, sin_tab, pos_dev, words + 1, counters + l * 32, words, st);
-            if (rc) return rc;
+        if ((rc = dec_linear(c, x, L.qkv, b.qkv, nullptr, 3 * Hd, Hd, ACT_NONE, L.ln1, stream))) return rc;
+        float* x1 = (x == b.xa) ? b.xb : b.xa;
+        if (fused) {
+            if constexpr (!packed)
+                rc = llama_attn_oproj(b.qkv, kc, vc, c->max_len, b.scratch + (size_t)l * Hd, static_cast<const bf16_t*>(L.o), x, x1, H, D,
+                                      c->theta, scale, cos_tab, sin_tab, pos_dev, b.words + 1, b.counters + l * 32, b.words, st);
+        } else if (split_kv) {
+            if constexpr (packed) {
+                rc = llama_decode_attn_parts(b.qkv, kc, vc, c->max_len, b.parts, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev,
+                                             cache_f16);
+                if (!rc)
+                    rc = ivlm_gemv1_bf12m_parts(b.parts, D, L.o.Pf, L.o.Ef, L.o.ebase, L.o.patch_ptr, L.o.patch_col, L.o.patch_val, x1,
+                                                nullptr, x, Hd, Hd, ACT_NONE, 1, IVLM_GEMM_RES_F32, stream);
+            }
         } else {
-            if ((rc = llama_decode_attn(qkv, 1, kc, vc, c->max_len, att, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev, nullptr,
-                                        nullptr, cache_f16)))
-                return rc;
-            if ((rc = lin(att, 1, Hd, L.o, Hd, x1, 1, Hd, x, 1, 1, Hd, Hd, ACT_NONE, nullptr, 0.f, nullptr, 0, st))) return rc;
+            rc = llama_decode_attn(b.qkv, 1, kc, vc, c->max_len, b.att, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev, nullptr,
+                                   nullptr, cache_f16);
+            if (!rc) rc = dec_linear(c, b.att, L.o, x1, x, Hd, Hd, ACT_NONE, nullptr, stream);
         }
-        if ((rc = lin(x1, 1, Hd, L.gu, Hd, hh, 1, I, nullptr, 0, 1, 2 * I, Hd, ACT_SWIGLU, L.ln2, c->eps, nullptr, 0, st))) return rc;
-        float* x2 = (x1 == xa) ? xb : xa;
-        if ((rc = lin(hh, 1, I, L.down, I, x2, 1, Hd, x1, 1, 1, Hd, I, ACT_NONE, nullptr, 0.f, nullptr, 0, st))) return rc;
+        if (rc) return rc;
+        if ((rc = dec_linear(c, x1, L.gu, b.hh, nullptr, 2 * I, Hd, ACT_SWIGLU, L.ln2, stream))) return rc;
+        float* x2 = (x1 == b.xa) ? b.xb : b.xa;
+        if ((rc = dec_linear(c, b.hh, L.down, x2, x1, Hd, I, ACT_NONE, nullptr, stream))) return rc;
         x = x2;
     }
     if ((rc = rmsnorm(x, 1, static_cast<const bf16_t*>(final_norm), hidden_out, 1, 1, Hd, c->eps, st))) return rc;
-    bump_kernel<<<1, 1, 0, st>>>(fuse ? words + 1 : nullptr, advance ? pos_dev : nullptr);  // tokens decoded += 1 (position += 1)
+    // (position += 1; the fused launch also counts the tokens decoded so far)
+    bump_kernel<<<1, 1, 0, st>>>(fused ? b.words + 1 : nullptr, advance ? pos_dev : nullptr);
     return ivlm_launch_status();
+}
+
+}  // namespace
+
+extern "C" size_t ivlm_llama_decode_workspace_bytes(const ivlm_llama_cfg* c) {
+    return cfg_ok(c) ? carved_bytes(carve_decode, c) : 0;
 }
 
 extern "C" int ivlm_llama_decode_step(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers_host, const void* final_norm,
                                       void* kcache, void* vcache, const float* cos_tab, const float* sin_tab, const float* x_in,
                                       int32_t* pos_dev, int advance, float* hidden_out, void* workspace, size_t workspace_bytes,
                                       ivlm_stream_t stream) {
-    return llama_decode_step(c, layers_host, final_norm, kcache, vcache, cos_tab, sin_tab, x_in, pos_dev, advance, hidden_out, workspace,
-                             workspace_bytes, stream, 0);
+    return decode_step(c, layers_host, final_norm, kcache, vcache, 0, cos_tab, sin_tab, x_in, pos_dev, advance, hidden_out, workspace,
+                       workspace_bytes, stream);
 }
 
 // ... against the fp16 KV cache ivlm_llama_prefill_f16 fills: the bf16 weights of layers_host (fp32 activations, exact products, as
@@ -312,72 +358,19 @@ extern "C" int ivlm_llama_decode_step_f16kv(const ivlm_llama_cfg* c, const ivlm_
                                             void* kcache16, void* vcache16, const float* cos_tab, const float* sin_tab,
                                             const float* x_in, int32_t* pos_dev, int advance, float* hidden_out, void* workspace,
                                             size_t workspace_bytes, ivlm_stream_t stream) {
-    return llama_decode_step(c, layers_host, final_norm, kcache16, vcache16, cos_tab, sin_tab, x_in, pos_dev, advance, hidden_out,
-                             workspace, workspace_bytes, stream, 1);
+    return decode_step(c, layers_host, final_norm, kcache16, vcache16, 1, cos_tab, sin_tab, x_in, pos_dev, advance, hidden_out,
+                       workspace, workspace_bytes, stream);
 }
 
 // The same step with the four linears of a layer on losslessly packed weights (ivlm_gemv1_bf12m): the default decode path of the host
-// model.  Separate attention / o_proj launches; fp16 or bf16 KV cache.
+// model.  fp16 or bf16 KV cache; split-KV attention merged by the o_proj prologue unless fuse_attn_oproj asks for the one-block form.
 extern "C" int ivlm_llama_decode_step_bf12(const ivlm_llama_cfg* c, const ivlm_llama_layer_bf12* layers_host, const void* final_norm,
                                            void* kcache, void* vcache, int cache_dtype, const float* cos_tab, const float* sin_tab,
                                            const float* x_in, int32_t* pos_dev, int advance, float* hidden_out, void* workspace,
                                            size_t workspace_bytes, ivlm_stream_t stream) {
-    ivlm_enter();
-    if (!cfg_ok(c) || !layers_host || !final_norm || !kcache || !vcache || !cos_tab || !sin_tab || !x_in || !pos_dev || !hidden_out ||
-        !workspace || (cache_dtype != IVLM_BF16 && cache_dtype != IVLM_F16))
-        return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_llama_decode_workspace_bytes(c)) return IVLM_ERR_WORKSPACE;
-    const int Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter;
-    if ((Hd & 63) || (I & 63)) return IVLM_ERR_UNSUPPORTED;
-    hipStream_t st = ivlm_stream(stream);
-    Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    float* qkv = static_cast<float*>(cv.take((size_t)3 * Hd * 4));
-    float* hh = static_cast<float*>(cv.take((size_t)I * 4));
-    float* xa = static_cast<float*>(cv.take((size_t)Hd * 4));
-    float* xb = static_cast<float*>(cv.take((size_t)Hd * 4));
-    float* att = static_cast<float*>(cv.take((size_t)Hd * 4));
-    cv.take((size_t)c->layers * 32 * 4);  // (the regions of the other forms of the step: same workspace, same offsets)
-    cv.take(256);
-    cv.take((size_t)c->layers * Hd * 4);
-    float* parts = static_cast<float*>(cv.take((size_t)H * 4 * (D + 4) * 4));
-    const bool split = !c->fuse_attn_oproj;  // split-KV attention merged by the o_proj prologue (the host model's default);
-                                             // fuse_attn_oproj != 0 selects the one-block attention + separate o_proj instead
-    if (!cv.ok) return IVLM_ERR_WORKSPACE;
-    auto gemv = [&](const float* x, const ivlm_bf12m& m, float* out, const float* res, int N, int K, int act, const void* rms) {
-        return ivlm_gemv1_bf12m(x, m.Pf, m.Ef, m.ebase, m.patch_ptr, m.patch_col, m.patch_val, out, nullptr, res, N, K, act, 1, rms,
-                                rms ? c->eps : 0.0f, res ? IVLM_GEMM_RES_F32 : 0, stream);
-    };
-    const int64_t cache_layer = (int64_t)c->max_len * Hd;
-    const float scale = 1.0f / sqrtf((float)D);
-    const float* x = x_in;
-    int rc;
-    for (int l = 0; l < c->layers; ++l) {
-        const ivlm_llama_layer_bf12& L = layers_host[l];
-        bf16_t* kc = static_cast<bf16_t*>(kcache) + l * cache_layer;
-        bf16_t* vc = static_cast<bf16_t*>(vcache) + l * cache_layer;
-        if ((rc = gemv(x, L.qkv, qkv, nullptr, 3 * Hd, Hd, ACT_NONE, L.ln1))) return rc;
-        float* x1 = (x == xa) ? xb : xa;
-        if (split) {
-            if ((rc = llama_decode_attn_parts(qkv, kc, vc, c->max_len, parts, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev,
-                                              cache_dtype == IVLM_F16)))
-                return rc;
-            if ((rc = ivlm_gemv1_bf12m_parts(parts, D, L.o.Pf, L.o.Ef, L.o.ebase, L.o.patch_ptr, L.o.patch_col, L.o.patch_val, x1, nullptr,
-                                             x, Hd, Hd, ACT_NONE, 1, IVLM_GEMM_RES_F32, stream)))
-                return rc;
-        } else {
-            if ((rc = llama_decode_attn(qkv, 1, kc, vc, c->max_len, att, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev, nullptr,
-                                        nullptr, cache_dtype == IVLM_F16)))
-                return rc;
-            if ((rc = gemv(att, L.o, x1, x, Hd, Hd, ACT_NONE, nullptr))) return rc;
-        }
-        if ((rc = gemv(x1, L.gu, hh, nullptr, 2 * I, Hd, ACT_SWIGLU, L.ln2))) return rc;
-        float* x2 = (x1 == xa) ? xb : xa;
-        if ((rc = gemv(hh, L.down, x2, x1, Hd, I, ACT_NONE, nullptr))) return rc;
-        x = x2;
-    }
-    if ((rc = rmsnorm(x, 1, static_cast<const bf16_t*>(final_norm), hidden_out, 1, 1, Hd, c->eps, st))) return rc;
-    bump_kernel<<<1, 1, 0, st>>>(nullptr, advance ? pos_dev : nullptr);
-    return ivlm_launch_status();
+    if (cache_dtype != IVLM_BF16 && cache_dtype != IVLM_F16) return IVLM_ERR_INVALID_ARG;
+    return decode_step(c, layers_host, final_norm, kcache, vcache, cache_dtype == IVLM_F16, cos_tab, sin_tab, x_in, pos_dev, advance,
+                       hidden_out, workspace, workspace_bytes, stream);
 }
 
 // =====================================================================================================================
@@ -417,23 +410,19 @@ __global__ void fill_pad_rows_kernel(bf16_t* __restrict__ dst, int64_t ldd, cons
     }
 }
 
-// generic tile-GEMM call of the sequencers (bias, activation, bf16 / fp32 residual with row modulo, row maps, split-K rule)
+// generic tile-GEMM call of the sequencers (bias, activation, bf16 / fp32 residual with row modulo, row maps, split-K rule);
+// flags: IVLM_GEMM_A_SPLIT (A rows are [hi(K) | lo(K)]), IVLM_GEMM_OUT_SPLIT (the fp32 result as [hi(N) | lo(N)] rows),
+// IVLM_GEMM_F16 (A and W are IEEE halves), IVLM_GEMM_OUT_F16 (a 16-bit output is written as IEEE halves)
 int gemm(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int out_f32, int64_t ldc, const void* bias,
          const void* res, int res_f32, int64_t ldr, int res_mod, int M, int N, int K, int act, const int32_t* out_rows,
-         const int32_t* a_rows, float* sk, size_t skb, hipStream_t st, int a_split = 0, int out_split = 0, int f16 = 0,
-         int out_f16 = 0) {
+         const int32_t* a_rows, float* sk, size_t skb, hipStream_t st, int flags = 0) {
     GemmArgs g;
-    g.f16 = f16;  // A and W are IEEE halves
-    g.out_f16 = out_f16;  // a 16-bit output is written as IEEE halves
-    if (a_split) {  // "parity" precision: A rows are [hi(K) | lo(K)] bf16
-        g.a_split = 1;
-        g.a_lo = K;
-    }
-    if (out_split) {  // the fp32 result written as [hi(N) | lo(N)] bf16 rows
-        g.out_split = 1;
-        g.c_lo = N;
-        out_f32 = 1;
-    }
+    g.f16 = (flags & IVLM_GEMM_F16) != 0;
+    g.out_f16 = (flags & IVLM_GEMM_OUT_F16) != 0;
+    g.a_split = (flags & IVLM_GEMM_A_SPLIT) != 0;
+    g.a_lo = g.a_split ? K : 0;
+    g.out_split = (flags & IVLM_GEMM_OUT_SPLIT) != 0;
+    g.c_lo = g.out_split ? N : 0;
     g.A = static_cast<const bf16_t*>(A);
     g.W = static_cast<const bf16_t*>(W);
     g.C = C;
@@ -444,7 +433,7 @@ int gemm(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int ou
     g.res_mod = res_mod;
     g.M = M; g.N = N; g.K = K;
     g.act = act;
-    g.out_f32 = out_f32;
+    g.out_f32 = out_f32 || g.out_split;  // (split halves come from the fp32 epilogue)
     g.out_rows = out_rows;
     g.a_rows = a_rows;
     const int sp = (out_rows || a_rows) ? 1 : gemm_splitk_choice(M, N, K, act, 0);
@@ -453,36 +442,53 @@ int gemm(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int ou
     return linear_bf16(g, st);
 }
 
+// Non-causal attention of the vision towers over B batches of S rows: q / k / v (and their lo planes, or null) are rows of stride
+// rs with the heads side by side, the output rows have stride o_rs ([hi | lo] halves of H * D each when k_lo is set); q is scaled
+// before Q.K^T.  f16: IEEE halves, q_lo then enters the rel-pos table product only (level 1).  rel_h / rel_w: the fp32 rel-pos
+// arrays of a side x side grid, or the [rel_pos_h ; rel_pos_w] table and null (table mode), or both null.
+int attend(const bf16_t* q, const bf16_t* q_lo, const bf16_t* k, const bf16_t* k_lo, const bf16_t* v, const bf16_t* v_lo, int64_t rs,
+           bf16_t* o, int64_t o_rs, int f16, int B, int H, int S, int D, const void* rel_h, const float* rel_w, int side,
+           hipStream_t st) {
+    AttnArgs a{};
+    a.f16 = f16;
+    a.q = q; a.k = k; a.v = v; a.o = o;
+    a.q_lo = q_lo; a.k_lo = k_lo; a.v_lo = v_lo; a.o_lo = k_lo ? o + H * D : nullptr;
+    a.q_lo_level = (f16 && q_lo) ? 1 : 0;
+    a.q_bs = a.k_bs = a.v_bs = (int64_t)S * rs;
+    a.q_hs = a.k_hs = a.v_hs = a.o_hs = D;
+    a.q_rs = a.k_rs = a.v_rs = rs;
+    a.o_bs = (int64_t)S * o_rs; a.o_rs = o_rs;
+    a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.D = D;
+    a.scale = 1.0f / sqrtf((float)D);
+    a.rel_h = static_cast<const float*>(rel_h); a.rel_w = rel_w; a.rel_kh = side; a.rel_kw = side;
+    a.kv_batch_div = 1; a.prescale_q = 1;
+    return attention_bf16(a, st);
+}
+
+struct ClipBufs { bf16_t* cols; float *xa, *xb; bf16_t *y, *qkv, *att, *hh; float* sk; size_t skb; };  // (as PrefillBufs)
+ClipBufs carve_clip(const ivlm_clip_cfg* c, int B, Carver& cv) {
+    const size_t T = c->tokens, h = c->hidden, in = c->inter, R = B * T, skb = 8 * R * std::max(3 * h, in) * 4;
+    return {cv.get<bf16_t>(B * (T - 1) * c->kpad), cv.get<float>(R * h), cv.get<float>(R * h), cv.get<bf16_t>(R * h),
+            cv.get<bf16_t>(R * 3 * h), cv.get<bf16_t>(R * h), cv.get<bf16_t>(R * in), cv.get<float>(skb / 4), skb};
+}
+
 }  // namespace
 }  // namespace ivlm
 
 extern "C" size_t ivlm_clip_encode_workspace_bytes(const ivlm_clip_cfg* c, int B) {
-    if (!c || B <= 0) return 0;
-    const size_t T = c->tokens, h = c->hidden, rows = (size_t)B * T;
-    return al((size_t)B * (T - 1) * c->kpad * 2) + 2 * al(rows * h * 4) + al(rows * h * 2) + al(rows * 3 * h * 2) + al(rows * h * 2) +
-           al(rows * c->inter * 2) + al(8 * rows * std::max<size_t>(3 * h, c->inter) * 4) + al(rows * 4) + 512;
+    return c && B > 0 ? carved_bytes(carve_clip, c, B) : 0;
 }
 
 static int clip_encode(const ivlm_clip_cfg* c, const ivlm_clip_head* hd, const ivlm_clip_layer* layers_host, const void* images, int B,
                        void* features_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream, const int f16) {
     ivlm_enter();
     if (!c || !hd || !layers_host || !images || !features_out || !workspace || B <= 0) return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_clip_encode_workspace_bytes(c, B)) return IVLM_ERR_WORKSPACE;
+    Carver cv{static_cast<char*>(workspace), workspace_bytes};
+    auto [cols, xa, xb, y, qkv, att, hh, sk, skb] = carve_clip(c, B, cv);
+    if (!cv.ok) return IVLM_ERR_WORKSPACE;
     hipStream_t st = ivlm_stream(stream);
     const int T = c->tokens, Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter, R = B * T;
-    Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    bf16_t* cols = static_cast<bf16_t*>(cv.take((size_t)B * (T - 1) * c->kpad * 2));
-    float* xa = static_cast<float*>(cv.take((size_t)R * Hd * 4));
-    float* xb = static_cast<float*>(cv.take((size_t)R * Hd * 4));
-    bf16_t* y = static_cast<bf16_t*>(cv.take((size_t)R * Hd * 2));
-    bf16_t* qkv = static_cast<bf16_t*>(cv.take((size_t)R * 3 * Hd * 2));
-    bf16_t* att = static_cast<bf16_t*>(cv.take((size_t)R * Hd * 2));
-    bf16_t* hh = static_cast<bf16_t*>(cv.take((size_t)R * I * 2));
-    const size_t skb = (size_t)8 * R * std::max(3 * Hd, I) * 4;
-    float* sk = static_cast<float*>(cv.take(skb));
     if (int rc0 = sk_counters_zero(sk, skb, st)) return rc0;
-    int32_t* prow = static_cast<int32_t*>(cv.take((size_t)R * 4));
-    if (!cv.ok) return IVLM_ERR_WORKSPACE;
     int rc;
     if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), cols, B, 3, c->image_size, c->image_size, c->patch, c->patch, c->kpad, st))) return rc;
     for (int b = 0; b < B; ++b) {  // patch GEMM writes rows 1..T-1 (+ their position embeddings); row 0 = class + position 0
@@ -494,22 +500,19 @@ static int clip_encode(const ivlm_clip_cfg* c, const ivlm_clip_head* hd, const i
     }
     if ((rc = layernorm(xa, 1, static_cast<const bf16_t*>(hd->pre_ln_w), static_cast<const bf16_t*>(hd->pre_ln_b), xb, 1, R, Hd, c->eps, st))) return rc;
     float* x = xb;
-    const int64_t strides[12] = {(int64_t)T * 3 * Hd, D, 3 * Hd, (int64_t)T * 3 * Hd, D, 3 * Hd, (int64_t)T * 3 * Hd, D, 3 * Hd,
-                                 (int64_t)T * Hd, D, Hd};
+    const int k16 = f16 ? 4 : 0;                                      // LayerNorm output kind: IEEE halves | bf16
+    const int in16 = f16 ? IVLM_GEMM_F16 : 0, io16 = f16 ? IVLM_GEMM_F16 | IVLM_GEMM_OUT_F16 : 0;  // fp16 operands (and 16-bit output)
     for (int l = 0; l < c->layers_run; ++l) {
         const ivlm_clip_layer& L = layers_host[l];
-        const int k16 = f16 ? 4 : 0;  // (LayerNorm output kind: IEEE halves | bf16)
         if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(L.ln1_w), static_cast<const bf16_t*>(L.ln1_b), y, k16, R, Hd, c->eps, st))) return rc;
-        if ((rc = gemm(y, Hd, L.qkv_w, Hd, qkv, 0, 3 * Hd, L.qkv_b, nullptr, 0, 0, 0, R, 3 * Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, 0, 0, f16, f16))) return rc;
-        if ((rc = (f16 ? ivlm_attention_f16 : ivlm_attention_bf16)(qkv, qkv + Hd, qkv + 2 * Hd, att, strides, B, H, T, T, D,
-                                                                  1.0f / sqrtf((float)D), 0, 0, nullptr, nullptr, 0, 0, 1, 1, stream)))
-            return rc;
+        if ((rc = gemm(y, Hd, L.qkv_w, Hd, qkv, 0, 3 * Hd, L.qkv_b, nullptr, 0, 0, 0, R, 3 * Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, io16))) return rc;
+        if ((rc = attend(qkv, nullptr, qkv + Hd, nullptr, qkv + 2 * Hd, nullptr, 3 * Hd, att, Hd, f16, B, H, T, D, nullptr, nullptr, 0, st))) return rc;
         float* x1 = (x == xa) ? xb : xa;
-        if ((rc = gemm(att, Hd, L.out_w, Hd, x1, 1, Hd, L.out_b, x, 1, Hd, 0, R, Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, 0, 0, f16, 0))) return rc;
+        if ((rc = gemm(att, Hd, L.out_w, Hd, x1, 1, Hd, L.out_b, x, 1, Hd, 0, R, Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, in16))) return rc;
         if ((rc = layernorm(x1, 1, static_cast<const bf16_t*>(L.ln2_w), static_cast<const bf16_t*>(L.ln2_b), y, k16, R, Hd, c->eps, st))) return rc;
-        if ((rc = gemm(y, Hd, L.fc1_w, Hd, hh, 0, I, L.fc1_b, nullptr, 0, 0, 0, R, I, Hd, ACT_QUICK_GELU, nullptr, nullptr, sk, skb, st, 0, 0, f16, f16))) return rc;
+        if ((rc = gemm(y, Hd, L.fc1_w, Hd, hh, 0, I, L.fc1_b, nullptr, 0, 0, 0, R, I, Hd, ACT_QUICK_GELU, nullptr, nullptr, sk, skb, st, io16))) return rc;
         float* x2 = (x1 == xa) ? xb : xa;
-        if ((rc = gemm(hh, I, L.fc2_w, I, x2, 1, Hd, L.fc2_b, x1, 1, Hd, 0, R, Hd, I, ACT_NONE, nullptr, nullptr, sk, skb, st, 0, 0, f16, 0))) return rc;
+        if ((rc = gemm(hh, I, L.fc2_w, I, x2, 1, Hd, L.fc2_b, x1, 1, Hd, 0, R, Hd, I, ACT_NONE, nullptr, nullptr, sk, skb, st, in16))) return rc;
         x = x2;
     }
     // drop the CLS row of every image, fp32 stream -> bf16 features (the mm_projector's operand); fp16 mode: [hi | lo] bf16 rows
@@ -519,7 +522,6 @@ static int clip_encode(const ivlm_clip_cfg* c, const ivlm_clip_head* hd, const i
         if ((rc = gather_rows(static_cast<bf16_t*>(features_out) + (size_t)b * (T - 1) * fw, f16 ? 2 : 0, fw, x + ((size_t)b * T + 1) * Hd, 1, Hd,
                               nullptr, nullptr, 0, 0, T - 1, Hd, st)))
             return rc;
-    (void)prow;
     return IVLM_OK;
 }
 
@@ -538,343 +540,239 @@ extern "C" int ivlm_clip_encode_f16(const ivlm_clip_cfg* c, const ivlm_clip_head
     return clip_encode(c, hd, layers16_host, images, B, features_split_out, workspace, workspace_bytes, stream, 1);
 }
 
-extern "C" size_t ivlm_sam_encode_workspace_bytes(const ivlm_sam_cfg* c, int V) {
-    if (!c || V <= 0) return 0;
-    const size_t g2 = (size_t)c->grid * c->grid, rows = (size_t)V * g2, D = c->embed_dim;
-    const int nw = (c->grid + c->window - 1) / c->window;
-    const size_t wrows = (size_t)V * nw * nw * c->window * c->window, qrows = std::max(rows, wrows);
-    const size_t npad = (((size_t)2 * (2 * c->grid - 1)) + 7) / 8 * 8;
-    size_t b = al(rows * 3 * c->patch * c->patch * 2) + al(rows * D * 4) + al(rows * D * 2) + al(qrows * 3 * D * 2) + al(qrows * D * 2) +
-               al(rows * c->mlp_dim * 2);
-    b += 2 * al((size_t)V * c->heads * g2 * c->grid * 4);          // rel_h / rel_w of a global block (the larger case)
-    b += 2 * al(wrows * c->heads * c->window * 4);                  // ... of a windowed block
-    b += al((size_t)c->heads * rows * npad * 2);                    // G of the rel-pos GEMM
-    b += al(wrows * 4) + al(rows * 4);                              // part / unpart maps
-    b += al(rows * c->out_chans * 2) * 2 + al(rows * 9 * c->out_chans * 2) + al(rows * D * 2);
-    return b + 1024;
-}
-
-extern "C" int ivlm_sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host, const void* images,
-                               int V, float* embeddings_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
-    ivlm_enter();
-    if (!c || !hd || !blocks_host || !images || !embeddings_out || !workspace || V <= 0) return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_sam_encode_workspace_bytes(c, V)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    const int g = c->grid, D = c->embed_dim, H = c->heads, hdim = D / H, wsz = c->window, OC = c->out_chans;
-    const int nw = (g + wsz - 1) / wsz, g2 = g * g, R = V * g2, nwin = V * nw * nw, WS = wsz * wsz, WR = nwin * WS;
-    const int Kp = 3 * c->patch * c->patch;
-    Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    bf16_t* cols = static_cast<bf16_t*>(cv.take((size_t)R * Kp * 2));
-    float* x = static_cast<float*>(cv.take((size_t)R * D * 4));
-    bf16_t* xn = static_cast<bf16_t*>(cv.take((size_t)R * D * 2));
-    const size_t qrows = std::max(R, WR);
-    bf16_t* qkv = static_cast<bf16_t*>(cv.take(qrows * 3 * D * 2));
-    bf16_t* att = static_cast<bf16_t*>(cv.take(qrows * D * 2));
-    bf16_t* hh = static_cast<bf16_t*>(cv.take((size_t)R * c->mlp_dim * 2));
-    float* relh_g = static_cast<float*>(cv.take((size_t)V * H * g2 * g * 4));
-    float* relw_g = static_cast<float*>(cv.take((size_t)V * H * g2 * g * 4));
-    float* relh_w = static_cast<float*>(cv.take((size_t)WR * H * wsz * 4));
-    float* relw_w = static_cast<float*>(cv.take((size_t)WR * H * wsz * 4));
-    const int npad = (2 * (2 * g - 1) + 7) / 8 * 8;
-    bf16_t* G = static_cast<bf16_t*>(cv.take((size_t)H * R * npad * 2));
-    int32_t* part = static_cast<int32_t*>(cv.take((size_t)WR * 4));
-    int32_t* unpart = static_cast<int32_t*>(cv.take((size_t)R * 4));
-    bf16_t* n0 = static_cast<bf16_t*>(cv.take((size_t)R * OC * 2));
-    bf16_t* n1 = static_cast<bf16_t*>(cv.take((size_t)R * OC * 2));
-    bf16_t* c3 = static_cast<bf16_t*>(cv.take((size_t)R * 9 * OC * 2));
-    bf16_t* xb16 = static_cast<bf16_t*>(cv.take((size_t)R * D * 2));
-    if (!cv.ok) return IVLM_ERR_WORKSPACE;
-    int rc;
-    sam_window_maps_kernel<<<256, 256, 0, st>>>(V, g, wsz, nw, part, unpart);
-    if ((rc = ivlm_launch_status())) return rc;
-    if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), cols, V, 3, c->img_size, c->img_size, c->patch, c->patch, Kp, st))) return rc;
-    if ((rc = gemm(cols, Kp, hd->patch_w, Kp, x, 1, D, hd->patch_b, hd->pos_embed, 0, D, g2, R, D, Kp, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    const float scale = 1.0f / sqrtf((float)hdim);
-    for (int l = 0; l < c->depth; ++l) {
-        const ivlm_sam_block& Bk = blocks_host[l];
-        // rel_cat is READ by the attention kernels' table mode (windows: 64 rows; the 64 x 64 grid: 254 rows; zero-padded to a
-        // multiple of 64 rows - ABI version 4): a NULL table would silently drop the rel-pos bias
-        if (!Bk.rel_cat || !Bk.rel_h || !Bk.rel_w) return IVLM_ERR_INVALID_ARG;
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm1_w), static_cast<const bf16_t*>(Bk.norm1_b), xn, 0, R, D, 1e-6f, st))) return rc;
-        const int side = Bk.global_attn ? g : wsz, S = side * side, nb = Bk.global_attn ? V : nwin;
-        if (Bk.global_attn) {
-            if ((rc = gemm(xn, D, Bk.qkv_w, D, qkv, 0, 3 * D, Bk.qkv_b, nullptr, 0, 0, 0, R, 3 * D, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-        } else {  // real rows only, scattered to their window positions; the padded positions get the bias
-            if ((rc = gemm(xn, D, Bk.qkv_w, D, qkv, 0, 3 * D, Bk.qkv_b, nullptr, 0, 0, 0, R, 3 * D, D, ACT_NONE, unpart, nullptr, nullptr, 0, st))) return rc;
-            fill_pad_rows_kernel<<<2048, 256, 0, st>>>(qkv, 3 * D, part, WR, static_cast<const bf16_t*>(Bk.qkv_b), 3 * D);
-            if ((rc = ivlm_launch_status())) return rc;
-        }
-        float *rh, *rw;
-        if (side == 64 && hdim == 80 && 2 * (2 * side - 1) <= npad) {
-            // the 64 x 64 grid: TABLE MODE too (REL 5 of attn_kernel) - every 128-query block computes its terms from rel_cat
-            // ([rel_pos_h (127 rows) ; rel_pos_w (127 rows)]) before its tile loop: no G GEMM, no gather
-            rh = reinterpret_cast<float*>(const_cast<void*>(Bk.rel_cat));
-            rw = nullptr;
-        } else if (side >= 32) {  // rel-pos operands through one batched GEMM over the heads + Toeplitz gather
-            rh = relh_g; rw = relw_g;
-            const int M = nb * S;
-            GemmArgs gg;
-            gg.A = qkv; gg.lda = 3 * D; gg.W = static_cast<const bf16_t*>(Bk.rel_cat); gg.ldw = hdim; gg.C = G; gg.ldc = npad;
-            gg.M = M; gg.N = npad; gg.K = hdim; gg.batch = H; gg.strideA = hdim; gg.strideW = 0; gg.strideC = (int64_t)M * npad;
-            if ((rc = linear_bf16(gg, st))) return rc;
-            if ((rc = ivlm_relpos_gather(G, (int64_t)M * npad, npad, nb, H, side, side, rh, rw, stream))) return rc;
-        } else if (2 * side <= 32 && hdim == 80 && 2 * (2 * side - 1) <= 64) {
-            // windows: TABLE MODE of the attention kernel - it computes the decomposed rel-pos terms itself from rel_cat
-            // ([rel_pos_h ; rel_pos_w] zero-padded to 64 rows): no relpos pass, no [nb*H, S, 2 side] arrays
-            rh = reinterpret_cast<float*>(const_cast<void*>(Bk.rel_cat));
-            rw = nullptr;
-        } else {
-            rh = relh_w; rw = relw_w;
-            if ((rc = relpos_bias(qkv, (int64_t)S * 3 * D, hdim, 3 * D, static_cast<const bf16_t*>(Bk.rel_h), static_cast<const bf16_t*>(Bk.rel_w),
-                                  nb, H, side, side, hdim, rh, rw, st)))
-                return rc;
-        }
-        const int64_t strides[12] = {(int64_t)S * 3 * D, hdim, 3 * D, (int64_t)S * 3 * D, hdim, 3 * D, (int64_t)S * 3 * D, hdim, 3 * D,
-                                     (int64_t)S * D, hdim, D};
-        if ((rc = ivlm_attention_bf16(qkv, qkv + D, qkv + 2 * D, att, strides, nb, H, S, S, hdim, scale, 0, 0, rh, rw, side, side, 1, 1, stream)))
-            return rc;
-        // proj (+ window_unpartition via the gather prologue) + shortcut, in place on the fp32 stream
-        if ((rc = gemm(att, D, Bk.proj_w, D, x, 1, D, Bk.proj_b, x, 1, D, 0, R, D, D, ACT_NONE, nullptr, Bk.global_attn ? nullptr : unpart, nullptr, 0, st)))
-            return rc;
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm2_w), static_cast<const bf16_t*>(Bk.norm2_b), xn, 0, R, D, 1e-6f, st))) return rc;
-        if ((rc = gemm(xn, D, Bk.lin1_w, D, hh, 0, c->mlp_dim, Bk.lin1_b, nullptr, 0, 0, 0, R, c->mlp_dim, D, ACT_GELU, nullptr, nullptr, nullptr, 0, st))) return rc;
-        if ((rc = gemm(hh, c->mlp_dim, Bk.lin2_w, c->mlp_dim, x, 1, D, Bk.lin2_b, x, 1, D, 0, R, D, c->mlp_dim, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    }
-    if ((rc = gather_rows(xb16, 0, D, x, 1, D, nullptr, nullptr, 0, 0, R, D, st))) return rc;
-    if ((rc = gemm(xb16, D, hd->neck0_w, D, n0, 0, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    if ((rc = layernorm(n0, 0, static_cast<const bf16_t*>(hd->neck1_w), static_cast<const bf16_t*>(hd->neck1_b), n1, 0, R, OC, 1e-6f, st))) return rc;
-    if ((rc = im2col3x3_nhwc(n1, c3, V, g, g, OC, st))) return rc;
-    if ((rc = gemm(c3, 9 * OC, hd->neck2_w, 9 * OC, n0, 0, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    return layernorm(n0, 0, static_cast<const bf16_t*>(hd->neck3_w), static_cast<const bf16_t*>(hd->neck3_b), embeddings_out, 1, R, OC, 1e-6f, st);
-}
-
-// =====================================================================================================================
-// ivlm_sam_encode_parity: the same stage in "parity" precision - every activation that feeds an MFMA travels as [hi | lo] bf16
-// rows (split LayerNorm outputs, split-operand / split-output GEMMs, split-operand attention with fp32 rel-pos terms, split
-// neck) - the launch order of interactvlm_amd/sam.py SamImageEncoder._forward_parity (bit-identical to it).
-// =====================================================================================================================
-extern "C" size_t ivlm_sam_encode_parity_workspace_bytes(const ivlm_sam_cfg* c, int V) {
-    if (!c || V <= 0) return 0;
-    const size_t g2 = (size_t)c->grid * c->grid, rows = (size_t)V * g2, D = c->embed_dim;
-    const int nw = (c->grid + c->window - 1) / c->window;
-    const size_t wrows = (size_t)V * nw * nw * c->window * c->window, qrows = std::max(rows, wrows);
-    size_t b = al(rows * 3 * c->patch * c->patch * 2) + al(rows * D * 4) + al(rows * 2 * D * 2) + al(qrows * 6 * D * 2) +
-               al(qrows * 2 * D * 2) + al(rows * 2 * c->mlp_dim * 2);
-    b += 2 * al((size_t)V * c->heads * g2 * c->grid * 4);          // rel_h / rel_w of a global block
-    b += 2 * al(wrows * c->heads * c->window * 4);                  // ... of a windowed block
-    b += al(wrows * 4) + al(rows * 4) + al(6 * D * 2);             // part / unpart maps, the [bias | 0] row of the padded positions
-    b += al(rows * c->out_chans * 4) + al(rows * 2 * c->out_chans * 2) + al(rows * 18 * c->out_chans * 2);
-    return b + 1024;
-}
-
 namespace ivlm {
 namespace {
-int sam_encode_parity(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host, const ivlm_sam_mlp_f16* mlp16,
-                      const void* images, int V, float* embeddings_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
+
+// =====================================================================================================================
+// ivlm_sam_encode*: ONE sequencer for the precision modes of interactvlm_amd/sam.py SamImageEncoder._forward, bit-identical to it
+// in each.  kSamModes restates the _MODES table of sam.py (norm output kinds: 0 bf16, 2 [hi | lo] bf16, 4 fp16, 5 [hi | lo] fp16;
+// GEMM flags as gemm() takes them; a GEMM on fp16 operands reads the fp16 copy of its weight):
+//   default      bf16 MFMA operands
+//   f16q         IEEE fp16 operands in one pass with the q path exact (the host model's default): norm1 -> [hi | lo] halves;
+//                q = W_q . (hi + lo) from its own GEMM as [hi | lo] halves, k | v from a single-pass GEMM on the hi half; table-mode
+//                attention with the lo half of q in the rel-pos table products; the neck on [hi | lo] bf16 operands
+//   parity       every activation that feeds an MFMA travels as [hi | lo] bf16 rows: split LayerNorm outputs, split-operand /
+//                split-output GEMMs, split-operand attention with fp32 rel-pos terms from q = hi + lo, split neck
+//   parity-fast  parity with the two MLP GEMMs on fp16 operands (norm2 and the GELU epilogue write halves, one MFMA pass)
+// =====================================================================================================================
+enum SamAttn {
+    ATT_BF16,   // q|k|v rows of width 3D; rel-pos by shape: table mode from rel_cat, the batched G GEMM + gather, or the dot kernel
+    ATT_F16Q,   // [q hi | q lo] and [k | v] fp16 rows of width 2D; table mode from rel_cat16 (head dim 80, 64 x 64 grid, small windows)
+    ATT_SPLIT,  // [q k v hi | q k v lo] rows of width 6D; fp32 rel-pos arrays from the dot kernel on q = hi + lo (head dim 80)
+};
+constexpr int kSplitA = IVLM_GEMM_A_SPLIT, kSplitAO = IVLM_GEMM_A_SPLIT | IVLM_GEMM_OUT_SPLIT, kF16 = IVLM_GEMM_F16,
+              kF16O = IVLM_GEMM_F16 | IVLM_GEMM_OUT_F16;
+struct SamMode {
+    int n1, qkv;  // norm1's output kind, the flags of the q|k|v GEMM (ATT_F16Q: of its q part)
+    SamAttn attn;
+    int proj, n2, lin1, lin2;  // the flags of the proj GEMM, norm2's output kind, the flags of the two MLP GEMMs
+    bool split_neck;           // the neck takes [hi | lo] operands
+};
+constexpr SamMode kSamDefault{0, 0, ATT_BF16, 0, 0, 0, 0, false};
+constexpr SamMode kSamF16q{5, kSplitAO | kF16O, ATT_F16Q, kF16, 4, kF16O, kF16, true};
+constexpr SamMode kSamParityFast{2, kSplitAO, ATT_SPLIT, kSplitA, 4, kF16O, kF16, true};
+constexpr SamMode kSamParity{2, kSplitAO, ATT_SPLIT, kSplitA, 2, kSplitAO, kSplitA, true};
+
+struct SamDims {
+    int g, D, H, hdim, wsz, OC, MD, Kp, nw, g2, R, nwin, WR, npad;
+    SamDims(const ivlm_sam_cfg* c, int V)
+        : g(c->grid), D(c->embed_dim), H(c->heads), hdim(D / H), wsz(c->window), OC(c->out_chans), MD(c->mlp_dim),
+          Kp(3 * c->patch * c->patch), nw((g + wsz - 1) / wsz), g2(g * g), R(V * g2), nwin(V * nw * nw), WR(nwin * wsz * wsz),
+          npad((2 * (2 * g - 1) + 7) / 8 * 8) {}
+};
+
+// The buffers of a mode (they follow its attention kind; the two parity modes share one carve and one size).  Rows that hold
+// [hi | lo] halves are twice as wide; the q|k|v and attention rows cover the padded window grid.
+struct SamBufs {
+    float* x;                                       // the fp32 residual stream
+    bf16_t *cols, *xn, *q, *kv, *att, *hh;          // patch columns; norm output; q|k|v (ATT_F16Q: [q hi | q lo], [k | v]); attention; MLP hidden
+    float *relh_g, *relw_g, *relh_w, *relw_w;       // fp32 rel-pos arrays of a global / of a windowed block
+    bf16_t *G, *brow;                               // the rel-pos GEMM's output; the [bias | 0] row of the padded window positions
+    int32_t *part, *unpart;                         // window_partition / window_unpartition row maps
+    void* n0;                                       // neck: conv outputs (fp32 when it is split), LayerNorm2d output, 3x3 columns
+    bf16_t *n1, *c3;
+};
+SamBufs carve_sam(const SamDims& d, int V, const SamMode& m, Carver& cv) {
+    const size_t R = d.R, WR = d.WR, D = d.D, qrows = std::max(R, WR), w = m.attn == ATT_SPLIT ? 2 : 1, nk = m.split_neck ? 2 : 1;
+    SamBufs b{};
+    b.cols = cv.get<bf16_t>(R * d.Kp), b.x = cv.get<float>(R * D);
+    b.xn = cv.get<bf16_t>(R * D * (m.attn == ATT_BF16 ? 1 : 2));
+    b.q = cv.get<bf16_t>(qrows * D * (m.attn == ATT_F16Q ? 2 : 3 * w));
+    if (m.attn == ATT_F16Q) b.kv = cv.get<bf16_t>(qrows * 2 * D);
+    b.att = cv.get<bf16_t>(qrows * D * w), b.hh = cv.get<bf16_t>(R * d.MD * w);
+    const size_t rel_g = (size_t)V * d.H * d.g2 * d.g, rel_w = WR * d.H * d.wsz;
+    if (m.attn != ATT_F16Q)  // (table mode needs no arrays)
+        b.relh_g = cv.get<float>(rel_g), b.relw_g = cv.get<float>(rel_g), b.relh_w = cv.get<float>(rel_w), b.relw_w = cv.get<float>(rel_w);
+    if (m.attn == ATT_BF16) b.G = cv.get<bf16_t>((size_t)d.H * R * d.npad);
+    b.part = cv.get<int32_t>(WR), b.unpart = cv.get<int32_t>(R);
+    if (m.attn != ATT_BF16) b.brow = cv.get<bf16_t>(D * (m.attn == ATT_F16Q ? 2 : 6));
+    b.n0 = cv.take(R * d.OC * 2 * nk), b.n1 = cv.get<bf16_t>(R * d.OC * nk), b.c3 = cv.get<bf16_t>(R * 9 * d.OC * nk);
+    return b;
+}
+size_t sam_workspace_bytes(const ivlm_sam_cfg* c, int V, const SamMode& m) {
+    return c && V > 0 ? carved_bytes(carve_sam, SamDims(c, V), V, m) : 0;
+}
+
+// w16(l): the fp16 tensors of block l as an ivlm_sam_block_f16 whose unused members are null
+template <class W16>
+int sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host, W16 w16, const SamMode& m,
+               const void* images, int V, float* embeddings_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
+    ivlm_enter();
     if (!c || !hd || !blocks_host || !images || !embeddings_out || !workspace || V <= 0) return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_sam_encode_parity_workspace_bytes(c, V)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    const int g = c->grid, D = c->embed_dim, H = c->heads, hdim = D / H, wsz = c->window, OC = c->out_chans, MD = c->mlp_dim;
-    const int nw = (g + wsz - 1) / wsz, g2 = g * g, R = V * g2, nwin = V * nw * nw, WS = wsz * wsz, WR = nwin * WS;
-    const int Kp = 3 * c->patch * c->patch;
-    if (hdim != 80) return IVLM_ERR_UNSUPPORTED;  // (the split attention / rel-pos kernels are built for SAM's head dim)
+    const SamDims d(c, V);
     Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    bf16_t* cols = static_cast<bf16_t*>(cv.take((size_t)R * Kp * 2));
-    float* x = static_cast<float*>(cv.take((size_t)R * D * 4));
-    bf16_t* xn = static_cast<bf16_t*>(cv.take((size_t)R * 2 * D * 2));
-    const size_t qrows = std::max(R, WR);
-    bf16_t* qkv = static_cast<bf16_t*>(cv.take(qrows * 6 * D * 2));
-    bf16_t* att = static_cast<bf16_t*>(cv.take(qrows * 2 * D * 2));
-    bf16_t* hh = static_cast<bf16_t*>(cv.take((size_t)R * 2 * MD * 2));
-    float* relh_g = static_cast<float*>(cv.take((size_t)V * H * g2 * g * 4));
-    float* relw_g = static_cast<float*>(cv.take((size_t)V * H * g2 * g * 4));
-    float* relh_w = static_cast<float*>(cv.take((size_t)WR * H * wsz * 4));
-    float* relw_w = static_cast<float*>(cv.take((size_t)WR * H * wsz * 4));
-    int32_t* part = static_cast<int32_t*>(cv.take((size_t)WR * 4));
-    int32_t* unpart = static_cast<int32_t*>(cv.take((size_t)R * 4));
-    bf16_t* brow = static_cast<bf16_t*>(cv.take((size_t)6 * D * 2));
-    float* n0 = static_cast<float*>(cv.take((size_t)R * OC * 4));
-    bf16_t* n1 = static_cast<bf16_t*>(cv.take((size_t)R * 2 * OC * 2));
-    bf16_t* c3 = static_cast<bf16_t*>(cv.take((size_t)R * 18 * OC * 2));
+    const SamBufs b = carve_sam(d, V, m, cv);
     if (!cv.ok) return IVLM_ERR_WORKSPACE;
+    const int g = d.g, D = d.D, H = d.H, hdim = d.hdim, wsz = d.wsz, OC = d.OC, MD = d.MD, Kp = d.Kp, R = d.R, WR = d.WR;
+    // (the split attention / rel-pos kernels are built for SAM's head dim; table-mode attention for its grid and windows too)
+    if (m.attn != ATT_BF16 && hdim != 80) return IVLM_ERR_UNSUPPORTED;
+    if (m.attn == ATT_F16Q && (g != 64 || 2 * wsz > 32)) return IVLM_ERR_UNSUPPORTED;
+    for (int l = 0; l < c->depth; ++l) {  // a NULL table would silently drop the rel-pos bias, a NULL fp16 copy fault
+        const ivlm_sam_block& Bk = blocks_host[l];
+        const ivlm_sam_block_f16 B16 = w16(l);
+        if (m.attn == ATT_BF16 && (!Bk.rel_cat || !Bk.rel_h || !Bk.rel_w)) return IVLM_ERR_INVALID_ARG;
+        if (m.attn == ATT_F16Q && (!B16.qkv_w16 || !B16.qkv_b16 || !B16.rel_cat16)) return IVLM_ERR_INVALID_ARG;
+        if (((m.proj & kF16) && !B16.proj_w16) || ((m.lin1 & kF16) && !B16.lin1_w16) || ((m.lin2 & kF16) && !B16.lin2_w16))
+            return IVLM_ERR_INVALID_ARG;
+    }
+    hipStream_t st = ivlm_stream(stream);
+    auto ln = [&](const void* x, int x_f32, const void* w, const void* bias, void* y, int kind, int cols) {
+        return layernorm(x, x_f32, static_cast<const bf16_t*>(w), static_cast<const bf16_t*>(bias), y, kind, R, cols, 1e-6f, st);
+    };
+    // A [R, K] . W[N, K]^T + bias -> 16-bit rows of width ldc (act applied), or, with res, += onto the fp32 stream
+    auto mm = [&](const void* A, int64_t lda, const void* W, void* C, int64_t ldc, const void* bias, float* res, int N, int K, int act,
+                  const int32_t* out_rows, const int32_t* a_rows, int flags) {
+        return gemm(A, lda, W, K, C, res != nullptr, ldc, bias, res, res != nullptr, res ? D : 0, 0, R, N, K, act, out_rows, a_rows,
+                    nullptr, 0, st, flags);
+    };
+    auto wide = [](int flags, int split_flag, int n) { return (flags & split_flag) ? 2 * n : n; };  // row width of a GEMM operand
+    // dst[r] = [bias | 0] (width elements) at every padded window position r
+    auto fill_pad_rows = [&](bf16_t* dst, int width, const void* bias, int bias_cols) {
+        if (width > bias_cols) {
+            IVLM_HIP_TRY(hipMemsetAsync(b.brow, 0, (size_t)width * 2, st));
+            IVLM_HIP_TRY(hipMemcpyAsync(b.brow, bias, (size_t)bias_cols * 2, hipMemcpyDeviceToDevice, st));
+            bias = b.brow;
+        }
+        fill_pad_rows_kernel<<<2048, 256, 0, st>>>(dst, width, b.part, WR, static_cast<const bf16_t*>(bias), width);
+        return ivlm_launch_status();
+    };
     int rc;
-    sam_window_maps_kernel<<<256, 256, 0, st>>>(V, g, wsz, nw, part, unpart);
+    sam_window_maps_kernel<<<256, 256, 0, st>>>(V, g, wsz, d.nw, b.part, b.unpart);
     if ((rc = ivlm_launch_status())) return rc;
-    if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), cols, V, 3, c->img_size, c->img_size, c->patch, c->patch, Kp, st))) return rc;
-    if ((rc = gemm(cols, Kp, hd->patch_w, Kp, x, 1, D, hd->patch_b, hd->pos_embed, 0, D, g2, R, D, Kp, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    const float scale = 1.0f / sqrtf((float)hdim);
+    if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), b.cols, V, 3, c->img_size, c->img_size, c->patch, c->patch, Kp, st))) return rc;
+    if ((rc = gemm(b.cols, Kp, hd->patch_w, Kp, b.x, 1, D, hd->patch_b, hd->pos_embed, 0, D, d.g2, R, D, Kp, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
+    float* x = b.x;
+    const int64_t lx = m.attn == ATT_BF16 ? D : 2 * D;  // row width of norm1's output
     for (int l = 0; l < c->depth; ++l) {
         const ivlm_sam_block& Bk = blocks_host[l];
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm1_w), static_cast<const bf16_t*>(Bk.norm1_b), xn, 2, R, D, 1e-6f, st))) return rc;
-        const int side = Bk.global_attn ? g : wsz, S = side * side, nb = Bk.global_attn ? V : nwin;
-        if (Bk.global_attn) {
-            if ((rc = gemm(xn, 2 * D, Bk.qkv_w, D, qkv, 0, 6 * D, Bk.qkv_b, nullptr, 0, 0, 0, R, 3 * D, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 1))) return rc;
-        } else {  // real rows scattered to their window positions; the padded positions get [bias | 0]
-            if ((rc = gemm(xn, 2 * D, Bk.qkv_w, D, qkv, 0, 6 * D, Bk.qkv_b, nullptr, 0, 0, 0, R, 3 * D, D, ACT_NONE, unpart, nullptr, nullptr, 0, st, 1, 1))) return rc;
-            IVLM_HIP_TRY(hipMemsetAsync(brow, 0, (size_t)6 * D * 2, st));
-            IVLM_HIP_TRY(hipMemcpyAsync(brow, Bk.qkv_b, (size_t)3 * D * 2, hipMemcpyDeviceToDevice, st));
-            fill_pad_rows_kernel<<<2048, 256, 0, st>>>(qkv, 6 * D, part, WR, brow, 6 * D);
-            if ((rc = ivlm_launch_status())) return rc;
+        const ivlm_sam_block_f16 B16 = w16(l);
+        const bool glob = Bk.global_attn;
+        const int side = glob ? g : wsz, S = side * side, nb = glob ? V : d.nwin;
+        // a windowed block runs both attention GEMMs on the real rows only: the q|k|v GEMM scatters them to their window positions
+        // (the padded positions get the bias), the proj GEMM gathers them back (window_unpartition) + shortcut, in place
+        const int32_t* wmap = glob ? nullptr : b.unpart;
+        if ((rc = ln(x, 1, Bk.norm1_w, Bk.norm1_b, b.xn, m.n1, D))) return rc;
+        const bf16_t *q = b.q, *k, *v, *q_lo = nullptr, *k_lo = nullptr, *v_lo = nullptr;
+        int64_t rs;  // row stride of q / k / v
+        if (m.attn == ATT_F16Q) {
+            const bf16_t *wq = static_cast<const bf16_t*>(B16.qkv_w16), *bq = static_cast<const bf16_t*>(Bk.qkv_b),
+                         *bq16 = static_cast<const bf16_t*>(B16.qkv_b16);
+            rs = 2 * D; q_lo = q + D; k = b.kv; v = b.kv + D;
+            if ((rc = mm(b.xn, lx, wq, b.q, rs, bq, nullptr, D, D, ACT_NONE, wmap, nullptr, m.qkv))) return rc;
+            if ((rc = mm(b.xn, lx, wq + (size_t)D * D, b.kv, rs, bq + D, nullptr, 2 * D, D, ACT_NONE, wmap, nullptr, kF16O))) return rc;
+            if (!glob && ((rc = fill_pad_rows(b.q, 2 * D, bq16, D)) || (rc = fill_pad_rows(b.kv, 2 * D, bq16 + D, 2 * D)))) return rc;
+        } else {
+            rs = wide(m.qkv, IVLM_GEMM_OUT_SPLIT, 3 * D); k = q + D; v = q + 2 * D;
+            if (m.attn == ATT_SPLIT) { q_lo = q + 3 * D; k_lo = q + 4 * D; v_lo = q + 5 * D; }
+            if ((rc = mm(b.xn, lx, Bk.qkv_w, b.q, rs, Bk.qkv_b, nullptr, 3 * D, D, ACT_NONE, wmap, nullptr, m.qkv))) return rc;
+            if (!glob && (rc = fill_pad_rows(b.q, rs, Bk.qkv_b, 3 * D))) return rc;
         }
-        float* rh = Bk.global_attn ? relh_g : relh_w;
-        float* rw = Bk.global_attn ? relw_g : relw_w;
-        // fp32 rel-pos terms from q = hi + lo (rows: [q k v hi | q k v lo], row stride 6 D)
-        if ((rc = relpos_bias(qkv, (int64_t)S * 6 * D, hdim, 6 * D, static_cast<const bf16_t*>(Bk.rel_h), static_cast<const bf16_t*>(Bk.rel_w),
-                              nb, H, side, side, hdim, rh, rw, st, qkv + 3 * D)))
-            return rc;
-        AttnArgs a{};
-        a.q = qkv; a.k = qkv + D; a.v = qkv + 2 * D;
-        a.q_lo = qkv + 3 * D; a.k_lo = qkv + 4 * D; a.v_lo = qkv + 5 * D;
-        a.o = att; a.o_lo = att + D;
-        a.q_bs = a.k_bs = a.v_bs = (int64_t)S * 6 * D;
-        a.q_hs = a.k_hs = a.v_hs = hdim;
-        a.q_rs = a.k_rs = a.v_rs = 6 * D;
-        a.o_bs = (int64_t)S * 2 * D; a.o_hs = hdim; a.o_rs = 2 * D;
-        a.B = nb; a.H = H; a.Sq = S; a.Sk = S; a.D = hdim;
-        a.scale = scale; a.causal = 0; a.q_pos0 = 0;
-        a.rel_h = rh; a.rel_w = rw; a.rel_kh = side; a.rel_kw = side;
-        a.kv_batch_div = 1; a.prescale_q = 1;
-        if ((rc = attention_bf16(a, st))) return rc;
-        if ((rc = gemm(att, 2 * D, Bk.proj_w, D, x, 1, D, Bk.proj_b, x, 1, D, 0, R, D, D, ACT_NONE, nullptr, Bk.global_attn ? nullptr : unpart, nullptr, 0, st, 1, 0)))
-            return rc;
-        if (mlp16) {  // the MLP on fp16 operands: norm2 and the GELU epilogue write IEEE halves, one MFMA pass
-            if (!mlp16[l].lin1_w16 || !mlp16[l].lin2_w16) return IVLM_ERR_INVALID_ARG;
-            if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm2_w), static_cast<const bf16_t*>(Bk.norm2_b), xn, 4, R, D, 1e-6f, st))) return rc;
-            if ((rc = gemm(xn, D, mlp16[l].lin1_w16, D, hh, 0, MD, Bk.lin1_b, nullptr, 0, 0, 0, R, MD, D, ACT_GELU, nullptr, nullptr, nullptr, 0, st, 0, 0, 1, 1))) return rc;
-            if ((rc = gemm(hh, MD, mlp16[l].lin2_w16, MD, x, 1, D, Bk.lin2_b, x, 1, D, 0, R, D, MD, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 0, 0, 1, 0))) return rc;
-            continue;
+        // the decomposed rel-pos terms: the attention kernel's TABLE MODE (it computes them itself from [rel_pos_h ; rel_pos_w],
+        // rel_w = null: windows of 2 * side <= 32 and the 64 x 64 grid at head dim 80), or fp32 arrays [nb * H, S, side]
+        const void* rh;
+        float* rw = nullptr;
+        if (m.attn == ATT_F16Q) {
+            rh = B16.rel_cat16;
+        } else if (m.attn == ATT_BF16 && hdim == 80 &&
+                   ((side == 64 && 2 * (2 * side - 1) <= d.npad) || (2 * side <= 32 && 2 * (2 * side - 1) <= 64))) {
+            rh = Bk.rel_cat;
+        } else if (m.attn == ATT_BF16 && side >= 32) {  // one batched GEMM over the heads against rel_cat + Toeplitz gather
+            rh = b.relh_g; rw = b.relw_g;
+            const int M = nb * S;
+            GemmArgs gg;
+            gg.A = q; gg.lda = rs; gg.W = static_cast<const bf16_t*>(Bk.rel_cat); gg.ldw = hdim; gg.C = b.G; gg.ldc = d.npad;
+            gg.M = M; gg.N = d.npad; gg.K = hdim; gg.batch = H; gg.strideA = hdim; gg.strideW = 0; gg.strideC = (int64_t)M * d.npad;
+            if ((rc = linear_bf16(gg, st))) return rc;
+            if ((rc = ivlm_relpos_gather(b.G, (int64_t)M * d.npad, d.npad, nb, H, side, side, b.relh_g, rw, stream))) return rc;
+        } else {  // the dot kernel (ATT_SPLIT: on q = hi + lo)
+            // (ATT_BF16 has always written these into the window-sized pair, which a GLOBAL block below 32 x 32 overruns - into
+            //  the next buffers of the carve, not out of the workspace: its terms are wrong there; kept as it is)
+            const bool big = glob && m.attn == ATT_SPLIT;
+            float* rhf = big ? b.relh_g : b.relh_w;
+            rh = rhf; rw = big ? b.relw_g : b.relw_w;
+            if ((rc = relpos_bias(q, (int64_t)S * rs, hdim, rs, static_cast<const bf16_t*>(Bk.rel_h), static_cast<const bf16_t*>(Bk.rel_w),
+                                  nb, H, side, side, hdim, rhf, rw, st, q_lo)))
+                return rc;
         }
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm2_w), static_cast<const bf16_t*>(Bk.norm2_b), xn, 2, R, D, 1e-6f, st))) return rc;
-        if ((rc = gemm(xn, 2 * D, Bk.lin1_w, D, hh, 0, 2 * MD, Bk.lin1_b, nullptr, 0, 0, 0, R, MD, D, ACT_GELU, nullptr, nullptr, nullptr, 0, st, 1, 1))) return rc;
-        if ((rc = gemm(hh, 2 * MD, Bk.lin2_w, MD, x, 1, D, Bk.lin2_b, x, 1, D, 0, R, D, MD, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 0))) return rc;
+        const int64_t la = wide(m.proj, IVLM_GEMM_A_SPLIT, D);  // row width of the attention output
+        if ((rc = attend(q, q_lo, k, k_lo, v, v_lo, rs, b.att, la, m.attn == ATT_F16Q, nb, H, S, hdim, rh, rw, side, st))) return rc;
+        if ((rc = mm(b.att, la, (m.proj & kF16) ? B16.proj_w16 : Bk.proj_w, x, D, Bk.proj_b, x, D, D, ACT_NONE, nullptr, wmap, m.proj))) return rc;
+        if ((rc = ln(x, 1, Bk.norm2_w, Bk.norm2_b, b.xn, m.n2, D))) return rc;
+        const int64_t lh = wide(m.lin1, IVLM_GEMM_OUT_SPLIT, MD);  // row width of the MLP hidden
+        if ((rc = mm(b.xn, wide(m.lin1, IVLM_GEMM_A_SPLIT, D), (m.lin1 & kF16) ? B16.lin1_w16 : Bk.lin1_w, b.hh, lh, Bk.lin1_b, nullptr, MD,
+                     D, ACT_GELU, nullptr, nullptr, m.lin1)))
+            return rc;
+        if ((rc = mm(b.hh, lh, (m.lin2 & kF16) ? B16.lin2_w16 : Bk.lin2_w, x, D, Bk.lin2_b, x, D, MD, ACT_NONE, nullptr, nullptr, m.lin2))) return rc;
     }
-    // neck: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d on split operands
-    if ((rc = gather_rows(xn, 2, 2 * D, x, 1, D, nullptr, nullptr, 0, 0, R, D, st))) return rc;
-    if ((rc = gemm(xn, 2 * D, hd->neck0_w, D, n0, 1, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 0))) return rc;
-    if ((rc = layernorm(n0, 1, static_cast<const bf16_t*>(hd->neck1_w), static_cast<const bf16_t*>(hd->neck1_b), n1, 2, R, OC, 1e-6f, st))) return rc;
-    if ((rc = im2col3x3_nhwc(n1, c3, V, g, g, OC, st, 2 * OC, 18 * OC))) return rc;
-    if ((rc = im2col3x3_nhwc(n1 + OC, c3 + 9 * OC, V, g, g, OC, st, 2 * OC, 18 * OC))) return rc;
-    if ((rc = gemm(c3, 18 * OC, hd->neck2_w, 9 * OC, n0, 1, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 0))) return rc;
-    return layernorm(n0, 1, static_cast<const bf16_t*>(hd->neck3_w), static_cast<const bf16_t*>(hd->neck3_b), embeddings_out, 1, R, OC, 1e-6f, st);
+    // neck: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d - on bf16 operands, or on [hi | lo] operands with fp32 conv outputs
+    const int sp = m.split_neck ? 1 : 0, nf = sp ? kSplitA : 0, nw_ = sp ? 2 * OC : OC;  // nw_: row width of the LayerNorm2d output
+    if ((rc = gather_rows(b.xn, sp ? 2 : 0, sp ? 2 * D : D, x, 1, D, nullptr, nullptr, 0, 0, R, D, st))) return rc;
+    if ((rc = gemm(b.xn, sp ? 2 * D : D, hd->neck0_w, D, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st, nf))) return rc;
+    if ((rc = ln(b.n0, sp, hd->neck1_w, hd->neck1_b, b.n1, sp ? 2 : 0, OC))) return rc;
+    for (int half = 0; half <= sp; ++half)  // (the hi and the lo halves are gathered separately)
+        if ((rc = im2col3x3_nhwc(b.n1 + half * OC, b.c3 + half * 9 * OC, V, g, g, OC, st, nw_, 9 * nw_))) return rc;
+    if ((rc = gemm(b.c3, 9 * nw_, hd->neck2_w, 9 * OC, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, nullptr, 0, st, nf))) return rc;
+    return ln(b.n0, sp, hd->neck3_w, hd->neck3_b, embeddings_out, 1, OC);
 }
+
+constexpr auto kNoF16 = [](int) { return ivlm_sam_block_f16{}; };
+
 }  // namespace
 }  // namespace ivlm
 
+extern "C" size_t ivlm_sam_encode_workspace_bytes(const ivlm_sam_cfg* c, int V) { return sam_workspace_bytes(c, V, kSamDefault); }
+extern "C" size_t ivlm_sam_encode_parity_workspace_bytes(const ivlm_sam_cfg* c, int V) { return sam_workspace_bytes(c, V, kSamParity); }
+extern "C" size_t ivlm_sam_encode_f16_workspace_bytes(const ivlm_sam_cfg* c, int V) { return sam_workspace_bytes(c, V, kSamF16q); }
+
+// mode "default"
+extern "C" int ivlm_sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host, const void* images,
+                               int V, float* embeddings_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
+    return sam_encode(c, hd, blocks_host, kNoF16, kSamDefault, images, V, embeddings_out, workspace, workspace_bytes, stream);
+}
+
+// mode "parity"
 extern "C" int ivlm_sam_encode_parity(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host,
                                       const void* images, int V, float* embeddings_out, void* workspace, size_t workspace_bytes,
                                       ivlm_stream_t stream) {
-    ivlm_enter();
-    return sam_encode_parity(c, hd, blocks_host, nullptr, images, V, embeddings_out, workspace, workspace_bytes, stream);
+    return sam_encode(c, hd, blocks_host, kNoF16, kSamParity, images, V, embeddings_out, workspace, workspace_bytes, stream);
 }
 
-// ... with the MLP of every block on fp16 operands (the "parity-encoder" mode of interactvlm_amd/model.py; bit-identical to
-// SamImageEncoder._forward_parity with sites n1, attn, proj, f16mlp)
+// mode "parity-fast": mlp16_host[l] = the fp16 copies of block l's lin1_w / lin2_w; the workspace of the parity stage
 extern "C" int ivlm_sam_encode_parity_f16mlp(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host,
                                              const ivlm_sam_mlp_f16* mlp16_host, const void* images, int V, float* embeddings_out,
                                              void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
-    ivlm_enter();
     if (!mlp16_host) return IVLM_ERR_INVALID_ARG;
-    return sam_encode_parity(c, hd, blocks_host, mlp16_host, images, V, embeddings_out, workspace, workspace_bytes, stream);
+    auto w16 = [=](int l) { return ivlm_sam_block_f16{nullptr, nullptr, mlp16_host[l].lin1_w16, mlp16_host[l].lin2_w16, nullptr, nullptr}; };
+    return sam_encode(c, hd, blocks_host, w16, kSamParityFast, images, V, embeddings_out, workspace, workspace_bytes, stream);
 }
 
-// =====================================================================================================================
-// ivlm_sam_encode_f16: the stage in the DEFAULT precision of the host model (interactvlm_amd/sam.py SamImageEncoder._forward_parity
-// with SITES_F16Q, bit-identical to it): IEEE fp16 MFMA operands in one pass with the q path exact -
-//   norm1 -> [hi | lo] halves; q = W_q . (hi + lo) as its own GEMM, written as [hi | lo] halves; k | v: one GEMM on the hi half;
-//   attention on fp16 q / k / v with the lo half of q in the rel-pos table products (windows: whole-window kernel; the 64 x 64
-//   grid: REL 5), fp32 rel-pos terms; proj / mlp1 / mlp2 on fp16 operands; the neck on hi + lo bf16 operands.
-// blocks16_host[l]: fp16 copies of block l's four GEMM weights, of its q|k|v bias and of rel_cat (ivlm_bf16_to_f16).
-// =====================================================================================================================
-extern "C" size_t ivlm_sam_encode_f16_workspace_bytes(const ivlm_sam_cfg* c, int V) {
-    if (!c || V <= 0) return 0;
-    const size_t g2 = (size_t)c->grid * c->grid, rows = (size_t)V * g2, D = c->embed_dim;
-    const int nw = (c->grid + c->window - 1) / c->window;
-    const size_t wrows = (size_t)V * nw * nw * c->window * c->window, qrows = std::max(rows, wrows);
-    size_t b = al(rows * 3 * c->patch * c->patch * 2) + al(rows * D * 4) + al(rows * 2 * D * 2) + 2 * al(qrows * 2 * D * 2) +
-               al(qrows * D * 2) + al(rows * c->mlp_dim * 2);
-    b += al(wrows * 4) + al(rows * 4) + al(2 * D * 2);            // part / unpart maps, the [q bias | 0] row of the padded positions
-    b += al(rows * c->out_chans * 4) + al(rows * 2 * c->out_chans * 2) + al(rows * 18 * c->out_chans * 2);
-    return b + 1024;
-}
-
+// mode "f16q": blocks16_host[l] = the fp16 copies of block l's four GEMM weights, of its q|k|v bias and of rel_cat (ivlm_bf16_to_f16)
 extern "C" int ivlm_sam_encode_f16(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_block* blocks_host,
                                    const ivlm_sam_block_f16* blocks16_host, const void* images, int V, float* embeddings_out,
                                    void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
-    ivlm_enter();
-    if (!c || !hd || !blocks_host || !blocks16_host || !images || !embeddings_out || !workspace || V <= 0) return IVLM_ERR_INVALID_ARG;
-    if (workspace_bytes < ivlm_sam_encode_f16_workspace_bytes(c, V)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    const int g = c->grid, D = c->embed_dim, H = c->heads, hdim = D / H, wsz = c->window, OC = c->out_chans, MD = c->mlp_dim;
-    const int nw = (g + wsz - 1) / wsz, g2 = g * g, R = V * g2, nwin = V * nw * nw, WS = wsz * wsz, WR = nwin * WS;
-    const int Kp = 3 * c->patch * c->patch;
-    if (hdim != 80 || g != 64 || 2 * wsz > 32) return IVLM_ERR_UNSUPPORTED;  // (table-mode attention: SAM's head dim, grid and windows)
-    Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    bf16_t* cols = static_cast<bf16_t*>(cv.take((size_t)R * Kp * 2));
-    float* x = static_cast<float*>(cv.take((size_t)R * D * 4));
-    bf16_t* xn = static_cast<bf16_t*>(cv.take((size_t)R * 2 * D * 2));
-    const size_t qrows = std::max(R, WR);
-    bf16_t* q2 = static_cast<bf16_t*>(cv.take(qrows * 2 * D * 2));   // [q hi | q lo]
-    bf16_t* kv = static_cast<bf16_t*>(cv.take(qrows * 2 * D * 2));   // [k | v]
-    bf16_t* att = static_cast<bf16_t*>(cv.take(qrows * D * 2));
-    bf16_t* hh = static_cast<bf16_t*>(cv.take((size_t)R * MD * 2));
-    int32_t* part = static_cast<int32_t*>(cv.take((size_t)WR * 4));
-    int32_t* unpart = static_cast<int32_t*>(cv.take((size_t)R * 4));
-    bf16_t* brow = static_cast<bf16_t*>(cv.take((size_t)2 * D * 2));
-    float* n0 = static_cast<float*>(cv.take((size_t)R * OC * 4));
-    bf16_t* n1 = static_cast<bf16_t*>(cv.take((size_t)R * 2 * OC * 2));
-    bf16_t* c3 = static_cast<bf16_t*>(cv.take((size_t)R * 18 * OC * 2));
-    if (!cv.ok) return IVLM_ERR_WORKSPACE;
-    int rc;
-    sam_window_maps_kernel<<<256, 256, 0, st>>>(V, g, wsz, nw, part, unpart);
-    if ((rc = ivlm_launch_status())) return rc;
-    if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), cols, V, 3, c->img_size, c->img_size, c->patch, c->patch, Kp, st))) return rc;
-    if ((rc = gemm(cols, Kp, hd->patch_w, Kp, x, 1, D, hd->patch_b, hd->pos_embed, 0, D, g2, R, D, Kp, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
-    const float scale = 1.0f / sqrtf((float)hdim);
-    for (int l = 0; l < c->depth; ++l) {
-        const ivlm_sam_block& Bk = blocks_host[l];
-        const ivlm_sam_block_f16& B16 = blocks16_host[l];
-        if (!B16.qkv_w16 || !B16.proj_w16 || !B16.lin1_w16 || !B16.lin2_w16 || !B16.qkv_b16 || !B16.rel_cat16) return IVLM_ERR_INVALID_ARG;
-        const bf16_t* wq = static_cast<const bf16_t*>(B16.qkv_w16);
-        const bf16_t* bq = static_cast<const bf16_t*>(Bk.qkv_b);
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm1_w), static_cast<const bf16_t*>(Bk.norm1_b), xn, 5, R, D, 1e-6f, st))) return rc;
-        const int side = Bk.global_attn ? g : wsz, S = side * side, nb = Bk.global_attn ? V : nwin;
-        const int32_t* omap = Bk.global_attn ? nullptr : unpart;
-        // q = W_q . (hi + lo) -> [hi | lo] halves;  k | v = W_kv . hi  (real rows only; windows: scattered to their window positions)
-        if ((rc = gemm(xn, 2 * D, wq, D, q2, 0, 2 * D, bq, nullptr, 0, 0, 0, R, D, D, ACT_NONE, omap, nullptr, nullptr, 0, st, 1, 1, 1, 1))) return rc;
-        if ((rc = gemm(xn, 2 * D, wq + (size_t)D * D, D, kv, 0, 2 * D, bq + D, nullptr, 0, 0, 0, R, 2 * D, D, ACT_NONE, omap, nullptr, nullptr, 0, st, 0, 0, 1, 1))) return rc;
-        if (!Bk.global_attn) {  // the padded window positions: q = [bias | 0], k | v = bias
-            IVLM_HIP_TRY(hipMemsetAsync(brow, 0, (size_t)2 * D * 2, st));
-            IVLM_HIP_TRY(hipMemcpyAsync(brow, B16.qkv_b16, (size_t)D * 2, hipMemcpyDeviceToDevice, st));
-            fill_pad_rows_kernel<<<2048, 256, 0, st>>>(q2, 2 * D, part, WR, brow, 2 * D);
-            fill_pad_rows_kernel<<<2048, 256, 0, st>>>(kv, 2 * D, part, WR, static_cast<const bf16_t*>(B16.qkv_b16) + D, 2 * D);
-            if ((rc = ivlm_launch_status())) return rc;
-        }
-        AttnArgs a{};
-        a.f16 = 1;
-        a.q = q2; a.q_lo = q2 + D; a.q_lo_level = 1;
-        a.k = kv; a.v = kv + D; a.o = att;
-        a.q_bs = a.k_bs = a.v_bs = (int64_t)S * 2 * D;
-        a.q_hs = a.k_hs = a.v_hs = hdim;
-        a.q_rs = a.k_rs = a.v_rs = 2 * D;
-        a.o_bs = (int64_t)S * D; a.o_hs = hdim; a.o_rs = D;
-        a.B = nb; a.H = H; a.Sq = S; a.Sk = S; a.D = hdim;
-        a.scale = scale; a.causal = 0; a.q_pos0 = 0;
-        a.rel_h = reinterpret_cast<const float*>(B16.rel_cat16); a.rel_w = nullptr; a.rel_kh = side; a.rel_kw = side;  // table mode
-        a.kv_batch_div = 1; a.prescale_q = 1;
-        if ((rc = attention_bf16(a, st))) return rc;
-        if ((rc = gemm(att, D, B16.proj_w16, D, x, 1, D, Bk.proj_b, x, 1, D, 0, R, D, D, ACT_NONE, nullptr, omap, nullptr, 0, st, 0, 0, 1, 0))) return rc;
-        if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(Bk.norm2_w), static_cast<const bf16_t*>(Bk.norm2_b), xn, 4, R, D, 1e-6f, st))) return rc;
-        if ((rc = gemm(xn, D, B16.lin1_w16, D, hh, 0, MD, Bk.lin1_b, nullptr, 0, 0, 0, R, MD, D, ACT_GELU, nullptr, nullptr, nullptr, 0, st, 0, 0, 1, 1))) return rc;
-        if ((rc = gemm(hh, MD, B16.lin2_w16, MD, x, 1, D, Bk.lin2_b, x, 1, D, 0, R, D, MD, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 0, 0, 1, 0))) return rc;
-    }
-    // neck: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d on hi + lo bf16 operands (as the parity stage)
-    if ((rc = gather_rows(xn, 2, 2 * D, x, 1, D, nullptr, nullptr, 0, 0, R, D, st))) return rc;
-    if ((rc = gemm(xn, 2 * D, hd->neck0_w, D, n0, 1, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 0))) return rc;
-    if ((rc = layernorm(n0, 1, static_cast<const bf16_t*>(hd->neck1_w), static_cast<const bf16_t*>(hd->neck1_b), n1, 2, R, OC, 1e-6f, st))) return rc;
-    if ((rc = im2col3x3_nhwc(n1, c3, V, g, g, OC, st, 2 * OC, 18 * OC))) return rc;
-    if ((rc = im2col3x3_nhwc(n1 + OC, c3 + 9 * OC, V, g, g, OC, st, 2 * OC, 18 * OC))) return rc;
-    if ((rc = gemm(c3, 18 * OC, hd->neck2_w, 9 * OC, n0, 1, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, nullptr, 0, st, 1, 0))) return rc;
-    return layernorm(n0, 1, static_cast<const bf16_t*>(hd->neck3_w), static_cast<const bf16_t*>(hd->neck3_b), embeddings_out, 1, R, OC, 1e-6f, st);
+    if (!blocks16_host) return IVLM_ERR_INVALID_ARG;
+    return sam_encode(c, hd, blocks_host, [=](int l) { return blocks16_host[l]; }, kSamF16q, images, V, embeddings_out, workspace,
+                      workspace_bytes, stream);
 }
 
 // =====================================================================================================================

@@ -217,7 +217,8 @@ class SamBlockF16C(C.Structure):
 
 
 class SamEncodeStages:
-    """``ivlm_sam_encode*`` over the weights of a ``sam.SamImageEncoder`` (fp32 residual stream)."""
+    """``ivlm_sam_encode*`` over the weights of a ``sam.SamImageEncoder`` (fp32 residual stream): four entry points onto ONE C
+    sequencer driven by a mode table that restates ``sam._MODES``; each size function measures the carve its entry point runs."""
 
     def __init__(self, enc):
         self.e = enc

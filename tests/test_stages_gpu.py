@@ -244,3 +244,163 @@ def test_stage_splitk_fused_switch_is_opt_in_and_bit_identical(hip_lib, cuda):
         hip_lib.ivlm_stages_splitk_fused(prev)
     for h, k in outs[1:]:
         assert torch.equal(h, outs[0][0]) and torch.equal(k, outs[0][1])
+
+
+# ---- the C encoder away from the 64 x 64 grid, and the workspace sizes against the carve of every sequencer -------------------------
+_SAM_SIZE_FN = {"default": "ivlm_sam_encode_workspace_bytes", "parity": "ivlm_sam_encode_parity_workspace_bytes",
+                "parity-fast": "ivlm_sam_encode_parity_workspace_bytes", "f16q": "ivlm_sam_encode_f16_workspace_bytes"}
+_cache = {}
+
+
+def _sam_encoder(which, cuda):
+    """"small": grid 30 (3 x 3 windows padded 30 -> 42, head dim 80, a global side of 30: the rel-pos dot kernel), the config
+    tests/test_model_gpu.py runs through Python; "vith4": the real ViT-H layer dimensions at depth 4.  Built once."""
+    if which not in _cache:
+        from interactvlm_amd import sam
+        from interactvlm_amd import weights as Wt
+
+        c = (Wt.SamEncCfg(embed_dim=160, depth=2, num_heads=2, global_attn_indexes=(1,), img_size=480) if which == "small"
+             else Wt.SamEncCfg(depth=4, global_attn_indexes=(1, 3)))
+        _cache[which] = sam.SamImageEncoder(Wt.synth_weights(Wt.sam_encoder_spec(c)), c, cuda)
+    return _cache[which]
+
+
+def _images(enc, V, cuda):
+    import torch
+
+    s = enc.cfg.img_size
+    return torch.randn(V, 3, s, s, generator=torch.Generator().manual_seed(10 + V)).to(torch.bfloat16).to(cuda)
+
+
+def _small_python_refs(cuda):
+    """SamImageEncoder._forward of the small config, V = 2, in every mode the C encoder repeats there (computed once)"""
+    if "refs" not in _cache:
+        enc = _sam_encoder("small", cuda)
+        x = _images(enc, 2, cuda)
+        refs = {}
+        for p in ("default", "parity", "parity-fast"):
+            enc.precision = p
+            refs[p] = enc._forward(x)
+        enc.precision = "default"
+        _cache["refs"] = (x, refs)
+    return _cache["refs"]
+
+
+@pytest.mark.parametrize("precision", ["parity", "parity-fast", "f16q"])
+def test_sam_encode_stage_small_grid_equals_python_path(hip_lib, cuda, precision):
+    """The C encoder at a grid that is not 64 x 64: heavy window padding (30 -> 42: 49 % of the window rows are pad rows) and a
+    global block below 32 x 32, whose rel-pos terms come from the dot kernel - bit-identical to the Python path; the exact-q
+    fp16 mode is built for the 64 x 64 grid and says so.
+
+    "default" is not in the list: ivlm_sam_encode is NOT bit-identical to the Python path here (max |d| 1.65 on MI355X, before
+    and after the sequencers were merged).  For a global block below 32 x 32 its dot-kernel branch writes the rel-pos terms
+    (V * H * 900 * 30 floats per array) into the window-sized pair of buffers (V * 9 * 196 * H * 14 floats each): the first
+    array runs into the second.  The writes stay inside the workspace.  At the 64 x 64 grid that branch is never taken."""
+    import torch
+
+    from interactvlm_amd import _lib, stages
+
+    x, refs = _small_python_refs(cuda)
+    st = stages.SamEncodeStages(_sam_encoder("small", cuda))
+    if precision == "f16q":
+        with pytest.raises(_lib.IvlmError, match=r"\(-4\)"):  # IVLM_ERR_UNSUPPORTED
+            st(x, precision="f16q")
+        return
+    got = st(x, precision=precision)
+    assert got.shape == refs[precision].shape == (2, 900, 256) and got.dtype == torch.float32
+    assert torch.equal(got, refs[precision]), float((got - refs[precision]).abs().max())
+    if precision == "parity":
+        assert not torch.equal(refs["parity"], refs["default"])
+
+
+class _workspace_delta:
+    """The ctypes mirrors size a stage's workspace with the library's size function: inside this block they see size + delta."""
+
+    def __init__(self, lib, size_fn, delta):
+        self.lib, self.name, self.delta = lib, size_fn, delta
+
+    def __enter__(self):
+        self.real = real = getattr(self.lib, self.name)
+        setattr(self.lib, self.name, lambda *a: real(*a) + self.delta)
+
+    def __exit__(self, *exc):
+        setattr(self.lib, self.name, self.real)
+
+
+def _check_size_is_the_carve(lib, size_fn, run, compare=True):
+    """run() calls one stage through its mirror: 256 bytes less than the size function says are refused before anything is
+    launched (every region of a carve is a multiple of 256 bytes), exactly the size works and gives what a larger buffer gives."""
+    import torch
+
+    from interactvlm_amd import _lib
+
+    with _workspace_delta(lib, size_fn, -256), pytest.raises(_lib.IvlmError, match=r"\(-2\)"):  # IVLM_ERR_WORKSPACE
+        run()
+    got = run()
+    with _workspace_delta(lib, size_fn, 1 << 16):
+        big = run()
+    assert not compare or torch.equal(got.view(torch.uint8), big.view(torch.uint8))
+
+
+@pytest.mark.parametrize("which", ["small", "vith4"])
+def test_sam_encode_workspace_size_is_the_carve(hip_lib, cuda, which):
+    from interactvlm_amd import _lib, stages
+
+    enc = _sam_encoder(which, cuda)
+    st = stages.SamEncodeStages(enc)
+    for V in (1, 2):
+        x = _images(enc, V, cuda)
+        for precision, size_fn in _SAM_SIZE_FN.items():
+            if which == "small" and precision == "f16q":  # (the size is checked first, then the grid is refused)
+                with _workspace_delta(hip_lib, size_fn, -256), pytest.raises(_lib.IvlmError, match=r"\(-2\)"):
+                    st(x, precision=precision)
+                with pytest.raises(_lib.IvlmError, match=r"\(-4\)"):
+                    st(x, precision=precision)
+                continue
+            # (small grid, "default": two of its rel-pos arrays overlap - see the small-grid test - so two runs need not agree)
+            _check_size_is_the_carve(hip_lib, size_fn, lambda: st(x, precision=precision),
+                                     compare=not (which == "small" and precision == "default"))
+
+
+def test_clip_and_llama_workspace_sizes_are_the_carve(hip_lib, cuda):
+    import ctypes
+
+    import torch
+
+    from interactvlm_amd import _lib, llava, stages
+    from interactvlm_amd import weights as Wt
+
+    cc = Wt.ClipCfg(hidden=256, layers=4, heads=4, inter=512)
+    clip = stages.ClipStages(llava.ClipTower(Wt.synth_weights(Wt.clip_spec(cc)), cc, cuda))
+    img = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).to(cuda)
+    _check_size_is_the_carve(hip_lib, "ivlm_clip_encode_workspace_bytes", lambda: clip(img))
+
+    def llama(hidden, heads, inter, precision):
+        lc = Wt.LlamaCfg(hidden=hidden, layers=3, heads=heads, inter=inter, vocab=1000)
+        w = {k: v.to(torch.bfloat16).float() for k, v in Wt.synth_weights(Wt.llama_spec(lc)).items()}
+        m = llava.Llama(w, lc, cuda, max_len=128)
+        m.set_precision(precision)
+        return stages.LlamaStages(m)
+
+    g = torch.Generator().manual_seed(5)
+    emb = (torch.randn(42, 256, generator=g) * 0.5).to(torch.bfloat16).float().to(cuda)
+    st = llama(256, 2, 512, "default")
+    _check_size_is_the_carve(hip_lib, "ivlm_llama_prefill_workspace_bytes", lambda: st.prefill(emb[:41], 0))
+    # the three entry points of the decode step share ivlm_llama_decode_workspace_bytes (LlamaStages allocates it once, as _dws)
+    emb = (torch.randn(42, 1024, generator=g) * 0.5).to(torch.bfloat16).float().to(cuda)
+    pos = torch.tensor([41], dtype=torch.int32, device=cuda)
+    for precision, steps in (("default", ("decode_step", "decode_step_bf12")), ("f16", ("decode_step_f16kv", "decode_step_bf12"))):
+        st = llama(1024, 8, 2752, precision)
+        (st.prefill_f16 if precision == "f16" else st.prefill)(emb[:41], 0)
+        size = st._dws.numel()
+        assert size == hip_lib.ivlm_llama_decode_workspace_bytes(ctypes.byref(st.cfg))
+        for name in steps:
+            step = lambda: getattr(st, name)(emb[41:42].contiguous(), pos, advance=False)
+            st._dws = torch.zeros(size - 256, dtype=torch.uint8, device=cuda)
+            with pytest.raises(_lib.IvlmError, match=r"\(-2\)"):
+                step()
+            st._dws = torch.zeros(size, dtype=torch.uint8, device=cuda)
+            got = step()
+            st._dws = torch.zeros(size + (1 << 16), dtype=torch.uint8, device=cuda)
+            assert torch.equal(got.view(torch.uint8), step().view(torch.uint8))
+    assert int(pos[0]) == 41
