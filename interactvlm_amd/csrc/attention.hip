@@ -1218,7 +1218,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
             }
         }
         // ---- one-pass softmax over the S valid keys (log2 domain; padded keys -> probability exactly 0) -------------------
-        constexpr int ktl = KT - 1;  // the only tile that can hold padded keys
+        constexpr int ktl = KT - 1;  // the only tile that can hold padded keys (dispatch: S > 192)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             if (ktl * 16 + g * 4 + r >= S) s[ktl][r] = kNegBig;
@@ -1444,7 +1444,9 @@ int launch_d(const AttnArgs& a, hipStream_t st) {
     // every shape of the path (SAM global 634 vs 604 us, windows 151 vs 132 us) - the loop is bound by the issue latency of
     // the dependent softmax chain, not by the two waves of a SIMD contending for the same unit
     if constexpr (DV == 80) {  // SAM's windows: the whole-window kernel (default precision: table mode; SPLIT: array mode)
-        const bool win = g_win_v2 && a.rel_h && a.Sq <= 208 && a.Sq == a.Sk && !a.causal && a.prescale_q && a.H <= 65535 &&
+        // (192 < Sq: the whole-window kernel masks padded keys in its LAST 16-key tile only - in a smaller window the zero K rows of
+        //  the tiles before it would score 0 + a stray rel-pos term and count in the softmax; those windows take the generic kernel)
+        const bool win = g_win_v2 && a.rel_h && a.Sq > 192 && a.Sq <= 208 && a.Sq == a.Sk && !a.causal && a.prescale_q && a.H <= 65535 &&
                          a.B <= 65535 && a.rel_kh == a.rel_kw && 2 * a.rel_kh <= 32 && a.Sq == a.rel_kh * a.rel_kw;
         if (win && !a.q_lo && !a.rel_w) return a.f16 ? launch_win<false, true>(a, st) : launch_win<false>(a, st);
         if (win && a.q_lo && !a.rel_w && a.f16) return a.q_lo_level >= 2 ? launch_win<false, true, 2>(a, st) : launch_win<false, true, 1>(a, st);

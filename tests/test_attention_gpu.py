@@ -1,10 +1,26 @@
 """GPU parity of the fused attention kernel against plain PyTorch fp32 softmax(QK^T)V on the same
 bf16-rounded inputs (the HIP kernel keeps softmax in fp32 and rounds P to bf16 for the PV MFMA)."""
 import math
+import os
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _attn_ref as R  # noqa: E402  (fp64 reference, emulation of the documented roundings, normalised error)
+
 pytestmark = pytest.mark.gpu
+
+
+def _assert_tracks_rounding(got, q, k, v, scale, causal=False, q_pos0=0):
+    """The error against fp64 in units of the kernel's documented rounding: at most 2 x (max) / 1.5 x (rms) what a plain emulation of
+    those roundings gives on the same inputs (tests/test_attn_ref_cpu.py caps the emulation's own figures)."""
+    o, wabs = R.ref64(q, k, v, scale, causal, q_pos0)
+    emu = R.ratio_stats(R.emulate(q, k, v, scale, causal, q_pos0, rt=q.dtype), o, wabs, q.dtype)
+    gs = R.ratio_stats(got.cpu(), o, wabs, q.dtype)
+    print(f"\nratio max {gs[0]:.3f} rms {gs[1]:.3f} (emulation: max {emu[0]:.3f} rms {emu[1]:.3f})")
+    assert gs[0] <= R.MAX_MARGIN * emu[0] and gs[1] <= R.RMS_MARGIN * emu[1], (gs, emu)
 
 
 @pytest.fixture(autouse=True, params=["4-wave", "ping-pong"])
@@ -57,6 +73,7 @@ def test_attention_vs_torch(hip_lib, cuda, B, H, Sq, Sk, D, causal, q_pos0):
     assert got.shape == (B, H, Sq, D)
     err = (got.float().cpu() - ref).abs().max().item()
     assert err < 2e-2, f"max err {err}"
+    _assert_tracks_rounding(got, q, k, v, scale, causal, q_pos0)
 
 
 def test_attention_fused_qkv_layout_and_kv_broadcast(hip_lib, cuda):
@@ -135,6 +152,7 @@ def test_attention_rescale_branch_forced(hip_lib, cuda):
     ref = _ref(q, k, v, 0.125)
     got = ops.attention(q.to(cuda), k.to(cuda), v.to(cuda), 0.125)
     assert (got.float().cpu() - ref).abs().max().item() < 2e-2
+    _assert_tracks_rounding(got, q, k, v, 0.125)
 
 
 @pytest.mark.parametrize("SH,SW,B,H", [(14, 14, 5, 4), (64, 64, 2, 3), (6, 10, 2, 2)])
