@@ -88,6 +88,25 @@ __device__ __forceinline__ float groups_sum(float x) {
 // global loads of the next tiles that were issued precisely so that they stay in flight across the barrier.
 __device__ __forceinline__ void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// LDS layout of attn_kernel's K / V tiles: the kernel takes its strides and pointers from it, the launcher the dynamic bytes.
+template <int DQK, int DV, int REL, bool SPLIT>
+struct AttnLds {
+    static constexpr int KS = DQK / 32, DT = DV / 16;  // MFMA k-steps / 16-wide output tiles over the head dim
+    // plane strides carry one extra row: the staging stores (8 consecutive lanes of a ds_write_b128 = 8 consecutive 16-byte
+    // chunks of a key) then walk 8 distinct 16-byte bank slots instead of hitting one slot 2x (K) / 4x (V); the fragment
+    // reads of one plane are only rotated by it
+    static constexpr int KPL = kKV * 32 + 32;  // elements per k-step plane  [key][32] (+ 64 B)
+    static constexpr int VPL = kKV * 16 + 16;  // elements per d-tile plane  [key][16] (+ 32 B)
+    static constexpr int KBUF = KS * KPL, VBUF = DT * VPL;
+    static constexpr int KB2 = SPLIT ? 2 * KBUF : KBUF, VB2 = SPLIT ? 2 * VBUF : VBUF;  // elements per buffer (SPLIT: [hi planes | lo planes])
+    static constexpr int kGW = 16 * 65;  // REL 4: floats of a wave's table-product scratch (64 table rows x 16 queries, row stride 65)
+    // SPLIT: the tiles live in dynamic LDS (2 x the bytes, one block of 8 waves per CU) - byte offsets of
+    // [2 K buffers | 2 V buffers | the rel_h block of REL 2 or the scratch of REL 4 (they never coincide)]
+    static constexpr size_t k_off = 0, v_off = k_off + 2 * KB2 * sizeof(bf16_t), r_off = v_off + 2 * VB2 * sizeof(bf16_t);
+    static constexpr size_t bytes = !SPLIT ? 0 : r_off + (REL == 2 ? kQPerBlock * kKV : REL == 4 ? 8 * kGW : 0) * sizeof(float);
+    static_assert(bytes <= 160 * 1024, "the split tiles must fit the LDS");
+};
+
 // REL: 0 no bias; 1 rel-pos folded into the QK^T MFMA (KH + KW <= 32: one extra k-step whose Q' operand is
 // [rel_h | rel_w] and whose K' operand is the one-hot (kh, KH + kw) code of the key: exact, no VALU);
 // 2 rel_kw == 64 == key-tile: rel_w is tile-invariant (held as packed bf16 in registers), rel_h is one
@@ -124,33 +143,27 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
     constexpr int kQPerWave = 16 * QT;         // (shadows the namespace constant)
     constexpr int NT = (PP || SPLIT) ? 512 : 256;  // threads per block
     constexpr int kQBlk = PP ? 2 * kQPerBlock : kQPerBlock;
-    constexpr int KS = DQK / 32;        // MFMA k-steps over the head dim
-    constexpr int DT = DV / 16;         // 16-wide output tiles over the head dim
+    using L = AttnLds<DQK, DV, REL, SPLIT>;
+    constexpr int KS = L::KS, DT = L::DT;
     constexpr int DCH = DV / 8;         // 16-byte chunks per K/V row actually present in memory
     constexpr int NCH = kKV * DCH;      // chunks per K (or V) tile
     constexpr int CPT = (NCH + NT - 1) / NT;
-    // plane strides carry one extra row: the staging stores (8 consecutive lanes of a ds_write_b128 = 8 consecutive 16-byte
-    // chunks of a key) then walk 8 distinct 16-byte bank slots instead of hitting one slot 2x (K) / 4x (V); the fragment
-    // reads of one plane are only rotated by it
-    constexpr int KPL = kKV * 32 + 32;   // elements per k-step plane  [key][32] (+ 64 B)
-    constexpr int VPL = kKV * 16 + 16;   // elements per d-tile plane  [key][16] (+ 32 B)
-    constexpr int KBUF = KS * KPL;
-    constexpr int VBUF = DT * VPL;
-    // (SPLIT: the tiles live in dynamic LDS - [hi planes | lo planes] per buffer, 2 x the bytes)
+    constexpr int KPL = L::KPL, VPL = L::VPL, KBUF = L::KBUF, VBUF = L::VBUF, KB2 = L::KB2, VB2 = L::VB2, kGW = L::kGW;
+    // (SPLIT: the tiles live in dynamic LDS)
     __shared__ __attribute__((aligned(16))) bf16_t Ks_[2][SPLIT ? 8 : KBUF];
     __shared__ __attribute__((aligned(16))) bf16_t Vs_[2][SPLIT ? 8 : VBUF];
     // REL 2: rel_h[query][key row] of the block's queries, one value per (query, key tile).  Read from global at its point of use it is a dependent load in every tile, and the s_waitcnt the
     // compiler puts in front of it also drains the K/V prefetches of the following tiles.
     __shared__ __attribute__((aligned(16))) float Rh_[(R2 && !SPLIT) ? kQBlk * kKV : 4];
-    // REL 4: per-wave scratch of the rel-pos table product G^T = T . Q^T (64 table rows x 16 queries, row stride 65 floats)
-    constexpr int kGW = 16 * 65;
+    // REL 4: per-wave scratch of the rel-pos table product G^T = T . Q^T
     __shared__ float Gs_[(REL == 4 && !SPLIT) ? (NT / 64) * kGW : 4];
     extern __shared__ __attribute__((aligned(16))) unsigned char attn_dyn[];
-    constexpr int KB2 = SPLIT ? 2 * KBUF : KBUF, VB2 = SPLIT ? 2 * VBUF : VBUF;  // elements per buffer
+    // (pointer chain, not attn_dyn + offset: the form the compiler folds into the fragment addresses; the layout pins it)
+    static_assert(L::k_off == 0 && L::v_off == 2 * KB2 * sizeof(bf16_t) && L::r_off == L::v_off + 2 * VB2 * sizeof(bf16_t), "AttnLds");
     bf16_t* const Ks0 = SPLIT ? reinterpret_cast<bf16_t*>(attn_dyn) : &Ks_[0][0];
     bf16_t* const Vs0 = SPLIT ? Ks0 + 2 * KB2 : &Vs_[0][0];
     float* const Rh = SPLIT ? reinterpret_cast<float*>(Vs0 + 2 * VB2) : &Rh_[0];
-    float* const Gs = SPLIT ? Rh : &Gs_[0];  // (SPLIT: the dynamic region behind the tiles; REL 2 and REL 4 never coincide)
+    float* const Gs = SPLIT ? Rh : &Gs_[0];
     auto Ks = [&](int buf) __attribute__((always_inline)) { return Ks0 + buf * KB2; };
     auto Vs = [&](int buf) __attribute__((always_inline)) { return Vs0 + buf * VB2; };
 
@@ -883,6 +896,28 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
 // amplifies q's rounding (a term is q . R with |R| ~ 6 x the |k| * scale of the score product: tools/emulate_f16_sites.py), Q.K^T and
 // P.V stay single fp16: 12 extra MFMAs per query tile; 2: the lo half also enters Q.K^T and the softmax weights are split for P.V
 // (3 % closer, +74 MFMAs per tile).
+// LDS layout (all of it dynamic): the kernel takes its strides and pointers from it, the launcher the block size and the bytes.
+template <bool SPLIT>
+struct WinLds {
+    static constexpr int NT = SPLIT ? 512 : 1024;  // threads per block
+    static constexpr int NGW = SPLIT ? 8 : 13;     // waves that own a table-product scratch slice (a query tile)
+    static constexpr int KS = 3, DT = 5;
+    static constexpr int KT = 13, VS = 7;  // 16-key tiles (208 padded keys) of the score pass, 32-key steps (224) of the P.V pass
+    static constexpr int SPK = KT * 16, SPV = VS * 32;
+    static constexpr int KPL = SPK * 32 + 32, VPL = SPV * 16 + 16;  // plane strides (elements), padded like the tiles of attn_kernel
+    static constexpr int KBUF = KS * KPL, VBUF = DT * VPL;
+    static constexpr int kGW = 16 * 65;            // floats of a wave's table-product scratch
+    static constexpr int TPL = 64 * 32;            // elements per k-step plane of the rel-pos table
+    // byte offsets: [K hi | K lo (SPLIT) | V hi | V lo (SPLIT) | table mode only: one-hot rel-pos operands [KT][64 lanes] x 16 B |
+    //                table-product scratch | the rel-pos table in K-plane layout]
+    static constexpr size_t kh_off = 0, kl_off = kh_off + KBUF * sizeof(bf16_t);
+    static constexpr size_t vh_off = kh_off + (SPLIT ? 2 : 1) * KBUF * sizeof(bf16_t), vl_off = vh_off + VBUF * sizeof(bf16_t);
+    static constexpr size_t hot_off = vh_off + (SPLIT ? 2 : 1) * VBUF * sizeof(bf16_t);
+    static constexpr size_t gs_off = hot_off + KT * 64 * 16, tb_off = gs_off + NGW * kGW * sizeof(float);
+    static constexpr size_t bytes = SPLIT ? hot_off : tb_off + KS * TPL * sizeof(bf16_t);
+    static_assert(bytes <= 160 * 1024, "window tiles must fit the LDS");
+};
+
 template <bool SPLIT, bool F16 = false, int QLV = 0>
 __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArgs a) {
     static_assert(!(SPLIT && F16), "fp16 operands are single-pass");
@@ -894,24 +929,19 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
     // SPLIT: 8 waves (two per SIMD, 240 registers: held under 256 with scheduling barriers in the fragment loops), the 13 query tiles
     // in two rounds.  Default precision: 126 registers allow 16 waves (four per SIMD) - every query tile has a wave of its own (ONE
     // round; the kernel is latency-bound: ~12 % MFMA utilisation), the other three waves only help staging.
-    constexpr int NT = SPLIT ? 512 : 1024, NWV = NT / 64;
-    constexpr int NGW = SPLIT ? 8 : 13;  // waves that own a table-product scratch slice (a query tile)
-    constexpr int DV = 80, KS = 3, DT = 5, DCH = 10;
-    constexpr int KT = 13;            // 16-key tiles (208 padded keys) of the score pass
-    constexpr int VS = 7;             // 32-key steps (224 padded keys) of the P.V pass
-    constexpr int SPK = KT * 16, SPV = VS * 32;
-    constexpr int KPL = SPK * 32 + 32, VPL = SPV * 16 + 16;   // plane strides (elements), padded like the tiles of attn_kernel
-    constexpr int KBUF = KS * KPL, VBUF = DT * VPL;
-    constexpr int kGW = 16 * 65;
+    using L = WinLds<SPLIT>;
+    constexpr int NT = L::NT, NWV = NT / 64, NGW = L::NGW;
+    constexpr int DV = 80, KS = L::KS, DT = L::DT, DCH = 10;
+    constexpr int KT = L::KT, VS = L::VS, SPK = L::SPK, SPV = L::SPV;
+    constexpr int KPL = L::KPL, VPL = L::VPL, kGW = L::kGW, TPL = L::TPL;
     extern __shared__ __attribute__((aligned(16))) unsigned char win_dyn[];
-    bf16_t* const Kh = reinterpret_cast<bf16_t*>(win_dyn);
-    bf16_t* const Kl = Kh + KBUF;                              // (SPLIT only)
-    bf16_t* const Vh = Kh + (SPLIT ? 2 : 1) * KBUF;
-    bf16_t* const Vl = Vh + VBUF;                              // (SPLIT only)
-    u32x4_t* const Hot = reinterpret_cast<u32x4_t*>(Vh + (SPLIT ? 2 : 1) * VBUF);  // one-hot rel-pos operands [KT][64 lanes]
-    float* const Gs = reinterpret_cast<float*>(Hot + KT * 64);                    // (table mode only)
-    bf16_t* const Tb = reinterpret_cast<bf16_t*>(Gs + NGW * kGW);                   // (table mode) the rel-pos table, K-plane layout
-    constexpr int TPL = 64 * 32;
+    bf16_t* const Kh = reinterpret_cast<bf16_t*>(win_dyn + L::kh_off);
+    bf16_t* const Kl = reinterpret_cast<bf16_t*>(win_dyn + L::kl_off);      // (SPLIT only)
+    bf16_t* const Vh = reinterpret_cast<bf16_t*>(win_dyn + L::vh_off);
+    bf16_t* const Vl = reinterpret_cast<bf16_t*>(win_dyn + L::vl_off);      // (SPLIT only)
+    u32x4_t* const Hot = reinterpret_cast<u32x4_t*>(win_dyn + L::hot_off);  // (table mode only, like Gs and Tb)
+    float* const Gs = reinterpret_cast<float*>(win_dyn + L::gs_off);
+    bf16_t* const Tb = reinterpret_cast<bf16_t*>(win_dyn + L::tb_off);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, g = lane >> 4;
@@ -1310,152 +1340,174 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
     }
 }
 
-static int g_xcd_map = 1;  // REL 5: XCD-aware block map (A/B hook: ivlm_attention_xcd_map)
-static int g_win_v2 = 1;  // 0: the generic flash kernel for windows too (A/B hook: ivlm_attention_window_kernel)
+// ======================================================================================================================
+// Dispatch: attn_route() decides, attn_launch() maps the decision to an instantiation.
+//   * the rel-pos form is classified once; kRelRules below is the table of what each form runs and which variants it has.
+//     Every form needs D = 80, no causal mask and prescale_q (only SAM's ViT uses rel-pos; keeps the build small).
+//   * bf16 and fp16 without rel-pos: D in {16, 32, 64, 80, 128}, causal or not.  fp16 has no ping-pong kernels (the hook is ignored).
+//   * split ("parity": all four lo planes) builds the shapes of the path only: without rel-pos D 128 causal (LLaMA prefill) and
+//     D 64 non-causal (CLIP); SAM's ViT with the rel-pos terms as arrays or from a window table.
+//   * fp16 q_lo ("exact q") at level 1 with the terms as ARRAYS is the plain fp16 kernel: the lo half of q is already in the terms
+//     (ivlm_relpos_* on hi + lo).  Any other (form, level) needs the form's QLV kernel; q_lo without rel-pos is refused.
+//   * the whole-window kernel takes SAM's 14 x 14 windows (192 < Sq <= 208: it masks padded keys in its LAST 16-key tile only - in
+//     a smaller window the zero K rows of the tiles before it would score 0 + a stray rel-pos term and count in the softmax; those
+//     windows take the flash kernel): table mode for single operands (fp16: q_lo at level 1 or 2 -> QLV), array mode for split
+//     (no LDS left for the table product).  Hook ivlm_attention_window_kernel(0): the flash kernel for windows too.
+//   * the 8-wave ping-pong block is opt-in (hook ivlm_attention_pingpong(1)): measured 5-15 % SLOWER than two 4-wave blocks per CU
+//     (SAM global 634 vs 604 us, windows 151 vs 132 us) - the loop is bound by the issue latency of the dependent softmax chain.
+static int g_xcd_map = 1;   // REL 5: XCD-aware block map (A/B hook: ivlm_attention_xcd_map)
+static int g_win_v2 = 1;    // 0: the generic flash kernel for windows too (A/B hook: ivlm_attention_window_kernel)
+static int g_attn_pp = -1;  // -1 automatic; 0 / 1 force the 4-wave / 8-wave ping-pong kernel (benchmark hook)
 
-template <bool SPLIT, bool F16 = false, int QLV = 0>
+// window: win_attn_kernel<split, f16, qlv>, else attn_kernel<DQK, D, causal, rel, pp, split, f16, qlv>
+struct Route { bool window, causal; int rel; bool pp, split, f16; int qlv; };
+
+enum RelForm { kNoRel, kTabWin, kTabGrid, kArr64, kArrSmall, kArrAny };
+enum PpRule { kPpHonoured, kPpDropped, kPpRefused };  // what the bf16 kernels of a form do with the ping-pong hook
+constexpr struct { int rel; PpRule pp; bool split; int qlv; } kRelRules[] = {  // qlv: the fp16 q_lo level the form has a kernel for
+    /* kNoRel                                                            */ {0, kPpHonoured, true, 0},
+    /* kTabWin:   table [64, D], square window with 2 * side <= 32       */ {4, kPpDropped, true, 0},
+    /* kTabGrid:  table [>= 254, D], the 64 x 64 grid                    */ {5, kPpRefused, false, 1},
+    /* kArr64:    arrays, rel_kw == 64 == key tile, Sk == rel_kh * rel_kw */ {2, kPpHonoured, true, 2},
+    /* kArrSmall: arrays, rel_kh + rel_kw <= 32                          */ {1, kPpHonoured, true, 0},
+    /* kArrAny:   arrays, any other grid                                 */ {3, kPpDropped, true, 0},
+};
+
+static int attn_route(const AttnArgs& a, int pp_hook, int win_hook, Route* out) {
+    if (!a.q || !a.k || !a.v || !a.o || a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Sk <= 0) return IVLM_ERR_INVALID_ARG;
+    if (a.H > 65535 || a.B > 65535 || a.kv_batch_div <= 0) return IVLM_ERR_INVALID_ARG;
+    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs | a.q_bs | a.k_bs | a.v_bs) & 7)
+        return IVLM_ERR_UNSUPPORTED;  // 16-byte row chunks
+    if ((a.o_rs | a.o_hs | a.o_bs) & 3) return IVLM_ERR_UNSUPPORTED;
+    if (a.rel_h && (a.rel_kh <= 0 || a.rel_kw <= 0)) return IVLM_ERR_INVALID_ARG;
+    const bool f16 = a.f16 != 0;
+    if (a.rel_h && !a.rel_w) {  // table mode: square windows whose 2 * side terms fit one MFMA k-step, or the 64 x 64 grid (REL 5)
+        if (a.rel_kh != a.rel_kw || (2 * a.rel_kh > 32 && a.rel_kh != kKV) || a.Sq != a.rel_kh * a.rel_kw || a.Sk != a.Sq || a.D != 80 ||
+            (reinterpret_cast<uintptr_t>(a.rel_h) & 15))
+            return IVLM_ERR_UNSUPPORTED;
+        if (a.rel_kh == kKV && a.q_lo && !f16) return IVLM_ERR_UNSUPPORTED;  // (split x grid table, before the lo planes are counted)
+    }
+    if (f16) {  // fp16 operands: at most a lo plane of q ("exact q")
+        if (a.k_lo || a.v_lo || a.o_lo) return IVLM_ERR_INVALID_ARG;
+    } else if ((a.q_lo || a.k_lo || a.v_lo || a.o_lo) && !(a.q_lo && a.k_lo && a.v_lo && a.o_lo)) {
+        return IVLM_ERR_INVALID_ARG;
+    }
+    if (a.D != 16 && a.D != 32 && a.D != 64 && a.D != 80 && a.D != 128) return IVLM_ERR_UNSUPPORTED;
+
+    const RelForm form = !a.rel_h                                            ? kNoRel
+                         : !a.rel_w                                          ? (a.rel_kh == kKV ? kTabGrid : kTabWin)
+                         : a.rel_kw == kKV && a.Sk == a.rel_kh * a.rel_kw    ? kArr64
+                         : a.rel_kh + a.rel_kw <= 32                         ? kArrSmall
+                                                                             : kArrAny;
+    const bool qlo = a.q_lo && !(f16 && a.q_lo_level < 2 && a.rel_w);  // (fp16 level 1 with arrays: as without q_lo)
+    const bool split = qlo && !f16;
+    const int level = qlo && f16 ? (a.q_lo_level >= 2 ? 2 : 1) : 0;
+    const bool pp = pp_hook && !f16 && !split;
+    *out = Route{false, a.causal != 0, 0, false, split, f16, level};
+
+    const bool win = a.D == 80 && win_hook && a.rel_h && a.Sq > 192 && a.Sq <= 208 && a.Sq == a.Sk && !a.causal && a.prescale_q &&
+                     a.H <= 65535 && a.B <= 65535 && a.rel_kh == a.rel_kw && 2 * a.rel_kh <= 32 && a.Sq == a.rel_kh * a.rel_kw;
+    out->window = win && (a.rel_w != nullptr) == split;
+    if (out->window) return IVLM_OK;
+    const auto& rule = kRelRules[form];
+    if (form != kNoRel && (a.D != 80 || a.causal || !a.prescale_q)) return IVLM_ERR_UNSUPPORTED;
+    if (form == kNoRel && split && !(a.D == 128 && a.causal) && !(a.D == 64 && !a.causal)) return IVLM_ERR_UNSUPPORTED;
+    if (split && !rule.split) return IVLM_ERR_UNSUPPORTED;
+    if (level && level != rule.qlv) return IVLM_ERR_UNSUPPORTED;
+    if (pp && rule.pp == kPpRefused) return IVLM_ERR_UNSUPPORTED;
+    out->rel = rule.rel;
+    out->pp = pp && rule.pp == kPpHonoured;
+    return IVLM_OK;
+}
+
+// dynamic LDS above the default limit: allowed once per kernel and device (done: one mask per instantiation)
+static void allow_dynamic_lds(ivlm_dev_mask_t& done, const void* kfn, size_t bytes) {
+    if (!ivlm_dev_pending(done)) return;
+    (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    ivlm_dev_done(done);
+}
+
+template <int DQK, int DV, bool CAUSAL, int REL, bool PP, bool SPLIT, bool F16, int QLV>
+static int launch_flash(const AttnArgs& a, hipStream_t st) {
+    constexpr size_t lds = AttnLds<DQK, DV, REL, SPLIT>::bytes;
+    constexpr int QB = PP ? 2 * kQPerBlock : kQPerBlock;
+    auto kfn = attn_kernel<DQK, DV, CAUSAL, REL, PP, SPLIT, F16, QLV>;
+    if constexpr (lds != 0) {
+        static ivlm_dev_mask_t attr_set{0};
+        allow_dynamic_lds(attr_set, reinterpret_cast<const void*>(kfn), lds);
+    }
+    const dim3 grid = REL == 5 ? dim3((a.Sq / QB) * a.H * a.B) : dim3((a.Sq + QB - 1) / QB, a.H, a.B);  // (REL 5: 1-D, block map in the kernel)
+    kfn<<<grid, (PP || SPLIT) ? 512 : 256, lds, st>>>(a);
+    return ivlm_launch_status();
+}
+
+template <bool SPLIT, bool F16, int QLV>
 static int launch_win(const AttnArgs& a, hipStream_t st) {
-    constexpr int KS = 3, DT = 5, KPL = 13 * 16 * 32 + 32, VPL = 7 * 32 * 16 + 16;
-    constexpr size_t lds = (size_t)(SPLIT ? 2 : 1) * (KS * KPL + DT * VPL) * 2 +
-                           (SPLIT ? 0 : (size_t)13 * 64 * 16 + 13 * 16 * 65 * 4 + 3 * 64 * 32 * 2);
-    static_assert(lds <= 160 * 1024, "window tiles must fit the LDS");
+    using L = WinLds<SPLIT>;
     auto kfn = win_attn_kernel<SPLIT, F16, QLV>;
     static ivlm_dev_mask_t attr_set{0};
-    if (ivlm_dev_pending(attr_set)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        ivlm_dev_done(attr_set);
-    }
-    kfn<<<dim3(a.H * a.B), SPLIT ? 512 : 1024, lds, st>>>(a);
+    allow_dynamic_lds(attr_set, reinterpret_cast<const void*>(kfn), L::bytes);
+    kfn<<<dim3(a.H * a.B), L::NT, L::bytes, st>>>(a);
     return ivlm_launch_status();
 }
 
-static int g_attn_pp = -1;  // -1 automatic; 0 / 1 force the 4-wave / 8-wave ping-pong kernel (benchmark hook)
-void attn_set_pingpong(int mode) { g_attn_pp = mode; }
+constexpr int route_key(bool c, int rel, bool pp, bool s, bool f, int qlv) { return c | rel << 1 | pp << 4 | s << 5 | f << 6 | qlv << 7; }
 
-// SPLIT kernels (dynamic LDS: K and V tiles as hi + lo planes, double-buffered, + the rel_h block of REL 2)
-template <int DQK, int DV, bool CAUSAL, int REL>
-int launch_split_k(const AttnArgs& a, hipStream_t st) {
-    constexpr int KS = DQK / 32, DT = DV / 16;
-    constexpr size_t lds = (size_t)(2 * 2 * KS * (kKV * 32 + 32) + 2 * 2 * DT * (kKV * 16 + 16)) * 2 +
-                           (REL == 2 ? (size_t)kQPerBlock * kKV * 4 : (REL == 4 ? (size_t)8 * 16 * 65 * 4 : 0));
-    auto kfn = attn_kernel<DQK, DV, CAUSAL, REL, false, true>;
-    static ivlm_dev_mask_t attr_set{0};  // per instantiation
-    if (ivlm_dev_pending(attr_set)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        ivlm_dev_done(attr_set);
-    }
-    dim3 grid((a.Sq + kQPerBlock - 1) / kQPerBlock, a.H, a.B);
-    kfn<<<grid, 512, lds, st>>>(a);
-    return ivlm_launch_status();
-}
-
-// the shapes of the path only (keeps the build small): CLIP (64, plain), SAM ViT (80, rel-pos), LLaMA prefill (128, causal)
+// The instantiations that exist, per head dim: a route outside this list is a compile-time absence and an error at run time.
 template <int DQK, int DV>
-int launch_split(const AttnArgs& a, hipStream_t st) {
-    const bool rel = a.rel_h != nullptr;
-    if constexpr (DV == 128) {
-        if (a.causal && !rel) return launch_split_k<DQK, DV, true, 0>(a, st);
-    } else if constexpr (DV == 64) {
-        if (!a.causal && !rel) return launch_split_k<DQK, DV, false, 0>(a, st);
-    } else if constexpr (DV == 80) {
-        if (!a.causal && rel && a.prescale_q) {
-            if (!a.rel_w) return launch_split_k<DQK, DV, false, 4>(a, st);  // rel-pos terms from the table, in the kernel
-            if (a.rel_kw == kKV && a.Sk == a.rel_kh * a.rel_kw) return launch_split_k<DQK, DV, false, 2>(a, st);
-            if (a.rel_kh + a.rel_kw <= 32) return launch_split_k<DQK, DV, false, 1>(a, st);
-            return launch_split_k<DQK, DV, false, 3>(a, st);
-        }
+static int launch_flash_d(const Route& r, const AttnArgs& a, hipStream_t st) {
+    constexpr bool ANY = DV > 0, SAM = DV == 80;
+#define ATTN_CASE(BUILT, CAUSAL, REL, PP, SPLIT, F16, QLV)                                               \
+    case route_key(CAUSAL, REL, PP, SPLIT, F16, QLV):                                                    \
+        if constexpr (BUILT) return launch_flash<DQK, DV, CAUSAL, REL, PP, SPLIT, F16, QLV>(a, st); else break;
+    switch (route_key(r.causal, r.rel, r.pp, r.split, r.f16, r.qlv)) {
+        //        head dims  CAUSAL REL PP SPLIT F16 QLV
+        ATTN_CASE(ANY,       false, 0, false, false, false, 0)
+        ATTN_CASE(ANY,       true,  0, false, false, false, 0)
+        ATTN_CASE(ANY,       false, 0, true,  false, false, 0)
+        ATTN_CASE(ANY,       true,  0, true,  false, false, 0)
+        ATTN_CASE(ANY,       false, 0, false, false, true,  0)
+        ATTN_CASE(ANY,       true,  0, false, false, true,  0)
+        ATTN_CASE(DV == 64,  false, 0, false, true,  false, 0)
+        ATTN_CASE(DV == 128, true,  0, false, true,  false, 0)
+        ATTN_CASE(SAM,       false, 1, false, false, false, 0)
+        ATTN_CASE(SAM,       false, 2, false, false, false, 0)
+        ATTN_CASE(SAM,       false, 3, false, false, false, 0)
+        ATTN_CASE(SAM,       false, 4, false, false, false, 0)
+        ATTN_CASE(SAM,       false, 5, false, false, false, 0)
+        ATTN_CASE(SAM,       false, 1, true,  false, false, 0)
+        ATTN_CASE(SAM,       false, 2, true,  false, false, 0)
+        ATTN_CASE(SAM,       false, 1, false, true,  false, 0)
+        ATTN_CASE(SAM,       false, 2, false, true,  false, 0)
+        ATTN_CASE(SAM,       false, 3, false, true,  false, 0)
+        ATTN_CASE(SAM,       false, 4, false, true,  false, 0)
+        ATTN_CASE(SAM,       false, 1, false, false, true,  0)
+        ATTN_CASE(SAM,       false, 2, false, false, true,  0)
+        ATTN_CASE(SAM,       false, 3, false, false, true,  0)
+        ATTN_CASE(SAM,       false, 4, false, false, true,  0)
+        ATTN_CASE(SAM,       false, 5, false, false, true,  0)
+        ATTN_CASE(SAM,       false, 5, false, false, true,  1)
+        ATTN_CASE(SAM,       false, 2, false, false, true,  2)
     }
+#undef ATTN_CASE
     return IVLM_ERR_UNSUPPORTED;
 }
 
-// fp16 operands (a.f16): the shapes of the path, like the split kernels
-template <int DQK, int DV>
-int launch_f16(const AttnArgs& a, hipStream_t st) {
-    const bool rel = a.rel_h != nullptr;
-    dim3 grid((a.Sq + kQPerBlock - 1) / kQPerBlock, a.H, a.B);
-    if constexpr (DV == 80) {  // SAM's 64 x 64 grid in table mode (REL 5): the terms computed in the kernel, q_lo (level 1) in them
-        if (!a.causal && rel && a.prescale_q && !a.rel_w && a.rel_kh == kKV && a.rel_kw == kKV && a.Sq == kKV * kKV && a.Sk == a.Sq) {
-            if (a.q_lo && a.q_lo_level >= 2) return IVLM_ERR_UNSUPPORTED;
-            const dim3 g1((a.Sq / kQPerBlock) * a.H * a.B);  // (REL 5: 1-D, XCD-aware block map in the kernel)
-            if (a.q_lo) attn_kernel<DQK, DV, false, 5, false, false, true, 1><<<g1, 256, 0, st>>>(a);
-            else attn_kernel<DQK, DV, false, 5, false, false, true, 0><<<g1, 256, 0, st>>>(a);
-            return ivlm_launch_status();
-        }
+static int attn_launch(const Route& r, const AttnArgs& a, hipStream_t st) {
+    if (r.window) {
+        if (r.split) return launch_win<true, false, 0>(a, st);
+        if (!r.f16) return launch_win<false, false, 0>(a, st);
+        if (r.qlv == 0) return launch_win<false, true, 0>(a, st);
+        return r.qlv == 1 ? launch_win<false, true, 1>(a, st) : launch_win<false, true, 2>(a, st);
     }
-    if (a.q_lo && a.q_lo_level < 2 && a.rel_w) {
-        // level 1 with the terms as arrays: the lo half of q is already in them (ivlm_relpos_* on hi + lo) - the plain fp16 kernel
-    } else if (a.q_lo) {  // level 2 (QLO): SAM's global grid with the rel-pos terms as arrays (windows take the whole-window kernel)
-        if constexpr (DV == 80) {
-            if (!a.causal && rel && a.prescale_q && a.rel_w && a.rel_kw == kKV && a.Sk == a.rel_kh * a.rel_kw) {
-                attn_kernel<DQK, DV, false, 2, false, false, true, 2><<<grid, 256, 0, st>>>(a);
-                return ivlm_launch_status();
-            }
-        }
-        return IVLM_ERR_UNSUPPORTED;
+    switch (a.D) {
+        case 16: return launch_flash_d<32, 16>(r, a, st);
+        case 32: return launch_flash_d<32, 32>(r, a, st);
+        case 64: return launch_flash_d<64, 64>(r, a, st);
+        case 80: return launch_flash_d<96, 80>(r, a, st);
+        case 128: return launch_flash_d<128, 128>(r, a, st);
+        default: return IVLM_ERR_UNSUPPORTED;
     }
-    if (!rel) {  // plain / causal attention at every head dim (CLIP and LLaMA towers of any configuration)
-        if (a.causal) attn_kernel<DQK, DV, true, 0, false, false, true><<<grid, 256, 0, st>>>(a);
-        else attn_kernel<DQK, DV, false, 0, false, false, true><<<grid, 256, 0, st>>>(a);
-        return ivlm_launch_status();
-    }
-    if constexpr (DV == 80) {
-        if (!a.causal && rel && a.prescale_q) {
-            if (!a.rel_w) attn_kernel<DQK, DV, false, 4, false, false, true><<<grid, 256, 0, st>>>(a);
-            else if (a.rel_kw == kKV && a.Sk == a.rel_kh * a.rel_kw) attn_kernel<DQK, DV, false, 2, false, false, true><<<grid, 256, 0, st>>>(a);
-            else if (a.rel_kh + a.rel_kw <= 32) attn_kernel<DQK, DV, false, 1, false, false, true><<<grid, 256, 0, st>>>(a);
-            else attn_kernel<DQK, DV, false, 3, false, false, true><<<grid, 256, 0, st>>>(a);
-            return ivlm_launch_status();
-        }
-    }
-    return IVLM_ERR_UNSUPPORTED;
-}
-
-template <int DQK, int DV, bool PP>
-int launch_dp(const AttnArgs& a, hipStream_t st) {
-    constexpr int NT = PP ? 512 : 256, QB = PP ? 2 * kQPerBlock : kQPerBlock;
-    dim3 grid((a.Sq + QB - 1) / QB, a.H, a.B);
-    const bool rel = a.rel_h != nullptr;
-    if (a.causal) {
-        if (rel) return IVLM_ERR_UNSUPPORTED;
-        attn_kernel<DQK, DV, true, 0, PP><<<grid, NT, 0, st>>>(a);
-    } else if (rel) {
-        if (DV != 80) return IVLM_ERR_UNSUPPORTED;  // only SAM's ViT uses rel-pos; keeps the build small
-        if (!a.prescale_q) return IVLM_ERR_UNSUPPORTED;
-        if (!a.rel_w && a.rel_kh == kKV && a.rel_kw == kKV && a.Sq == kKV * kKV && a.Sk == a.Sq) {  // the 64 x 64 grid in table mode
-            if constexpr (DV == 80 && !PP) attn_kernel<DQK, DV, false, 5, false><<<dim3((a.Sq / kQPerBlock) * a.H * a.B), 256, 0, st>>>(a);
-            else return IVLM_ERR_UNSUPPORTED;
-        } else if (!a.rel_w)  // rel_h is the bf16 table [64, D]: the rel-pos terms are computed in the kernel (windows: 2 * side <= 32)
-            attn_kernel<DQK, DV, false, DV == 80 ? 4 : 0, false><<<dim3((a.Sq + kQPerBlock - 1) / kQPerBlock, a.H, a.B), 256, 0, st>>>(a);
-        else if (a.rel_kw == kKV && a.Sk == a.rel_kh * a.rel_kw)
-            attn_kernel<DQK, DV, false, DV == 80 ? 2 : 0, PP><<<grid, NT, 0, st>>>(a);
-        else if (a.rel_kh + a.rel_kw <= 32)
-            attn_kernel<DQK, DV, false, DV == 80 ? 1 : 0, PP><<<grid, NT, 0, st>>>(a);
-        else
-            attn_kernel<DQK, DV, false, DV == 80 ? 3 : 0, false><<<dim3((a.Sq + kQPerBlock - 1) / kQPerBlock, a.H, a.B), 256, 0, st>>>(a);
-    } else {
-        attn_kernel<DQK, DV, false, 0, PP><<<grid, NT, 0, st>>>(a);
-    }
-    return ivlm_launch_status();
-}
-
-template <int DQK, int DV>
-int launch_d(const AttnArgs& a, hipStream_t st) {
-    // the 8-wave ping-pong block (256 queries) is opt-in: measured 5-15 % SLOWER than two independent 4-wave blocks per CU on
-    // every shape of the path (SAM global 634 vs 604 us, windows 151 vs 132 us) - the loop is bound by the issue latency of
-    // the dependent softmax chain, not by the two waves of a SIMD contending for the same unit
-    if constexpr (DV == 80) {  // SAM's windows: the whole-window kernel (default precision: table mode; SPLIT: array mode)
-        // (192 < Sq: the whole-window kernel masks padded keys in its LAST 16-key tile only - in a smaller window the zero K rows of
-        //  the tiles before it would score 0 + a stray rel-pos term and count in the softmax; those windows take the generic kernel)
-        const bool win = g_win_v2 && a.rel_h && a.Sq > 192 && a.Sq <= 208 && a.Sq == a.Sk && !a.causal && a.prescale_q && a.H <= 65535 &&
-                         a.B <= 65535 && a.rel_kh == a.rel_kw && 2 * a.rel_kh <= 32 && a.Sq == a.rel_kh * a.rel_kw;
-        if (win && !a.q_lo && !a.rel_w) return a.f16 ? launch_win<false, true>(a, st) : launch_win<false>(a, st);
-        if (win && a.q_lo && !a.rel_w && a.f16) return a.q_lo_level >= 2 ? launch_win<false, true, 2>(a, st) : launch_win<false, true, 1>(a, st);
-        if (win && a.q_lo && a.rel_w && !a.f16) return launch_win<true>(a, st);
-    }
-    if (a.f16) return launch_f16<DQK, DV>(a, st);
-    if (a.q_lo) return launch_split<DQK, DV>(a, st);
-    const bool pp = g_attn_pp > 0;
-    return pp ? launch_dp<DQK, DV, true>(a, st) : launch_dp<DQK, DV, false>(a, st);
 }
 
 // rel_h[bh,q,kh] = q_vec . rel_pos_h[qh - kh + KH - 1],  rel_w[bh,q,kw] = q_vec . rel_pos_w[qw - kw + KW - 1]
@@ -1636,64 +1688,32 @@ int relpos_gather(const bf16_t* G, int64_t g_hs, int npad, int B, int H, int SH,
 }
 
 int attention_bf16(const AttnArgs& a_in, hipStream_t st) {
+    Route r;
+    if (const int rc = attn_route(a_in, g_attn_pp > 0, g_win_v2, &r)) return rc;
     AttnArgs a = a_in;
     a.xcd_map = g_xcd_map;
-    if (!a.q || !a.k || !a.v || !a.o || a.B <= 0 || a.H <= 0 || a.Sq <= 0 || a.Sk <= 0) return IVLM_ERR_INVALID_ARG;
-    if (a.H > 65535 || a.B > 65535 || a.kv_batch_div <= 0) return IVLM_ERR_INVALID_ARG;
-    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.q_hs | a.k_hs | a.v_hs | a.q_bs | a.k_bs | a.v_bs) & 7)
-        return IVLM_ERR_UNSUPPORTED;  // 16-byte row chunks
-    if ((a.o_rs | a.o_hs | a.o_bs) & 3) return IVLM_ERR_UNSUPPORTED;
-    if (a.rel_h && (a.rel_kh <= 0 || a.rel_kw <= 0)) return IVLM_ERR_INVALID_ARG;
-    if (a.rel_h && !a.rel_w) {  // table mode: square windows whose 2 * side terms fit one MFMA k-step, or the 64 x 64 grid (REL 5)
-        if (a.rel_kh != a.rel_kw || (2 * a.rel_kh > 32 && a.rel_kh != kKV) || a.Sq != a.rel_kh * a.rel_kw || a.Sk != a.Sq || a.D != 80 ||
-            (reinterpret_cast<uintptr_t>(a.rel_h) & 15))
-            return IVLM_ERR_UNSUPPORTED;
-        if (a.rel_kh == kKV && a.q_lo && !a.f16) return IVLM_ERR_UNSUPPORTED;  // (the split kernels take the terms as arrays)
-    }
-    if (a.f16) {  // fp16 operands: at most a lo plane of q ("exact q")
-        if (a.k_lo || a.v_lo || a.o_lo) return IVLM_ERR_INVALID_ARG;
-    } else if ((a.q_lo || a.k_lo || a.v_lo || a.o_lo) && !(a.q_lo && a.k_lo && a.v_lo && a.o_lo)) {
-        return IVLM_ERR_INVALID_ARG;
-    }
-    switch (a.D) {
-        case 16: return launch_d<32, 16>(a, st);
-        case 32: return launch_d<32, 32>(a, st);
-        case 64: return launch_d<64, 64>(a, st);
-        case 80: return launch_d<96, 80>(a, st);
-        case 128: return launch_d<128, 128>(a, st);
-        default: return IVLM_ERR_UNSUPPORTED;
-    }
+    return attn_launch(r, a, st);
 }
 
 int relpos_bias(const bf16_t* q, int64_t q_bs, int64_t q_hs, int64_t q_rs, const bf16_t* tab_h, const bf16_t* tab_w,
                 int B, int H, int SH, int SW, int D, float* rel_h, float* rel_w, hipStream_t st, const bf16_t* q_lo) {
     if (!q || !tab_h || !tab_w || !rel_h || !rel_w || (D & 7)) return IVLM_ERR_INVALID_ARG;
-    if (q_lo == q) {  // (q_lo == q: no lo plane - the bf16 q of the default path, but results kept in fp32, not rounded to bf16)
-        if (D != 80 || SH > 128 || SW > 128 || H > 65535 || B > 65535 || ((q_bs | q_hs | q_rs) & 7) ||
-            (reinterpret_cast<uintptr_t>(q) & 15))
-            return IVLM_ERR_UNSUPPORTED;
+    // q_lo == q: no lo plane - the bf16 q of the default path, but results kept in fp32, not rounded to bf16;
+    // any other q_lo: "parity" precision, q as hi + lo planes, unrounded fp32 results.  Both: SAM head dim only, no fallback.
+    const bool keep = q_lo == q, split = q_lo && !keep;
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(q) | (split ? reinterpret_cast<uintptr_t>(q_lo) : 0);
+    if ((D == 80 || (D == 64 && !q_lo)) && SH <= 128 && SW <= 128 && H <= 65535 && B <= 65535 && ((q_bs | q_hs | q_rs) & 7) == 0 &&
+        (ptrs & 15) == 0) {
         const size_t lds = (size_t)(2 * SH - 1 + 2 * SW - 1) * (D + 8) * 2;
-        relpos_rows_kernel<10, false, false><<<dim3((SH * SW + 255) / 256, H, B), 256, lds, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w,
-                                                                                                H, SH, SW, rel_h, rel_w, nullptr);
-        return ivlm_launch_status();
+        const auto rows = [&](auto kfn, const bf16_t* lo) {
+            kfn<<<dim3((SH * SW + 255) / 256, H, B), 256, lds, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w, H, SH, SW, rel_h, rel_w, lo);
+            return ivlm_launch_status();
+        };
+        if (keep) return rows(relpos_rows_kernel<10, false, false>, nullptr);
+        if (split) return rows(relpos_rows_kernel<10, true>, q_lo);
+        return D == 80 ? rows(relpos_rows_kernel<10>, nullptr) : rows(relpos_rows_kernel<8>, nullptr);
     }
-    if (q_lo) {  // "parity" precision: q as hi + lo planes, unrounded fp32 results (SAM head dim only)
-        if (D != 80 || SH > 128 || SW > 128 || H > 65535 || B > 65535 || ((q_bs | q_hs | q_rs) & 7) ||
-            ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(q_lo)) & 15))
-            return IVLM_ERR_UNSUPPORTED;
-        const size_t lds = (size_t)(2 * SH - 1 + 2 * SW - 1) * (D + 8) * 2;
-        relpos_rows_kernel<10, true><<<dim3((SH * SW + 255) / 256, H, B), 256, lds, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w, H, SH,
-                                                                                         SW, rel_h, rel_w, q_lo);
-        return ivlm_launch_status();
-    }
-    if ((D == 80 || D == 64) && SH <= 128 && SW <= 128 && H <= 65535 && B <= 65535 &&
-        ((q_bs | q_hs | q_rs) & 7) == 0 && (reinterpret_cast<uintptr_t>(q) & 15) == 0) {
-        const size_t lds = (size_t)(2 * SH - 1 + 2 * SW - 1) * (D + 8) * 2;
-        dim3 grid((SH * SW + 255) / 256, H, B);
-        if (D == 80) relpos_rows_kernel<10><<<grid, 256, lds, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w, H, SH, SW, rel_h, rel_w);
-        else relpos_rows_kernel<8><<<grid, 256, lds, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w, H, SH, SW, rel_h, rel_w);
-        return ivlm_launch_status();
-    }
+    if (q_lo) return IVLM_ERR_UNSUPPORTED;
     const int64_t total = (int64_t)B * H * SH * SW * (SH + SW);
     const int grid = (int)((total + 255) / 256 < 65535 * 4 ? (total + 255) / 256 : 65535 * 4);
     relpos_kernel<<<grid, 256, 0, st>>>(q, q_bs, q_hs, q_rs, tab_h, tab_w, B, H, SH, SW, D, rel_h, rel_w);
@@ -1760,55 +1780,51 @@ int ivlm_attention_window_kernel(int v2) {  // benchmark/test hook: 1 (default) 
 }
 
 int ivlm_attention_pingpong(int mode) {  // benchmark/test hook: -1 automatic, 0 four-wave kernel, 1 eight-wave ping-pong
-    ivlm::attn_set_pingpong(mode);
+    ivlm::g_attn_pp = mode;
     return 0;
 }
 
-static int attention_16(const void* q, const void* k, const void* v, void* o, const int64_t* strides /*[12]*/, int B,
-                        int H, int Sq, int Sk, int D, float scale, int causal, int q_pos0, const float* rel_h,
-                        const float* rel_w, int rel_kh, int rel_kw, int kv_batch_div, int prescale_q, int f16, ivlm_stream_t stream,
-                        const void* q_lo = nullptr, int q_lo_level = 0) {
+// The C arguments as AttnArgs (lo planes: null, or 16-byte aligned like the hi ones), then the route and the launch.
+static int attention_c(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* v, const void* v_lo, void* o,
+                       void* o_lo, const int64_t* strides /*[12]*/, int B, int H, int Sq, int Sk, int D, float scale, int causal,
+                       int q_pos0, const float* rel_h, const float* rel_w, int rel_kh, int rel_kw, int kv_batch_div, int prescale_q,
+                       int f16, int q_lo_level, ivlm_stream_t stream) {
     ivlm_enter();
     if (!strides) return IVLM_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(q_lo) | reinterpret_cast<uintptr_t>(k_lo) | reinterpret_cast<uintptr_t>(v_lo)) & 15)
+        return IVLM_ERR_INVALID_ARG;
     ivlm::AttnArgs a;
-    a.f16 = f16;
-    a.q_lo = static_cast<const bf16_t*>(q_lo);
-    a.q_lo_level = q_lo_level;
-    if (reinterpret_cast<uintptr_t>(q_lo) & 15) return IVLM_ERR_INVALID_ARG;
-    a.q = static_cast<const bf16_t*>(q);
-    a.k = static_cast<const bf16_t*>(k);
-    a.v = static_cast<const bf16_t*>(v);
-    a.o = static_cast<bf16_t*>(o);
+    a.q = static_cast<const bf16_t*>(q); a.q_lo = static_cast<const bf16_t*>(q_lo);
+    a.k = static_cast<const bf16_t*>(k); a.k_lo = static_cast<const bf16_t*>(k_lo);
+    a.v = static_cast<const bf16_t*>(v); a.v_lo = static_cast<const bf16_t*>(v_lo);
+    a.o = static_cast<bf16_t*>(o); a.o_lo = static_cast<bf16_t*>(o_lo);
     a.q_bs = strides[0]; a.q_hs = strides[1]; a.q_rs = strides[2];
     a.k_bs = strides[3]; a.k_hs = strides[4]; a.k_rs = strides[5];
     a.v_bs = strides[6]; a.v_hs = strides[7]; a.v_rs = strides[8];
     a.o_bs = strides[9]; a.o_hs = strides[10]; a.o_rs = strides[11];
     a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D;
-    a.scale = scale;
-    a.causal = causal;
-    a.q_pos0 = q_pos0;
-    a.rel_h = rel_h;
-    a.rel_w = rel_w;
-    a.rel_kh = rel_kh;
-    a.rel_kw = rel_kw;
+    a.scale = scale; a.causal = causal; a.q_pos0 = q_pos0;
+    a.rel_h = rel_h; a.rel_w = rel_w; a.rel_kh = rel_kh; a.rel_kw = rel_kw;
     a.kv_batch_div = kv_batch_div < 1 ? 1 : kv_batch_div;
     a.prescale_q = prescale_q;
+    a.f16 = f16;
+    a.q_lo_level = q_lo_level;
     return ivlm::attention_bf16(a, ivlm_stream(stream));
 }
 
 int ivlm_attention_bf16(const void* q, const void* k, const void* v, void* o, const int64_t* strides /*[12]*/, int B,
                         int H, int Sq, int Sk, int D, float scale, int causal, int q_pos0, const float* rel_h,
                         const float* rel_w, int rel_kh, int rel_kw, int kv_batch_div, int prescale_q, ivlm_stream_t stream) {
-    return attention_16(q, k, v, o, strides, B, H, Sq, Sk, D, scale, causal, q_pos0, rel_h, rel_w, rel_kh, rel_kw, kv_batch_div,
-                        prescale_q, 0, stream);
+    return attention_c(q, nullptr, k, nullptr, v, nullptr, o, nullptr, strides, B, H, Sq, Sk, D, scale, causal, q_pos0, rel_h, rel_w,
+                       rel_kh, rel_kw, kv_batch_div, prescale_q, 0, 0, stream);
 }
 
 // the same operator on IEEE fp16 q / k / v / o (and, in table mode, an fp16 rel-pos table): see ivlm_hip.h
 int ivlm_attention_f16(const void* q, const void* k, const void* v, void* o, const int64_t* strides /*[12]*/, int B,
                        int H, int Sq, int Sk, int D, float scale, int causal, int q_pos0, const float* rel_h,
                        const float* rel_w, int rel_kh, int rel_kw, int kv_batch_div, int prescale_q, ivlm_stream_t stream) {
-    return attention_16(q, k, v, o, strides, B, H, Sq, Sk, D, scale, causal, q_pos0, rel_h, rel_w, rel_kh, rel_kw, kv_batch_div,
-                        prescale_q, 1, stream);
+    return attention_c(q, nullptr, k, nullptr, v, nullptr, o, nullptr, strides, B, H, Sq, Sk, D, scale, causal, q_pos0, rel_h, rel_w,
+                       rel_kh, rel_kw, kv_batch_div, prescale_q, 1, 0, stream);
 }
 
 // ... with q as hi + lo IEEE halves (q_lo: the strides of q): the "exact q" attention of the fp16 mode (SAM shapes), see ivlm_hip.h
@@ -1816,7 +1832,8 @@ int ivlm_attention_f16_qsplit(const void* q, const void* q_lo, const void* k, co
                               int B, int H, int Sq, int Sk, int D, float scale, const float* rel_h, const float* rel_w, int rel_kh,
                               int rel_kw, int level, ivlm_stream_t stream) {
     if (!q_lo || (level != 1 && level != 2)) return IVLM_ERR_INVALID_ARG;
-    return attention_16(q, k, v, o, strides, B, H, Sq, Sk, D, scale, 0, 0, rel_h, rel_w, rel_kh, rel_kw, 1, 1, 1, stream, q_lo, level);
+    return attention_c(q, q_lo, k, nullptr, v, nullptr, o, nullptr, strides, B, H, Sq, Sk, D, scale, 0, 0, rel_h, rel_w, rel_kh, rel_kw,
+                       1, 1, 1, level, stream);
 }
 
 int ivlm_attention_bf16_split(const void* q, const void* q_lo, const void* k, const void* k_lo, const void* v, const void* v_lo,
@@ -1824,33 +1841,9 @@ int ivlm_attention_bf16_split(const void* q, const void* q_lo, const void* k, co
                               int causal, int q_pos0, const float* rel_h, const float* rel_w, int rel_kh, int rel_kw,
                               int kv_batch_div, int prescale_q, ivlm_stream_t stream) {
     ivlm_enter();
-    if (!strides || !q_lo || !k_lo || !v_lo || !o_lo) return IVLM_ERR_INVALID_ARG;
-    ivlm::AttnArgs a;
-    a.q = static_cast<const bf16_t*>(q);
-    a.k = static_cast<const bf16_t*>(k);
-    a.v = static_cast<const bf16_t*>(v);
-    a.o = static_cast<bf16_t*>(o);
-    a.q_lo = static_cast<const bf16_t*>(q_lo);
-    a.k_lo = static_cast<const bf16_t*>(k_lo);
-    a.v_lo = static_cast<const bf16_t*>(v_lo);
-    a.o_lo = static_cast<bf16_t*>(o_lo);
-    a.q_bs = strides[0]; a.q_hs = strides[1]; a.q_rs = strides[2];
-    a.k_bs = strides[3]; a.k_hs = strides[4]; a.k_rs = strides[5];
-    a.v_bs = strides[6]; a.v_hs = strides[7]; a.v_rs = strides[8];
-    a.o_bs = strides[9]; a.o_hs = strides[10]; a.o_rs = strides[11];
-    a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.D = D;
-    a.scale = scale;
-    a.causal = causal;
-    a.q_pos0 = q_pos0;
-    a.rel_h = rel_h;
-    a.rel_w = rel_w;
-    a.rel_kh = rel_kh;
-    a.rel_kw = rel_kw;
-    a.kv_batch_div = kv_batch_div < 1 ? 1 : kv_batch_div;
-    a.prescale_q = prescale_q;
-    if ((reinterpret_cast<uintptr_t>(q_lo) | reinterpret_cast<uintptr_t>(k_lo) | reinterpret_cast<uintptr_t>(v_lo)) & 15)
-        return IVLM_ERR_INVALID_ARG;
-    return ivlm::attention_bf16(a, ivlm_stream(stream));
+    if (!q_lo || !k_lo || !v_lo || !o_lo) return IVLM_ERR_INVALID_ARG;
+    return attention_c(q, q_lo, k, k_lo, v, v_lo, o, o_lo, strides, B, H, Sq, Sk, D, scale, causal, q_pos0, rel_h, rel_w, rel_kh, rel_kw,
+                       kv_batch_div, prescale_q, 0, 0, stream);
 }
 
 int ivlm_relpos_bias(const void* q, int64_t q_bs, int64_t q_hs, int64_t q_rs, const void* tab_h, const void* tab_w,

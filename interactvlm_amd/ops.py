@@ -770,6 +770,30 @@ def relpos_table64(tab_h, tab_w):
     return t
 
 
+def _attn_operands(q, k, v, o, rel, rel_tab, prescale_q, grid_table):
+    """What ``attention`` and ``attention_split`` pass alike: the stride array, the rel_h / rel_w pointers, kh, kw, the prescale flag."""
+    import ctypes
+
+    st = (ctypes.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, o) for i in range(3)))
+    rel_h = rel_w = None
+    kh = kw = 0
+    if rel is not None:
+        rel_h, rel_w = rel
+        assert rel_h.dtype == torch.float32 and rel_h.is_contiguous() and rel_w.is_contiguous()
+        kh, kw = rel_h.shape[-1], rel_w.shape[-1]
+    if rel_tab is not None:  # table mode: rel_h = the 16-bit table, rel_w = NULL
+        rel_h, kh = rel_tab
+        kw = kh
+        assert rel is None and rel_h.dtype == q.dtype and rel_h.is_contiguous()
+        if grid_table:
+            assert rel_h.shape[1] == q.shape[3]
+            assert rel_h.shape[0] == 64 if 2 * kh <= 32 else (kh == 64 and rel_h.shape[0] >= 254)  # windows | the 64 x 64 grid
+        else:  # (the split kernels: windows only)
+            assert rel_h.shape == (64, q.shape[3])
+    pre = 1 if (prescale_q or rel is not None or rel_tab is not None) else 0
+    return st, _p(rel_h), _p(rel_w), kh, kw, pre
+
+
 def attention(q, k, v, scale, causal=False, q_pos0=0, rel=None, out=None, prescale_q=False, rel_tab=None, q_lo=None, q_lo_level=1):
     """q [B,H,Sq,D], k/v [Bk,H,Sk,D] (arbitrary strides, last dim contiguous; B % Bk == 0: K/V of batch
     b // (B//Bk)) -> o [B,H,Sq,D] as a view of a [B,Sq,H,D] buffer (so o.transpose(1,2) is contiguous).
@@ -786,30 +810,17 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, rel=None, out=None, presca
     if out is None:
         out = torch.empty(B, Sq, H, D, dtype=dt, device=q.device).permute(0, 2, 1, 3)
     assert out.stride(3) == 1 and out.dtype == dt
-    st = (ctypes.c_int64 * 12)(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-                               v.stride(0), v.stride(1), v.stride(2), out.stride(0), out.stride(1), out.stride(2))
-    rel_h = rel_w = None
-    kh = kw = 0
-    if rel is not None:
-        rel_h, rel_w = rel
-        assert rel_h.dtype == torch.float32 and rel_h.is_contiguous() and rel_w.is_contiguous()
-        kh, kw = rel_h.shape[-1], rel_w.shape[-1]
-    if rel_tab is not None:  # table mode: rel_h = the bf16 table, rel_w = NULL
-        rel_h, kh = rel_tab
-        kw = kh
-        assert rel is None and rel_h.dtype == dt and rel_h.is_contiguous() and rel_h.shape[1] == D
-        assert rel_h.shape[0] == 64 if 2 * kh <= 32 else (kh == 64 and rel_h.shape[0] >= 254)  # windows | the 64 x 64 grid
+    st, rel_h, rel_w, kh, kw, pre = _attn_operands(q, k, v, out, rel, rel_tab, prescale_q, grid_table=True)
     if q_lo is not None:  # fp16 "exact q": q = q + q_lo as IEEE halves (SAM shapes; the strides of q)
         assert dt == F16 and q_lo.dtype == F16 and q_lo.stride() == q.stride() and q_lo.shape == q.shape and not causal and B == Bk
         check(lib.ivlm_attention_f16_qsplit(q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                            ctypes.cast(st, ctypes.c_void_p), B, H, Sq, Sk, D, float(scale), _p(rel_h), _p(rel_w),
+                                            ctypes.cast(st, ctypes.c_void_p), B, H, Sq, Sk, D, float(scale), rel_h, rel_w,
                                             kh, kw, int(q_lo_level), _stream()), "attention_f16_qsplit")
         return out
     fn = lib.ivlm_attention_f16 if dt == F16 else lib.ivlm_attention_bf16
     check(fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
              ctypes.cast(st, ctypes.c_void_p), B, H, Sq, Sk, D, float(scale), 1 if causal else 0,
-             int(q_pos0), _p(rel_h), _p(rel_w), kh, kw, B // Bk,
-             1 if (prescale_q or rel is not None or rel_tab is not None) else 0, _stream()), "attention")
+             int(q_pos0), rel_h, rel_w, kh, kw, B // Bk, pre, _stream()), "attention")
     return out
 
 
@@ -829,23 +840,11 @@ def attention_split(q, q_lo, k, k_lo, v, v_lo, scale, causal=False, q_pos0=0, re
         out = torch.empty(B, Sq, 2, H, D, dtype=BF16, device=q.device)
     assert out.shape == (B, Sq, 2, H, D) and out.stride(4) == 1
     oh, ol = out[:, :, 0].permute(0, 2, 1, 3), out[:, :, 1].permute(0, 2, 1, 3)  # [B,H,Sq,D] views
-    st = (ctypes.c_int64 * 12)(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-                               v.stride(0), v.stride(1), v.stride(2), oh.stride(0), oh.stride(1), oh.stride(2))
-    rel_h = rel_w = None
-    kh = kw = 0
-    if rel is not None:
-        rel_h, rel_w = rel
-        assert rel_h.dtype == torch.float32 and rel_h.is_contiguous() and rel_w.is_contiguous()
-        kh, kw = rel_h.shape[-1], rel_w.shape[-1]
-    if rel_tab is not None:  # table mode (see ``attention``)
-        rel_h, kh = rel_tab
-        kw = kh
-        assert rel is None and rel_h.dtype == BF16 and rel_h.shape == (64, D) and rel_h.is_contiguous()
+    st, rel_h, rel_w, kh, kw, pre = _attn_operands(q, k, v, oh, rel, rel_tab, prescale_q, grid_table=False)
     check(lib.ivlm_attention_bf16_split(q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), k_lo.data_ptr(), v.data_ptr(),
                                         v_lo.data_ptr(), oh.data_ptr(), ol.data_ptr(), ctypes.cast(st, ctypes.c_void_p), B, H,
-                                        Sq, Sk, D, float(scale), 1 if causal else 0, int(q_pos0), _p(rel_h), _p(rel_w), kh, kw,
-                                        B // Bk, 1 if (prescale_q or rel is not None or rel_tab is not None) else 0, _stream()),
-          "attention_split")
+                                        Sq, Sk, D, float(scale), 1 if causal else 0, int(q_pos0), rel_h, rel_w, kh, kw,
+                                        B // Bk, pre, _stream()), "attention_split")
     return out.view(B * Sq, 2 * H * D)
 
 
