@@ -822,6 +822,23 @@ int ivlm_seg_iou_counts(const float *pred, const void *gt, int gt_dtype, int V, 
 int ivlm_afford_metrics(const float *gt, const float *pred, int B, int n, const float *thresholds, int T, float mae_div,
                         float *out, int32_t *valid, ivlm_stream_t stream);
 
+/* Contact-weighted human-object distance (contact_pair.hip; the contact term of the reference's joint fitting stage,
+ * optim/optimizer.py `contact_loss`) with both gradients, without the [N_o,N_h] distance matrix:
+ *   L = sum_ij p_i q_j |o_i - h_j| / S,  S = (sum p)(sum q)
+ * o f32 [B or 1, N_o, 3], h f32 [B or 1, N_h, 3] (rows contiguous; o_batch_stride / h_batch_stride = elements between poses, 0 =
+ * one pose shared by the batch), p [N_o] / q [N_h] contact probabilities >= 0 of p_dtype (IVLM_F32 or IVLM_BF16), shared by the
+ * batch -> value_out f32 [B] = L; grad_o f32 [B,N_o,3] = dL/do and grad_h f32 [B,N_h,3] = dL/dh per pose (either may be NULL: not
+ * computed).  A pair closer than 1e-19 contributes 0 to the value and to both gradients; S == 0 gives L = NaN.  Vertices of
+ * probability 0 are skipped (their gradient is 0) without changing a bit of the result.  No atomics, every sum in a fixed order:
+ * the same bits every call.  The longest serial fp32 accumulation is IVLM_CONTACT_PAIR_CHAIN terms; what follows it is summed in
+ * fp64.  N_o, N_h <= 2^20 and B <= 65535, else IVLM_ERR_UNSUPPORTED before any launch.  workspace:
+ * ivlm_contact_pair_workspace_bytes(B, N_o, N_h) bytes (0 for sizes that are not supported), 16-byte aligned. */
+#define IVLM_CONTACT_PAIR_CHAIN 512
+size_t ivlm_contact_pair_workspace_bytes(int B, int N_o, int N_h);
+int ivlm_contact_pair(const float *o, const float *h, const void *p, const void *q, int p_dtype, int B, int N_o, int N_h,
+                      int64_t o_batch_stride, int64_t h_batch_stride, float *value_out, float *grad_o, float *grad_h,
+                      void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

@@ -172,6 +172,12 @@ int seg_iou_counts(const float* pred, const void* gt, int gt_dtype, int V, int H
 int afford_metrics(const float* gt, const float* pred, int B, int n, const float* thresholds, int T, float mae_div, float* out,
                    int32_t* valid, hipStream_t st);
 
+// ---- contact-weighted human-object distance with both gradients (contact_pair.hip) ---------------------
+size_t contact_pair_workspace_bytes(int B, int n_o, int n_h);
+int contact_pair(const float* o, const float* h, const void* p, const void* q, int p_dtype, int B, int n_o, int n_h,
+                 int64_t o_bstride, int64_t h_bstride, float* value, float* grad_o, float* grad_h, void* ws, size_t ws_bytes,
+                 hipStream_t st);
+
 // ---- rasterisation (raster.hip) -------------------------------------------------------------------
 size_t raster_workspace_bytes(int n_prims_verts, int H, int W);
 int rasterize_mesh(const float* verts, int nv, const int32_t* faces, int nf, const float* cam12_host, float fov_deg,
