@@ -839,6 +839,59 @@ int ivlm_contact_pair(const float *o, const float *h, const void *p, const void 
                       int64_t o_batch_stride, int64_t h_batch_stride, float *value_out, float *grad_o, float *grad_h,
                       void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 
+/* ICP between the object's and the human's contact points (contact_icp.hip; the reference's optim/icp/icp.py `ICP`, which
+ * initialises the object pose of the joint fitting stage).  Row-vector convention: s x R + T ~ y.
+ * x f32 [B or 1, N_o, 3] object points, y f32 [B or 1, N_h, 3] human points, xn / yn their normals (both or neither; NULL: 3-D
+ * queries), w f32 [B or 1, N_o] weights >= 0 (NULL: 1), *_batch_stride = elements between poses (0 = shared by the batch),
+ * init_R f32 [B,3,3] / init_T [B,3] / init_s [B] the B starts (each may be NULL: identity).  flags: IVLM_ICP_ESTIMATE_SCALE,
+ * IVLM_ICP_ALLOW_REFLECTION, IVLM_ICP_REQUERY.
+ *   without IVLM_ICP_REQUERY: what the reference computes - ONE nearest-neighbour pass of [s x R + T, n] (normals as given, not
+ *     rotated) against [y, -m], one alignment of the original x with the neighbours and its rmse; iterations = min(2,
+ *     max_iterations) and converged = (max_iterations >= 2), because the reference never rebuilds its query and accepts any
+ *     non-increase of the rmse.  All max_iterations history rows hold that transform.
+ *   with IVLM_ICP_REQUERY: max_iterations x (nearest neighbours of [s x R + T, n R] for the current transform, alignment); a pose
+ *     ends when (prev_rmse - rmse) / prev_rmse <= relative_rmse_thr (from its second iteration on) or rmse == 0; its blocks then
+ *     exit at once and its later history rows repeat its final transform.
+ * -> R_out f32 [B,3,3], T_out [B,3], s_out [B], rmse_out [B], converged_out i32 [B], iterations_out i32 [B], nn_idx_out i32
+ * [B,N_o] (the correspondences the returned transform was aligned to), hist_R f32 [max_iterations,B,3,3], hist_T [.,B,3], hist_s
+ * [.,B].  Everything is enqueued on the stream: no host synchronisation.  The alignment is that of ivlm_points_align.  Nearest
+ * neighbours: direct fp32 sum of squared differences, lowest index on an exact tie.  No atomics, fixed summation orders, moments
+ * and solve in fp64: the same bits every call and for a pose whatever the batch around it.  N_o, N_h <= 2^20, B <= 65535, else
+ * IVLM_ERR_UNSUPPORTED.  workspace: ivlm_contact_icp_workspace_bytes(B, N_o) bytes (0 for sizes that are not supported), 16-byte
+ * aligned; O(B N_o), nothing scales with N_o N_h. */
+#define IVLM_ICP_ESTIMATE_SCALE 1
+#define IVLM_ICP_ALLOW_REFLECTION 2
+#define IVLM_ICP_REQUERY 4
+size_t ivlm_contact_icp_workspace_bytes(int B, int N_o);
+int ivlm_contact_icp(const float *x, const float *y, const float *xn, const float *yn, const float *w, const float *init_R,
+                     const float *init_T, const float *init_s, int B, int N_o, int N_h, int64_t x_batch_stride, int64_t y_batch_stride,
+                     int64_t xn_batch_stride, int64_t yn_batch_stride, int64_t w_batch_stride, int max_iterations, float relative_rmse_thr,
+                     int flags, float *R_out, float *T_out, float *s_out, float *rmse_out, int32_t *converged_out, int32_t *iterations_out,
+                     int32_t *nn_idx_out, float *hist_R, float *hist_T, float *hist_s, void *workspace, size_t workspace_bytes,
+                     ivlm_stream_t stream);
+
+/* Weighted similarity alignment of corresponding points (the reference's `corresponding_points_alignment`, Umeyama):
+ *   mu_x = sum w x / max(sum w, 1e-9), Xc = w (x - mu_x), Yc = w (y - mu_y), C = Xc^T Yc / max(sum w, 1e-9) = U S V^T,
+ *   E = diag(1, 1, det(U V^T)) unless IVLM_ICP_ALLOW_REFLECTION, R = U E V^T,
+ *   s = trace(E S) / max(sum |Xc|^2 / max(sum w, 1e-9), 1e-9) with IVLM_ICP_ESTIMATE_SCALE, else 1;  T = mu_y - s mu_x R.
+ * X, Y f32 [B or 1, N, 3], w f32 [B or 1, N] or NULL -> R_out [B,3,3], T_out [B,3], s_out [B].  Moments, the 3x3 Jacobi SVD and the
+ * solve are fp64, rounded once to fp32.  A rank-deficient C still gives an orthonormal R (of determinant +1 unless reflections are
+ * allowed).  workspace: ivlm_contact_icp_workspace_bytes(B, N). */
+int ivlm_points_align(const float *X, const float *Y, const float *w, int B, int N, int64_t x_batch_stride, int64_t y_batch_stride,
+                      int64_t w_batch_stride, int flags, float *R_out, float *T_out, float *s_out, void *workspace, size_t workspace_bytes,
+                      ivlm_stream_t stream);
+
+/* Nearest target of every query by squared L2 distance (pytorch3d knn_points with K = 1): q f32 [B or 1, N_o, D], t f32 [B or 1,
+ * N_h, D], D = 3 or 6 -> idx_out i32 [B,N_o], d2_out f32 [B,N_o] (may be NULL).  d^2 is the direct fp32 sum of squared differences
+ * (relative error <= 8 * 2^-24); the lowest index wins an exact tie. */
+int ivlm_contact_nearest(const float *q, const float *t, int D, int B, int N_o, int N_h, int64_t q_batch_stride, int64_t t_batch_stride,
+                         int32_t *idx_out, float *d2_out, ivlm_stream_t stream);
+
+/* The `filter_contacts` step of the reference's optim/fit.py without its [N_o,N_h] array: keep_out u8 [N_o] =
+ * (max_j d_ij > c_pos) or (has_neg and min_j d_ij < c_neg), d_ij = dot(o_i / |o_i|, -h_j / |h_j|) (norms clamped at 1e-12). */
+int ivlm_contact_normal_filter(const float *obj_normals, const float *human_normals, int N_o, int N_h, float c_pos, float c_neg,
+                               int has_neg, uint8_t *keep_out, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

@@ -178,6 +178,20 @@ int contact_pair(const float* o, const float* h, const void* p, const void* q, i
                  int64_t o_bstride, int64_t h_bstride, float* value, float* grad_o, float* grad_h, void* ws, size_t ws_bytes,
                  hipStream_t st);
 
+// ---- ICP between the contact point sets, point alignment, nearest neighbours, normal filter (contact_icp.hip) ----
+size_t contact_icp_workspace_bytes(int B, int n_o);
+int contact_icp(const float* x, const float* y, const float* xn, const float* yn, const float* w, const float* init_R, const float* init_T,
+                const float* init_s, int B, int n_o, int n_h, int64_t x_bs, int64_t y_bs, int64_t xn_bs, int64_t yn_bs, int64_t w_bs,
+                int max_iterations, float relative_rmse_thr, int flags, float* R, float* T, float* s, float* rmse, int32_t* converged,
+                int32_t* iterations, int32_t* nn_idx, float* hist_R, float* hist_T, float* hist_s, void* ws, size_t ws_bytes,
+                hipStream_t st);
+int points_align(const float* X, const float* Y, const float* w, int B, int n, int64_t x_bs, int64_t y_bs, int64_t w_bs, int flags,
+                 float* R, float* T, float* s, void* ws, size_t ws_bytes, hipStream_t st);
+int contact_nearest(const float* q, const float* t, int D, int B, int n_o, int n_h, int64_t q_bs, int64_t t_bs, int32_t* idx, float* d2,
+                    hipStream_t st);
+int contact_normal_filter(const float* on, const float* hn, int n_o, int n_h, float c_pos, float c_neg, int has_neg, uint8_t* keep,
+                          hipStream_t st);
+
 // ---- rasterisation (raster.hip) -------------------------------------------------------------------
 size_t raster_workspace_bytes(int n_prims_verts, int H, int W);
 int rasterize_mesh(const float* verts, int nv, const int32_t* faces, int nf, const float* cam12_host, float fov_deg,
