@@ -685,6 +685,11 @@ int ivlm_decode_parts_tuning(int ranges); /* A/B hook: 2 or 4 (default) key rang
 /* A/B hook: grids of at most this many 16-row blocks run 16 waves per block (default 256 = one block per CU), larger ones 8;
    a negative value: the same limit without the 8-deep prefetch of long rows. */
 void ivlm_gemv1_bf12m_tuning(int wide_max_blocks);
+/* A/B hook: who stages the activation row of ivlm_gemv1_bf12m / _parts in LDS.  0: the block as a whole, behind the first weight
+   loads and in front of a barrier.  1 (default): in the 16-wave forms without RMSNorm prologue (o_proj, down_proj) every wave the K
+   range its own MFMA steps read, loaded before the first weight loads, no block barrier in front of the K loop; the other forms
+   as under 0 (measured slower per wave).  The same bits out under both. */
+int ivlm_gemv1_bf12m_staging(int form);
 /* The packed matrix (row layout) back as bf16 [N, K] (the losslessness check; not on the path). */
 int ivlm_unpack_bf12(const void *P, int64_t ldp, const void *E, int64_t lde, const int32_t *ebase, const int32_t *patch_ptr,
                      const int32_t *patch_col, const void *patch_val, int N, int K, void *w_out, ivlm_stream_t stream);

@@ -233,7 +233,21 @@ __device__ __forceinline__ bf16x8m_t frag_p12m(uint32_t x0, uint32_t x1, uint32_
 // 2.44 ms per token)
 // PARTS: the activation row is not read from g.A but merged, while it is staged, from the four (o, max, sum) partials per head that
 // llama_decode_attn_parts wrote: x[h][d] = sum_s e^(m_s - M) o_s[d] / sum_s e^(m_s - M) l_s (the o_proj of the decode step).
-template <bool RMS, int kWavesM, int U, bool PARTS = false>
+// WSTG: who stages the activation planes (A/B hook: ivlm_gemv1_bf12m_staging).
+//   false  the block, chunk c of the row by thread c mod blockDim, AFTER the first weight loads are issued, and a block barrier in
+//          front of the K loop: the first use of x waits, in order, for the whole first weight batch, and the conversions, the LDS
+//          writes and the barrier run with no new weight load on its way.  With three 8-wave blocks per CU the other blocks'
+//          requests keep the HBM queue full meanwhile.
+//   true   (the 16-wave forms without RMSNorm prologue: one block per CU, nothing else covers the staging - o_proj, down_proj)
+//          every wave stages exactly the K range [64 s0, 64 s1) that its own MFMA steps read, so nothing but the wave's own (in-order)
+//          LDS queue stands between its plane writes and its fragment reads; the loads of that range (L2 hits) are issued BEFORE
+//          the first weight loads (HBM) and their first use is a counted wait that leaves the weights in flight.  The block barrier
+//          moves behind the K loop, in front of the patch tail (any column).  Same planes, same sums, the same bits out.
+//          The first kXEarly chunks per lane are held in registers across the weight issue; longer rows finish in a plain loop.
+//          (Measured slower in the 8-wave RMS form - q|k|v, gate|up: 21.6 instead of 20.6 us per launch; there the sum of squares
+//          must keep its block-strided partition, a second read of x, and every early load delays the weights behind it in the
+//          CU's L1 queue: tools/experiments/README.md.)
+template <bool RMS, int kWavesM, int U, bool PARTS = false, bool WSTG = false>
 __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12m_kernel(GemmArgs g, P12M p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // x * 2^64 as three bf16 planes [3][K]
     __shared__ float s_red[kWavesM];
@@ -246,6 +260,56 @@ __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12
     const int64_t base = (int64_t)blockIdx.x * nsp * 64 + lane;
     const u32x4_t* pp = p.P + base;
     const u32x2_t* ep = p.E + base;
+    static_assert(!WSTG || (!RMS && kWavesM == 16), "per-wave staging: the 16-wave forms without RMSNorm prologue");
+    // ---- WSTG: the wave's own activation chunks (4 elements each), issued first ----
+    // chunks per lane held in registers: 4 (K <= 16384; the 7B down_proj needs 3); o_proj 1 (K <= 4096: the addresses of the
+    // partials are ~60 instructions per chunk in front of the first weight load)
+    constexpr int kXEarly = !WSTG ? 0 : PARTS ? 1 : 4;
+    constexpr int kXE = kXEarly ? kXEarly : 1;
+    const int nch = K >> 2;
+    const int cw0 = s0 * 16 + lane, cw1 = s1 * 16;  // this lane's chunks: cw0, cw0 + 64, .. < cw1 (none in a wave behind the row's end)
+    const f32x4v_t* xg4 = reinterpret_cast<const f32x4v_t*>(g.A);
+    const u32x2_t* gg2 = reinterpret_cast<const u32x2_t*>(g.rms_w);
+    f32x4v_t xq[kXE], oq[PARTS ? kXE : 1][4];
+    u32x2_t mlq[PARTS ? kXE : 1][4];
+    // the partials of the head chunk c lies in: (max, sum) as one 8-byte word and the chunk's four o values, per key range
+    auto load_parts = [&](int c, u32x2_t* ml, f32x4v_t* o4) {
+        // (the head of the chunk: in the WSTG form this stands in front of the first weight load, and a head dimension that is a
+        //  power of two - every model's - spares it the integer division)
+        const unsigned pd = p.pD;
+        const int k = c << 2, hd = (pd & (pd - 1)) ? (int)((unsigned)k / pd) : k >> __builtin_ctz(pd), d0 = k - hd * p.pD, ps = p.pD + 4;
+        const float* ph = p.parts + (int64_t)hd * p.pS * ps;
+#pragma unroll
+        for (int s2 = 0; s2 < 4; ++s2) {
+            const int sc = s2 < p.pS ? s2 : 0;  // (pS = 2: ranges 2, 3 repeat range 0 with weight 0)
+            ml[s2] = *reinterpret_cast<const u32x2_t*>(ph + sc * ps + p.pD);
+            o4[s2] = *reinterpret_cast<const f32x4v_t*>(ph + sc * ps + d0);
+        }
+    };
+    if (WSTG) {  // (only the chunks that exist: every load here passes the CU's L1 in front of the weights)
+#pragma unroll
+        for (int i = 0; i < kXEarly; ++i) {
+            const int c = cw0 + 64 * i;
+            xq[i] = f32x4v_t{0.0f, 0.0f, 0.0f, 0.0f};
+            if (PARTS) {
+#pragma unroll
+                for (int s2 = 0; s2 < 4; ++s2) {
+                    mlq[i][s2] = u32x2_t{0u, 0u};
+                    oq[i][s2] = f32x4v_t{0.0f, 0.0f, 0.0f, 0.0f};
+                }
+            }
+            if (c < cw1) {
+                if (PARTS) {
+                    load_parts(c, mlq[i], oq[i]);
+                } else {
+#ifndef IVLM_ABL_XSTAGE
+                    xq[i] = xg4[c];
+#endif
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (the weight loads below stay behind the activation loads)
+    }
     u32x4_t w[U];
     u32x2_t e[U];
 #pragma unroll
@@ -280,53 +344,38 @@ __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12
         }
         load_fin();
     }
+    if (WSTG) __builtin_amdgcn_sched_barrier(0);  // (no use of an activation load above this line)
     // ---- stage x * 2^64 (x * gamma * 2^64) as hi + lo + lo2 bf16 planes, sum(x^2) of the unscaled row ----
     const float xs = __builtin_ldexpf(1.0f, kXScaleExp);
     float ssq = 0.0f;
     uint32_t* xw = reinterpret_cast<uint32_t*>(smem);
-#ifdef IVLM_ABL_XSTAGE  // (ablation, never in the product build: the upper bound of what producer-side x staging could save -
-                        //  no x / gamma loads, no hi + lo + lo2 split, no sum of squares; the planes get a constant)
-    for (int c = threadIdx.x; c < (K >> 2) && !PARTS; c += 64 * kWavesM) {
-        *reinterpret_cast<u32x2_t*>(xw + 2 * c) = u32x2_t{0x5f805f80u, 0x5f805f80u};
-        *reinterpret_cast<u32x2_t*>(xw + (K >> 1) + 2 * c) = u32x2_t{0u, 0u};
-        *reinterpret_cast<u32x2_t*>(xw + K + 2 * c) = u32x2_t{0u, 0u};
-        ssq = 1.0f;
-    }
-    for (int c = threadIdx.x; c < (PARTS ? (K >> 2) : 0); c += 64 * kWavesM) {
-#else
-    for (int c = threadIdx.x; c < (K >> 2); c += 64 * kWavesM) {
-#endif
-        f32x4v_t xv4;
-        if (PARTS) {
-            const int k = c << 2, hd = k / p.pD, d0 = k - hd * p.pD, ps = p.pD + 4;
-            const float* ph = p.parts + (int64_t)hd * p.pS * ps;
-            float m[4], l[4];
-            f32x4v_t o4[4];
+    auto merge_parts = [&](const u32x2_t* ml, const f32x4v_t* o4) {
+        float m[4], l[4];
 #pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                const int sc = s2 < p.pS ? s2 : 0;  // (pS = 2: ranges 2, 3 repeat range 0 with weight 0)
-                m[s2] = ph[sc * ps + p.pD];
-                l[s2] = ph[sc * ps + p.pD + 1];
-                o4[s2] = *reinterpret_cast<const f32x4v_t*>(ph + sc * ps + d0);
-            }
-            const float M = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
-            float den = 0.0f;
-            xv4 = f32x4v_t{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                const float wgt = s2 < p.pS ? __expf(m[s2] - M) : 0.0f;
-                den = fmaf(wgt, l[s2], den);
-                xv4 += o4[s2] * wgt;
-            }
-            xv4 = xv4 * (1.0f / den);
-        } else {
-            xv4 = reinterpret_cast<const f32x4v_t*>(g.A)[c];
+        for (int s2 = 0; s2 < 4; ++s2) {
+            m[s2] = __uint_as_float(ml[s2][0]);
+            l[s2] = __uint_as_float(ml[s2][1]);
         }
+        const float M = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
+        float den = 0.0f;
+        f32x4v_t xv4 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int s2 = 0; s2 < 4; ++s2) {
+            const float wgt = s2 < p.pS ? __expf(m[s2] - M) : 0.0f;
+            den = fmaf(wgt, l[s2], den);
+            xv4 += o4[s2] * wgt;
+        }
+        return xv4 * (1.0f / den);
+    };
+    auto sum_squares = [&](const f32x4v_t& xv4) {
+        const float v[4] = {xv4[0], xv4[1], xv4[2], xv4[3]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ssq += v[j] * v[j];
+    };
+    // chunk c of the row: times gamma (RMS), times 2^64, split into the three planes
+    auto stage = [&](int c, const f32x4v_t& xv4, const u32x2_t& gv) {
         float v[4] = {xv4[0], xv4[1], xv4[2], xv4[3]};
         if (RMS) {
-            const u32x2_t gv = *(reinterpret_cast<const u32x2_t*>(g.rms_w) + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ssq += v[j] * v[j];
             v[0] *= __uint_as_float(gv[0] << 16);
             v[1] *= __uint_as_float(gv[0] & 0xffff0000u);
             v[2] *= __uint_as_float(gv[1] << 16);
@@ -347,12 +396,69 @@ __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12
         *reinterpret_cast<u32x2_t*>(xw + 2 * c) = u32x2_t{hi[0], hi[1]};
         *reinterpret_cast<u32x2_t*>(xw + (K >> 1) + 2 * c) = u32x2_t{lo[0], lo[1]};
         *reinterpret_cast<u32x2_t*>(xw + K + 2 * c) = u32x2_t{l2[0], l2[1]};
+    };
+#ifdef IVLM_ABL_XSTAGE  // (ablation, never in the product build: the bound of what hiding the x staging could save - no x / gamma
+                        //  loads, no hi + lo + lo2 split, no sum of squares; the planes get a constant.  Not for the PARTS form.)
+    auto stage_const = [&](int c) {
+        *reinterpret_cast<u32x2_t*>(xw + 2 * c) = u32x2_t{0x5f805f80u, 0x5f805f80u};
+        *reinterpret_cast<u32x2_t*>(xw + (K >> 1) + 2 * c) = u32x2_t{0u, 0u};
+        *reinterpret_cast<u32x2_t*>(xw + K + 2 * c) = u32x2_t{0u, 0u};
+        ssq = 1.0f;
+    };
+    constexpr bool ABL = !PARTS;
+#else
+    auto stage_const = [&](int) {};
+    constexpr bool ABL = false;
+#endif
+    if (ABL) {
+        if (WSTG) {
+            for (int c = cw0; c < cw1; c += 64) stage_const(c);
+        } else {
+            for (int c = threadIdx.x; c < nch; c += 64 * kWavesM) stage_const(c);
+        }
+    } else if (WSTG) {
+        const u32x2_t no_gamma = {0u, 0u};
+#pragma unroll
+        for (int i = 0; i < kXEarly; ++i) {
+            const int c = cw0 + 64 * i;
+            if (c < cw1) stage(c, PARTS ? merge_parts(mlq[i], oq[i]) : xq[i], no_gamma);
+        }
+        for (int c = cw0 + 64 * kXEarly; c < cw1; c += 64) {
+            u32x2_t ml[4];
+            f32x4v_t o4[4], xv4;
+            if (PARTS) {
+                load_parts(c, ml, o4);
+                xv4 = merge_parts(ml, o4);
+            } else {
+                xv4 = xg4[c];
+            }
+            stage(c, xv4, no_gamma);
+        }
+    } else {
+        for (int c = threadIdx.x; c < nch; c += 64 * kWavesM) {
+            u32x2_t ml[4], gv = {0u, 0u};
+            f32x4v_t o4[4], xv4;
+            if (PARTS) {
+                load_parts(c, ml, o4);
+                xv4 = merge_parts(ml, o4);
+            } else {
+                xv4 = xg4[c];
+            }
+            if (RMS) {
+                gv = gg2[c];
+                sum_squares(xv4);
+            }
+            stage(c, xv4, gv);
+        }
     }
     if (RMS) {
         ssq = wave_sum(ssq);
         if (lane == 0) s_red[wave] = ssq;
     }
-    __syncthreads();
+    // WSTG: the wave reads only planes it wrote itself, through its own in-order LDS queue: the compiler must keep the order, the
+    // hardware does.  Otherwise the block's planes are complete behind this barrier.
+    if (WSTG) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    else __syncthreads();
     // A fragments: lane (i = lane & 15: plane min(i, 2); q = lane >> 4) reads k = step * 32 + q * 8 .. + 7 of its plane
     const int plane = min(lane & 15, 2);
     const u32x4_t* xa = reinterpret_cast<const u32x4_t*>(smem) + ((plane * K) >> 3) + (lane >> 4);
@@ -381,6 +487,7 @@ __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12
         }
     }
     if (lane < 16) s_part[wave][lane] = d[0] + d[1] + d[2];
+    if (WSTG) __syncthreads();  // the tail reads columns that other waves staged
     // ---- the tail: wave w owns the patches of row w (and w + 8 in the 8-wave form) of the block (the nonzero weights outside the row's exponent window:
     //      exact bf16 values, on average < 1 per row) against (hi + lo + lo2)[col] = the fp32 activation * 2^64 (the three parts add up
     //      exactly); the 16 finishing lanes of wave 0 fetch their row's exponent base / bias / residual meanwhile ----
@@ -675,6 +782,8 @@ extern "C" int ivlm_unpack_bf12(const void* P, int64_t ldp, const void* E, int64
 int g_skinny_p12m_tiles = 0;       // 0 = rule in ivlm_gemv16_bf12m (A/B hook: ivlm_gemv16_bf12m_tuning)
 int g_p12m_wide_max_blocks = 256;  // A/B hooks: ivlm_gemv1_bf12m_tuning
 int g_p12m_deep = 1;
+int g_p12m_staging = 1;  // 1 = per-wave activation staging in the forms that gain, 0 = block-cooperative everywhere (A/B hook:
+                         // ivlm_gemv1_bf12m_staging)
 namespace ivlm {
 int g_decode_parts_S = 4;  // key ranges per head of the split-KV attention / o_proj pair (A/B hook: ivlm_decode_parts_tuning; 2 or 4)
 }
@@ -719,23 +828,29 @@ static int gemv1_bf12m(const float* x, const float* parts, int pD, const void* P
         }
         ivlm_launch(kfn, grid, dim3(64 * waves), (size_t)K * 6, st, g, p);
     };
-    static ivlm_dev_mask_t set[8];  // (zero-initialised; one mask per instantiation, one bit per device)
+    static ivlm_dev_mask_t set[11];  // (zero-initialised; one mask per instantiation, one bit per device)
+    // per-wave staging where it was measured faster: one 16-wave block per CU and no RMSNorm prologue (o_proj, down_proj)
+    const bool wstg = g_p12m_staging && wide && !rms_w;
     if (parts) {  // (the o_proj of a decode step: K = hidden, never the 8-deep form)
-        if (wide) go(gemv1_p12m_kernel<false, 16, 4, true>, 16, set[6]);
-        else go(gemv1_p12m_kernel<false, 8, 4, true>, 8, set[7]);
+        if (wstg) go(gemv1_p12m_kernel<false, 16, 4, true, true>, 16, set[8]);
+        else if (wide) go(gemv1_p12m_kernel<false, 16, 4, true, false>, 16, set[6]);
+        else go(gemv1_p12m_kernel<false, 8, 4, true, false>, 8, set[7]);
         return ivlm_launch_status();
     }
     // (one block per CU and a long row - down_proj: 8 step pairs in flight per lane, so that most of the block's 264 KB is requested
-    //  BEFORE the x staging, which otherwise runs with only the first 96 KB on their way)
+    //  up front)
     const bool deep = wide && (K >> 6) > 4 * 16 && g_p12m_deep;
     if (rms_w) {
-        if (deep) go(gemv1_p12m_kernel<true, 16, 8>, 16, set[4]);
-        else if (wide) go(gemv1_p12m_kernel<true, 16, 4>, 16, set[0]);
-        else go(gemv1_p12m_kernel<true, 8, 4>, 8, set[1]);
+        if (deep) go(gemv1_p12m_kernel<true, 16, 8, false, false>, 16, set[4]);
+        else if (wide) go(gemv1_p12m_kernel<true, 16, 4, false, false>, 16, set[0]);
+        else go(gemv1_p12m_kernel<true, 8, 4, false, false>, 8, set[1]);
+    } else if (wstg) {
+        if (deep) go(gemv1_p12m_kernel<false, 16, 8, false, true>, 16, set[9]);
+        else go(gemv1_p12m_kernel<false, 16, 4, false, true>, 16, set[10]);
     } else {
-        if (deep) go(gemv1_p12m_kernel<false, 16, 8>, 16, set[5]);
-        else if (wide) go(gemv1_p12m_kernel<false, 16, 4>, 16, set[2]);
-        else go(gemv1_p12m_kernel<false, 8, 4>, 8, set[3]);
+        if (deep) go(gemv1_p12m_kernel<false, 16, 8, false, false>, 16, set[5]);
+        else if (wide) go(gemv1_p12m_kernel<false, 16, 4, false, false>, 16, set[2]);
+        else go(gemv1_p12m_kernel<false, 8, 4, false, false>, 8, set[3]);
     }
     return ivlm_launch_status();
 }
@@ -761,6 +876,12 @@ extern "C" int ivlm_gemv1_bf12m_parts(const float* parts, int D, const void* Pf,
 extern "C" void ivlm_gemv1_bf12m_tuning(int wide_max_blocks) {
     g_p12m_deep = wide_max_blocks >= 0;  // (negative: |value| as the limit, without the 8-deep form)
     g_p12m_wide_max_blocks = wide_max_blocks < 0 ? -wide_max_blocks : wide_max_blocks;
+}
+
+extern "C" int ivlm_gemv1_bf12m_staging(int form) {
+    if (form != 0 && form != 1) return IVLM_ERR_INVALID_ARG;
+    g_p12m_staging = form;
+    return IVLM_OK;
 }
 
 extern "C" int ivlm_decode_parts_tuning(int ranges) {

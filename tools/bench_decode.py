@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--precision", default="f16", help="tower precision: f16 (the default mode of the model) | default (bf16)")
     ap.add_argument("--splits", type=int, default=0, help="split-KV ranges per head (0 = library default)")
     ap.add_argument("--wide", type=int, default=-1, help="ivlm_gemv1_bf12m_tuning: 16-wave blocks up to this many row blocks (-1 = default)")
+    ap.add_argument("--staging", type=int, default=-1, help="ivlm_gemv1_bf12m_staging: 0 = block-cooperative x staging, 1 = per wave (-1 = default)")
     ap.add_argument("--tiles", type=int, default=0, help="skinny MFMA tiles per block (0 = automatic)")
     a = ap.parse_args()
     from interactvlm_amd import llava, synthetic
@@ -49,6 +50,8 @@ def main():
         assert _lib.load().ivlm_decode_parts_tuning(int(os.environ["PARTS_S"])) == 0
     if a.wide != -1:
         _lib.load().ivlm_gemv1_bf12m_tuning(a.wide)
+    if a.staging != -1:
+        assert _lib.load().ivlm_gemv1_bf12m_staging(a.staging) == 0
     if a.splits:
         assert _lib.load().ivlm_llama_decode_attn_splits(a.splits) == 0
         llm.decode_splitkv = True
