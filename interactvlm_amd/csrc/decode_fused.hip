@@ -60,8 +60,16 @@ template <int NB>  // NB = 16-byte chunks per lane per row = hidden / 512 (8 for
 __global__ __launch_bounds__(kDecThreads) void attn_oproj_kernel(AttnOprojArgs a) {
     const int hidden = a.H * a.D;
     if ((int)blockIdx.x < a.H) {
-        llama_decode_attn_body<true, true>(blockIdx.x, a.qkv, a.kcache, a.vcache, a.attn, a.H, a.D, 0, a.theta, a.scale,
-                                           a.cos_tab, a.sin_tab, a.pos_dev, a.tmax);
+        const int pos = __builtin_amdgcn_readfirstlane(*a.pos_dev);
+        // (a position past the cache slab: nothing appended, the row is left as it is - the counter below is still bumped)
+        if (pos < a.tmax && pos < kMaxT) {
+            const RangeOut r = decode_attn_range<kDecThreads, true, false, false, true>(
+                blockIdx.x, a.qkv, a.kcache, a.vcache, nullptr, nullptr, a.H, a.D, pos, 0, pos + 1, true, a.theta, a.scale, a.cos_tab,
+                a.sin_tab);
+            // the output row goes out with agent-scope stores: its consumers are inside this launch
+            if ((int)threadIdx.x < a.D)
+                __hip_atomic_store(a.attn + blockIdx.x * a.D + threadIdx.x, r.o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's agent-scope stores are performed
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_fetch_add(a.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

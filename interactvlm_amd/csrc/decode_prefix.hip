@@ -5,11 +5,11 @@
 //   shared phase (llama_prefix_shared_kernel, grid H x S): the keys [0, P) of slab 0 are cut into S ranges.  A block stages 64 K / V
 //       rows of its range in LDS (coalesced 16-byte loads, K and V of a chunk in flight together), computes the 64 x B scores (one key
 //       per lane, four queries per wave, q broadcast from LDS), an online softmax per query and o += p.V for all B queries, and
-//       publishes unnormalised (o, max, sum) per query: parts[h][s][b][D + 4], plain stores.
+//       publishes unnormalised (o, max, sum) per query: parts[h][s][b][decode_parts_stride(D)], plain stores.
 //   own phase + merge (llama_prefix_own_kernel, grid H x B, the next launch on the same stream - the kernel boundary is the
 //       synchronisation, no counter, no block waits for another): sequence b does RoPE of q and k, appends its new row at pos_dev[b]
-//       of ITS slab, attends over its own rows [P, pos_dev[b]] (the split-KV kernel's body on that range) and merges the S shared
-//       partials (range order) and its own by the online-softmax rule.  The order is fixed, so a launch is reproducible.
+//       of ITS slab, attends over its own rows [P, pos_dev[b]] (decode_attn_range on that range) and merges the S shared partials
+//       (range order) and its own by the online-softmax rule (merge_ranges).  The order is fixed, so a launch is reproducible.
 //
 // Arithmetic: the single-token kernel's with fp32 I/O (decode_attn.h): fp32 q, fp32 softmax, the cached rows as stored (bf16 or
 // IEEE fp16), the sequence's own new row unrounded; the appended rows are bit-identical to the plain batched kernel's.  The result
@@ -22,8 +22,8 @@ namespace {
 using namespace decattn;
 
 namespace prefix {
-constexpr int kT = 256, kChunk = 64, kMaxB = 16, kMaxSplits = 16, kMinPer = 16;
-constexpr int kG = kT / 16, kU = 6, kTile = kG * kU;  // own phase: 16 groups of 16 lanes, 96 keys per tile (as splitkv)
+constexpr int kT = 256, kChunk = 64, kMaxB = 16, kMinPer = 16;
+constexpr int kG = kT / 16;  // staging rows per sweep (16 lanes share a row)
 __host__ __device__ inline int clampP(int P, int tmax) {
     const int cap = tmax < kMaxT ? tmax : kMaxT;
     return P < 0 ? 0 : (P > cap ? cap : P);
@@ -66,19 +66,11 @@ __global__ __launch_bounds__(prefix::kT) void llama_prefix_shared_kernel(
         if (i < B) {
             const int pos = pos_dev[i];
             if (pos >= 0 && pos < tmax && pos < kMaxT) {
-                float c, s;
-                if (ct) {
-                    c = ct[pos * half + d];
-                    s = stab[pos * half + d];
-                } else {
-                    const float ang = (float)pos * powf(theta, -(float)(2 * d) / (float)D);
-                    c = cosf(ang);
-                    s = sinf(ang);
-                }
+                const CosSin r = rope_cos_sin(ct, stab, pos, d, half, D, theta);
                 const float* row = qkv + i * ldq + (int64_t)h * D;
                 const float q0 = row[d], q1 = row[d + half];
-                qa = q0 * c - q1 * s;
-                qb = q1 * c + q0 * s;
+                qa = q0 * r.c - q1 * r.s;
+                qb = q1 * r.c + q0 * r.s;
             }
         }
         q_t[d][i] = qa;
@@ -193,14 +185,15 @@ __global__ __launch_bounds__(prefix::kT) void llama_prefix_shared_kernel(
         for (int i = 0; i < kMaxB; ++i) red[i * kMaxD + pd] = acc[i];
     }
     __syncthreads();
-    float* mine = part + ((int64_t)h * S + sp) * B * (D + 4);
+    const int pstride = decode_parts_stride(D);
+    float* mine = part + ((int64_t)h * S + sp) * B * pstride;
     if (pks == 0 && pd < D) {
 #pragma unroll
         for (int i = 0; i < kMaxB; ++i)
-            if (i < B) mine[i * (D + 4) + pd] = acc[i] + red[i * kMaxD + pd];
+            if (i < B) mine[i * pstride + pd] = acc[i] + red[i * kMaxD + pd];
     } else if (pks == 1 && pd < B) {
-        mine[pd * (D + 4) + D] = m_s[pd];
-        mine[pd * (D + 4) + D + 1] = l_s[pd];
+        mine[pd * pstride + D] = m_s[pd];
+        mine[pd * pstride + D + 1] = l_s[pd];
     }
 }
 
@@ -211,7 +204,6 @@ __global__ __launch_bounds__(prefix::kT) void llama_prefix_own_kernel(
     const float* __restrict__ ct, const float* __restrict__ stab, const int32_t* __restrict__ pos_dev,
     const int32_t* __restrict__ prefix_len_dev, int tmax, const float* __restrict__ part, int S) {
     using namespace prefix;
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
     const int h = blockIdx.x, b = blockIdx.y, B = gridDim.y;
     const int t = threadIdx.x;
     const int pos = __builtin_amdgcn_readfirstlane(pos_dev[b]);
@@ -221,174 +213,17 @@ __global__ __launch_bounds__(prefix::kT) void llama_prefix_own_kernel(
         return;
     }
     const int P = clampP(__builtin_amdgcn_readfirstlane(*prefix_len_dev), tmax);
-    const float* qkv = qkv_all + b * ldq;
-    bf16_t* kcache = kcache_all + b * cache_stride;
-    bf16_t* vcache = vcache_all + b * cache_stride;
-    // the sequence's own keys [P, pos]; a position inside the prefix (excluded by the caller): own range empty, nothing appended
+    // the sequence's own keys [P, pos]; a position inside the prefix (excluded by the caller): own range empty, nothing appended.
+    // The arithmetic of the plain batched kernel on that range: the appended rows are the same bit for bit.
     const bool owner = pos >= P;
-    const int k0 = P, k1 = owner ? pos + 1 : P;
-    const int len = k1 - k0;
-    __shared__ float q_s[kMaxD];
-    __shared__ float knew_s[kMaxD];
-    __shared__ float vnew_s[kMaxD];
-    __shared__ float sc[kMaxT];
-    __shared__ float red[2 * kT / 64];
-    __shared__ float partl[kG][kMaxD];
-    const int half = D >> 1;
-    const int sub = t & 15, grp = t >> 4;
-    const int nch = D >> 3;
-    const int csub = sub < nch ? sub : nch - 1;
-    const int64_t rstride = (int64_t)H * D;
-    const bf16_t* kb = kcache + (int64_t)h * D + csub * 8;
-    const bf16_t* vb = vcache + (int64_t)h * D + csub * 8;
-    u32x4_t kr[kU], vr[kU];
-    const int jmax = pos > 0 ? pos - 1 : 0;  // loads are clamped (rows 0 .. pos-1 of this slab) and unconditional, masked where used
-    if (len > 0) {
-#pragma unroll
-        for (int i = 0; i < kU; ++i) {
-            int j = k0 + grp + kG * i;
-            j = j < jmax ? j : jmax;
-            kr[i] = *reinterpret_cast<const u32x4_t*>(kb + j * rstride);
-            vr[i] = *reinterpret_cast<const u32x4_t*>(vb + j * rstride);
-        }
-    }
-    // ---- RoPE on q and the new k; append k, v (the arithmetic of llama_decode_attn_body: the same rows bit for bit) -------------
-    if (t < half) {
-        const int64_t q = (int64_t)h * D, k = (int64_t)H * D + h * D;
-        float c, s;
-        if (ct) {
-            c = ct[pos * half + t];
-            s = stab[pos * half + t];
-        } else {
-            const float ang = (float)pos * powf(theta, -(float)(2 * t) / (float)D);
-            c = cosf(ang);
-            s = sinf(ang);
-        }
-        const float q0 = qkv[q + t], q1 = qkv[q + t + half];
-        q_s[t] = q0 * c - q1 * s;
-        q_s[t + half] = q1 * c + q0 * s;
-        if (owner) {
-            const float k0f = qkv[k + t], k1f = qkv[k + t + half];
-            const float kaf = k0f * c - k1f * s, kbf = k1f * c + k0f * s;
-            knew_s[t] = kaf;
-            knew_s[t + half] = kbf;
-            bf16_t* kc = kcache + ((int64_t)pos * H + h) * D;
-            kc[t] = f32_to_h16<CF16>(kaf);
-            kc[t + half] = f32_to_h16<CF16>(kbf);
-        }
-    } else if (owner && t >= 128 && t < 128 + D) {
-        const int d = t - 128;
-        const float v = qkv[2 * (int64_t)H * D + h * D + d];
-        vnew_s[d] = v;
-        vcache[((int64_t)pos * H + h) * D + d] = f32_to_h16<CF16>(v);
-    }
-    __syncthreads();
-    // ---- scores of the own range ------------------------------------------------------------------------------------------------
-    float qr[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qr[e] = sub < nch ? q_s[sub * 8 + e] : 0.0f;
-    auto score = [&](const u32x4_t& kv, int j) {
-        float d = 0.0f;
-        if (sub < nch) {
-            if (j < pos) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    d += pair_lo_f32<CF16>(kv[e]) * qr[2 * e];
-                    d += pair_hi_f32<CF16>(kv[e]) * qr[2 * e + 1];
-                }
-            } else if (j == pos) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d += knew_s[sub * 8 + e] * qr[e];
-            }
-        }
-        d += __shfl_xor(d, 8, 64);
-        d += __shfl_xor(d, 4, 64);
-        d += __shfl_xor(d, 2, 64);
-        d += __shfl_xor(d, 1, 64);
-        if (sub == 0 && j < k1) sc[j - k0] = d * scale;
-    };
-    if (len > 0) {
-#pragma unroll
-        for (int i = 0; i < kU; ++i) score(kr[i], k0 + grp + kG * i);
-        for (int j0 = k0 + kTile; j0 < k1; j0 += kTile) {  // longer answers: further tiles
-#pragma unroll
-            for (int i = 0; i < kU; ++i) {
-                int j = j0 + grp + kG * i;
-                j = j < jmax ? j : jmax;
-                kr[i] = *reinterpret_cast<const u32x4_t*>(kb + j * rstride);
-            }
-#pragma unroll
-            for (int i = 0; i < kU; ++i) score(kr[i], j0 + grp + kG * i);
-        }
-    }
-    __syncthreads();
-    // ---- softmax of the own range: local max, p = e^(s - m), local sum ------------------------------------------------------------
-    constexpr int NW = kT / 64;
-    float mx = -1.0e30f;
-    for (int j = t; j < len; j += kT) mx = fmaxf(mx, sc[j]);
-    mx = wave_max(mx);
-    if ((t & 63) == 0) red[t >> 6] = mx;
-    __syncthreads();
-    mx = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, red[w]);
-    float sum = 0.0f;
-    for (int j = t; j < len; j += kT) {
-        const float p = __expf(sc[j] - mx);
-        sc[j] = p;
-        sum += p;
-    }
-    sum = wave_sum(sum);
-    if ((t & 63) == 0) red[NW + (t >> 6)] = sum;
-    __syncthreads();
-    float tot = 0.0f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) tot += red[NW + w];
-    // ---- o = sum p v over the own range (unnormalised) ----------------------------------------------------------------------------
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
-    auto pv = [&](const u32x4_t& vv, int j) {
-        if (j < k1 && sub < nch) {
-            const float p = sc[j - k0];
-            if (j < pos) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[2 * e] += p * pair_lo_f32<CF16>(vv[e]);
-                    acc[2 * e + 1] += p * pair_hi_f32<CF16>(vv[e]);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += p * vnew_s[sub * 8 + e];
-            }
-        }
-    };
-    if (len > 0) {
-#pragma unroll
-        for (int i = 0; i < kU; ++i) pv(vr[i], k0 + grp + kG * i);
-        for (int j0 = k0 + kTile; j0 < k1; j0 += kTile) {
-#pragma unroll
-            for (int i = 0; i < kU; ++i) {
-                int j = j0 + grp + kG * i;
-                j = j < jmax ? j : jmax;
-                vr[i] = *reinterpret_cast<const u32x4_t*>(vb + j * rstride);
-            }
-#pragma unroll
-            for (int i = 0; i < kU; ++i) pv(vr[i], j0 + grp + kG * i);
-        }
-    }
-    if (sub < nch) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) partl[grp][sub * 8 + e] = acc[e];
-    }
-    __syncthreads();
+    const RangeOut own = decode_attn_range<kT, true, false, CF16, false>(h, qkv_all + b * ldq, kcache_all + b * cache_stride,
+                                                                          vcache_all + b * cache_stride, nullptr, nullptr, H, D, pos, P,
+                                                                          owner ? pos + 1 : P, owner, theta, scale, ct, stab);
     if (t >= D) return;
     // ---- merge: the S shared partials in range order, then the own range (written by the previous launch: plain loads) -----------
-    float own = 0.0f;
-#pragma unroll
-    for (int g2 = 0; g2 < kG; ++g2) own += partl[g2][t];
-    const float* base = part + ((int64_t)h * S * B + b) * (D + 4);
-    const int64_t sstride = (int64_t)B * (D + 4);
+    const int pstride = decode_parts_stride(D);
+    const float* base = part + ((int64_t)h * S * B + b) * pstride;
+    const int64_t sstride = (int64_t)B * pstride;
     float pm[kMaxSplits], pl[kMaxSplits], po[kMaxSplits];
 #pragma unroll
     for (int s2 = 0; s2 < kMaxSplits; ++s2) {
@@ -397,33 +232,14 @@ __global__ __launch_bounds__(prefix::kT) void llama_prefix_own_kernel(
         pl[s2] = ps[D + 1];
         po[s2] = ps[t];
     }
-    const bool have_own = len > 0 && tot > 0.0f;
-    float M = have_own ? mx : -1.0e30f;
-#pragma unroll
-    for (int s2 = 0; s2 < kMaxSplits; ++s2)
-        if (s2 < S && pl[s2] > 0.0f) M = fmaxf(M, pm[s2]);
-    float num = 0.0f, den = 0.0f;
-#pragma unroll
-    for (int s2 = 0; s2 < kMaxSplits; ++s2) {
-        if (s2 < S && pl[s2] > 0.0f) {  // (an empty range published l = 0)
-            const float wgt = __expf(pm[s2] - M);
-            num += wgt * po[s2];
-            den += wgt * pl[s2];
-        }
-    }
-    if (have_own) {
-        const float wgt = __expf(mx - M);
-        num += wgt * own;
-        den += wgt * tot;
-    }
-    o[(int64_t)h * D + t] = den > 0.0f ? num / den : 0.0f;
+    o[(int64_t)h * D + t] = merge_ranges(pm, pl, po, S, own.l > 0.0f, own);
 }
 
 }  // namespace
 
 size_t llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D) {
     if (B <= 0 || H <= 0 || D <= 0) return 0;
-    return (size_t)H * prefix::splits(H) * B * (D + 4) * sizeof(float);
+    return (size_t)H * prefix::splits(H) * B * decode_parts_stride(D) * sizeof(float);
 }
 
 int llama_decode_attn_batch_prefix(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,

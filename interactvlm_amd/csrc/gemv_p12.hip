@@ -863,7 +863,7 @@ extern "C" int ivlm_gemv1_bf12m(const float* x, const void* Pf, const void* Ef, 
                        flags, stream);
 }
 
-// ... with the activation row merged from the split-KV attention partials parts[K / D][4][D + 4] of ivlm_llama_decode_attn_parts (the
+// ... with the activation row merged from the split-KV attention partials of ivlm_llama_decode_attn_parts (the parts layout of kernels.h; the
 // o_proj of a decode step: no RMSNorm prologue)
 extern "C" int ivlm_gemv1_bf12m_parts(const float* parts, int D, const void* Pf, const void* Ef, const int32_t* ebase,
                                       const int32_t* patch_ptr, const int32_t* patch_col, const void* patch_val, void* C, const void* bias,

@@ -221,6 +221,11 @@ int llama_decode_attn_splitkv(const float* qkv, bf16_t* kcache, bf16_t* vcache, 
                               float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
                               int cache_f16, void* scratch, size_t scratch_bytes);
 
+// the "parts" layout between the split-KV attention and the consumer that merges it (the packed o_proj GEMV, ivlm_gemv1_bf12m_parts):
+// parts[H][g_decode_parts_S][decode_parts_stride(D)] fp32, a row = o unnormalised [D] | max | sum | 2 pad (16-byte rows)
+extern int g_decode_parts_S;  // key ranges per head: 4, or 2 (A/B hook ivlm_decode_parts_tuning, gemv_p12.hip)
+constexpr int kDecodePartsMaxS = 4;
+__host__ __device__ constexpr int decode_parts_stride(int D) { return D + 4; }
 int llama_decode_attn_parts(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* parts, int H, int D, int pos, float theta,
                             float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
                             int cache_f16);

@@ -248,12 +248,12 @@ namespace {
 
 // One carve for every form of the decode step (the caller zeroes it at the start of a generation, whichever form it then calls):
 // activations | the fused launch's state: per-layer arrival counters (128 B apart), words [0] status, [1] tokens decoded so far,
-// per-layer attention rows | the split-KV attention partials of the packed step [heads][4][head_dim + 4]
+// per-layer attention rows | the split-KV attention partials of the packed step (the parts layout of kernels.h, at its largest)
 struct DecodeBufs { float *qkv, *hh, *xa, *xb, *att; int32_t *counters, *words; float *scratch, *parts; };
 DecodeBufs carve_decode(const ivlm_llama_cfg* c, Carver& cv) {
     const size_t h = c->hidden, L = c->layers, H = c->heads;
     return {cv.get<float>(3 * h), cv.get<float>(c->inter), cv.get<float>(h), cv.get<float>(h), cv.get<float>(h),
-            cv.get<int32_t>(L * 32), cv.get<int32_t>(64), cv.get<float>(L * h), cv.get<float>(H * 4 * (h / H + 4))};
+            cv.get<int32_t>(L * 32), cv.get<int32_t>(64), cv.get<float>(L * h), cv.get<float>(H * kDecodePartsMaxS * decode_parts_stride(h / H))};
 }
 
 // The "linear" of a decode step, out = act(W . rmsnorm(x)) + res on fp32 activations with exact products (rms: the norm weight of the

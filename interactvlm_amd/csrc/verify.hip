@@ -11,7 +11,7 @@
 //                       kernel with all rows on one slab would race.
 //   spec_accept       : n_acc = leading draft tokens equal to the previous row's argmax, next token = argmax of row n_acc,
 //                       pos += n_acc + 1 (one thread; graph-capturable).
-#include "kernels.h"
+#include "decode_attn.h"
 
 namespace ivlm {
 namespace {
@@ -45,15 +45,8 @@ __global__ __launch_bounds__(kVThreads) void llama_verify_attn_kernel(const floa
     // ---- RoPE on q and k, append k / v (rounding as the single-token kernel) -------------------------------------------------
     for (int e = t; e < kv * half; e += kVThreads) {
         const int i = e / half, d = e - i * half, p = pos + i;
-        float c, s;
-        if (ct) {
-            c = ct[p * half + d];
-            s = stab[p * half + d];
-        } else {
-            const float ang = (float)p * powf(theta, -(float)(2 * d) / (float)D);
-            c = cosf(ang);
-            s = sinf(ang);
-        }
+        const decattn::CosSin r = decattn::rope_cos_sin(ct, stab, p, d, half, D, theta);
+        const float c = r.c, s = r.s;
         const float* row = qkv + i * ldq;
         const int64_t q = (int64_t)h * D, kk = rstride + h * D;
         const float q0 = row[q + d], q1 = row[q + d + half];
