@@ -7,17 +7,17 @@
 //   gemv1_kernel  M = 1, fp32 x (the decode path proper): 1024-thread blocks, ONE row per wave, no persistence - see below;
 //   gemv_kernel   M <= 8, bf16 or fp32 x: persistent blocks, two rows per wave (SwiGLU over the row-interleaved gate / up
 //                 weights completes inside the wave), software-pipelined over (row group, chunk batch) steps.
+// The activation switch, the row prologue and the row finish are those of gemv_common.h.
 #include <stdlib.h>
 
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemv_common.h"
 
 namespace ivlm {
 namespace {
 
 constexpr int kMaxM = 8;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;  // native vector: nontemporal-loadable
 
 __device__ __forceinline__ float dot8(const u32x4_t& w, const u32x4_t& x) {
     float acc = 0.0f;
@@ -29,25 +29,12 @@ __device__ __forceinline__ float dot8(const u32x4_t& w, const u32x4_t& x) {
     return acc;
 }
 
-__device__ __forceinline__ float act_apply(float x, int act) {
-    switch (act) {
-        case ACT_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-        case ACT_QUICK_GELU: return x / (1.0f + __expf(-1.702f * x));
-        case ACT_RELU: return x < 0.0f ? 0.0f : x;  // (torch.relu semantics: a NaN stays a NaN; fmaxf would turn it into 0)
-        case ACT_SILU: return x / (1.0f + __expf(-x));
-        case ACT_SIGMOID: return 1.0f / (1.0f + __expf(-x));
-        default: return x;
-    }
-}
-
 // ROWS weight rows per wave (2: enables the SwiGLU epilogue and doubles the loads in flight; 1: small N, more
 // waves).  XLDS: the activation rows (optionally RMS-normalised: x * gamma) are staged ONCE per block in LDS
 // together with their row scale, instead of every wave re-deriving them from global memory for every weight row.
 // AF32: the activations are fp32 (fp32 residual stream / fp32 hidden states): they stay fp32 in LDS and every product
 // bf16 weight x fp32 activation is exact - the decode path carries no operand rounding at all (it is HBM-bound: the
 // extra LDS bytes and the 8 FMAs per 16-byte weight chunk instead of 8 packed multiplies are free).
-typedef __attribute__((ext_vector_type(4))) float f32x4v_t;
-
 __device__ __forceinline__ float dot8f(const u32x4_t& w, const f32x4v_t& xa, const f32x4v_t& xb) {
     float acc = __uint_as_float(w[0] << 16) * xa[0];
     acc = fmaf(__uint_as_float(w[0] & 0xffff0000u), xa[1], acc);
@@ -58,10 +45,6 @@ __device__ __forceinline__ float dot8f(const u32x4_t& w, const f32x4v_t& xa, con
     acc = fmaf(__uint_as_float(w[3] << 16), xb[2], acc);
     acc = fmaf(__uint_as_float(w[3] & 0xffff0000u), xb[3], acc);
     return acc;
-}
-
-__device__ __forceinline__ float gemm_residual_f32_or_bf16(const GemmArgs& g, int64_t col) {  // row 0 (M = 1)
-    return g.res_f32 ? reinterpret_cast<const float*>(g.residual)[col] : bf16_to_f32(g.residual[col]);
 }
 
 template <int M, int ROWS, bool RMS, bool XLDS, bool AF32>
@@ -115,12 +98,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemmArgs g) {
                     const f32x4v_t* xp = reinterpret_cast<const f32x4v_t*>(Af + (int64_t)m * g.lda) + 2 * c;
                     f32x4v_t xa = xp[0], xb = xp[1];
                     if (RMS) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) ssq[m] += xa[j] * xa[j] + xb[j] * xb[j];
-                        xa[0] *= __uint_as_float(gv[0] << 16); xa[1] *= __uint_as_float(gv[0] & 0xffff0000u);
-                        xa[2] *= __uint_as_float(gv[1] << 16); xa[3] *= __uint_as_float(gv[1] & 0xffff0000u);
-                        xb[0] *= __uint_as_float(gv[2] << 16); xb[1] *= __uint_as_float(gv[2] & 0xffff0000u);
-                        xb[2] *= __uint_as_float(gv[3] << 16); xb[3] *= __uint_as_float(gv[3] & 0xffff0000u);
+                        sum_squares8(ssq[m], xa, xb);
+                        scale_by_gamma8(xa, xb, gv);
                     }
                     xf[(2 * m) * nchunk + c] = xa;  // two planes: consecutive lanes read consecutive 16 bytes
                     xf[(2 * m + 1) * nchunk + c] = xb;
@@ -205,25 +184,19 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemmArgs g) {
                 float v0 = a0[m] + (g.bias ? bf16_to_f32(g.bias[n0]) : 0.0f);
                 float v1 = a1[m] + (g.bias ? bf16_to_f32(g.bias[n1]) : 0.0f);
                 if (ROWS == 2 && g.act == ACT_SWIGLU) {
-                    const float o = (v0 / (1.0f + __expf(-v0))) * v1;
-                    const int64_t idx = (int64_t)m * g.ldc + pr;
-                    if (g.out_f32) static_cast<float*>(g.C)[idx] = o;
-                    else static_cast<bf16_t*>(g.C)[idx] = f32_to_bf16(o);
+                    gemv_store(g, (int64_t)m * g.ldc + pr, (v0 / (1.0f + __expf(-v0))) * v1);
                     continue;
                 }
-                v0 = act_apply(v0, g.act);
-                v1 = act_apply(v1, g.act);
+                v0 = gemv_act(v0, g.act);
+                v1 = gemv_act(v1, g.act);
                 if (g.residual) {
                     const int64_t rrow = g.res_mod > 0 ? (m % g.res_mod) : m;
-                    if (g.res_f32) {
-                        const float* R = reinterpret_cast<const float*>(g.residual);
-                        v0 += R[rrow * g.ldr + n0];
-                        v1 += R[rrow * g.ldr + n1];
-                    } else {
-                        v0 += bf16_to_f32(g.residual[rrow * g.ldr + n0]);
-                        v1 += bf16_to_f32(g.residual[rrow * g.ldr + n1]);
-                    }
+                    v0 += gemm_residual_at(g, g.residual, rrow * g.ldr + n0);
+                    v1 += gemm_residual_at(g, g.residual, rrow * g.ldr + n1);
                 }
+                // (the pair under ONE branch on the output type, not two gemv_store calls: with those the compiler's resource report
+                //  gives gemv_kernel<6, 2, false, true, false> 171 instead of 167 VGPRs - more than 168 - and 2 instead of 3 waves
+                //  per SIMD)
                 if (g.out_f32) {
                     float* C = static_cast<float*>(g.C) + (int64_t)m * g.ldc;
                     C[n0] = v0;
@@ -261,7 +234,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemmArgs g) {
 // balances the CUs, 32 resident waves per CU hide the latency, and x is staged once per 16 rows (16 KB of L2 reads per
 // 128 KB of weights).  Same arithmetic as gemv_kernel<1, 1, RMS, true, true> (fp32 x in two LDS planes, exact products,
 // per-lane ascending chunk order), so results are identical up to the block-level sum(x^2) order of the RMS prologue.
-constexpr int kG1Waves = 16;
+constexpr int kG1Waves = kRowWaves;
 
 // (KS = 2 waves per weight row - K halves, partial sums through LDS - was measured for the 4096-row matrices, which put only
 //  16 waves on each CU: 3-6 % slower on every shape.  KS stays a template parameter for that A/B: ivlm_gemv1_tuning.)
@@ -283,27 +256,7 @@ __global__ __launch_bounds__(64 * kG1Waves, 8) void gemv1_kernel(GemmArgs g) {
     u32x4_t w[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(wp + min(c_lo + lane + 64 * u, nchunk - 1));
-    // ---- stage x (x * gamma) in LDS, sum(x^2) ----
-    float ssq = 0.0f;
-    for (int c = threadIdx.x; c < nchunk; c += 64 * kG1Waves) {
-        const f32x4v_t* xp = reinterpret_cast<const f32x4v_t*>(g.A) + 2 * c;
-        f32x4v_t xa = xp[0], xb = xp[1];
-        if (RMS) {
-            const u32x4_t gv = *(reinterpret_cast<const u32x4_t*>(g.rms_w) + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ssq += xa[j] * xa[j] + xb[j] * xb[j];
-            xa[0] *= __uint_as_float(gv[0] << 16); xa[1] *= __uint_as_float(gv[0] & 0xffff0000u);
-            xa[2] *= __uint_as_float(gv[1] << 16); xa[3] *= __uint_as_float(gv[1] & 0xffff0000u);
-            xb[0] *= __uint_as_float(gv[2] << 16); xb[1] *= __uint_as_float(gv[2] & 0xffff0000u);
-            xb[2] *= __uint_as_float(gv[3] << 16); xb[3] *= __uint_as_float(gv[3] & 0xffff0000u);
-        }
-        xf[c] = xa;
-        xf[nchunk + c] = xb;
-    }
-    if (RMS) {
-        ssq = wave_sum(ssq);
-        if (lane == 0) s_red[wave] = ssq;
-    }
+    stage_row_f32<RMS, false>(g, xf, nchunk, 64 * kG1Waves, s_red, lane, wave);  // x (x * gamma) in LDS, sum(x^2)
     __syncthreads();
     float acc = 0.0f;
     // rows longer than one batch of U chunks per lane (down_proj: K = 11008): each half of the batch is refilled with the NEXT batch's
@@ -334,36 +287,14 @@ __global__ __launch_bounds__(64 * kG1Waves, 8) void gemv1_kernel(GemmArgs g) {
 #pragma unroll
         for (int i = 1; i < KS; ++i) acc += s_val[wave + i];
     }
-    if (RMS) {
-        float q = 0.0f;
-#pragma unroll
-        for (int i = 0; i < kG1Waves; ++i) q += s_red[i];
-        acc *= rsqrtf(q / (float)g.K + g.rms_eps);
-    }
-    float v = acc + ((g.bias && live) ? bf16_to_f32(g.bias[row]) : 0.0f);
-    if (KS == 1 && g.act == ACT_SWIGLU) {  // rows (gate_j, up_j) interleaved: the even wave finishes the pair
-        if (lane == 0) s_val[wave] = v;
-        __syncthreads();
-        if (lane != 0 || (wave & 1) || !live) return;
-        const float o = (v / (1.0f + __expf(-v))) * s_val[wave + 1];
-        const int64_t idx = row >> 1;
-        if (g.out_f32) static_cast<float*>(g.C)[idx] = o;
-        else static_cast<bf16_t*>(g.C)[idx] = f32_to_bf16(o);
-        return;
-    }
-    if (lane != 0 || !live) return;
-    v = act_apply(v, g.act);
-    if (g.residual) v += gemm_residual_f32_or_bf16(g, row);
-    if (g.out_f32) static_cast<float*>(g.C)[row] = v;
-    else static_cast<bf16_t*>(g.C)[row] = f32_to_bf16(v);
+    finish_row<RMS, KS == 1>(g, acc, row, live, lane, wave, s_red, s_val);  // (K halves: only the first wave of a row is left)
 }
 
 // ---- e4m3 WEIGHTS for the batch-1 decode linears (BASELINE.json configs[4]; opt-in variant) -----------------------------------
 // The decode step is HBM-bound on the weight bytes, so this is where fp8 pays most: half the bytes per token.  W is a byte
 // matrix [N, K] of OCP e4m3 values with ONE per-tensor scale (W ~ q * *scale_w: the tensor the fp8 prefill GEMM also uses); the
-// activation row stays fp32 in LDS and the products q x x are exact in fp32 (the only error is the weight quantisation).  Same
-// shape as gemv1_kernel: 1024-thread blocks, one row per wave, 16-byte non-temporal loads (16 weights each), fused RMSNorm
-// prologue, SwiGLU / residual epilogues.  Rows of K bytes: K % 16 == 0.
+// activation row stays fp32 in LDS and the products q x x are exact in fp32 (the only error is the weight quantisation).
+// 16-byte non-temporal loads (16 weights each).  Rows of K bytes: K % 16 == 0.
 typedef __attribute__((ext_vector_type(2))) float f32x2v_t;
 
 __device__ __forceinline__ float dot16_fp8(const u32x4_t& w, const f32x4v_t& a0, const f32x4v_t& a1, const f32x4v_t& b0,
@@ -399,26 +330,7 @@ __global__ __launch_bounds__(64 * kG1Waves, 8) void gemv1_fp8w_kernel(GemmArgs g
     u32x4_t w[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) w[u] = __builtin_nontemporal_load(wp + min(lane + 64 * u, nw16 - 1));
-    float ssq = 0.0f;
-    for (int c = threadIdx.x; c < nchunk; c += 64 * kG1Waves) {
-        const f32x4v_t* xp = reinterpret_cast<const f32x4v_t*>(g.A) + 2 * c;
-        f32x4v_t xa = xp[0], xb = xp[1];
-        if (RMS) {
-            const u32x4_t gv = *(reinterpret_cast<const u32x4_t*>(g.rms_w) + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ssq += xa[j] * xa[j] + xb[j] * xb[j];
-            xa[0] *= __uint_as_float(gv[0] << 16); xa[1] *= __uint_as_float(gv[0] & 0xffff0000u);
-            xa[2] *= __uint_as_float(gv[1] << 16); xa[3] *= __uint_as_float(gv[1] & 0xffff0000u);
-            xb[0] *= __uint_as_float(gv[2] << 16); xb[1] *= __uint_as_float(gv[2] & 0xffff0000u);
-            xb[2] *= __uint_as_float(gv[3] << 16); xb[3] *= __uint_as_float(gv[3] & 0xffff0000u);
-        }
-        xf[c] = xa;
-        xf[nchunk + c] = xb;
-    }
-    if (RMS) {
-        ssq = wave_sum(ssq);
-        if (lane == 0) s_red[wave] = ssq;
-    }
+    stage_row_f32<RMS, false>(g, xf, nchunk, 64 * kG1Waves, s_red, lane, wave);
     __syncthreads();
     float acc = 0.0f;
     for (int c = lane; c < nw16; c += 64 * U) {
@@ -434,28 +346,7 @@ __global__ __launch_bounds__(64 * kG1Waves, 8) void gemv1_fp8w_kernel(GemmArgs g
         }
     }
     acc = wave_sum(acc) * (*g.scale_w);
-    if (RMS) {
-        float q = 0.0f;
-#pragma unroll
-        for (int i = 0; i < kG1Waves; ++i) q += s_red[i];
-        acc *= rsqrtf(q / (float)g.K + g.rms_eps);
-    }
-    float v = acc + ((g.bias && live) ? bf16_to_f32(g.bias[row]) : 0.0f);
-    if (g.act == ACT_SWIGLU) {
-        if (lane == 0) s_val[wave] = v;
-        __syncthreads();
-        if (lane != 0 || (wave & 1) || !live) return;
-        const float o = (v / (1.0f + __expf(-v))) * s_val[wave + 1];
-        const int64_t idx = row >> 1;
-        if (g.out_f32) static_cast<float*>(g.C)[idx] = o;
-        else static_cast<bf16_t*>(g.C)[idx] = f32_to_bf16(o);
-        return;
-    }
-    if (lane != 0 || !live) return;
-    v = act_apply(v, g.act);
-    if (g.residual) v += gemm_residual_f32_or_bf16(g, row);
-    if (g.out_f32) static_cast<float*>(g.C)[row] = v;
-    else static_cast<bf16_t*>(g.C)[row] = f32_to_bf16(v);
+    finish_row<RMS>(g, acc, row, live, lane, wave, s_red, s_val);
 }
 
 int g_gemv1_ksplit = 0;  // 0 = rule below (A/B hook: ivlm_gemv1_tuning)
@@ -463,17 +354,11 @@ int g_gemv1_lds_floor = 0;  // dynamic LDS requested by grids of <= one block pe
 
 template <bool RMS, int KS>
 static void launch_gemv1_ks(const GemmArgs& g, hipStream_t st) {
-    static ivlm_dev_mask_t set{0};
-    auto kfn = gemv1_kernel<RMS, KS>;
-    if (ivlm_dev_pending(set)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        ivlm_dev_done(set);
-    }
     const int rows_per_block = kG1Waves / KS;
     const int blocks = (g.N + rows_per_block - 1) / rows_per_block;
     size_t lds = (size_t)g.K * 4;
     if (blocks <= 256 && (size_t)g_gemv1_lds_floor > lds) lds = (size_t)g_gemv1_lds_floor;
-    ivlm_launch(kfn, dim3(blocks), dim3(64 * kG1Waves), lds, st, g);
+    ivlm_launch_lds_cap<gemv1_kernel<RMS, KS>>(128 * 1024, dim3(blocks), dim3(64 * kG1Waves), lds, st, g);
 }
 
 static int launch_gemv1(const GemmArgs& g, hipStream_t st) {
@@ -580,18 +465,11 @@ static int launch_gemv(const GemmArgs& g, hipStream_t st) {
     const int slots = gemv_cu_count() * per_cu;
     const int gpw = std::max(1, (ngroups + 4 * slots - 1) / (4 * slots));  // row groups per wave
     const int blocks = (ngroups + 4 * gpw - 1) / (4 * gpw);
-#define IVLM_GEMV_GO(ROWS, RMS, XL, AF)                                                                               \
-    do {                                                                                                              \
-        auto kfn = gemv_kernel<M, ROWS, RMS, XL, AF>;                                                                 \
-        if (lds > 48 * 1024) {                                                                                        \
-            static ivlm_dev_mask_t set{0};                                                                            \
-            if (ivlm_dev_pending(set)) {                                                                              \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                          64 * 1024);                                                                 \
-                ivlm_dev_done(set);                                                                                   \
-            }                                                                                                         \
-        }                                                                                                             \
-        ivlm_launch(kfn, dim3(blocks), dim3(256), lds, st, g);                                                        \
+#define IVLM_GEMV_GO(ROWS, RMS, XL, AF)                                                                            \
+    do {                                                                                                           \
+        constexpr auto kfn = gemv_kernel<M, ROWS, RMS, XL, AF>;                                                    \
+        if (lds > 48 * 1024) ivlm_launch_lds_cap<kfn>(64 * 1024, dim3(blocks), dim3(256), lds, st, g);             \
+        else ivlm_launch(kfn, dim3(blocks), dim3(256), lds, st, g);                                                \
     } while (0)
 #define IVLM_GEMV_ROWS(ROWS)                                                                   \
     if (g.a_f32) {                                                                             \
@@ -631,22 +509,9 @@ int gemv1_fp8w(const GemmArgs& g, hipStream_t st) {
     if (!g.A || !g.W || !g.C || !g.scale_w || g.M != 1 || !g.a_f32 || g.N <= 0 || g.K <= 0) return IVLM_ERR_INVALID_ARG;
     if ((g.K & 15) || (g.ldw & 15) || (size_t)g.K * 4 > 60 * 1024) return IVLM_ERR_UNSUPPORTED;
     if (g.act == ACT_SWIGLU && ((g.N & 1) || g.residual)) return IVLM_ERR_UNSUPPORTED;
-    static ivlm_dev_mask_t set0{0}, set1{0};
-    if (g.rms_w) {
-        auto kfn = gemv1_fp8w_kernel<true>;
-        if (ivlm_dev_pending(set1)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            ivlm_dev_done(set1);
-        }
-        ivlm_launch(kfn, dim3((g.N + kG1Waves - 1) / kG1Waves), dim3(64 * kG1Waves), (size_t)g.K * 4, st, g);
-    } else {
-        auto kfn = gemv1_fp8w_kernel<false>;
-        if (ivlm_dev_pending(set0)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            ivlm_dev_done(set0);
-        }
-        ivlm_launch(kfn, dim3((g.N + kG1Waves - 1) / kG1Waves), dim3(64 * kG1Waves), (size_t)g.K * 4, st, g);
-    }
+    const dim3 grid((g.N + kG1Waves - 1) / kG1Waves), block(64 * kG1Waves);
+    if (g.rms_w) ivlm_launch_lds_cap<gemv1_fp8w_kernel<true>>(64 * 1024, grid, block, (size_t)g.K * 4, st, g);
+    else ivlm_launch_lds_cap<gemv1_fp8w_kernel<false>>(64 * 1024, grid, block, (size_t)g.K * 4, st, g);
     return ivlm_launch_status();
 }
 
@@ -672,22 +537,10 @@ extern "C" int ivlm_gemv_fp8w(const float* x, const void* Wq, int64_t ldw, const
                               const void* residual, int N, int K, int act, int out_f32, const void* rms_w, float rms_eps, int flags,
                               ivlm_stream_t stream) {
     ivlm_enter();
-    ivlm::GemmArgs g;
-    g.A = reinterpret_cast<const bf16_t*>(x);
-    g.a_f32 = 1;
+    ivlm::GemmArgs g = ivlm::gemv_row_args(x, C, bias, residual, N, K, act, out_f32, rms_w, rms_eps, flags);
     g.W = static_cast<const bf16_t*>(Wq);
     g.ldw = ldw;
     g.scale_w = scale_w;
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    g.M = 1; g.N = N; g.K = K;
-    g.lda = K;
-    g.act = act;
-    g.out_f32 = out_f32;
-    g.rms_w = static_cast<const bf16_t*>(rms_w);
-    g.rms_eps = rms_eps;
     return ivlm::gemv1_fp8w(g, ivlm_stream(stream));
 }
 

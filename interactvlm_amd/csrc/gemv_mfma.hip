@@ -19,31 +19,13 @@
 //   * AF32: fp32 activation rows (fp32 residual stream): each 8-element x fragment is split into a bf16 "hi" and a bf16 "lo"
 //     part (x = hi + lo to 2^-17) and meets the weight fragment in TWO MFMAs - the kernel is HBM-bound, the second MFMA is
 //     free, and the batched decode step then agrees with the batch-1 GEMV (exact fp32 products) to ~1e-5 relative.
-#include "gemm_common.h"
+// The tile finish and the tiles-per-block rule are those of gemv_common.h (shared with gemv_p12.hip).
+#include "gemv_common.h"
 
 namespace ivlm {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 constexpr int kWaves = 8, kThreads = kWaves * 64;
-
-__device__ __forceinline__ float act_apply(float x, int act) {
-    switch (act) {
-        case ACT_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-        case ACT_QUICK_GELU: return x / (1.0f + __expf(-1.702f * x));
-        case ACT_RELU: return x < 0.0f ? 0.0f : x;  // (torch.relu semantics: a NaN stays a NaN; fmaxf would turn it into 0)
-        case ACT_SILU: return x / (1.0f + __expf(-x));
-        case ACT_SIGMOID: return 1.0f / (1.0f + __expf(-x));
-        default: return x;
-    }
-}
-
-// fp32 pair -> packed bf16 (hardware RNE) and the packed bf16 of the remainders: x = hi + lo to 2^-17
-__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = pack_bf16x2(a, b);
-    const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
-    lo = pack_bf16x2(ra, rb);
-}
 
 // T = 16-row weight tiles per block.  Every block re-reads the M x K activation rows (L2 hits, but they share the CU's
 // load path with the weight stream: at M = 8 fp32 rows the activations of a one-tile block are as many bytes as its
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(kThreads, 2) void skinny_mfma_kernel(GemmArgs g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     uint32_t h, l;
-                    split_pair(f[2 * j], f[2 * j + 1], h, l);
+                    split_bf16x2(f[2 * j], f[2 * j + 1], h, l);
                     hi[j] = h;
                     lo[j] = l;
                 }
@@ -146,46 +128,9 @@ __global__ __launch_bounds__(kThreads, 2) void skinny_mfma_kernel(GemmArgs g) {
         ssq += __shfl_xor(ssq, 32);
         if (kg == 0) s_ssq[wave][r] = ssq;
     }
-    const int m = threadIdx.x >> 4, n = threadIdx.x & 15;
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int nt = n0 + 16 * t;
-        if (t > 0) __syncthreads();  // the previous tile's s_fin readers are done
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_part[wave][r][kg * 4 + i] = acc[t][i];
-        __syncthreads();
-        if (threadIdx.x < 256) {
-            float v = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) v += s_part[w][m][n];
-            if (RMS) {
-                float q = 0.0f;
-#pragma unroll
-                for (int w = 0; w < kWaves; ++w) q += s_ssq[w][m];
-                v *= rsqrtf(q / (float)g.K + g.rms_eps);
-            }
-            const int nn = min(nt + n, g.N - 1);
-            s_fin[m][n] = v + (g.bias ? bf16_to_f32(g.bias[nn]) : 0.0f);
-        }
-        __syncthreads();
-        if (threadIdx.x >= 256 || m >= g.M || nt + n >= g.N) continue;
-        float v = s_fin[m][n];
-        int64_t col = nt + n;
-        if (g.act == ACT_SWIGLU) {  // rows (gate_j, up_j) interleaved: even n pairs with n + 1
-            if (n & 1) continue;
-            const float up = s_fin[m][n + 1];
-            v = (v / (1.0f + __expf(-v))) * up;
-            col >>= 1;
-        } else {
-            v = act_apply(v, g.act);
-            if (g.residual) {
-                const int64_t rrow = g.res_mod > 0 ? (m % g.res_mod) : m;
-                v += gemm_residual_at(g, g.residual, rrow * g.ldr + col);
-            }
-        }
-        if (g.out_f32) static_cast<float*>(g.C)[(int64_t)m * g.ldc + col] = v;
-        else static_cast<bf16_t*>(g.C)[(int64_t)m * g.ldc + col] = f32_to_bf16(v);
-    }
+    for (int t = 0; t < T; ++t)
+        skinny_finish_tile<RMS, kWaves>(g, acc[t], n0 + 16 * t, t == 0, s_part, s_ssq, s_fin, [](float v, int, int) { return v; });
 }
 
 template <int T>
@@ -199,21 +144,7 @@ void skinny_launch(const GemmArgs& g, int blocks, hipStream_t st) {
     }
 }
 
-int g_skinny_tiles = 0;  // 0 = rule below; tools/bench_decode.py sweeps it
-
-// tiles per block: fewest (blocks per CU) x (tiles per block), then the most tiles (least activation re-reading)
-int skinny_tiles(int N) {
-    if (g_skinny_tiles >= 10) return N > 16384 ? g_skinny_tiles % 10 : (N > 8192 ? g_skinny_tiles / 10 : 1);  // sweep hook: 10 q + g
-    if (g_skinny_tiles > 0) return g_skinny_tiles;
-    const int tiles = (N + 15) / 16, cus = 256;
-    int best = 1, best_cost = 1 << 30;
-    for (int t : {1, 2, 3}) {  // (4 and 6 tiles per block measured slower: gate|up 230 blocks of 6 tiles 4.56 ms per step, 459 of 3: 4.44)
-        const int blocks = (tiles + t - 1) / t;
-        const int cost = ((blocks + cus - 1) / cus) * t;
-        if (cost <= best_cost) { best = t; best_cost = cost; }
-    }
-    return best;
-}
+int g_skinny_tiles = 0;  // 0 = skinny_tiles(); tools/bench_decode.py sweeps it (sweep encoding: see gemv_mfma_bf16)
 
 }  // namespace
 
@@ -221,7 +152,8 @@ int gemv_mfma_bf16(const GemmArgs& g, hipStream_t st) {
     if (!g.A || !g.W || !g.C || g.M <= 0 || g.M > 16 || g.N <= 0 || g.K <= 0) return IVLM_ERR_INVALID_ARG;
     if ((g.K & 7) || (g.lda & (g.a_f32 ? 3 : 7)) || (g.ldw & 7) || g.batch != 1) return IVLM_ERR_UNSUPPORTED;
     if (g.act == ACT_SWIGLU && ((g.N & 1) || g.residual)) return IVLM_ERR_UNSUPPORTED;
-    const int T = skinny_tiles(g.N);
+    const int gt = g_skinny_tiles;
+    const int T = gt >= 10 ? (g.N > 16384 ? gt % 10 : (g.N > 8192 ? gt / 10 : 1)) : skinny_tiles(g.N, gt);  // (sweep hook: 10 q + g)
     const int blocks = (g.N + 16 * T - 1) / (16 * T);
     switch (T) {
         case 1: skinny_launch<1>(g, blocks, st); break;

@@ -13,27 +13,18 @@
 // operations (byte permute, mask, bit-field extract, shift-add; code 0 gives exactly 0.0), multiplies it with x * 2^64 (x is staged
 // once per block in LDS, pre-scaled by an exact power of two so that the tiny products stay normal fp32 numbers) and the row sum is
 // scaled back by 2^(ebase - 100) - exact power-of-two scalings, so the arithmetic is that of gemv1_kernel (bf16 weight x fp32
-// activation products, exact; fp32 accumulation) up to the summation order.  Same shape as gemv1_kernel: 1024-thread blocks, one row
-// per wave, non-temporal loads (16 B of P + 8 B of E per lane and step = 16 weights), fused RMSNorm prologue, SwiGLU / residual
-// epilogues.
+// activation products, exact; fp32 accumulation) up to the summation order.  Non-temporal loads: 16 B of P + 8 B of E per lane and step
+// = 16 weights.  Prologues, finishes and the activation switch are those of gemv_common.h.
 #include <algorithm>
 
-#include "kernels.h"
+#include "gemv_common.h"
 
 namespace ivlm {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4v_t;
 
-constexpr int kWaves = 16;
-// x is staged as x * 2^64: an exact power-of-two scaling, chosen in the MIDDLE of fp32's exponent range (2^100 turned any
-// |x| >= 2^28 ~ 2.7e8 into inf and the row into NaN, a range gemv1_kernel's plain fp32 x does not have).  A rebuilt weight is
-// 1.m x 2^(code - 127) with code 1 .. 15, i.e. 2^-126 .. 2^-111, so the products x * 2^64 * w are normal fp32 numbers for
-// 2^-64 <~ |x| < 2^64 (5e-20 .. 1.8e19) and every result inside that range is independent of the scale (the hi / lo / lo2 split and
-// the fp32 accumulation are scale-invariant): bit-identical to the 2^100 staging on every activation the model produces.
-constexpr int kXScaleExp = 64;
+constexpr int kWaves = kRowWaves;
 
 struct P12 {
     const uint8_t* P;   // [N][ldp]
@@ -65,17 +56,6 @@ __device__ __forceinline__ float dot4_p12(uint32_t pw, uint32_t e16, const f32x4
     return acc;
 }
 
-__device__ __forceinline__ float act1(float x, int act) {
-    switch (act) {
-        case ACT_GELU: return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-        case ACT_QUICK_GELU: return x / (1.0f + __expf(-1.702f * x));
-        case ACT_RELU: return x < 0.0f ? 0.0f : x;  // (torch.relu semantics: a NaN stays a NaN; fmaxf would turn it into 0)
-        case ACT_SILU: return x / (1.0f + __expf(-x));
-        case ACT_SIGMOID: return 1.0f / (1.0f + __expf(-x));
-        default: return x;
-    }
-}
-
 template <bool RMS>
 __global__ __launch_bounds__(64 * kWaves, 8) void gemv1_p12_kernel(GemmArgs g, P12 p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -101,28 +81,7 @@ __global__ __launch_bounds__(64 * kWaves, 8) void gemv1_p12_kernel(GemmArgs g, P
     }
     const int eb = p.ebase[rr];
     const int p0 = p.patch_ptr[rr], p1 = p.patch_ptr[rr + 1];
-    // ---- stage x * 2^64 (x * gamma * 2^64) in LDS, sum(x^2) of the unscaled row ----
-    const float xs = __builtin_ldexpf(1.0f, kXScaleExp);
-    float ssq = 0.0f;
-    for (int c = threadIdx.x; c < nchunk; c += 64 * kWaves) {
-        const f32x4v_t* xp = reinterpret_cast<const f32x4v_t*>(g.A) + 2 * c;
-        f32x4v_t xa = xp[0], xb = xp[1];
-        if (RMS) {
-            const u32x4_t gv = *(reinterpret_cast<const u32x4_t*>(g.rms_w) + c);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ssq += xa[j] * xa[j] + xb[j] * xb[j];
-            xa[0] *= __uint_as_float(gv[0] << 16); xa[1] *= __uint_as_float(gv[0] & 0xffff0000u);
-            xa[2] *= __uint_as_float(gv[1] << 16); xa[3] *= __uint_as_float(gv[1] & 0xffff0000u);
-            xb[0] *= __uint_as_float(gv[2] << 16); xb[1] *= __uint_as_float(gv[2] & 0xffff0000u);
-            xb[2] *= __uint_as_float(gv[3] << 16); xb[3] *= __uint_as_float(gv[3] & 0xffff0000u);
-        }
-        xf[c] = xa * xs;
-        xf[nchunk + c] = xb * xs;
-    }
-    if (RMS) {
-        ssq = wave_sum(ssq);
-        if (lane == 0) s_red[wave] = ssq;
-    }
+    stage_row_f32<RMS, true>(g, xf, nchunk, 64 * kWaves, s_red, lane, wave);  // x * 2^64 (x * gamma * 2^64); sum(x^2) of the unscaled row
     __syncthreads();
     float acc = 0.0f;
     for (int c = lane; c < nw16; c += 64 * U) {
@@ -154,28 +113,7 @@ __global__ __launch_bounds__(64 * kWaves, 8) void gemv1_p12_kernel(GemmArgs g, P
         pacc = fmaf(bf16_to_f32(p.patch_val[i]), xv, pacc);
     }
     acc = __builtin_ldexpf(wave_sum(acc), eb - kXScaleExp) + __builtin_ldexpf(wave_sum(pacc), -kXScaleExp);
-    if (RMS) {
-        float q = 0.0f;
-#pragma unroll
-        for (int i = 0; i < kWaves; ++i) q += s_red[i];
-        acc *= rsqrtf(q / (float)g.K + g.rms_eps);
-    }
-    float v = acc + ((g.bias && live) ? bf16_to_f32(g.bias[row]) : 0.0f);
-    if (g.act == ACT_SWIGLU) {  // rows (gate_j, up_j) interleaved: the even wave finishes the pair
-        if (lane == 0) s_val[wave] = v;
-        __syncthreads();
-        if (lane != 0 || (wave & 1) || !live) return;
-        const float o = (v / (1.0f + __expf(-v))) * s_val[wave + 1];
-        const int64_t idx = row >> 1;
-        if (g.out_f32) static_cast<float*>(g.C)[idx] = o;
-        else static_cast<bf16_t*>(g.C)[idx] = f32_to_bf16(o);
-        return;
-    }
-    if (lane != 0 || !live) return;
-    v = act1(v, g.act);
-    if (g.residual) v += g.res_f32 ? reinterpret_cast<const float*>(g.residual)[row] : bf16_to_f32(g.residual[row]);
-    if (g.out_f32) static_cast<float*>(g.C)[row] = v;
-    else static_cast<bf16_t*>(g.C)[row] = f32_to_bf16(v);
+    finish_row<RMS>(g, acc, row, live, lane, wave, s_red, s_val);
 }
 
 // =====================================================================================================================================
@@ -531,29 +469,20 @@ __global__ __launch_bounds__(64 * kWavesM, kWavesM == 16 ? 4 : 6) void gemv1_p12
     if (g.act == ACT_SWIGLU) {  // rows (gate_j, up_j) interleaved: the even lane finishes the pair
         const float up = __shfl_down(v, 1, 64);
         if (lane & 1) return;
-        const float o = (v / (1.0f + __expf(-v))) * up;
-        const int64_t idx = row >> 1;
-        if (g.out_f32) static_cast<float*>(g.C)[idx] = o;
-        else static_cast<bf16_t*>(g.C)[idx] = f32_to_bf16(o);
+        gemv_store(g, row >> 1, (v / (1.0f + __expf(-v))) * up);
         return;
     }
-    v = act1(v, g.act) + __uint_as_float(g.res_f32 ? res_raw : res_raw << 16);
-    if (g.out_f32) static_cast<float*>(g.C)[row] = v;
-    else static_cast<bf16_t*>(g.C)[row] = f32_to_bf16(v);
+    gemv_store(g, row, gemv_act(v, g.act) + __uint_as_float(g.res_f32 ? res_raw : res_raw << 16));
 }
 
 // =====================================================================================================================================
 // M <= 16 activation rows (the batched decode step, BASELINE configs[2]: one token of each of B sequences) on the same packed weights:
-// the structure of skinny_mfma_kernel (gemv_mfma.hip) - block = T tiles of 16 weight rows x 8 waves over K, activation fragments loaded
-// straight from L2 (fp32 rows, split into hi + lo bf16 operands in registers: x = hi + lo to 2^-17, two MFMAs per weight fragment), the 8
-// partial 16 x 16 tiles summed through LDS in wave order - with the weight fragments rebuilt from the fragment-layout planes (1 KB
-// contiguous per wave instruction instead of 16 rows x 64 B, 0.75 x the bytes; two VALU operations per weight, shared by all M rows).
+// the structure of skinny_mfma_kernel (gemv_mfma.hip), sharing its tile finish (gemv_common.h) - block = T tiles of 16 weight rows x 8
+// waves over K, activation fragments loaded straight from L2 (fp32 rows, split into hi + lo bf16 operands in registers: x = hi + lo to
+// 2^-17, two MFMAs per weight fragment), the 8 partial 16 x 16 tiles summed through LDS in wave order - with the weight fragments rebuilt
+// from the fragment-layout planes (1 KB contiguous per wave instruction instead of 16 rows x 64 B, 0.75 x the bytes; two VALU operations
+// per weight, shared by all M rows).
 // A operand = the 16 weight rows, B operand = the activation rows: lane holds C[weight row 4 kg + i][activation row r].
-__device__ __forceinline__ void split_pair_p12(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = pack_bf16x2(a, b);
-    lo = pack_bf16x2(a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u));
-}
-
 template <bool RMS, int T>
 __global__ __launch_bounds__(512, 2) void skinny_p12m_kernel(GemmArgs g, P12M p) {
     constexpr int kW = 8, U = 2;  // waves per block; step pairs in flight per lane (4 MFMA k-steps)
@@ -625,7 +554,7 @@ __global__ __launch_bounds__(512, 2) void skinny_p12m_kernel(GemmArgs g, P12M p)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     uint32_t h2, l2;
-                    split_pair_p12(f[2 * j] * xs, f[2 * j + 1] * xs, h2, l2);
+                    split_bf16x2(f[2 * j] * xs, f[2 * j + 1] * xs, h2, l2);
                     hi[j] = h2;
                     lo[j] = l2;
                 }
@@ -644,56 +573,24 @@ __global__ __launch_bounds__(512, 2) void skinny_p12m_kernel(GemmArgs g, P12M p)
         ssq += __shfl_xor(ssq, 32);
         if (kg == 0) s_ssq[wave][r] = ssq;
     }
-    const int m = threadIdx.x >> 4, n = threadIdx.x & 15;
     const float* xg = reinterpret_cast<const float*>(g.A);
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int nt = ((int)blockIdx.x * T + t) * 16;
-        if (t > 0) __syncthreads();  // the previous tile's s_fin readers are done
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s_part[wave][r][kg * 4 + i] = acc[t][i];
-        __syncthreads();
-        if (threadIdx.x < 256 && nt < g.N) {
-            float v = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kW; ++w) v += s_part[w][m][n];
-            const int nn = nt + n;  // (N % 16 == 0)
-            v = __builtin_ldexpf(v, p.ebase[nn] - kXScaleExp);
-            if (m < g.M) {  // the nonzero weights outside the row's exponent window: exact bf16 values x fp32 activations
-                for (int i = p.patch_ptr[nn]; i < p.patch_ptr[nn + 1]; ++i) {
-                    const int col = p.patch_col[i];
-                    float xv = xg[(int64_t)m * g.lda + col];
-                    if (RMS) xv *= bf16_to_f32(g.rms_w[col]);
-                    v = fmaf(bf16_to_f32(p.patch_val[i]), xv, v);
-                }
-            }
-            if (RMS) {
-                float q = 0.0f;
-#pragma unroll
-                for (int w = 0; w < kW; ++w) q += s_ssq[w][m];
-                v *= rsqrtf(q / (float)K + g.rms_eps);
-            }
-            s_fin[m][n] = v + (g.bias ? bf16_to_f32(g.bias[nn]) : 0.0f);
-        }
-        __syncthreads();
-        if (threadIdx.x >= 256 || m >= g.M || nt >= g.N) continue;
-        float v = s_fin[m][n];
-        int64_t col = nt + n;
-        if (g.act == ACT_SWIGLU) {  // rows (gate_j, up_j) interleaved: even n pairs with n + 1
-            if (n & 1) continue;
-            const float up = s_fin[m][n + 1];
-            v = (v / (1.0f + __expf(-v))) * up;
-            col >>= 1;
-        } else {
-            v = act1(v, g.act);
-            if (g.residual) {
-                const int64_t idx = (int64_t)m * g.ldr + col;
-                v += g.res_f32 ? reinterpret_cast<const float*>(g.residual)[idx] : bf16_to_f32(g.residual[idx]);
+    // the sum of a tile entry comes back by 2^(ebase - 64), then the row's nonzero weights outside its exponent window: exact bf16 values
+    // x fp32 activations
+    auto fix = [&](float v, int m, int nn) {
+        v = __builtin_ldexpf(v, p.ebase[nn] - kXScaleExp);
+        if (m < g.M) {
+            for (int i = p.patch_ptr[nn]; i < p.patch_ptr[nn + 1]; ++i) {
+                const int col = p.patch_col[i];
+                float xv = xg[(int64_t)m * g.lda + col];
+                if (RMS) xv *= bf16_to_f32(g.rms_w[col]);
+                v = fmaf(bf16_to_f32(p.patch_val[i]), xv, v);
             }
         }
-        if (g.out_f32) static_cast<float*>(g.C)[(int64_t)m * g.ldc + col] = v;
-        else static_cast<bf16_t*>(g.C)[(int64_t)m * g.ldc + col] = f32_to_bf16(v);
-    }
+        return v;
+    };
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        skinny_finish_tile<RMS, kW>(g, acc[t], ((int)blockIdx.x * T + t) * 16, t == 0, s_part, s_ssq, s_fin, fix);  // (N % 16 == 0)
 }
 
 // exact reconstruction of the bf16 matrix (the losslessness check of the tests; not on the path): one thread per weight
@@ -730,39 +627,13 @@ extern "C" int ivlm_gemv1_bf12(const float* x, const void* P, int64_t ldp, const
     if (!x || !C || !p12_ok(P, ldp, E, lde, ebase, patch_ptr, patch_col, patch_val, N, K)) return IVLM_ERR_INVALID_ARG;
     if ((size_t)K * 4 > 60 * 1024) return IVLM_ERR_UNSUPPORTED;  // the fp32 x image lives in LDS
     if (act == ACT_SWIGLU && ((N & 1) || residual)) return IVLM_ERR_UNSUPPORTED;
-    GemmArgs g;
-    g.A = reinterpret_cast<const bf16_t*>(x);
-    g.a_f32 = 1;
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    g.M = 1; g.N = N; g.K = K;
-    g.lda = K;
-    g.act = act;
-    g.out_f32 = out_f32;
-    g.rms_w = static_cast<const bf16_t*>(rms_w);
-    g.rms_eps = rms_eps;
+    const GemmArgs g = gemv_row_args(x, C, bias, residual, N, K, act, out_f32, rms_w, rms_eps, flags);
     P12 p{static_cast<const uint8_t*>(P), static_cast<const uint8_t*>(E), ldp, lde, ebase, patch_ptr, patch_col,
           static_cast<const bf16_t*>(patch_val)};
     hipStream_t st = ivlm_stream(stream);
-    static ivlm_dev_mask_t set0{0}, set1{0};
     const dim3 grid((N + kWaves - 1) / kWaves), block(64 * kWaves);
-    if (rms_w) {
-        auto kfn = gemv1_p12_kernel<true>;
-        if (ivlm_dev_pending(set1)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            ivlm_dev_done(set1);
-        }
-        ivlm_launch(kfn, grid, block, (size_t)K * 4, st, g, p);
-    } else {
-        auto kfn = gemv1_p12_kernel<false>;
-        if (ivlm_dev_pending(set0)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            ivlm_dev_done(set0);
-        }
-        ivlm_launch(kfn, grid, block, (size_t)K * 4, st, g, p);
-    }
+    if (rms_w) ivlm_launch_lds_cap<gemv1_p12_kernel<true>>(64 * 1024, grid, block, (size_t)K * 4, st, g, p);
+    else ivlm_launch_lds_cap<gemv1_p12_kernel<false>>(64 * 1024, grid, block, (size_t)K * 4, st, g, p);
     return ivlm_launch_status();
 }
 
@@ -779,13 +650,19 @@ extern "C" int ivlm_unpack_bf12(const void* P, int64_t ldp, const void* E, int64
     return ivlm_launch_status();
 }
 
-int g_skinny_p12m_tiles = 0;       // 0 = rule in ivlm_gemv16_bf12m (A/B hook: ivlm_gemv16_bf12m_tuning)
+int g_skinny_p12m_tiles = 0;       // 0 = skinny_tiles() (A/B hook: ivlm_gemv16_bf12m_tuning)
 int g_p12m_wide_max_blocks = 256;  // A/B hooks: ivlm_gemv1_bf12m_tuning
 int g_p12m_deep = 1;
 int g_p12m_staging = 1;  // 1 = per-wave activation staging in the forms that gain, 0 = block-cooperative everywhere (A/B hook:
                          // ivlm_gemv1_bf12m_staging)
 namespace ivlm {
 int g_decode_parts_S = 4;  // key ranges per head of the split-KV attention / o_proj pair (A/B hook: ivlm_decode_parts_tuning; 2 or 4)
+}
+
+template <bool RMS, int kWavesM, int U, bool PARTS, bool WSTG>
+static void launch_p12m(const GemmArgs& g, const P12M& p, hipStream_t st) {
+    constexpr auto kfn = gemv1_p12m_kernel<RMS, kWavesM, U, PARTS, WSTG>;
+    ivlm_launch_lds_cap<kfn>(100 * 1024, dim3(g.N / 16), dim3(64 * kWavesM), (size_t)g.K * 6, st, g, p);
 }
 
 // MFMA variant on the fragment layout (see gemv1_p12m_kernel): Pf / Ef = the P / E bytes of ivlm_gemv1_bf12 re-ordered as
@@ -803,54 +680,34 @@ static int gemv1_bf12m(const float* x, const float* parts, int pD, const void* P
     if (parts && (pD <= 0 || (pD & 3) || K % pD != 0 || rms_w)) return IVLM_ERR_INVALID_ARG;
     if ((N & 15) || (K & 63) || (size_t)K * 6 > 100 * 1024) return IVLM_ERR_UNSUPPORTED;
     if (act == ACT_SWIGLU && residual) return IVLM_ERR_UNSUPPORTED;
-    GemmArgs g;
-    g.A = reinterpret_cast<const bf16_t*>(x);
-    g.a_f32 = 1;
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    g.M = 1; g.N = N; g.K = K;
-    g.lda = K;
-    g.act = act;
-    g.out_f32 = out_f32;
-    g.rms_w = static_cast<const bf16_t*>(rms_w);
-    g.rms_eps = rms_eps;
+    const GemmArgs g = gemv_row_args(x, C, bias, residual, N, K, act, out_f32, rms_w, rms_eps, flags);
     P12M p{static_cast<const u32x4_t*>(Pf), static_cast<const u32x2_t*>(Ef), ebase, patch_ptr, patch_col,
            static_cast<const bf16_t*>(patch_val), parts, pD, g_decode_parts_S};
     hipStream_t st = ivlm_stream(stream);
     const dim3 grid(N / 16);
     const bool wide = grid.x <= (unsigned)g_p12m_wide_max_blocks;  // at most one block per CU: 16 waves per block
-    auto go = [&](auto kfn, int waves, ivlm_dev_mask_t& set) {
-        if (ivlm_dev_pending(set)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-            ivlm_dev_done(set);
-        }
-        ivlm_launch(kfn, grid, dim3(64 * waves), (size_t)K * 6, st, g, p);
-    };
-    static ivlm_dev_mask_t set[11];  // (zero-initialised; one mask per instantiation, one bit per device)
     // per-wave staging where it was measured faster: one 16-wave block per CU and no RMSNorm prologue (o_proj, down_proj)
     const bool wstg = g_p12m_staging && wide && !rms_w;
     if (parts) {  // (the o_proj of a decode step: K = hidden, never the 8-deep form)
-        if (wstg) go(gemv1_p12m_kernel<false, 16, 4, true, true>, 16, set[8]);
-        else if (wide) go(gemv1_p12m_kernel<false, 16, 4, true, false>, 16, set[6]);
-        else go(gemv1_p12m_kernel<false, 8, 4, true, false>, 8, set[7]);
+        if (wstg) launch_p12m<false, 16, 4, true, true>(g, p, st);
+        else if (wide) launch_p12m<false, 16, 4, true, false>(g, p, st);
+        else launch_p12m<false, 8, 4, true, false>(g, p, st);
         return ivlm_launch_status();
     }
     // (one block per CU and a long row - down_proj: 8 step pairs in flight per lane, so that most of the block's 264 KB is requested
     //  up front)
     const bool deep = wide && (K >> 6) > 4 * 16 && g_p12m_deep;
     if (rms_w) {
-        if (deep) go(gemv1_p12m_kernel<true, 16, 8, false, false>, 16, set[4]);
-        else if (wide) go(gemv1_p12m_kernel<true, 16, 4, false, false>, 16, set[0]);
-        else go(gemv1_p12m_kernel<true, 8, 4, false, false>, 8, set[1]);
+        if (deep) launch_p12m<true, 16, 8, false, false>(g, p, st);
+        else if (wide) launch_p12m<true, 16, 4, false, false>(g, p, st);
+        else launch_p12m<true, 8, 4, false, false>(g, p, st);
     } else if (wstg) {
-        if (deep) go(gemv1_p12m_kernel<false, 16, 8, false, true>, 16, set[9]);
-        else go(gemv1_p12m_kernel<false, 16, 4, false, true>, 16, set[10]);
+        if (deep) launch_p12m<false, 16, 8, false, true>(g, p, st);
+        else launch_p12m<false, 16, 4, false, true>(g, p, st);
     } else {
-        if (deep) go(gemv1_p12m_kernel<false, 16, 8, false, false>, 16, set[5]);
-        else if (wide) go(gemv1_p12m_kernel<false, 16, 4, false, false>, 16, set[2]);
-        else go(gemv1_p12m_kernel<false, 8, 4, false, false>, 8, set[3]);
+        if (deep) launch_p12m<false, 16, 8, false, false>(g, p, st);
+        else if (wide) launch_p12m<false, 16, 4, false, false>(g, p, st);
+        else launch_p12m<false, 8, 4, false, false>(g, p, st);
     }
     return ivlm_launch_status();
 }
@@ -906,31 +763,13 @@ extern "C" int ivlm_gemv16_bf12m(const float* x, int64_t lda, int M, const void*
     if (act == ACT_SWIGLU && residual) return IVLM_ERR_UNSUPPORTED;
     //  the row strides of the output and of the residual must hold a whole row
     if (ldc < (act == ACT_SWIGLU ? N / 2 : N) || (residual && ldr < N)) return IVLM_ERR_INVALID_ARG;
-    GemmArgs g;
-    g.A = reinterpret_cast<const bf16_t*>(x);
-    g.a_f32 = 1;
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    g.M = M; g.N = N; g.K = K;
+    GemmArgs g = gemv_row_args(x, C, bias, residual, N, K, act, out_f32, rms_w, rms_eps, flags);
+    g.M = M;
     g.lda = lda; g.ldc = ldc; g.ldr = ldr;
-    g.act = act;
-    g.out_f32 = out_f32;
-    g.rms_w = static_cast<const bf16_t*>(rms_w);
-    g.rms_eps = rms_eps;
     P12M p{static_cast<const u32x4_t*>(Pf), static_cast<const u32x2_t*>(Ef), ebase, patch_ptr, patch_col,
            static_cast<const bf16_t*>(patch_val), nullptr, 0, 0};
     hipStream_t st = ivlm_stream(stream);
-    const int tiles = N / 16;
-    int T = g_skinny_p12m_tiles;
-    if (T <= 0) {  // fewest (blocks per CU) x (tiles per block), then the most tiles (least activation re-reading): as skinny_tiles()
-        int best_cost = 1 << 30;
-        for (int t : {1, 2, 3}) {
-            const int blocks = (tiles + t - 1) / t, cost = ((blocks + 255) / 256) * t;
-            if (cost <= best_cost) { T = t; best_cost = cost; }
-        }
-    }
+    const int tiles = N / 16, T = skinny_tiles(N, g_skinny_p12m_tiles);
     const dim3 grid((tiles + T - 1) / T), block(512);
     if (rms_w) {
         if (T == 1) ivlm_launch(skinny_p12m_kernel<true, 1>, grid, block, 0, st, g, p);

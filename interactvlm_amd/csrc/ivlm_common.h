@@ -72,6 +72,18 @@ static inline void ivlm_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipS
     else hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds, st, args...);
 }
 
+// ... of a kernel that asks for more dynamic LDS than the 48 KB every kernel may have: raises KFN's cap to `cap` bytes on the first
+// launch on each device.  The mask is a static of this function's instantiation, i.e. one per kernel instantiation.
+template <auto KFN, typename... A>
+static inline void ivlm_launch_lds_cap(int cap, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    static ivlm_dev_mask_t set{0};
+    if (ivlm_dev_pending(set)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KFN), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+        ivlm_dev_done(set);
+    }
+    ivlm_launch(KFN, grid, block, lds, st, args...);
+}
+
 // ---- bf16 <-> f32 (round-to-nearest-even), raw 16-bit storage -------------------------------
 typedef uint16_t bf16_t;
 
