@@ -897,6 +897,60 @@ int ivlm_contact_nearest(const float *q, const float *t, int D, int B, int N_o, 
 int ivlm_contact_normal_filter(const float *obj_normals, const float *human_normals, int N_o, int N_h, float c_pos, float c_neg,
                                int has_neg, uint8_t *keep_out, ivlm_stream_t stream);
 
+/* Differentiable soft silhouette of a posed mesh (silhouette.hip; what the reference's joint fitting stage renders with pytorch3d's
+ * SoftSilhouetteShader for its mask and centroid terms), without a [H W, F] array.
+ *   u = fx X / Z + px, v = fy Y / Z + py; pixel (row i, col j) has its centre at (j + 0.5, i + 0.5); kappa = (2 / min(H, W))^2
+ *   d_k = smallest squared distance in pixels^2 from the pixel centre to the three edge segments of face k (t = clamp(dot(b - a,
+ *   p - a) / |b - a|^2, 0, 1); an edge with |b - a|^2 <= 1e-8 uses |p - b|^2); the face counts at the pixel if the pixel is strictly
+ *   inside it or kappa d_k < blur_radius; s_k = -kappa d_k inside, +kappa d_k outside; p_k = sigmoid(-s_k / sigma);
+ *   alpha = 1 - prod_k (1 - p_k) over every counted face (no K-nearest cap).  A face whose screen area is zero, or that has a vertex
+ *   with Z <= 1e-6 or an index outside [0, N), is skipped whole.  d alpha / d s_k = -(1 - alpha) p_k / sigma; nothing flows through t.
+ * forward: verts f32 [B,N,3], faces i32 [F,3] (shared by the batch) -> alpha_out f32 [B,H,W]; the workspace keeps 1 - alpha, the
+ *   projected faces and their pixel boxes for the backward.
+ * backward: the SAME verts, sizes, camera, sigma, blur_radius and workspace as the forward call it follows; grad_alpha f32 [B,H,W];
+ *   vert_face_offsets i32 [N+1] and vert_face_list i32 [3F]: per vertex the slots (face * 3 + corner) of its incident faces in
+ *   ascending order (CSR; built once per topology by the caller) -> grad_verts_out f32 [B,N,3] = dL/d(X, Y, Z).
+ * No floating-point atomics, every sum in a fixed order, no host read: the same bits every call, for a pose whatever the batch around
+ * it, and under graph replay.  1 - alpha is 1 / D with D = prod (1 + e^(-s_k / sigma)) in fp32, one rounding per face, D clamped at
+ * 1e30.  The backward adds at most IVLM_SILHOUETTE_CHAIN fp32 terms per lane before fp64 takes over.  Documented errors, in units of
+ * 2^-24, with M = the largest of H, W, |u|, |v|, |u - px|, |v - py| over the face's vertices:
+ *   |delta sqrt(d_k)| <= IVLM_SILHOUETTE_POS_ULPS M  (projection 2 sqrt 2, the differences p - a, b - a and the residual 6 sqrt 2)
+ *   plus a relative IVLM_SILHOUETTE_REL_ULPS on d_k  (the dot 2, kappa / sigma 1, log2 e 1, its product 1, slack 1)
+ *   plus an absolute IVLM_SILHOUETTE_EXP_ULPS on the exponent argument s_k / sigma  (v_exp_f32 1 ulp = 2, the product's fma 1)
+ *   |delta t| <= IVLM_SILHOUETTE_T_ULPS |p - a| / |b - a|  (the backward only: t enters d at second order)
+ * B <= 65535, N, F <= 2^22, H, W <= 16384, sigma > 0, blur_radius >= 0, all finite, else IVLM_ERR_UNSUPPORTED before any launch.
+ * workspace: ivlm_soft_silhouette_workspace_bytes(B, N, F, H, W) bytes (0 for sizes that are not supported), 16-byte aligned;
+ * B (4 H W + 72 F + 8 N) bytes and padding: O(B (H W + F + N)). */
+#define IVLM_SILHOUETTE_CHAIN 32
+#define IVLM_SILHOUETTE_POS_ULPS 12
+#define IVLM_SILHOUETTE_REL_ULPS 6
+#define IVLM_SILHOUETTE_EXP_ULPS 3
+#define IVLM_SILHOUETTE_T_ULPS 8
+size_t ivlm_soft_silhouette_workspace_bytes(int B, int N, int F, int H, int W);
+int ivlm_soft_silhouette_forward(const float *verts, const int32_t *faces, int B, int N, int F, int H, int W, float fx, float fy,
+                                 float px, float py, float sigma, float blur_radius, float *alpha_out, void *workspace,
+                                 size_t workspace_bytes, ivlm_stream_t stream);
+int ivlm_soft_silhouette_backward(const float *verts, const int32_t *vert_face_offsets, const int32_t *vert_face_list,
+                                  const float *grad_alpha, int B, int N, int F, int H, int W, float fx, float fy, float px, float py,
+                                  float sigma, float blur_radius, float *grad_verts_out, void *workspace, size_t workspace_bytes,
+                                  ivlm_stream_t stream);
+
+/* The image losses of the fitting stage as one reduction (silhouette.hip): alpha f32 [B,H,W], target f32 [B or 1,H,W]
+ * (target_batch_stride = elements between poses, 0 = one mask shared by the batch) -> sums f64 [B,5] = (sum alpha, sum alpha t,
+ * sum t, sum i alpha, sum j alpha), loss_out f32 [B] = 1 - sum(alpha t) / (sum alpha + sum t) (the reference's "union" is the sum of
+ * both images; 1 when that sum is 0), centroid_out f32 [B,2] = (sum i alpha, sum j alpha) / sum alpha in (row, col) index units, the
+ * image centre (H / 2, W / 2) when sum alpha == 0.  Every element is converted to fp64 before it is added (fixed order): the longest
+ * fp32 chain is IVLM_SILHOUETTE_TERMS_CHAIN.  With grad_alpha_out != NULL the call is the backward instead: it reads target, sums (of
+ * the forward call), g_loss f32 [B] and g_centroid f32 [B,2] and writes grad_alpha_out f32 [B,H,W] = g_loss d loss / d alpha +
+ * g_centroid . d centroid / d alpha (the centroid's part is 0 when sum alpha == 0); alpha, loss_out, centroid_out and workspace are
+ * not read.  B <= 65535, H, W <= 16384, else IVLM_ERR_UNSUPPORTED.  workspace (forward): IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H)
+ * bytes, 8-byte aligned. */
+#define IVLM_SILHOUETTE_TERMS_CHAIN 1
+#define IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H) ((size_t)(B) * (size_t)(H) * 40)
+int ivlm_silhouette_terms(const float *alpha, const float *target, int64_t target_batch_stride, int B, int H, int W, float *loss_out,
+                          float *centroid_out, double *sums, const float *g_loss, const float *g_centroid, float *grad_alpha_out,
+                          void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

@@ -4,7 +4,7 @@
     d_ij = |o_i - h_j|,  S = (sum p)(sum q),  L = sum_ij p_i q_j d_ij / S
 
 No [N_o, N_h] array exists anywhere; vertices of probability 0 cost nothing and change no bit of the result.  The rest of
-``optim/`` (silhouette renderers, ICP) is not built.  There is no CPU fallback.
+the fit: ``contact_icp`` (the start), ``silhouette`` (mask and centroid terms), ``fit`` (the loop).  There is no CPU fallback.
 """
 from __future__ import annotations
 

@@ -178,6 +178,17 @@ int contact_pair(const float* o, const float* h, const void* p, const void* q, i
                  int64_t o_bstride, int64_t h_bstride, float* value, float* grad_o, float* grad_h, void* ws, size_t ws_bytes,
                  hipStream_t st);
 
+// ---- differentiable soft silhouette and its image losses (silhouette.hip) ------------------------------
+size_t soft_silhouette_workspace_bytes(int B, int N, int F, int H, int W);
+int soft_silhouette_forward(const float* verts, const int32_t* faces, int B, int N, int F, int H, int W, float fx, float fy, float px,
+                            float py, float sigma, float blur, float* alpha, void* ws, size_t ws_bytes, hipStream_t st);
+int soft_silhouette_backward(const float* verts, const int32_t* vf_off, const int32_t* vf_list, const float* galpha, int B, int N, int F,
+                             int H, int W, float fx, float fy, float px, float py, float sigma, float blur, float* gverts, void* ws,
+                             size_t ws_bytes, hipStream_t st);
+int silhouette_terms(const float* alpha, const float* target, int64_t t_bstride, int B, int H, int W, float* loss, float* centroid,
+                     double* sums, const float* g_loss, const float* g_centroid, float* galpha, void* ws, size_t ws_bytes,
+                     hipStream_t st);
+
 // ---- ICP between the contact point sets, point alignment, nearest neighbours, normal filter (contact_icp.hip) ----
 size_t contact_icp_workspace_bytes(int B, int n_o);
 int contact_icp(const float* x, const float* y, const float* xn, const float* yn, const float* w, const float* init_R, const float* init_T,
