@@ -951,6 +951,35 @@ int ivlm_silhouette_terms(const float *alpha, const float *target, int64_t targe
                           float *centroid_out, double *sums, const float *g_loss, const float *g_centroid, float *grad_alpha_out,
                           void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 
+/* The rigid transform of the object-pose fit for B poses at once (pose.hip; the reference's optim/utils.py `apply_transformation`):
+ *   a1, a2 = the two interleaved columns of rot6d (a1_i = rot6d[2 i], a2_i = rot6d[2 i + 1]); b1 = a1 / max(|a1|, 1e-12);
+ *   b2 likewise from a2 - (b1 . a2) b1; b3 = b1 x b2; R = [b1 b2 b3] by columns;  y_n = (s v_n) R + t with row vectors.
+ * forward: verts f32 [N,3] (shared by the batch), rot6d f32 [B,6], translation f32 [B,3], scale f32 [B] -> out f32 [B,N,3].  One
+ *   launch; every block rebuilds its pose's R (fp64, rounded once), no host read.
+ * backward: the same verts, rot6d and scale; grad_out f32 [B,N,3] -> grad_rot6d f32 [B,6], grad_translation f32 [B,3], grad_scale
+ *   f32 [B]; each may be NULL (not computed), not all three.  Two launches: twelve fp64 partial sums (sum v^T g and sum g) per block
+ *   of IVLM_POSE_CHUNK vertices and pose, then per pose the partials in ascending chunk order and the analytic chain through the
+ *   Gram-Schmidt in fp64.  dL/dt = sum g, dL/dR = s G, dL/ds = sum_ij R_ij G_ij.
+ * No floating-point atomics, every sum in a fixed order that depends on N only, no host read: the same bits every call, for a pose
+ * whatever the batch around it and its place in it, and under graph replay.  Every term is converted to fp64 before it is added: the
+ * longest fp32 chain is IVLM_POSE_CHAIN.  Documented errors, in units of 2^-24:
+ *   |delta y_nj| <= IVLM_POSE_FWD_ULPS (s sum_i |v_ni| |R_ij| + |t_j|)  (R rounded once 1, s v 1, three fma 3, slack 1)
+ *   |delta dL/dtheta| <= IVLM_POSE_GRAD_ULPS sum_n |d y_n / d theta| |g_n|  (the allowance the fit's plain-torch transform has; the
+ *   fp64 sums here use the final rounding 1 and a few 2^-53 sum |terms|)
+ * B <= 65535, N <= 2^22, else IVLM_ERR_UNSUPPORTED before any launch.  workspace (backward only):
+ * ivlm_pose_transform_workspace_bytes(B, N) bytes (0 for sizes that are not supported), 16-byte aligned; 96 B ceil(N /
+ * IVLM_POSE_CHUNK) bytes and padding. */
+#define IVLM_POSE_CHUNK 1024
+#define IVLM_POSE_CHAIN 1
+#define IVLM_POSE_FWD_ULPS 6
+#define IVLM_POSE_GRAD_ULPS 16
+size_t ivlm_pose_transform_workspace_bytes(int B, int N);
+int ivlm_pose_transform_forward(const float *verts, const float *rot6d, const float *translation, const float *scale, int B, int N,
+                                float *out, ivlm_stream_t stream);
+int ivlm_pose_transform_backward(const float *verts, const float *rot6d, const float *scale, const float *grad_out, int B, int N,
+                                 float *grad_rot6d, float *grad_translation, float *grad_scale, void *workspace,
+                                 size_t workspace_bytes, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

@@ -189,6 +189,13 @@ int silhouette_terms(const float* alpha, const float* target, int64_t t_bstride,
                      double* sums, const float* g_loss, const float* g_centroid, float* galpha, void* ws, size_t ws_bytes,
                      hipStream_t st);
 
+// ---- the rigid transform of B poses, forward and backward (pose.hip) ----------------------------------
+size_t pose_transform_workspace_bytes(int B, int N);
+int pose_transform_forward(const float* verts, const float* rot6d, const float* trans, const float* scale, int B, int N, float* out,
+                           hipStream_t st);
+int pose_transform_backward(const float* verts, const float* rot6d, const float* scale, const float* grad_out, int B, int N,
+                            float* grad_r6, float* grad_t, float* grad_s, void* ws, size_t ws_bytes, hipStream_t st);
+
 // ---- ICP between the contact point sets, point alignment, nearest neighbours, normal filter (contact_icp.hip) ----
 size_t contact_icp_workspace_bytes(int B, int n_o);
 int contact_icp(const float* x, const float* y, const float* xn, const float* yn, const float* w, const float* init_R, const float* init_T,

@@ -3,7 +3,9 @@ loop that composes ``contact_icp`` (the start), ``soft_silhouette`` + ``silhouet
 ``contact_distance`` (the contact term), for B starts at once.
 
 Not the reference's: no Phong render, no depth image, no logging or video.  The rigid transform is applied pose by pose with the
-operations of a single-pose run, so that every start of a batch computes the bits of its own unbatched run.
+operations of a single-pose run, so that every start of a batch computes the bits of its own unbatched run; with
+``fused_transform=True`` it is ``pose.pose_transform`` (csrc/pose.hip), which keeps that property in three launches per step.
+``search_object_pose`` (many starts, one loop, the winner picked on the device) is an addition: the reference fits one start.
 """
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ import torch.nn.functional as F
 
 from .contact_icp import contact_icp
 from .contact_pair import contact_distance
+from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_transform
 from .silhouette import silhouette_terms, soft_silhouette
 
 # optim/cfg/fit.yaml
@@ -84,12 +87,14 @@ class ObjectPoseFit(nn.Module):
 
     rotation_init [B,6] (or [6]), translation_init [B,3], scaling_init a number or [B]; obj_vertices [N,3], obj_faces [F,3],
     human_vertices [N_h,3], obj_contact_probs [N], human_contact_probs [N_h], target_mask [H,W]; focal / principal as
-    ``soft_silhouette`` takes them.  ``vars`` selects what is optimised: "pose", "scale" or both.
+    ``soft_silhouette`` takes them.  ``vars`` selects what is optimised: "pose", "scale" or both.  fused_transform=True moves the
+    object with ``pose.pose_transform`` (one launch for the batch, two for its backward) instead of the pose-by-pose torch
+    operations of ``apply_transformation``: the same transform within the documented errors of that kernel, not the same bits.
     forward(loss_weights, step=None) -> (total [B], {term: [B]})."""
 
     def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
                  human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
-                 blur_radius=None):
+                 blur_radius=None, fused_transform=False):
         super().__init__()
         unknown = set(vars) - {"pose", "scale"}
         if unknown:
@@ -110,6 +115,7 @@ class ObjectPoseFit(nn.Module):
         else:
             self.register_buffer("scale", scale)
         self.step = 0
+        self.fused_transform = bool(fused_transform)
         self.camera = (focal, principal)
         self.sigma, self.blur_radius = sigma, blur_radius
         self.register_buffer("obj_vertices", obj_vertices.detach().float())
@@ -124,6 +130,8 @@ class ObjectPoseFit(nn.Module):
         self.register_buffer("target_mask_centroid", mask_bbox_centre(mask))
 
     def object_vertices(self):
+        if self.fused_transform:
+            return pose_transform(self.obj_vertices, self.rotation, self.translation, self.scale)
         return apply_transformation(self.obj_vertices, self.rotation, self.translation, self.scale)
 
     def forward(self, loss_weights=None, step=None):
@@ -156,13 +164,13 @@ class ObjectPoseFit(nn.Module):
 
 def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                     init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250, early_stop=False,
-                    sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10):
+                    sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=False):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
     init = (R6 [B,6], T [B,3], s number or [B]) gives the B starts; None takes one start from ``contact_icp`` between the object
     vertices of contact probability > icp_threshold[0] and the human vertices of probability > icp_threshold[1] (selecting them
     reads the device once, before the loop).  early_stop ends the loop when every start has |previous - current| < 1e-6: the only
-    host read of the loop, made only when asked for.
+    host read of the loop, made only when asked for.  fused_transform: see ``ObjectPoseFit``.
     -> dict(rotation [B,6], translation [B,3], scale [B], object_vertices [B,N,3], history [iterations,B] (device tensor))."""
     if not isinstance(max_iter, int) or max_iter < 1:
         raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
@@ -174,7 +182,7 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
         icp = contact_icp(o_sel.float(), h_sel.float(), max_iterations=icp_max_iterations)
         init = (matrix_to_rot6d(icp.R), icp.T, 1.0)
     model = ObjectPoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
-                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius)
+                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform)
     groups = []
     if "pose" in vars:
         groups += [{"params": [model.rotation], "lr": 5e-2}, {"params": [model.translation], "lr": 1e-2}]
@@ -199,3 +207,101 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
         verts = model.object_vertices()
     return {"rotation": model.rotation.detach(), "translation": model.translation.detach(), "scale": model.scale.detach(),
             "object_vertices": verts, "history": torch.stack(history)}
+
+
+def select_best(scores):
+    """scores [K] -> the index of the smallest finite score, a 0-dim int64 tensor on the scores' device.  A non-finite score (NaN,
+    +-inf) ranks last, ties go to the lowest index, and scores that are all non-finite give 0.  No host read: the minimum, then the
+    smallest index among the elements equal to it.  Works on CPU tensors too."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 1 or scores.shape[0] < 1 or not scores.is_floating_point():
+        raise ValueError(f"scores: expected a floating-point [K] with K >= 1, got "
+                         f"{tuple(scores.shape) if isinstance(scores, torch.Tensor) else type(scores).__name__}")
+    K = scores.shape[0]
+    key = torch.where(torch.isfinite(scores), scores, torch.full_like(scores, float("inf")))
+    idx = torch.arange(K, dtype=torch.int64, device=scores.device)
+    return torch.where(key == key.min(), idx, torch.full_like(idx, K)).min()
+
+
+_SEARCH_FIT_KWARGS = ("hum_centroid_offset", "vars", "loss_weights", "max_iter", "sigma", "blur_radius", "icp_threshold",
+                      "icp_max_iterations")
+
+
+def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
+                       rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, **fit_kwargs):
+    """A multi-start ``fit_object_pose``: K starts around one pose, fitted in one loop with the fused transform, scored and ranked on
+    the device.  NOT the reference's, which runs one start (optim/fit.py): contact patches and a silhouette leave rotational
+    ambiguities that a local fit from one start does not resolve.
+
+    rotations [K,3,3] (None: the 24 ``pose.cube_rotations()``); init = (R0 [3,3], T0 [3], s0) (None: identity, zero, 1): start k is
+    ``pose.pose_starts``' R_k = rotations[k] @ R0 at T0, s0.  icp=True first runs ONE ``contact_icp`` call with init = (R_k, T0, s0)
+    for all K starts, between the object vertices of contact probability > icp_threshold[0] and the human vertices of probability >
+    icp_threshold[1] (the selection of ``fit_object_pose(init=None)``: it reads the device once, before anything else), with
+    obj_normals [N,3] / human_normals [N_h,3] of the whole meshes forwarded when given, and takes R, T of every start from its result.
+    Then ``fit_object_pose(init=starts, fused_transform=True, **fit_kwargs)``; fit_kwargs are that function's hum_centroid_offset,
+    vars, loss_weights, max_iter, sigma, blur_radius, icp_threshold, icp_max_iterations (early_stop is refused: it ends a loop
+    when all of ITS starts have settled).  The score of a start is one more forward at its returned parameters, without gradients,
+    with every configured term (kick_in >= 0) on; history[-1] is the total BEFORE the last update and is not the score.
+
+    chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
+    computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
+
+    -> the dict of ``fit_object_pose`` for all K starts (rotation [K,6], translation [K,3], scale [K], object_vertices [K,N,3],
+    history [iterations,K]) plus scores [K], best_index (0-dim int64 device tensor, ``select_best``) and best = {rotation [6],
+    translation [3], scale [], object_vertices [N,3]} gathered with index_select.  The only host reads are those of
+    ``fit_object_pose`` and of the silhouette's topology cache, before the loop."""
+    if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
+        raise ValueError(f"chunk: expected None or an integer >= 1, got {chunk!r}")
+    if "early_stop" in fit_kwargs:
+        raise ValueError("early_stop: not available in search_object_pose (it would make a start's result depend on chunk)")
+    unknown = sorted(set(fit_kwargs) - set(_SEARCH_FIT_KWARGS))
+    if unknown:
+        raise ValueError(f"unexpected arguments {unknown}: expected a subset of {list(_SEARCH_FIT_KWARGS)} (the transform is always fused)")
+    if not isinstance(obj_vertices, torch.Tensor) or obj_vertices.dim() != 2 or obj_vertices.shape[1] != 3:
+        raise ValueError(f"obj_vertices: expected [N,3], got "
+                         f"{tuple(obj_vertices.shape) if isinstance(obj_vertices, torch.Tensor) else type(obj_vertices).__name__}")
+    if (obj_normals is None) != (human_normals is None):
+        raise ValueError("normals must be given for both sides or for neither")
+    dev = obj_vertices.device
+    if rotations is None:
+        rotations = cube_rotations()
+    check_rotations(rotations)
+    if init is None:
+        init = (None, None, 1.0)
+    if not isinstance(init, (tuple, list)) or len(init) != 3:
+        raise ValueError("init: expected (R0 [3,3], T0 [3], s0)")
+    R0, T0, s0 = init
+    R0, T0, s0 = check_start(R0, T0, s0, dev)
+    K = rotations.shape[0]
+    R = compose_rotations(rotations.detach().to(dev), R0)
+    T, s = T0.expand(K, 3).contiguous(), s0.expand(K).contiguous()
+    if icp:
+        threshold = fit_kwargs.get("icp_threshold", (0.3, 0.5))
+        o_on, h_on = obj_contact_probs.float() > threshold[0], human_contact_probs.float() > threshold[1]
+        o_sel, h_sel = obj_vertices[o_on], human_vertices[h_on]
+        if o_sel.shape[0] < 1 or h_sel.shape[0] < 1:
+            raise ValueError("icp=True needs contact vertices above icp_threshold on both meshes for contact_icp")
+        normals = (obj_normals[o_on].float(), human_normals[h_on].float()) if obj_normals is not None else (None, None)
+        found = contact_icp(o_sel.float(), h_sel.float(), normals[0], normals[1], init=(R, T, s),
+                            max_iterations=fit_kwargs.get("icp_max_iterations", 10))
+        R, T = found.R, found.T
+    R6 = matrix_to_rot6d(R)
+    weights = fit_kwargs.get("loss_weights")
+    every_term = max([0] + [v["kick_in"] for v in (DEFAULT_LOSS_WEIGHTS if weights is None else weights).values()])
+    scene = (obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal)
+    step = K if chunk is None else chunk
+    parts, scores = [], []
+    for lo in range(0, K, step):
+        sel = slice(lo, min(lo + step, K))
+        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, **fit_kwargs)
+        final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], *scene, fit_kwargs.get("hum_centroid_offset"),
+                              fit_kwargs.get("vars", ("pose",)), fit_kwargs.get("sigma", 1e-4), fit_kwargs.get("blur_radius"),
+                              fused_transform=True)
+        with torch.no_grad():
+            scores.append(final(weights, step=every_term)[0])
+        parts.append(out)
+    result = {k: torch.cat([p[k] for p in parts], dim=1 if k == "history" else 0) for k in parts[0]}
+    result["scores"] = torch.cat(scores)
+    best = select_best(result["scores"])
+    result["best_index"] = best
+    result["best"] = {k: result[k].index_select(0, best.reshape(1))[0] for k in ("rotation", "translation", "scale", "object_vertices")}
+    return result
