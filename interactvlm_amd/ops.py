@@ -1087,10 +1087,25 @@ def dense_pe(gauss, h, w, dtype=torch.float32):
     return pe
 
 
+def _rope_extents(qkv, width, H, D, pos0, table, caches):
+    """The kernels index rows pos0 .. pos0 + T - 1 of the table and of the caches and ``width`` columns of qkv without looking at
+    any length: what they cannot see is checked here, before the launch."""
+    T, end = qkv.shape[0], int(pos0) + qkv.shape[0]
+    assert qkv.dim() == 2 and T > 0 and int(pos0) >= 0 and qkv.shape[-1] >= width, f"qkv {tuple(qkv.shape)}: needs {width} columns"
+    if table is not None:
+        for t in table:
+            assert t.is_cuda and t.dtype == F32 and t.is_contiguous(), "rope table: contiguous fp32 on the device"
+            assert t.dim() == 2 and t.shape[1] == D // 2 and t.shape[0] >= end, f"rope table {tuple(t.shape)}: needs [>= {end}, {D // 2}]"
+    for c in caches:
+        if c is not None:
+            assert c.is_contiguous() and c.shape[0] >= end and c.numel() >= end * H * D, f"cache {tuple(c.shape)}: needs {end} rows of {H * D}"
+
+
 def rope_kv(qkv, H, D, pos0, theta, kcache=None, vcache=None, table=None):
     """qkv [T, 3*H*D] (in place). table = (cos, sin) fp32 [Tmax, D/2] from rope_table()."""
     lib = _lib.load()
     assert qkv.dtype in (BF16, F16) and qkv.stride(-1) == 1 and (kcache is None or (kcache.dtype == qkv.dtype == vcache.dtype))
+    _rope_extents(qkv, 3 * H * D, H, D, pos0, table, (kcache, vcache))
     T = qkv.shape[0]
     check((lib.ivlm_rope_kv_f16 if qkv.dtype == F16 else lib.ivlm_rope_kv)(qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0), float(theta), _p(kcache), _p(vcache),
                                                                            _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()), "rope_kv")
@@ -1104,6 +1119,7 @@ def rope_kv_split(qkv, H, D, pos0, caches, table):
     assert qkv.dtype == BF16 and qkv.stride(-1) == 1 and qkv.shape[-1] == 6 * H * D
     T = qkv.shape[0]
     kc = caches if caches is not None else (None,) * 4
+    _rope_extents(qkv, 6 * H * D, H, D, pos0, table, kc)
     check(lib.ivlm_rope_kv_split(qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0), _p(kc[0]), _p(kc[1]), _p(kc[2]), _p(kc[3]),
                                  table[0].data_ptr(), table[1].data_ptr(), _stream()), "rope_kv_split")
     return qkv
