@@ -257,11 +257,23 @@ void ivlm_skinny_tuning(int tiles_per_block);
 
 /* Benchmark hook: column split of GEMMs whose 256 x 256 tile count under-fills its last round (default 1 = on). */
 int ivlm_gemm_nsplit(int on);
-/* Benchmark/test hook: force the GEMM block tile (64 = 128x64, 128, 256, 512 = the 8-phase 256x256 kernel, 320 = 256x320, 176;
- * 0 = automatic choice). Returns the previous value. */
+/* Benchmark/test hook: force the GEMM block tile (64 = 128x64, 96 = 128x96, 128, 256, 512 = the 8-phase 256x256 kernel, 320 = 256x320,
+ * 176 = 176x128; 0 = automatic choice) of every tile GEMM of the library - the op-level entry points and the GEMMs inside the stage
+ * sequencers alike; a tile a call has no kernel for falls back as without the hook.  Returns the previous value. */
 int ivlm_gemm_tile_override(int tile);
 /* Benchmark/test hook: automatic choice of the 256 x 320 tile for N % 320 == 0 (SAM ViT-H widths; default on). Returns the previous value. */
 int ivlm_gemm_tile320(int on);
+/* Test/benchmark hook: the launches ONE call of a tile-GEMM entry point (M > 16) would make under the current hooks, written to
+ * `records` instead of being made - nothing is launched, no GPU is needed.  entry: 0 ivlm_gemm_bf16, 1 ivlm_gemm_bf16_panel,
+ * 2 ivlm_gemm_fp8, 3 ivlm_gemm_bf16_splitk, 4 ivlm_gemm_bf16_splitk_fused; the other arguments are that entry point's (out_kind: its
+ * out_f32 / out_kind; has_*: whether the pointer is given; what an entry point does not take is ignored).  A record is 9 int32:
+ * (family, BM, BN, operand kind 0 bf16 / 1 e4m3 / 2 fp16, fp32 epilogue 0 / 1, activation, grid.x, grid.z, dynamic LDS bytes) with
+ * family 0 = the tile kernels of gemm.hip, 1 = the 8-phase 256 x 256 kernel, 2 = 256 x 320, 3 = the split-K reduce launch, 4 = "the
+ * launch before also reduces" (fused split-K), -1 = the call returns the error code in BM.  A column split gives two records.
+ * Returns the number of records, IVLM_ERR_WORKSPACE if they exceed max_records, IVLM_ERR_INVALID_ARG for M <= 16 / no buffer. */
+int ivlm_gemm_route_query(int entry, int M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int64_t a_kstep,
+                          int64_t w_kstep, int64_t c_panel, int act, int out_kind, int has_bias, int has_residual, int res_mod,
+                          int batch, int flags, int has_out_rows, int has_a_rows, int splits, int32_t *records, int max_records);
 
 /* nn.LayerNorm over the last dim (also SAM LayerNorm2d with NHWC activations, common.py:32-42);
  * x / y bf16 or fp32 (dtype codes), fp32 statistics, cols % 8 == 0, cols <= 8192.  gelu_after != 0 fuses the exact-erf GELU
@@ -627,7 +639,9 @@ int ivlm_gemm_splitk_choice(int M, int N, int K, int act, int has_rms);
  * two-launch form (partials + ordered reduction) by default.  on = 1 selects the reduction FUSED into the GEMM launch
  * (ivlm_gemm_bf16_splitk_fused: same values bit for bit, one launch less, measured 2 - 3 x slower on MI355X; the arrival counters then
  * live in the last 16 KB of the sequencer's split-K region and every stage call zeroes them once); on = 0 switches back; any other
- * value only queries.  Default: the environment's IVLM_SPLITK_FUSED=1 at first use, else off.  Returns the previous setting. */
+ * value only queries.  Default: the environment's IVLM_SPLITK_FUSED=1 at first use, else off.  Returns the previous setting.
+ * A stage call reads the switch once, when it starts, and runs to its end in that form; do NOT flip the switch while a stage call
+ * is in flight on another thread (the call itself stays consistent, but which form it runs is then a race). */
 int ivlm_stages_splitk_fused(int on);
 
 /* Batch-1 decode linear over LOSSLESSLY packed bf16 weights ("bf12", 1.5 bytes per weight instead of 2; the decode step of

@@ -1749,19 +1749,12 @@ int ivlm_relpos_bias_f16(const void* q, const void* q_lo, int64_t q_bs, int64_t 
     if (q_bs != (int64_t)S * q_rs || ((q_rs | q_hs) & 7) || (reinterpret_cast<uintptr_t>(q) & 15)) return IVLM_ERR_UNSUPPORTED;  // rows of all (b, s) uniformly strided
     const int64_t M = (int64_t)B * S;
     if (M > 0x7fffffff || g_bytes < (size_t)H * M * npad * 4) return IVLM_ERR_WORKSPACE;
-    ivlm::GemmArgs g;
-    g.A = static_cast<const bf16_t*>(q); g.lda = q_rs;
-    g.W = static_cast<const bf16_t*>(cat16); g.ldw = D;
-    g.C = G_ws; g.ldc = npad;
-    g.M = (int)M; g.N = npad; g.K = D;
+    ivlm::GemmArgs g = ivlm::gemm_args(q, q_rs, cat16, D, G_ws, npad, nullptr, nullptr, 0, 0, (int)M, npad, D, ivlm::ACT_NONE, 1,
+                                       IVLM_GEMM_F16 | (q_lo ? IVLM_GEMM_A_SPLIT : 0));
     g.batch = H; g.strideA = q_hs; g.strideW = 0; g.strideC = M * npad;
-    g.out_f32 = 1;
-    g.f16 = 1;
     if (q_lo) {
-        const int64_t off = static_cast<const bf16_t*>(q_lo) - static_cast<const bf16_t*>(q);
-        if (off < D || (off & 7)) return IVLM_ERR_INVALID_ARG;  // the lo plane lies behind the hi plane of the same rows
-        g.a_split = 1;
-        g.a_lo = off;
+        g.a_lo = static_cast<const bf16_t*>(q_lo) - static_cast<const bf16_t*>(q);
+        if (g.a_lo < D || (g.a_lo & 7)) return IVLM_ERR_INVALID_ARG;  // the lo plane lies behind the hi plane of the same rows
     }
     const int rc = ivlm::gemm_bf16(g, ivlm_stream(stream));
     if (rc != IVLM_OK) return rc;

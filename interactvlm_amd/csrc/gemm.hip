@@ -18,7 +18,10 @@
 //     consecutive N of one output row: bias/activation/residual and an 8-byte (bf16x4) store.
 //   * epilogues: bias, GELU(erf) / quick-GELU / ReLU / SiLU, SwiGLU over interleaved gate/up rows,
 //     residual add (optionally row-modulo for broadcast tables), bf16 or fp32 output.
+#include <algorithm>
+
 #include "gemm_common.h"
+#include "gemm_route.h"
 
 namespace ivlm {
 namespace {
@@ -227,45 +230,54 @@ __global__ __launch_bounds__(CFG::kThreads, CFG::kMinBlocks) void gemm_bf16_kern
 using Cfg128 = TileCfg<2, 2, 4, 4>;
 using Cfg256 = TileCfg<2, 4, 8, 4>;
 
-template <int ACT, bool OUT_F32, typename CFG, int OPK = 0>
-int launch_cfg(const GemmArgs& g, hipStream_t st) {
-    const int tiles = ((g.M + CFG::BM - 1) / CFG::BM) * ((g.N + CFG::BN - 1) / CFG::BN);
-    dim3 grid(tiles, 1, g.batch);
-    auto kfn = gemm_bf16_kernel<ACT, OUT_F32, CFG, OPK>;
-    if (CFG::kLdsBytes > 64 * 1024) {
-        static ivlm_dev_mask_t attr_set{0};  // per instantiation, one bit per device
-        if (ivlm_dev_pending(attr_set)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      CFG::kLdsBytes);
-            ivlm_dev_done(attr_set);
-        }
-    }
-    ivlm_launch(kfn, grid, dim3(CFG::kThreads), CFG::kLdsBytes, st, g);
-    return ivlm_launch_status();
-}
-
 using Cfg128x64 = TileCfg<2, 2, 4, 2>;  // 128 x 64 block: more tiles for skinny problems (LLM prefill o/down)
 // Row-stationary tile for the LLaMA prefill (M = 330 = two row tiles of 176): a wave owns ALL rows of a 32-column strip, so each A
 // fragment read feeds 2 MFMAs and each W fragment 11 (0.59 LDS reads per MFMA against 0.75 for the 128 x 64 tile), the tile's
 // arithmetic intensity is 74 FLOP per DMA byte against 43, and 2 x 172 tiles of gate|up fit the 512 block slots in ONE round
-// (3 x 172 tiles of 128 x 128 need a second round for 4 tiles).  Cold weights (tools/bench_prefill_gemm.py): gate|up 115 -> 86 us,
-// q|k|v 73 -> 60 us (with 2 K slices); o / down (N = 4096) do not gain.
+// (3 x 172 tiles of 128 x 128 need a second round for 4 tiles).  Cold weights (tools/experiments/bench_prefill_gemm.py): gate|up
+// 115 -> 86 us, q|k|v 73 -> 60 us (with 2 K slices); o / down (N = 4096) do not gain.
 using Cfg176x128 = TileCfg<1, 4, 11, 2>;     // 176 x 128, 2 blocks per CU (78 KB of LDS each)
 // (352 x 128 - all 330 rows in one block, one wave per SIMD with its accumulators in AGPRs - was built and measured: 134 us for
 //  q|k|v and 136 us for gate|up against 60 / 86 us for 176 x 128: a single wave per SIMD cannot hide its own LDS latency.)
-using Cfg128x96 = TileCfg<2, 2, 4, 3>;  // 128 x 96 block: M ~ 330 prefill against wide N (3 tile rows: see choose_tile)
+using Cfg128x96 = TileCfg<2, 2, 4, 3>;  // 128 x 96 block: M ~ 330 prefill against wide N (3 tile rows: see auto_tile)
 
-// Pick the block tile from the tile counts (measured with tools/bench_gemm.py):
-//   * fewer than ~400 tiles of 128^2 (under one resident wave at 2 blocks/CU): halve the tile (128x64) to
-//     put more CUs to work (LLM prefill o/down, CLIP: +15-30 %);
-//   * 256^2 (+10 % on SAM qkv / mlp1) when it fills whole waves of the 256 CUs (quantisation efficiency >= 0.85);
-//   * 128^2 otherwise.
+// the launcher of this file's kernels: the tile configuration a GEMM_TILE route names
+struct GoTile {
+    const GemmRoute& r;
+    const GemmArgs& g;
+    hipStream_t st;
+    template <int ACT, int OPK, typename CFG>
+    int cfg() const {
+        if constexpr (gemm_instantiated(GEMM_TILE, CFG::BM, CFG::BN, OPK, ACT))
+            return gemm_launch<gemm_bf16_kernel<ACT, true, CFG, OPK>, gemm_bf16_kernel<ACT, false, CFG, OPK>>(r, CFG::kThreads, g, st);
+        return IVLM_ERR_UNSUPPORTED;  // (gemm_route names instantiated kernels only)
+    }
+    template <int ACT, int OPK>
+    int run() const {
+        switch (r.bm * 1000 + r.bn) {
+            case 128128: return cfg<ACT, OPK, Cfg128>();
+            case 128064: return cfg<ACT, OPK, Cfg128x64>();
+            case 128096: return cfg<ACT, OPK, Cfg128x96>();
+            case 176128: return cfg<ACT, OPK, Cfg176x128>();
+            case 256256: return cfg<ACT, OPK, Cfg256>();
+            default: return IVLM_ERR_UNSUPPORTED;
+        }
+    }
+};
+static_assert(Cfg176x128::kLdsBytes == 256 * (176 + 128), "gemm_route computes the tile kernels' LDS bytes as 256 * (BM + BN)");
+
+constexpr bool tile_code_ok(int t) { return t == 64 || t == 96 || t == 128 || t == 176 || t == 256 || t == 320 || t == 512; }
+
 // 256 x 320 tiles (gemm320.hip): N a multiple of 320 (SAM ViT-H: 1280 / 3840 / 5120) and enough row tiles that whole rounds of
 // the 256 CUs are filled - proj / mlp2 of the 4-view call are exactly ONE round instead of 1.25 rounds of 256^2 tiles
-inline bool tile320_fits(const GemmArgs& g) {
-    if (g.fp8 || g.out_fp8 || g.batch != 1 || g.a_kstep || g.w_kstep || g.c_panel || g.rms_w) return false;
-    if ((g.act != ACT_NONE && g.act != ACT_GELU) || g.N % 320 || g.M < 2048) return false;
-    if (!(g.out_f32 ? gemm_whole_lines_ok<true>(g, g.act) : gemm_whole_lines_ok<false>(g, g.act))) return false;  // (its only epilogue)
+// ... what the kernel can run at all (row-major bf16 / fp16 operands, its whole-line epilogue, the SAM encoder's activations)
+bool tile320_runs(const GemmArgs& g) {
+    if (g.fp8 || g.out_fp8 || g.a_kstep || g.w_kstep || g.c_panel || (g.act != ACT_NONE && g.act != ACT_GELU)) return false;
+    return g.out_f32 ? gemm_whole_lines_ok<true>(g, g.act) : gemm_whole_lines_ok<false>(g, g.act);  // (its only epilogue)
+}
+// ... and where it is chosen
+bool tile320_fits(const GemmArgs& g) {
+    if (!tile320_runs(g) || g.batch != 1 || g.rms_w || g.N % 320 || g.M < 2048) return false;
     // fp32 outputs only (SAM proj / mlp2: 1.25 rounds of 256^2 tiles -> one round).  The 16-bit-output GEMMs (qkv, mlp1) are also
     // faster on this tile ALONE (qkv 163 -> 155 us, encoder 29.64 -> 29.56 ms) but evaluate() is SLOWER with them on it (101.2 vs
     // 99.8 ms, alternating runs on one box; tile off everywhere: 100.5): a 256 x 320 tile holds its CU 25 % longer than a 256^2
@@ -277,11 +289,14 @@ inline bool tile320_fits(const GemmArgs& g) {
     const double q = (double)tiles / (double)(((tiles + 255) / 256) * 256);
     return tiles >= 256 && q >= 0.85 && (double)(tm * 256) / (double)g.M < 1.1;
 }
-static int g_tile320 = 1;  // benchmark hook (ivlm_gemm_tile320): 0 = never pick the 256 x 320 tile automatically
 
-inline int choose_tile(const GemmArgs& g) {
-    if (g.tile == 128 || g.tile == 256 || g.tile == 64 || g.tile == 96 || g.tile == 512 || g.tile == 176 || g.tile == 320) return g.tile;
-    if (g_tile320 && tile320_fits(g)) return 320;
+// Pick the block tile from the tile counts (measured with tools/bench_gemm.py):
+//   * fewer than ~400 tiles of 128^2 (under one resident wave at 2 blocks/CU): halve the tile (128x64) to
+//     put more CUs to work (LLM prefill o/down, CLIP: +15-30 %);
+//   * 256^2 (+10 % on SAM qkv / mlp1) when it fills whole waves of the 256 CUs (quantisation efficiency >= 0.85);
+//   * 128^2 otherwise.
+int auto_tile(const GemmArgs& g, const GemmSwitches& sw) {
+    if (sw.tile320 && tile320_fits(g)) return 320;
     if (g.M > 128 && g.M <= 352 && g.N >= 8192 && g.batch <= 2 && (g.act == ACT_NONE || g.act == ACT_SWIGLU)) return 176;  // LLaMA prefill, wide N
     const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch;
     // (128x96 tiles for the LLaMA prefill's wide projections, M ~ 330 = 3 tile rows: faster in the warm micro-benchmark -
@@ -297,64 +312,71 @@ inline int choose_tile(const GemmArgs& g) {
     return 128;
 }
 
-template <int ACT>
-int launch(const GemmArgs& g, hipStream_t st) {
-    if (g.fp8) {  // fp8 operands: the 8-phase 256^2 kernel, or 128x128 / 128x64 tiles for what it does not fit
-        const int t = choose_tile(g);
-        if (t == 512 || t == 256) return gemm_bf16_256p(g, st);
-        if (t == 64) return g.out_f32 ? launch_cfg<ACT, true, Cfg128x64, 1>(g, st) : launch_cfg<ACT, false, Cfg128x64, 1>(g, st);
-        return g.out_f32 ? launch_cfg<ACT, true, Cfg128, 1>(g, st) : launch_cfg<ACT, false, Cfg128, 1>(g, st);
+// the launches a dry run records instead of making (ivlm_gemm_route_query): 9 ints each, see ivlm_hip.h
+struct RouteLog {
+    int32_t* rec;
+    int cap, n;
+};
+thread_local RouteLog* t_route_log = nullptr;
+bool route_logged(int family, int bm, int bn, int opk, int out_f32, int act, int grid_x, int grid_z, int lds) {
+    RouteLog* log = t_route_log;
+    if (!log) return false;
+    if (log->n < log->cap) {
+        const int32_t v[9] = {family, bm, bn, opk, out_f32, act, grid_x, grid_z, lds};
+        std::copy(v, v + 9, log->rec + 9 * log->n);
     }
-    if (g.f16) {  // fp16 operands: the tilings of the bf16 path (the epilogues the three towers use: keeps the build small)
-        if constexpr (ACT == ACT_NONE || ACT == ACT_GELU || ACT == ACT_QUICK_GELU || ACT == ACT_SWIGLU) {
-            const int t = choose_tile(g);
-            if (t == 320) {
-                const int rc = gemm_bf16_320p(g, st);
-                if (rc != IVLM_ERR_UNSUPPORTED) return rc;
-            }
-            if (t == 512 || t == 256) return gemm_bf16_256p(g, st);
-            if (t == 176) {
-                if constexpr (ACT == ACT_NONE || ACT == ACT_SWIGLU)
-                    return g.out_f32 ? launch_cfg<ACT, true, Cfg176x128, 2>(g, st) : launch_cfg<ACT, false, Cfg176x128, 2>(g, st);
-            }
-            if (t == 64 || t == 176 || t == 96)
-                return g.out_f32 ? launch_cfg<ACT, true, Cfg128x64, 2>(g, st) : launch_cfg<ACT, false, Cfg128x64, 2>(g, st);
-            return g.out_f32 ? launch_cfg<ACT, true, Cfg128, 2>(g, st) : launch_cfg<ACT, false, Cfg128, 2>(g, st);
-        } else {
-            return IVLM_ERR_UNSUPPORTED;
-        }
-    }
-    switch (choose_tile(g)) {
-        case 320: {  // 256 x 320 (gemm320.hip); a FORCED 320 on a problem outside its epilogue falls through to 128^2
-            const int rc = gemm_bf16_320p(g, st);
-            if (rc != IVLM_ERR_UNSUPPORTED) return rc;
-            return g.out_f32 ? launch_cfg<ACT, true, Cfg128>(g, st) : launch_cfg<ACT, false, Cfg128>(g, st);
-        }
-        case 512: return gemm_bf16_256p(g, st);  // 256^2, 8-phase ping-pong pipeline (gemm256.hip)
-        case 256: return g.out_f32 ? launch_cfg<ACT, true, Cfg256>(g, st) : launch_cfg<ACT, false, Cfg256>(g, st);
-        case 64: return g.out_f32 ? launch_cfg<ACT, true, Cfg128x64>(g, st) : launch_cfg<ACT, false, Cfg128x64>(g, st);
-        case 96: return g.out_f32 ? launch_cfg<ACT, true, Cfg128x96>(g, st) : launch_cfg<ACT, false, Cfg128x96>(g, st);
-        case 176:  // (instantiated for the epilogues the prefill uses only: keeps the build small)
-            if constexpr (ACT == ACT_NONE || ACT == ACT_SWIGLU)
-                return g.out_f32 ? launch_cfg<ACT, true, Cfg176x128>(g, st) : launch_cfg<ACT, false, Cfg176x128>(g, st);
-            else
-                return g.out_f32 ? launch_cfg<ACT, true, Cfg128x64>(g, st) : launch_cfg<ACT, false, Cfg128x64>(g, st);
-        default: return g.out_f32 ? launch_cfg<ACT, true, Cfg128>(g, st) : launch_cfg<ACT, false, Cfg128>(g, st);
-    }
+    ++log->n;
+    return true;
 }
 
 }  // namespace
 
-static int g_nsplit = 1;  // benchmark hook: 0 = never split N
-void gemm_set_nsplit(int on) { g_nsplit = on; }
+GemmSwitches g_gemm_switches;
+
+GemmRoute gemm_route(const GemmArgs& g, const GemmSwitches& sw) {
+    GemmRoute r;
+    r.opk = g.fp8 ? 1 : (g.f16 ? 2 : 0);
+    r.out_f32 = g.out_f32 ? 1 : 0;
+    r.act = g.act;
+    // activations: all seven for bf16 operands, the towers' for fp16 / fp8 (an unknown code was never "unsupported" for bf16 / fp16)
+    if (!g.fp8 && (g.act < ACT_NONE || g.act > ACT_SIGMOID)) r.rc = IVLM_ERR_INVALID_ARG;
+    else if (r.opk != 0 && !gemm_tower_act(g.act)) r.rc = IVLM_ERR_UNSUPPORTED;
+    if (r.rc != IVLM_OK) return r;
+
+    int t = tile_code_ok(g.tile) ? g.tile : (sw.tile_override ? sw.tile_override : auto_tile(g, sw));
+    // fused split-K: only the tile kernels of this file carry the fix-up
+    if (g.sk.count && (t == 512 || t == 256 || t == 320)) t = 128;
+    r.bm = 128, r.bn = 128;  // (the fallback of everything below)
+    switch (t) {
+        case 320:  // a FORCED 320 on a problem outside its epilogue stays on 128^2
+            if (tile320_runs(g)) r.family = GEMM_320, r.bm = 256, r.bn = 320;
+            break;
+        case 512: r.family = GEMM_256P; break;                // 256^2, 8-phase ping-pong pipeline (gemm256.hip)
+        case 256: r.family = r.opk == 0 ? GEMM_TILE : GEMM_256P, r.bm = r.bn = 256; break;  // (the plain 256^2 kernel: bf16 only)
+        case 64: r.bn = 64; break;
+        case 96:  // bf16 only; fp16 takes 128 x 64, fp8 128^2
+            if (r.opk != 1) r.bn = r.opk == 0 ? 96 : 64;
+            break;
+        case 176:  // (instantiated for the epilogues the prefill uses only: keeps the build small); else 128 x 64, fp8 128^2
+            if (gemm_instantiated(GEMM_TILE, 176, 128, r.opk, g.act)) r.bm = 176;
+            else if (r.opk != 1) r.bn = 64;
+            break;
+        default: break;
+    }
+    if (r.family == GEMM_256P) r.bm = r.bn = 256;
+    r.grid_x = ((g.M + r.bm - 1) / r.bm) * ((g.N + r.bn - 1) / r.bn);
+    r.grid_z = g.batch;
+    r.lds = r.family == GEMM_256P ? kGemm256LdsBytes : (r.family == GEMM_320 ? kGemm320LdsBytes : 256 * (r.bm + r.bn));  // (two K tiles of A + W)
+    return r;
+}
 
 // Column split for the 256 x 256 path: a GEMM whose tile count is just over a whole number of rounds on the 256 CUs (SAM
 // proj / mlp2: 16384 x 1280 -> 64 x 5 = 320 tiles = one full round + a quarter-filled one, 62 % efficiency) runs as the
 // columns that DO fill whole rounds (4 x 256 = 1024 -> 256 tiles, 8-phase kernel) plus the remaining strip on 128 x 64 tiles
 // (512 small blocks, 2-3 per CU).  Two launches of the existing kernels; no partial sums, the epilogues are per column.
-static int nsplit_cols(const GemmArgs& g) {
-    if (!g_nsplit || g.tile != 0 || g.batch != 1 || g.act == ACT_SWIGLU || g.M < 4096 || (g.N & 255)) return 0;
-    if (g_tile320 && tile320_fits(g)) return 0;  // (whole rounds of 256 x 320 tiles: nothing to split off)
+static int nsplit_cols(const GemmArgs& g, const GemmSwitches& sw) {
+    if (!sw.nsplit || g.tile != 0 || sw.tile_override != 0 || g.batch != 1 || g.act == ACT_SWIGLU || g.M < 4096 || (g.N & 255)) return 0;
+    if (auto_tile(g, sw) == 320) return 0;  // (whole rounds of 256 x 320 tiles: nothing to split off)
     const long tm = (g.M + 255) / 256, tn = g.N / 256;
     const long tiles = tm * tn;
     const double q = (double)tiles / (double)(((tiles + 255) / 256) * 256);
@@ -366,7 +388,7 @@ static int nsplit_cols(const GemmArgs& g) {
 
 int gemm_bf16(const GemmArgs& g, hipStream_t st) {
     if (!g.A || !g.W || !g.C || g.M <= 0 || g.N <= 0 || g.K <= 0 || g.batch <= 0) return IVLM_ERR_INVALID_ARG;
-    if (const int n1 = nsplit_cols(g)) {
+    if (const int n1 = nsplit_cols(g, g_gemm_switches)) {
         GemmArgs a = g, b = g;
         a.N = n1;
         a.tile = 512;
@@ -403,25 +425,15 @@ int gemm_bf16(const GemmArgs& g, hipStream_t st) {
             return IVLM_ERR_INVALID_ARG;
         if (g.c_panel && (g.out_f32 || (g.N & 63) || g.c_panel < (int64_t)64 * g.M || g.out_rows)) return IVLM_ERR_UNSUPPORTED;
     }
-    if (g.fp8) {
-        if (!g.scale_a || !g.scale_w || (g.out_fp8 && (!g.scale_out || g.out_f32 || (g.ldc & 3)))) return IVLM_ERR_INVALID_ARG;
-        // (only the epilogues the fp8 paths use are instantiated: SAM encoder, CLIP, LLaMA prefill)
-        if (g.act == ACT_NONE) return launch<ACT_NONE>(g, st);
-        if (g.act == ACT_GELU) return launch<ACT_GELU>(g, st);
-        if (g.act == ACT_QUICK_GELU) return launch<ACT_QUICK_GELU>(g, st);
-        if (g.act == ACT_SWIGLU) return (g.N & 3) || g.residual ? IVLM_ERR_UNSUPPORTED : launch<ACT_SWIGLU>(g, st);
-        return IVLM_ERR_UNSUPPORTED;
-    }
-    if (g.out_fp8) return IVLM_ERR_UNSUPPORTED;
-    switch (g.act) {
-        case ACT_NONE: return launch<ACT_NONE>(g, st);
-        case ACT_GELU: return launch<ACT_GELU>(g, st);
-        case ACT_QUICK_GELU: return launch<ACT_QUICK_GELU>(g, st);
-        case ACT_RELU: return launch<ACT_RELU>(g, st);
-        case ACT_SILU: return launch<ACT_SILU>(g, st);
-        case ACT_SWIGLU: return launch<ACT_SWIGLU>(g, st);
-        case ACT_SIGMOID: return launch<ACT_SIGMOID>(g, st);
-        default: return IVLM_ERR_INVALID_ARG;
+    if (g.fp8 && (!g.scale_a || !g.scale_w || (g.out_fp8 && (!g.scale_out || g.out_f32 || (g.ldc & 3))))) return IVLM_ERR_INVALID_ARG;
+    if (g.out_fp8 && !g.fp8) return IVLM_ERR_UNSUPPORTED;
+    const GemmRoute r = gemm_route(g, g_gemm_switches);
+    if (r.rc != IVLM_OK) return r.rc;
+    if (route_logged(r.family, r.bm, r.bn, r.opk, r.out_f32, r.act, r.grid_x, r.grid_z, r.lds)) return IVLM_OK;
+    switch (r.family) {
+        case GEMM_256P: return gemm256_launch(r, g, st);
+        case GEMM_320: return gemm320_launch(r, g, st);
+        default: return gemm_dispatch(r, GoTile{r, g, st});
     }
 }
 
@@ -462,24 +474,25 @@ int gemm_bf16_splitk(const GemmArgs& g, int splits, float* workspace, size_t ws_
     p.residual = nullptr;
     p.act = ACT_NONE;
     if (counters && !g.fp8 && (g.N & 3) == 0) {
-        // fused reduction: the tile kernels of gemm.hip only (they carry the fixup), and a tile count the counter array covers
-        int t = choose_tile(p);
-        if (t == 512 || t == 256 || t == 320) t = 128;
+        // fused reduction: a tile count the counter array covers (gemm_route keeps a launch with sk.count on the tile kernels of this
+        // file: they carry the fixup)
         const long tiles = (long)((g.M + 127) / 128) * ((g.N + 63) / 64);  // (the smallest tile any of them uses: an upper bound)
         if (tiles <= kSplitKCounters) {
-            p.tile = t;
             p.sk.count = counters;
             p.sk.C = g.C; p.sk.bias = g.bias; p.sk.residual = g.residual;
             p.sk.ldc = g.ldc; p.sk.ldr = g.ldr; p.sk.c_lo = g.c_lo;
             p.sk.res_mod = g.res_mod; p.sk.act = g.act; p.sk.out_f32 = g.out_f32; p.sk.out_f16 = g.out_f16; p.sk.out_split = g.out_split;
             p.sk.res_f32 = g.res_f32;
-            return gemm_bf16(p, st);
+            const int rc = gemm_bf16(p, st);
+            if (rc == IVLM_OK) route_logged(4, 0, 0, 0, g.out_f32, g.act, 0, 0, 0);  // (a dry run notes "reduced in that launch")
+            return rc;
         }
     }
     const int rc = gemm_bf16(p, st);
     if (rc != IVLM_OK) return rc;
     const int64_t total = (int64_t)g.M * (g.N >> 2);
     const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
+    if (route_logged(3, 0, 0, 0, g.out_f32, g.act, blocks, 1, 0)) return IVLM_OK;
     if (g.out_f32) ivlm_launch(splitk_reduce_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, splits, g);
     else ivlm_launch(splitk_reduce_kernel<false>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, splits, g);
     return ivlm_launch_status();
@@ -487,15 +500,12 @@ int gemm_bf16_splitk(const GemmArgs& g, int splits, float* workspace, size_t ws_
 
 // dispatch: weight-streaming GEMV for M <= 8 (wave per row while the activation rows fit LDS, the split-K MFMA skinny
 // kernel of gemv_mfma.hip for the batched decode step: M up to 16 rows against big matrices), MFMA tile kernel otherwise
-static int g_skinny_min_m = 0;  // 0: automatic; > 0: every M in [min_m, 16] with K, N >= 1024 (benchmark hook)
-void gemv_mfma_set_min_m(int m) { g_skinny_min_m = m; }
-
 int linear_bf16(const GemmArgs& g, hipStream_t st) {
     if (g.batch == 1 && g.M <= 16 && g.K >= 1024 && g.N >= 1024 && !(g.K & 7) && !(g.lda & 7) && !(g.ldw & 7) &&
         !(g.act == ACT_SWIGLU && ((g.N & 1) || g.residual))) {
-        const bool skinny = g_skinny_min_m > 0 ? g.M >= g_skinny_min_m
-                                               : (g.M >= 5 || (g.M >= 3 && (size_t)g.M * g.K * 2 > 48 * 1024));
-        // (measured on the LLaMA-7B shapes, tools/bench_skinny.py: the wave-per-row GEMV wins for M <= 4 while its
+        const int min_m = g_gemm_switches.skinny_min_m;
+        const bool skinny = min_m > 0 ? g.M >= min_m : (g.M >= 5 || (g.M >= 3 && (size_t)g.M * g.K * 2 > 48 * 1024));
+        // (measured on the LLaMA-7B shapes, tools/experiments/bench_skinny.py: the wave-per-row GEMV wins for M <= 4 while its
         //  activation rows fit LDS - 5.0-5.7 TB/s at M = 1 - and falls to 0.9-2.5 TB/s at M = 8; this kernel holds
         //  3.4-4.4 TB/s for every M <= 8 and 2.9-3.4 TB/s at M = 16, where the 128x64 tile GEMM reaches 0.7-1.8 TB/s)
         // fp32 activations: exact in the GEMV (fp32 x in LDS) for one row, hi + lo bf16 operand split on the MFMA for more
@@ -522,56 +532,30 @@ int linear_bf16(const GemmArgs& g, hipStream_t st) {
     return gemm_bf16(g, st);
 }
 
-}  // namespace ivlm
-
-static int g_tile_override = 0;
-
-extern "C" int ivlm_gemv_mfma_min_m(int min_m) {  // benchmark/test hook: 0 = automatic choice
-    ivlm::gemv_mfma_set_min_m(min_m);
-    return 0;
-}
-
-extern "C" int ivlm_gemm_nsplit(int on) {  // benchmark hook: column split of under-filled 256 x 256 rounds (default on)
-    ivlm::gemm_set_nsplit(on);
-    return 0;
-}
-
-extern "C" int ivlm_gemm_tile320(int on) {  // benchmark hook: automatic choice of the 256 x 320 tile (default on); returns the previous value
-    const int prev = ivlm::g_tile320;
-    ivlm::g_tile320 = on ? 1 : 0;
-    return prev;
-}
-
-extern "C" int ivlm_gemm_tile_override(int tile) {
-    const int prev = g_tile_override;
-    if (tile == 0 || tile == 64 || tile == 96 || tile == 128 || tile == 256 || tile == 512 || tile == 176 || tile == 320) g_tile_override = tile;
-    return prev;
-}
-
-extern "C" int ivlm_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
-                              const void* bias, const void* residual, int64_t ldr, int res_mod, int M, int N, int K,
-                              int act, int out_f32, int batch, int64_t strideA, int64_t strideW, int64_t strideC,
-                              int64_t strideR, const void* rms_w, float rms_eps, int flags, const int32_t* out_rows,
-                              const int32_t* a_rows, ivlm_stream_t stream) {
-    ivlm_enter();
-    ivlm::GemmArgs g;
-    g.out_rows = out_rows;
-    g.a_rows = a_rows;
-    g.a_f32 = (flags & IVLM_GEMM_A_F32) ? 1 : 0;
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    if (flags & IVLM_GEMM_A_SPLIT) { g.a_split = 1; g.a_lo = K; }
-    if (flags & IVLM_GEMM_OUT_SPLIT) { g.out_split = 1; g.c_lo = act == ivlm::ACT_SWIGLU ? N / 2 : N; out_f32 = 1; }
-    if (flags & IVLM_GEMM_F16) g.f16 = 1;
-    if (flags & IVLM_GEMM_OUT_F16) g.out_f16 = 1;
-    if (flags & IVLM_GEMM_W_PANEL) {
-        if (M <= 16 || (K & 63) || batch > 1) return IVLM_ERR_UNSUPPORTED;
-        g.w_kstep = (int64_t)64 * N;
-        ldw = 64;
+// The split-K rule of the small-M tile GEMMs: the C sequencers and, through ivlm_gemm_splitk_choice, interactvlm_amd/ops.py ask this
+// function - one source of truth.  It encodes the 128 x 64 and 176 x 128 tiles of gemm_route and the skinny boundary of linear_bf16.
+int gemm_splitk_choice(int M, int N, int K, int act, int has_rms) {
+    if (M <= 8 || M > 1024 || act == ACT_SWIGLU || has_rms || (N & 3) || (K & 63)) return 1;
+    if (M <= 16 && N >= 1024 && K >= 1024) return 1;  // the skinny MFMA kernel takes these
+    if (M > 128 && M <= 352 && N >= 8192) {  // the row-stationary 176 x 128 tiles: two K slices when they leave CUs idle
+        const long t176 = (long)((M + 175) / 176) * ((N + 127) / 128);
+        return (t176 < 256 && (K / 64) % 2 == 0 && K / 2 >= 512) ? 2 : 1;
     }
-    if ((g.a_split || g.out_split || g.f16 || g.out_f16) && M <= 16) return IVLM_ERR_UNSUPPORTED;  // tile GEMM path only
-    g.rms_w = static_cast<const bf16_t*>(rms_w);
-    g.rms_eps = rms_eps;
-    g.tile = g_tile_override;
+    const long tiles = (long)((M + 127) / 128) * ((N + 63) / 64);
+    if (tiles >= 256) return 1;
+    int best = 1;
+    const int k64 = K / 64;
+    for (int sp = 2; sp <= std::min<long>(8, 1024 / tiles); ++sp)
+        if (k64 % sp == 0 && K / sp >= 512) best = sp;
+    return best;
+}
+
+// The plain (pointer, stride, shape) description of a GEMM and its IVLM_GEMM_* flags as GemmArgs.  What only one caller has (batch
+// strides, row maps of the panel forms, fp8 scales, the RMSNorm fusion) that caller adds.
+GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* residual,
+                   int64_t ldr, int res_mod, int M, int N, int K, int act, int out_f32, int flags, const int32_t* out_rows,
+                   const int32_t* a_rows) {
+    GemmArgs g;
     g.A = static_cast<const bf16_t*>(A);
     g.W = static_cast<const bf16_t*>(W);
     g.C = C;
@@ -581,7 +565,60 @@ extern "C" int ivlm_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t
     g.res_mod = res_mod;
     g.M = M; g.N = N; g.K = K;
     g.act = act;
+    g.out_rows = out_rows;
+    g.a_rows = a_rows;
+    g.a_f32 = (flags & IVLM_GEMM_A_F32) ? 1 : 0;
+    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
+    g.f16 = (flags & IVLM_GEMM_F16) ? 1 : 0;
+    g.out_f16 = (flags & IVLM_GEMM_OUT_F16) ? 1 : 0;
+    if (flags & IVLM_GEMM_A_SPLIT) { g.a_split = 1; g.a_lo = K; }
+    if (flags & IVLM_GEMM_OUT_SPLIT) { g.out_split = 1; g.c_lo = act == ACT_SWIGLU ? N / 2 : N; out_f32 = 1; }  // (split halves come from the fp32 epilogue)
     g.out_f32 = out_f32;
+    if (flags & IVLM_GEMM_W_PANEL) { g.w_kstep = (int64_t)64 * N; g.ldw = 64; }
+    return g;
+}
+
+}  // namespace ivlm
+
+using ivlm::g_gemm_switches;
+
+extern "C" int ivlm_gemv_mfma_min_m(int min_m) {  // benchmark/test hook: 0 = automatic choice
+    g_gemm_switches.skinny_min_m = min_m;
+    return 0;
+}
+
+extern "C" int ivlm_gemm_nsplit(int on) {  // benchmark hook: column split of under-filled 256 x 256 rounds (default on)
+    g_gemm_switches.nsplit = on;
+    return 0;
+}
+
+extern "C" int ivlm_gemm_tile320(int on) {  // benchmark hook: automatic choice of the 256 x 320 tile (default on); returns the previous value
+    const int prev = g_gemm_switches.tile320;
+    g_gemm_switches.tile320 = on ? 1 : 0;
+    return prev;
+}
+
+extern "C" int ivlm_gemm_tile_override(int tile) {
+    const int prev = g_gemm_switches.tile_override;
+    if (tile == 0 || ivlm::tile_code_ok(tile)) g_gemm_switches.tile_override = tile;
+    return prev;
+}
+
+extern "C" int ivlm_gemm_splitk_choice(int M, int N, int K, int act, int has_rms) {
+    return ivlm::gemm_splitk_choice(M, N, K, act, has_rms);
+}
+
+extern "C" int ivlm_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc,
+                              const void* bias, const void* residual, int64_t ldr, int res_mod, int M, int N, int K,
+                              int act, int out_f32, int batch, int64_t strideA, int64_t strideW, int64_t strideC,
+                              int64_t strideR, const void* rms_w, float rms_eps, int flags, const int32_t* out_rows,
+                              const int32_t* a_rows, ivlm_stream_t stream) {
+    ivlm_enter();
+    ivlm::GemmArgs g = ivlm::gemm_args(A, lda, W, ldw, C, ldc, bias, residual, ldr, res_mod, M, N, K, act, out_f32, flags, out_rows, a_rows);
+    if (g.w_kstep && ((K & 63) || batch > 1)) return IVLM_ERR_UNSUPPORTED;
+    if ((g.a_split || g.out_split || g.f16 || g.out_f16 || g.w_kstep) && M <= 16) return IVLM_ERR_UNSUPPORTED;  // tile GEMM path only
+    g.rms_w = static_cast<const bf16_t*>(rms_w);
+    g.rms_eps = rms_eps;
     g.batch = batch < 1 ? 1 : batch;
     g.strideA = strideA; g.strideW = strideW; g.strideC = strideC; g.strideR = strideR;
     return ivlm::linear_bf16(g, ivlm_stream(stream));
@@ -592,23 +629,11 @@ extern "C" int ivlm_gemm_bf16_panel(const void* A, int64_t lda, int64_t a_kstep,
                                     int K, int act, int out_f32, int flags, const int32_t* out_rows, const int32_t* a_rows,
                                     ivlm_stream_t stream) {
     ivlm_enter();
-    if (M <= 16) return IVLM_ERR_UNSUPPORTED;  // tile GEMM only
-    ivlm::GemmArgs g;
-    g.out_rows = out_rows;
-    g.a_rows = a_rows;
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    if (flags & IVLM_GEMM_A_F32) return IVLM_ERR_UNSUPPORTED;
-    g.tile = g_tile_override;
-    g.A = static_cast<const bf16_t*>(A);
-    g.W = static_cast<const bf16_t*>(W);
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.lda = a_kstep ? 64 : lda; g.ldw = w_kstep ? 64 : ldw; g.ldc = ldc; g.ldr = ldr;
+    if (M <= 16 || (flags & IVLM_GEMM_A_F32)) return IVLM_ERR_UNSUPPORTED;  // tile GEMM only
+    // (bf16 operands and outputs: of the flags, this form knows the fp32 residual only)
+    ivlm::GemmArgs g = ivlm::gemm_args(A, a_kstep ? 64 : lda, W, w_kstep ? 64 : ldw, C, ldc, bias, residual, ldr, 0, M, N, K, act, out_f32,
+                                       flags & IVLM_GEMM_RES_F32, out_rows, a_rows);
     g.a_kstep = a_kstep; g.w_kstep = w_kstep; g.c_panel = c_panel;
-    g.M = M; g.N = N; g.K = K;
-    g.act = act;
-    g.out_f32 = out_f32;
     return ivlm::gemm_bf16(g, ivlm_stream(stream));
 }
 
@@ -618,23 +643,12 @@ extern "C" int ivlm_gemm_fp8(const void* A, int64_t lda, const void* W, int64_t 
                              const int32_t* a_rows, ivlm_stream_t stream) {
     ivlm_enter();
     if ((K & 15) || (lda & 15) || (ldw & 15) || M <= 16) return IVLM_ERR_UNSUPPORTED;  // 16-byte granules; tile GEMM only
-    ivlm::GemmArgs g;
+    // byte matrices seen as 2-byte matrices of half the width (of the flags, this form knows the fp32 residual only)
+    ivlm::GemmArgs g = ivlm::gemm_args(A, lda / 2, W, ldw / 2, C, ldc, bias, residual, ldr, 0, M, N, K / 2, act, out_kind == IVLM_F32,
+                                       flags & IVLM_GEMM_RES_F32, out_rows, a_rows);
     g.fp8 = 1;
     g.out_fp8 = out_kind == 2 ? 1 : 0;
-    g.out_f32 = out_kind == IVLM_F32 ? 1 : 0;
     g.scale_a = scale_a; g.scale_w = scale_w; g.scale_out = scale_out;
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    g.out_rows = out_rows;
-    g.a_rows = a_rows;
-    g.A = static_cast<const bf16_t*>(A);
-    g.W = static_cast<const bf16_t*>(W);
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.lda = lda / 2; g.ldw = ldw / 2; g.ldc = ldc; g.ldr = ldr;  // byte matrices seen as 2-byte matrices of half the width
-    g.M = M; g.N = N; g.K = K / 2;
-    g.act = act;
-    g.tile = g_tile_override;
     return ivlm::gemm_bf16(g, ivlm_stream(stream));
 }
 
@@ -648,31 +662,9 @@ static int splitk_entry(const void* A, int64_t lda, const void* W, int64_t ldw, 
                                      int flags, ivlm_stream_t stream, int32_t* counters) {
     ivlm_enter();
     if (flags & IVLM_GEMM_A_F32) return IVLM_ERR_UNSUPPORTED;
-    ivlm::GemmArgs g;
-    g.res_f32 = (flags & IVLM_GEMM_RES_F32) ? 1 : 0;
-    if (flags & IVLM_GEMM_A_SPLIT) { g.a_split = 1; g.a_lo = K; }
-    if (flags & IVLM_GEMM_OUT_SPLIT) { g.out_split = 1; g.c_lo = N; out_f32 = 1; }
-    if (flags & IVLM_GEMM_F16) g.f16 = 1;
-    if (flags & IVLM_GEMM_OUT_F16) {
-        if (out_f32 && !g.out_split) return IVLM_ERR_INVALID_ARG;
-        g.out_f16 = 1;
-    }
-    if (flags & IVLM_GEMM_W_PANEL) {
-        if (K % (splits * 64) != 0) return IVLM_ERR_UNSUPPORTED;  // (whole panels per K slice)
-        g.w_kstep = (int64_t)64 * N;
-        ldw = 64;
-    }
-    g.tile = g_tile_override;
-    g.A = static_cast<const bf16_t*>(A);
-    g.W = static_cast<const bf16_t*>(W);
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(residual);
-    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr;
-    g.res_mod = res_mod;
-    g.M = M; g.N = N; g.K = K;
-    g.act = act;
-    g.out_f32 = out_f32;
+    if ((flags & IVLM_GEMM_OUT_F16) && out_f32 && !(flags & IVLM_GEMM_OUT_SPLIT)) return IVLM_ERR_INVALID_ARG;
+    if ((flags & IVLM_GEMM_W_PANEL) && K % (splits * 64) != 0) return IVLM_ERR_UNSUPPORTED;  // (whole panels per K slice)
+    const ivlm::GemmArgs g = ivlm::gemm_args(A, lda, W, ldw, C, ldc, bias, residual, ldr, res_mod, M, N, K, act, out_f32, flags, nullptr, nullptr);
     return ivlm::gemm_bf16_splitk(g, splits, static_cast<float*>(workspace), workspace_bytes, ivlm_stream(stream), counters);
 }
 
@@ -693,4 +685,32 @@ extern "C" int ivlm_gemm_bf16_splitk_fused(const void* A, int64_t lda, const voi
     if (!counters) return IVLM_ERR_INVALID_ARG;
     return splitk_entry(A, lda, W, ldw, C, ldc, bias, residual, ldr, res_mod, M, N, K, act, out_f32, splits, workspace, workspace_bytes,
                         flags, stream, counters);
+}
+
+// Test / benchmark hook: the launches one call of an entry point would make, recorded instead of made (see ivlm_hip.h).  The pointers
+// are dummies of the alignment a caller's would have; nothing dereferences them on the host.
+extern "C" int ivlm_gemm_route_query(int entry, int M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int64_t a_kstep,
+                                     int64_t w_kstep, int64_t c_panel, int act, int out_kind, int has_bias, int has_residual,
+                                     int res_mod, int batch, int flags, int has_out_rows, int has_a_rows, int splits,
+                                     int32_t* records, int max_records) {
+    if (!records || max_records < 1 || M <= 16) return IVLM_ERR_INVALID_ARG;  // (M <= 16: the GEMV paths, not routed here)
+    const auto dummy = [](int present, uintptr_t at) { return present ? reinterpret_cast<void*>(at << 16) : nullptr; };
+    const void *A = dummy(1, 1), *W = dummy(1, 2), *bias = dummy(has_bias, 4), *res = dummy(has_residual, 5);
+    void *C = dummy(1, 3), *ws = dummy(1, 8);
+    const int32_t *orow = static_cast<int32_t*>(dummy(has_out_rows, 6)), *arow = static_cast<int32_t*>(dummy(has_a_rows, 7));
+    const float* sc = static_cast<float*>(dummy(1, 9));
+    ivlm::RouteLog log{records, max_records, 0};
+    ivlm::t_route_log = &log;
+    int rc = IVLM_ERR_INVALID_ARG;
+    switch (entry) {
+        case 0: rc = ivlm_gemm_bf16(A, lda, W, ldw, C, ldc, bias, res, ldr, res_mod, M, N, K, act, out_kind, batch, 0, 0, 0, 0, nullptr, 0.f, flags, orow, arow, nullptr); break;
+        case 1: rc = ivlm_gemm_bf16_panel(A, lda, a_kstep, W, ldw, w_kstep, C, ldc, c_panel, bias, res, ldr, M, N, K, act, out_kind, flags, orow, arow, nullptr); break;
+        case 2: rc = ivlm_gemm_fp8(A, lda, W, ldw, C, ldc, bias, res, ldr, M, N, K, act, out_kind, sc, sc, sc, flags, orow, arow, nullptr); break;
+        case 3: rc = ivlm_gemm_bf16_splitk(A, lda, W, ldw, C, ldc, bias, res, ldr, res_mod, M, N, K, act, out_kind, splits, ws, SIZE_MAX, flags, nullptr); break;
+        case 4: rc = ivlm_gemm_bf16_splitk_fused(A, lda, W, ldw, C, ldc, bias, res, ldr, res_mod, M, N, K, act, out_kind, splits, ws, SIZE_MAX, static_cast<int32_t*>(dummy(1, 10)), flags, nullptr); break;
+        default: break;
+    }
+    if (rc != IVLM_OK) ivlm::route_logged(-1, rc, 0, 0, 0, 0, 0, 0, 0);
+    ivlm::t_route_log = nullptr;
+    return log.n <= max_records ? log.n : IVLM_ERR_WORKSPACE;
 }

@@ -25,6 +25,7 @@
 //   * LDS image and swizzle as in gemm.hip: DMA destination is lane-linear, so 16-byte chunk c of local row r is fetched
 //     from source chunk c ^ ((r >> 1) & 7) and read back with the same XOR.
 #include "gemm_common.h"
+#include "gemm_route.h"
 
 namespace ivlm {
 namespace {
@@ -219,50 +220,22 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs g) {
     }
 }
 
-template <int ACT>
-int launch256(const GemmArgs& g, hipStream_t st) {
-    const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
-    dim3 grid(tiles, 1, g.batch);
-#define IVLM_GO(F32, F8)                                                                                         \
-    do {                                                                                                         \
-        auto kfn = gemm256_kernel<ACT, F32, F8>;                                                                 \
-        static ivlm_dev_mask_t attr_set{0};                                                                      \
-        if (ivlm_dev_pending(attr_set)) {                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      kLds256);                                                                  \
-            ivlm_dev_done(attr_set);                                                                             \
-        }                                                                                                        \
-        ivlm_launch(kfn, grid, dim3(512), kLds256, st, g);                                                       \
-    } while (0)
-    if (g.fp8) {
-        if (g.out_f32) IVLM_GO(true, 1); else IVLM_GO(false, 1);
-    } else if (g.f16) {  // (instantiated for the epilogues of the three towers only)
-        if constexpr (ACT == ACT_NONE || ACT == ACT_GELU || ACT == ACT_QUICK_GELU || ACT == ACT_SWIGLU) {
-            if (g.out_f32) IVLM_GO(true, 2); else IVLM_GO(false, 2);
-        } else {
-            return IVLM_ERR_UNSUPPORTED;
-        }
-    } else {
-        if (g.out_f32) IVLM_GO(true, 0); else IVLM_GO(false, 0);
+static_assert(kLds256 == kGemm256LdsBytes, "the route's LDS size is this kernel's");
+struct Go256 {
+    const GemmRoute& r;
+    const GemmArgs& g;
+    hipStream_t st;
+    template <int ACT, int OPK>
+    int run() const {
+        if constexpr (gemm_instantiated(GEMM_256P, 256, 256, OPK, ACT))
+            return gemm_launch<gemm256_kernel<ACT, true, OPK>, gemm256_kernel<ACT, false, OPK>>(r, 512, g, st);
+        return IVLM_ERR_UNSUPPORTED;  // (gemm_route names instantiated kernels only)
     }
-#undef IVLM_GO
-    return ivlm_launch_status();
-}
+};
 
 }  // namespace
 
-// tile-256 8-phase variant (arguments already validated by gemm_bf16)
-int gemm_bf16_256p(const GemmArgs& g, hipStream_t st) {
-    switch (g.act) {
-        case ACT_NONE: return launch256<ACT_NONE>(g, st);
-        case ACT_GELU: return launch256<ACT_GELU>(g, st);
-        case ACT_QUICK_GELU: return launch256<ACT_QUICK_GELU>(g, st);
-        case ACT_RELU: return launch256<ACT_RELU>(g, st);
-        case ACT_SILU: return launch256<ACT_SILU>(g, st);
-        case ACT_SWIGLU: return launch256<ACT_SWIGLU>(g, st);
-        case ACT_SIGMOID: return launch256<ACT_SIGMOID>(g, st);
-        default: return IVLM_ERR_INVALID_ARG;
-    }
-}
+// tile-256 8-phase variant (arguments validated by gemm_bf16, routed by gemm_route)
+int gemm256_launch(const GemmRoute& r, const GemmArgs& g, hipStream_t st) { return gemm_dispatch(r, Go256{r, g, st}); }
 
 }  // namespace ivlm

@@ -20,6 +20,7 @@
 //   * TWO barriers per K tile (phases 1 and 4: they publish what the waits covered and order the restaging behind everyone's
 //     reads) against four in gemm256_kernel.
 #include "gemm_common.h"
+#include "gemm_route.h"
 
 namespace ivlm {
 namespace {
@@ -197,41 +198,22 @@ __global__ __launch_bounds__(512, 2) void gemm320_kernel(GemmArgs g) {
     gemm_store_strip_rows<OUT_F32>(g, strip, wc * 32, 32, mw, n0 + 256, lane);
 }
 
-template <int ACT>
-int launch320(const GemmArgs& g, hipStream_t st) {
-    const int tiles = ((g.M + 255) / 256) * ((g.N + 319) / 320);
-    dim3 grid(tiles, 1, g.batch);
-#define IVLM_GO(F32, OPK)                                                                                        \
-    do {                                                                                                         \
-        auto kfn = gemm320_kernel<ACT, F32, OPK>;                                                                \
-        static ivlm_dev_mask_t attr_set{0};                                                                      \
-        if (ivlm_dev_pending(attr_set)) {                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      kLds320);                                                                  \
-            ivlm_dev_done(attr_set);                                                                             \
-        }                                                                                                        \
-        ivlm_launch(kfn, grid, dim3(512), kLds320, st, g);                                                       \
-    } while (0)
-    if (g.f16) {
-        if (g.out_f32) IVLM_GO(true, 2); else IVLM_GO(false, 2);
-    } else {
-        if (g.out_f32) IVLM_GO(true, 0); else IVLM_GO(false, 0);
+static_assert(kLds320 == kGemm320LdsBytes, "the route's LDS size is this kernel's");
+struct Go320 {
+    const GemmRoute& r;
+    const GemmArgs& g;
+    hipStream_t st;
+    template <int ACT, int OPK>
+    int run() const {
+        if constexpr (gemm_instantiated(GEMM_320, 256, 320, OPK, ACT))
+            return gemm_launch<gemm320_kernel<ACT, true, OPK>, gemm320_kernel<ACT, false, OPK>>(r, 512, g, st);
+        return IVLM_ERR_UNSUPPORTED;  // (gemm_route names instantiated kernels only)
     }
-#undef IVLM_GO
-    return ivlm_launch_status();
-}
+};
 
 }  // namespace
 
-// 256 x 320 tile variant (arguments validated by gemm_bf16; bf16 / fp16 operands, row-major, the epilogues of the SAM encoder)
-int gemm_bf16_320p(const GemmArgs& g, hipStream_t st) {
-    if (g.fp8 || g.out_fp8 || g.a_kstep || g.w_kstep || g.c_panel) return IVLM_ERR_UNSUPPORTED;
-    if (!(g.out_f32 ? gemm_whole_lines_ok<true>(g, g.act) : gemm_whole_lines_ok<false>(g, g.act))) return IVLM_ERR_UNSUPPORTED;
-    switch (g.act) {
-        case ACT_NONE: return launch320<ACT_NONE>(g, st);
-        case ACT_GELU: return launch320<ACT_GELU>(g, st);
-        default: return IVLM_ERR_UNSUPPORTED;
-    }
-}
+// 256 x 320 tile variant (arguments validated by gemm_bf16; gemm_route sends only what its whole-line epilogue covers)
+int gemm320_launch(const GemmRoute& r, const GemmArgs& g, hipStream_t st) { return gemm_dispatch(r, Go320{r, g, st}); }
 
 }  // namespace ivlm

@@ -78,11 +78,15 @@ struct GemmArgs {
     SplitKFused sk;  // (set by gemm_bf16_splitk only)
 };
 
-// bf16 x bf16 -> fp32-accumulate MFMA GEMM with fused bias/activation/residual epilogue.
+// the plain (pointer, stride, shape) description of a GEMM and its IVLM_GEMM_* flags as GemmArgs (gemm.hip): batch 1, no K panels
+// but IVLM_GEMM_W_PANEL, no fp8, no RMSNorm fusion - the caller that has one of those sets it
+GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* residual,
+                   int64_t ldr, int res_mod, int M, int N, int K, int act, int out_f32, int flags, const int32_t* out_rows = nullptr,
+                   const int32_t* a_rows = nullptr);
+// bf16 x bf16 -> fp32-accumulate MFMA GEMM with fused bias/activation/residual epilogue; kernel, tile and grid: gemm_route.h
 int gemm_bf16(const GemmArgs& g, hipStream_t st);
-// 256x256 tile with the 8-phase ping-pong K loop (gemm256.hip); same contract as gemm_bf16
-int gemm_bf16_256p(const GemmArgs& g, hipStream_t st);
-int gemm_bf16_320p(const GemmArgs& g, hipStream_t st);  // 256 x 320 tiles (gemm320.hip)
+// K slices of a small-M tile GEMM (1 = none): the rule of the sequencers and, through ivlm_gemm_splitk_choice, of ops.py
+int gemm_splitk_choice(int M, int N, int K, int act, int has_rms);
 // split-K variant for small M (fp32 partials in `workspace`, >= splits*M*N*4 bytes); act != SWIGLU.  counters != null
 // (kSplitKCounters zeroed int32, left at zero): the reduction is fused into the GEMM launch (SplitKFused), else a second launch
 int gemm_bf16_splitk(const GemmArgs& g, int splits, float* workspace, size_t ws_bytes, hipStream_t st, int32_t* counters = nullptr);
@@ -266,7 +270,6 @@ int llama_attn_oproj(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax,
                      const float* x, float* x_out, int H, int D, float theta, float scale, const float* cos_tab,
                      const float* sin_tab, const int32_t* pos_dev, const int32_t* step_dev, int32_t* counter, int32_t* status,
                      hipStream_t st);
-int gemm_splitk_choice(int M, int N, int K, int act, int has_rms);
 
 // ---- skinny GEMM (gemv.hip): M <= 8 rows of activations against streamed weights -------------------
 int gemv_bf16(const GemmArgs& g, hipStream_t st);

@@ -21,23 +21,6 @@
 
 namespace ivlm {
 
-// the split-K rule of the small-M tile GEMMs (also exported: interactvlm_amd/ops.py asks this function, one source of truth)
-int gemm_splitk_choice(int M, int N, int K, int act, int has_rms) {
-    if (M <= 8 || M > 1024 || act == ACT_SWIGLU || has_rms || (N & 3) || (K & 63)) return 1;
-    if (M <= 16 && N >= 1024 && K >= 1024) return 1;  // the skinny MFMA kernel takes these
-    if (M > 128 && M <= 352 && N >= 8192) {  // the row-stationary 176 x 128 tiles (gemm.hip): two K slices when they leave CUs idle
-        const long t176 = (long)((M + 175) / 176) * ((N + 127) / 128);
-        return (t176 < 256 && (K / 64) % 2 == 0 && K / 2 >= 512) ? 2 : 1;
-    }
-    const long tiles = (long)((M + 127) / 128) * ((N + 63) / 64);
-    if (tiles >= 256) return 1;
-    int best = 1;
-    const int k64 = K / 64;
-    for (int sp = 2; sp <= std::min<long>(8, 1024 / tiles); ++sp)
-        if (k64 % sp == 0 && K / sp >= 512) best = sp;
-    return best;
-}
-
 namespace {
 
 inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -78,62 +61,59 @@ size_t carved_bytes(Carve carve, Args... args) {
 // When it is on, the arrival counters live in the LAST 16 KB of a sequencer's split-K region: every stage call zeroes them once
 // (sk_counters_zero, right after the region is carved) and the GEMMs leave them at zero; a product whose partials would reach into
 // them takes the two-launch form on the region BELOW the counters (sk_partial_bytes), so the partials can never overwrite them.
-int g_sk_fused = -1;  // -1: not read yet
+// Every sequencer reads the switch ONCE, into the SkRegion it hands to its GEMMs: the counters it zeroed (or did not) are the ones its
+// GEMMs count on (or do not), whatever the switch does meanwhile.
+std::atomic<int> g_sk_fused{-1};  // -1: not read yet
 bool sk_fused_on() {
-    if (g_sk_fused < 0) {
+    int v = g_sk_fused.load(std::memory_order_relaxed);
+    if (v < 0) {
         const char* e = getenv("IVLM_SPLITK_FUSED");
-        g_sk_fused = (e && e[0] == '1' && e[1] == 0) ? 1 : 0;
+        const int env = (e && e[0] == '1' && e[1] == 0) ? 1 : 0;
+        if (g_sk_fused.compare_exchange_strong(v, env)) v = env;  // (else: another thread or the hook set it first - v holds that)
     }
-    return g_sk_fused == 1;
+    return v == 1;
 }
+struct SkRegion {  // a stage call's split-K workspace (none: no split-K) and its snapshot of the switch
+    float* ws = nullptr;
+    size_t bytes = 0;
+    bool fused = false;
+};
 constexpr size_t kSkCounterBytes = (size_t)kSplitKCounters * 4;
-int32_t* sk_counters(float* sk, size_t skb, size_t partial_bytes) {
-    if (!sk_fused_on() || !sk || skb < partial_bytes + kSkCounterBytes + 16) return nullptr;
-    return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(sk) + ((skb - kSkCounterBytes) & ~(size_t)15));
+int32_t* sk_counters(const SkRegion& sk, size_t partial_bytes) {
+    if (!sk.fused || !sk.ws || sk.bytes < partial_bytes + kSkCounterBytes + 16) return nullptr;
+    return reinterpret_cast<int32_t*>(reinterpret_cast<char*>(sk.ws) + ((sk.bytes - kSkCounterBytes) & ~(size_t)15));
 }
 // bytes of the region the PARTIALS may use: everything when the fused form is off, the part below the counters when it is on
-size_t sk_partial_bytes(size_t skb) {
-    if (!sk_fused_on() || skb < kSkCounterBytes + 16) return skb;
-    return (skb - kSkCounterBytes) & ~(size_t)15;
+size_t sk_partial_bytes(const SkRegion& sk) {
+    if (!sk.fused || sk.bytes < kSkCounterBytes + 16) return sk.bytes;
+    return (sk.bytes - kSkCounterBytes) & ~(size_t)15;
 }
-int sk_counters_zero(float* sk, size_t skb, hipStream_t st);
-// one split-K product of a sequencer: fused when the switch is on and the partials stay below the counters, else the two-launch
-// form - on the region below the counters, or (partials larger than that) on the whole region with the counters re-zeroed after
-int sk_gemm(const GemmArgs& g, int sp, float* sk, size_t skb, hipStream_t st) {
-    const size_t pb = (size_t)sp * g.M * g.N * 4;
-    int32_t* c = sk_counters(sk, skb, pb);
-    if (c) return gemm_bf16_splitk(g, sp, sk, skb, st, c);
-    if (pb <= sk_partial_bytes(skb)) return gemm_bf16_splitk(g, sp, sk, sk_partial_bytes(skb), st, nullptr);
-    if (int rc = gemm_bf16_splitk(g, sp, sk, skb, st, nullptr)) return rc;
-    return sk_counters_zero(sk, skb, st);  // (only reachable with the switch on: the partials ran over the counter words)
-}
-int sk_counters_zero(float* sk, size_t skb, hipStream_t st) {
-    int32_t* c = sk_counters(sk, skb, 0);
+int sk_counters_zero(const SkRegion& sk, hipStream_t st) {
+    int32_t* c = sk_counters(sk, 0);
     if (c) IVLM_HIP_TRY(hipMemsetAsync(c, 0, kSkCounterBytes, st));
     return IVLM_OK;
 }
+// one split-K product of a sequencer: fused when the switch is on and the partials stay below the counters, else the two-launch
+// form - on the region below the counters, or (partials larger than that) on the whole region with the counters re-zeroed after
+int sk_gemm(const GemmArgs& g, int sp, const SkRegion& sk, hipStream_t st) {
+    const size_t pb = (size_t)sp * g.M * g.N * 4;
+    int32_t* c = sk_counters(sk, pb);
+    if (c) return gemm_bf16_splitk(g, sp, sk.ws, sk.bytes, st, c);
+    if (pb <= sk_partial_bytes(sk)) return gemm_bf16_splitk(g, sp, sk.ws, sk_partial_bytes(sk), st, nullptr);
+    if (int rc = gemm_bf16_splitk(g, sp, sk.ws, sk.bytes, st, nullptr)) return rc;
+    return sk_counters_zero(sk, st);  // (only reachable with the switch on: the partials ran over the counter words)
+}
 
-int lin(const void* A, int a_f32, int64_t lda, const void* W, int64_t ldw, void* C, int out_f32, int64_t ldc, const void* res,
-        int res_f32, int M, int N, int K, int act, const void* rms_w, float eps, float* splitk_ws, size_t splitk_bytes,
-        hipStream_t st, int f16 = 0, int out_f16 = 0) {
-    GemmArgs g;
-    g.f16 = f16;          // A and W are IEEE halves (the fp16-operand prefill)
-    g.out_f16 = out_f16;  // a 16-bit output is written as IEEE halves
-    g.A = static_cast<const bf16_t*>(A);
-    g.a_f32 = a_f32;
-    g.W = static_cast<const bf16_t*>(W);
-    g.C = C;
-    g.residual = static_cast<const bf16_t*>(res);
-    g.res_f32 = res_f32;
-    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = N;
-    g.M = M; g.N = N; g.K = K;
-    g.act = act;
-    g.out_f32 = out_f32;
+// the linears of the LLaMA stages; flags: IVLM_GEMM_A_F32 / RES_F32 / F16 (A and W are IEEE halves: the fp16-operand prefill) /
+// OUT_F16 (a 16-bit output is written as IEEE halves)
+int lin(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int out_f32, int64_t ldc, const void* res, int M, int N, int K,
+        int act, const void* rms_w, float eps, const SkRegion& sk, hipStream_t st, int flags) {
+    GemmArgs g = gemm_args(A, lda, W, ldw, C, ldc, nullptr, res, N, 0, M, N, K, act, out_f32, flags);
     g.rms_w = static_cast<const bf16_t*>(rms_w);
     g.rms_eps = eps;
-    const int sp = a_f32 ? 1 : gemm_splitk_choice(M, N, K, act, rms_w != nullptr);
+    const int sp = g.a_f32 ? 1 : gemm_splitk_choice(M, N, K, act, rms_w != nullptr);
     if (sp > 1 && (ldc & 3) == 0)
-        return sk_gemm(g, sp, splitk_ws, splitk_bytes, st);
+        return sk_gemm(g, sp, sk, st);
     return linear_bf16(g, st);
 }
 
@@ -149,12 +129,8 @@ using namespace ivlm;
 
 extern "C" int ivlm_stages_splitk_fused(int on) {
     const int prev = sk_fused_on() ? 1 : 0;
-    if (on == 0 || on == 1) g_sk_fused = on;
+    if (on == 0 || on == 1) g_sk_fused.store(on, std::memory_order_relaxed);
     return prev;
-}
-
-extern "C" int ivlm_gemm_splitk_choice(int M, int N, int K, int act, int has_rms) {
-    return gemm_splitk_choice(M, N, K, act, has_rms);
 }
 
 static bool cfg_ok(const ivlm_llama_cfg* c) {
@@ -187,11 +163,13 @@ static int llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers
         pos0 + T > c->max_len)
         return IVLM_ERR_INVALID_ARG;
     Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    auto [y, qkv, att, hh, xa, xb, sk, skb] = carve_prefill(c, T, cv);
+    auto [y, qkv, att, hh, xa, xb, skw, skb] = carve_prefill(c, T, cv);
     if (!cv.ok) return IVLM_ERR_WORKSPACE;
+    const SkRegion sk{skw, skb, sk_fused_on()};
     hipStream_t st = ivlm_stream(stream);
     const int Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter;
-    if (int rc0 = sk_counters_zero(sk, skb, st)) return rc0;
+    if (int rc0 = sk_counters_zero(sk, st)) return rc0;
+    const int in16 = f16 ? IVLM_GEMM_F16 : 0, io16 = f16 ? IVLM_GEMM_F16 | IVLM_GEMM_OUT_F16 : 0;  // fp16 operands (and 16-bit outputs)
     const int64_t cache_layer = (int64_t)c->max_len * Hd;
     const float* x = x_in;
     int rc;
@@ -200,7 +178,7 @@ static int llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers
         bf16_t* kc = static_cast<bf16_t*>(kcache) + l * cache_layer;
         bf16_t* vc = static_cast<bf16_t*>(vcache) + l * cache_layer;
         if ((rc = rmsnorm(x, 1, static_cast<const bf16_t*>(L.ln1), y, f16 ? 4 : 0, T, Hd, c->eps, st))) return rc;
-        if ((rc = lin(y, 0, Hd, L.qkv, Hd, qkv, 0, 3 * Hd, nullptr, 0, T, 3 * Hd, Hd, ACT_NONE, nullptr, 0.f, sk, skb, st, f16, f16))) return rc;
+        if ((rc = lin(y, Hd, L.qkv, Hd, qkv, 0, 3 * Hd, nullptr, T, 3 * Hd, Hd, ACT_NONE, nullptr, 0.f, sk, st, io16))) return rc;
         if ((rc = rope_kv(qkv, 3 * Hd, T, H, D, pos0, c->theta, kc, vc, st, cos_tab, sin_tab, f16))) return rc;
         AttnArgs a{};
         a.f16 = f16;
@@ -215,11 +193,11 @@ static int llama_prefill(const ivlm_llama_cfg* c, const ivlm_llama_layer* layers
         a.kv_batch_div = 1; a.prescale_q = 0;
         if ((rc = attention_bf16(a, st))) return rc;
         float* x1 = (x == xa) ? xb : xa;
-        if ((rc = lin(att, 0, Hd, L.o, Hd, x1, 1, Hd, x, 1, T, Hd, Hd, ACT_NONE, nullptr, 0.f, sk, skb, st, f16, 0))) return rc;
+        if ((rc = lin(att, Hd, L.o, Hd, x1, 1, Hd, x, T, Hd, Hd, ACT_NONE, nullptr, 0.f, sk, st, in16 | IVLM_GEMM_RES_F32))) return rc;
         if ((rc = rmsnorm(x1, 1, static_cast<const bf16_t*>(L.ln2), y, f16 ? 4 : 0, T, Hd, c->eps, st))) return rc;
-        if ((rc = lin(y, 0, Hd, L.gu, Hd, hh, 0, I, nullptr, 0, T, 2 * I, Hd, ACT_SWIGLU, nullptr, 0.f, sk, skb, st, f16, f16))) return rc;
+        if ((rc = lin(y, Hd, L.gu, Hd, hh, 0, I, nullptr, T, 2 * I, Hd, ACT_SWIGLU, nullptr, 0.f, sk, st, io16))) return rc;
         float* x2 = (x1 == xa) ? xb : xa;
-        if ((rc = lin(hh, 0, I, L.down, I, x2, 1, Hd, x1, 1, T, Hd, I, ACT_NONE, nullptr, 0.f, sk, skb, st, f16, 0))) return rc;
+        if ((rc = lin(hh, I, L.down, I, x2, 1, Hd, x1, T, Hd, I, ACT_NONE, nullptr, 0.f, sk, st, in16 | IVLM_GEMM_RES_F32))) return rc;
         x = x2;
     }
     return rmsnorm(x, 1, static_cast<const bf16_t*>(final_norm), hidden_out, 1, T, Hd, c->eps, st);
@@ -260,8 +238,8 @@ DecodeBufs carve_decode(const ivlm_llama_cfg* c, Carver& cv) {
 // RMSNorm prologue or null; SwiGLU: N = 2 * inter interleaved gate / up rows -> inter outputs): on a bf16 matrix ...
 int dec_linear(const ivlm_llama_cfg* c, const float* x, const void* W, float* out, const float* res, int N, int K, int act,
                const void* rms, ivlm_stream_t stream) {
-    return lin(x, 1, K, W, K, out, 1, act == ACT_SWIGLU ? N / 2 : N, res, res ? 1 : 0, 1, N, K, act, rms, rms ? c->eps : 0.f, nullptr, 0,
-               ivlm_stream(stream));
+    return lin(x, K, W, K, out, 1, act == ACT_SWIGLU ? N / 2 : N, res, 1, N, K, act, rms, rms ? c->eps : 0.f, SkRegion{}, ivlm_stream(stream),
+               IVLM_GEMM_A_F32 | (res ? IVLM_GEMM_RES_F32 : 0));
 }
 // ... or on a losslessly packed one
 int dec_linear(const ivlm_llama_cfg* c, const float* x, const ivlm_bf12m& m, float* out, const float* res, int N, int K, int act,
@@ -415,30 +393,12 @@ __global__ void fill_pad_rows_kernel(bf16_t* __restrict__ dst, int64_t ldd, cons
 // IVLM_GEMM_F16 (A and W are IEEE halves), IVLM_GEMM_OUT_F16 (a 16-bit output is written as IEEE halves)
 int gemm(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int out_f32, int64_t ldc, const void* bias,
          const void* res, int res_f32, int64_t ldr, int res_mod, int M, int N, int K, int act, const int32_t* out_rows,
-         const int32_t* a_rows, float* sk, size_t skb, hipStream_t st, int flags = 0) {
-    GemmArgs g;
-    g.f16 = (flags & IVLM_GEMM_F16) != 0;
-    g.out_f16 = (flags & IVLM_GEMM_OUT_F16) != 0;
-    g.a_split = (flags & IVLM_GEMM_A_SPLIT) != 0;
-    g.a_lo = g.a_split ? K : 0;
-    g.out_split = (flags & IVLM_GEMM_OUT_SPLIT) != 0;
-    g.c_lo = g.out_split ? N : 0;
-    g.A = static_cast<const bf16_t*>(A);
-    g.W = static_cast<const bf16_t*>(W);
-    g.C = C;
-    g.bias = static_cast<const bf16_t*>(bias);
-    g.residual = static_cast<const bf16_t*>(res);
-    g.res_f32 = res_f32;
-    g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr;
-    g.res_mod = res_mod;
-    g.M = M; g.N = N; g.K = K;
-    g.act = act;
-    g.out_f32 = out_f32 || g.out_split;  // (split halves come from the fp32 epilogue)
-    g.out_rows = out_rows;
-    g.a_rows = a_rows;
+         const int32_t* a_rows, const SkRegion& sk, hipStream_t st, int flags = 0) {
+    const GemmArgs g = gemm_args(A, lda, W, ldw, C, ldc, bias, res, ldr, res_mod, M, N, K, act, out_f32,
+                                 flags | (res_f32 ? IVLM_GEMM_RES_F32 : 0), out_rows, a_rows);
     const int sp = (out_rows || a_rows) ? 1 : gemm_splitk_choice(M, N, K, act, 0);
-    if (sp > 1 && (ldc & 3) == 0 && sk && skb >= (size_t)sp * M * N * 4)
-        return sk_gemm(g, sp, sk, skb, st);
+    if (sp > 1 && (ldc & 3) == 0 && sk.ws && sk.bytes >= (size_t)sp * M * N * 4)
+        return sk_gemm(g, sp, sk, st);
     return linear_bf16(g, st);
 }
 
@@ -484,17 +444,18 @@ static int clip_encode(const ivlm_clip_cfg* c, const ivlm_clip_head* hd, const i
     ivlm_enter();
     if (!c || !hd || !layers_host || !images || !features_out || !workspace || B <= 0) return IVLM_ERR_INVALID_ARG;
     Carver cv{static_cast<char*>(workspace), workspace_bytes};
-    auto [cols, xa, xb, y, qkv, att, hh, sk, skb] = carve_clip(c, B, cv);
+    auto [cols, xa, xb, y, qkv, att, hh, skw, skb] = carve_clip(c, B, cv);
     if (!cv.ok) return IVLM_ERR_WORKSPACE;
+    const SkRegion sk{skw, skb, sk_fused_on()};
     hipStream_t st = ivlm_stream(stream);
     const int T = c->tokens, Hd = c->hidden, H = c->heads, D = Hd / H, I = c->inter, R = B * T;
-    if (int rc0 = sk_counters_zero(sk, skb, st)) return rc0;
+    if (int rc0 = sk_counters_zero(sk, st)) return rc0;
     int rc;
     if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), cols, B, 3, c->image_size, c->image_size, c->patch, c->patch, c->kpad, st))) return rc;
     for (int b = 0; b < B; ++b) {  // patch GEMM writes rows 1..T-1 (+ their position embeddings); row 0 = class + position 0
         float* xrow = xa + (size_t)b * T * Hd;
         if ((rc = gemm(cols + (size_t)b * (T - 1) * c->kpad, c->kpad, hd->patch_w, c->kpad, xrow + Hd, 1, Hd, nullptr,
-                       static_cast<const bf16_t*>(hd->pos) + Hd, 0, Hd, 0, T - 1, Hd, c->kpad, ACT_NONE, nullptr, nullptr, sk, skb, st)))
+                       static_cast<const bf16_t*>(hd->pos) + Hd, 0, Hd, 0, T - 1, Hd, c->kpad, ACT_NONE, nullptr, nullptr, sk, st)))
             return rc;
         if ((rc = gather_rows(xrow, 1, Hd, hd->cls_row, 1, Hd, nullptr, nullptr, 0, 0, 1, Hd, st))) return rc;
     }
@@ -505,14 +466,14 @@ static int clip_encode(const ivlm_clip_cfg* c, const ivlm_clip_head* hd, const i
     for (int l = 0; l < c->layers_run; ++l) {
         const ivlm_clip_layer& L = layers_host[l];
         if ((rc = layernorm(x, 1, static_cast<const bf16_t*>(L.ln1_w), static_cast<const bf16_t*>(L.ln1_b), y, k16, R, Hd, c->eps, st))) return rc;
-        if ((rc = gemm(y, Hd, L.qkv_w, Hd, qkv, 0, 3 * Hd, L.qkv_b, nullptr, 0, 0, 0, R, 3 * Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, io16))) return rc;
+        if ((rc = gemm(y, Hd, L.qkv_w, Hd, qkv, 0, 3 * Hd, L.qkv_b, nullptr, 0, 0, 0, R, 3 * Hd, Hd, ACT_NONE, nullptr, nullptr, sk, st, io16))) return rc;
         if ((rc = attend(qkv, nullptr, qkv + Hd, nullptr, qkv + 2 * Hd, nullptr, 3 * Hd, att, Hd, f16, B, H, T, D, nullptr, nullptr, 0, st))) return rc;
         float* x1 = (x == xa) ? xb : xa;
-        if ((rc = gemm(att, Hd, L.out_w, Hd, x1, 1, Hd, L.out_b, x, 1, Hd, 0, R, Hd, Hd, ACT_NONE, nullptr, nullptr, sk, skb, st, in16))) return rc;
+        if ((rc = gemm(att, Hd, L.out_w, Hd, x1, 1, Hd, L.out_b, x, 1, Hd, 0, R, Hd, Hd, ACT_NONE, nullptr, nullptr, sk, st, in16))) return rc;
         if ((rc = layernorm(x1, 1, static_cast<const bf16_t*>(L.ln2_w), static_cast<const bf16_t*>(L.ln2_b), y, k16, R, Hd, c->eps, st))) return rc;
-        if ((rc = gemm(y, Hd, L.fc1_w, Hd, hh, 0, I, L.fc1_b, nullptr, 0, 0, 0, R, I, Hd, ACT_QUICK_GELU, nullptr, nullptr, sk, skb, st, io16))) return rc;
+        if ((rc = gemm(y, Hd, L.fc1_w, Hd, hh, 0, I, L.fc1_b, nullptr, 0, 0, 0, R, I, Hd, ACT_QUICK_GELU, nullptr, nullptr, sk, st, io16))) return rc;
         float* x2 = (x1 == xa) ? xb : xa;
-        if ((rc = gemm(hh, I, L.fc2_w, I, x2, 1, Hd, L.fc2_b, x1, 1, Hd, 0, R, Hd, I, ACT_NONE, nullptr, nullptr, sk, skb, st, in16))) return rc;
+        if ((rc = gemm(hh, I, L.fc2_w, I, x2, 1, Hd, L.fc2_b, x1, 1, Hd, 0, R, Hd, I, ACT_NONE, nullptr, nullptr, sk, st, in16))) return rc;
         x = x2;
     }
     // drop the CLS row of every image, fp32 stream -> bf16 features (the mm_projector's operand); fp16 mode: [hi | lo] bf16 rows
@@ -643,7 +604,7 @@ int sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_bl
     auto mm = [&](const void* A, int64_t lda, const void* W, void* C, int64_t ldc, const void* bias, float* res, int N, int K, int act,
                   const int32_t* out_rows, const int32_t* a_rows, int flags) {
         return gemm(A, lda, W, K, C, res != nullptr, ldc, bias, res, res != nullptr, res ? D : 0, 0, R, N, K, act, out_rows, a_rows,
-                    nullptr, 0, st, flags);
+                    SkRegion{}, st, flags);
     };
     auto wide = [](int flags, int split_flag, int n) { return (flags & split_flag) ? 2 * n : n; };  // row width of a GEMM operand
     // dst[r] = [bias | 0] (width elements) at every padded window position r
@@ -660,7 +621,7 @@ int sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_bl
     sam_window_maps_kernel<<<256, 256, 0, st>>>(V, g, wsz, d.nw, b.part, b.unpart);
     if ((rc = ivlm_launch_status())) return rc;
     if ((rc = im2col_nchw(static_cast<const bf16_t*>(images), b.cols, V, 3, c->img_size, c->img_size, c->patch, c->patch, Kp, st))) return rc;
-    if ((rc = gemm(b.cols, Kp, hd->patch_w, Kp, b.x, 1, D, hd->patch_b, hd->pos_embed, 0, D, d.g2, R, D, Kp, ACT_NONE, nullptr, nullptr, nullptr, 0, st))) return rc;
+    if ((rc = gemm(b.cols, Kp, hd->patch_w, Kp, b.x, 1, D, hd->patch_b, hd->pos_embed, 0, D, d.g2, R, D, Kp, ACT_NONE, nullptr, nullptr, SkRegion{}, st))) return rc;
     float* x = b.x;
     const int64_t lx = m.attn == ATT_BF16 ? D : 2 * D;  // row width of norm1's output
     for (int l = 0; l < c->depth; ++l) {
@@ -699,9 +660,8 @@ int sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_bl
         } else if (m.attn == ATT_BF16 && side >= 32) {  // one batched GEMM over the heads against rel_cat + Toeplitz gather
             rh = b.relh_g; rw = b.relw_g;
             const int M = nb * S;
-            GemmArgs gg;
-            gg.A = q; gg.lda = rs; gg.W = static_cast<const bf16_t*>(Bk.rel_cat); gg.ldw = hdim; gg.C = b.G; gg.ldc = d.npad;
-            gg.M = M; gg.N = d.npad; gg.K = hdim; gg.batch = H; gg.strideA = hdim; gg.strideW = 0; gg.strideC = (int64_t)M * d.npad;
+            GemmArgs gg = gemm_args(q, rs, Bk.rel_cat, hdim, b.G, d.npad, nullptr, nullptr, 0, 0, M, d.npad, hdim, ACT_NONE, 0, 0);
+            gg.batch = H; gg.strideA = hdim; gg.strideW = 0; gg.strideC = (int64_t)M * d.npad;
             if ((rc = linear_bf16(gg, st))) return rc;
             if ((rc = ivlm_relpos_gather(b.G, (int64_t)M * d.npad, d.npad, nb, H, side, side, b.relh_g, rw, stream))) return rc;
         } else {  // the dot kernel (ATT_SPLIT: on q = hi + lo)
@@ -727,11 +687,11 @@ int sam_encode(const ivlm_sam_cfg* c, const ivlm_sam_head* hd, const ivlm_sam_bl
     // neck: 1x1 conv, LayerNorm2d, 3x3 conv, LayerNorm2d - on bf16 operands, or on [hi | lo] operands with fp32 conv outputs
     const int sp = m.split_neck ? 1 : 0, nf = sp ? kSplitA : 0, nw_ = sp ? 2 * OC : OC;  // nw_: row width of the LayerNorm2d output
     if ((rc = gather_rows(b.xn, sp ? 2 : 0, sp ? 2 * D : D, x, 1, D, nullptr, nullptr, 0, 0, R, D, st))) return rc;
-    if ((rc = gemm(b.xn, sp ? 2 * D : D, hd->neck0_w, D, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, nullptr, 0, st, nf))) return rc;
+    if ((rc = gemm(b.xn, sp ? 2 * D : D, hd->neck0_w, D, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, D, ACT_NONE, nullptr, nullptr, SkRegion{}, st, nf))) return rc;
     if ((rc = ln(b.n0, sp, hd->neck1_w, hd->neck1_b, b.n1, sp ? 2 : 0, OC))) return rc;
     for (int half = 0; half <= sp; ++half)  // (the hi and the lo halves are gathered separately)
         if ((rc = im2col3x3_nhwc(b.n1 + half * OC, b.c3 + half * 9 * OC, V, g, g, OC, st, nw_, 9 * nw_))) return rc;
-    if ((rc = gemm(b.c3, 9 * nw_, hd->neck2_w, 9 * OC, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, nullptr, 0, st, nf))) return rc;
+    if ((rc = gemm(b.c3, 9 * nw_, hd->neck2_w, 9 * OC, b.n0, sp, OC, nullptr, nullptr, 0, 0, 0, R, OC, 9 * OC, ACT_NONE, nullptr, nullptr, SkRegion{}, st, nf))) return rc;
     return ln(b.n0, sp, hd->neck3_w, hd->neck3_b, embeddings_out, 1, OC);
 }
 
@@ -787,8 +747,7 @@ struct DecCtx {
     hipStream_t st;
     ivlm_stream_t stream;
     Carver* cv;
-    float* sk;
-    size_t skb;
+    SkRegion sk;
     int rc = 0;
     void* take(size_t b) {
         void* p = cv->take(b);
@@ -810,7 +769,7 @@ struct DecCtx {
     // act(x_split . [W|W]^T + bias) + residual -> fp32 [M, N]
     float* lin(const bf16_t* xs, const ivlm_lin& L, int M, int act, const float* res, float* dst = nullptr) {
         float* o = dst ? dst : static_cast<float*>(take((size_t)M * L.n * 4));
-        if (o && !rc) rc = gemm(xs, 2 * L.k, L.w2, 2 * L.k, o, 1, L.n, L.b, res, 1, L.n, 0, M, L.n, 2 * L.k, act, nullptr, nullptr, sk, skb, st);
+        if (o && !rc) rc = gemm(xs, 2 * L.k, L.w2, 2 * L.k, o, 1, L.n, L.b, res, 1, L.n, 0, M, L.n, 2 * L.k, act, nullptr, nullptr, sk, st);
         return o;
     }
     float* norm(const float* x, const void* w, const void* b, int64_t rows, int cols, float eps, int gelu = 0) {
@@ -858,10 +817,11 @@ extern "C" int ivlm_sam_decode(const ivlm_sam_dec* w, int V, int grid, int n_tex
     Carver cv{static_cast<char*>(workspace), workspace_bytes};
     DecCtx x;
     x.st = st; x.stream = stream; x.cv = &cv;
-    x.skb = (size_t)8 * V * Nt * std::max(w->layers[0].lin1.n, C) * 4;
-    x.sk = static_cast<float*>(x.take(x.skb));
-    if (x.sk) {
-        if (int rc0 = sk_counters_zero(x.sk, x.skb, st)) return rc0;
+    x.sk.bytes = (size_t)8 * V * Nt * std::max(w->layers[0].lin1.n, C) * 4;
+    x.sk.ws = static_cast<float*>(x.take(x.sk.bytes));
+    x.sk.fused = sk_fused_on();
+    if (x.sk.ws) {
+        if (int rc0 = sk_counters_zero(x.sk, st)) return rc0;
     }
     // tokens = [iou token ; mask tokens ; text embeds], the same set for every view
     float* tokens = static_cast<float*>(x.take((size_t)Nt * C * 4));

@@ -5,6 +5,7 @@ requires CUDA(HIP) tensors and raises if the extension is missing — there is n
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import torch
@@ -347,22 +348,16 @@ def _splitk_counters(device):
 
 
 def _splitk_choice(M, N, K, act, rms):
-    """number of K slices (1 = plain kernel): only where the 128x64 tiling leaves most of the 256 CUs idle."""
-    if not SPLITK or M <= 8 or M > 1024 or act == "swiglu" or rms is not None or N % 4 or K % 64:
+    """number of K slices (1 = plain kernel): only where the tiling leaves most of the 256 CUs idle.  The rule is the library's
+    (gemm_splitk_choice in csrc/gemm.hip, the one the C sequencers use)."""
+    if not SPLITK:
         return 1
-    if M <= 16 and N >= 1024 and K >= 1024:
-        return 1  # the skinny split-K MFMA kernel (csrc/gemv_mfma.hip) takes these
-    if 128 < M <= 352 and N >= 8192:  # the row-stationary 176 x 128 tiles (gemm.hip): two K slices when they leave CUs idle
-        t176 = ((M + 175) // 176) * ((N + 127) // 128)
-        return 2 if (t176 < 256 and (K // 64) % 2 == 0 and K // 2 >= 512) else 1
-    tiles = ((M + 127) // 128) * ((N + 63) // 64)
-    if tiles >= 256:
-        return 1
-    best, k64 = 1, K // 64
-    for sp in range(2, min(8, 1024 // tiles) + 1):
-        if k64 % sp == 0 and K // sp >= 512:
-            best = sp
-    return best
+    return _splitk_rule(M, N, K, ACT[act], 0 if rms is None else 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _splitk_rule(M, N, K, act, has_rms):
+    return _lib.load().ivlm_gemm_splitk_choice(M, N, K, act, has_rms)
 
 
 GEMM_A_F32, GEMM_RES_F32, GEMM_A_SPLIT, GEMM_OUT_SPLIT, GEMM_F16, GEMM_OUT_F16, GEMM_W_PANEL = 1, 2, 4, 8, 16, 32, 64

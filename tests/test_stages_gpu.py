@@ -83,6 +83,31 @@ def test_llama_prefill_and_decode_step_equal_python_path(hip_lib, cuda, hidden, 
     assert rc == -2
 
 
+def test_llama_prefill_equals_python_path_under_a_forced_tile(hip_lib, cuda):
+    """ivlm_gemm_tile_override applies to the GEMMs inside the C sequencer as it does to the Python-sequenced ones (the tile is
+    resolved in gemm_route, not by the callers that fill the arguments): the prefill of 41 rows - tile GEMMs, M > 16 - with the
+    128 x 64 tile forced, C sequencer against Python path, hidden states and KV cache bit for bit."""
+    import torch
+
+    from interactvlm_amd import llava, stages
+    from interactvlm_amd import weights as Wt
+
+    lc = Wt.LlamaCfg(hidden=256, layers=3, heads=2, inter=512, vocab=1000)
+    w = {k: v.to(torch.bfloat16).float() for k, v in Wt.synth_weights(Wt.llama_spec(lc)).items()}
+    T0 = 41
+    emb = (torch.randn(T0, 256, generator=torch.Generator().manual_seed(5)) * 0.5).to(torch.bfloat16).float().to(cuda)
+    a, b = llava.Llama(w, lc, cuda, max_len=512), llava.Llama(w, lc, cuda, max_len=512)
+    prev = hip_lib.ivlm_gemm_tile_override(64)
+    try:
+        ha = a.forward(emb, 0)
+        hb = stages.LlamaStages(b).prefill(emb, 0)
+        torch.cuda.synchronize()
+    finally:
+        hip_lib.ivlm_gemm_tile_override(prev)
+    assert torch.equal(hb, ha), float((hb - ha).abs().max())
+    assert torch.equal(b.kcache[:, :T0], a.kcache[:, :T0]) and torch.equal(b.vcache[:, :T0], a.vcache[:, :T0])
+
+
 def test_clip_encode_stage_equals_python_path(hip_lib, cuda):
     import torch
 
