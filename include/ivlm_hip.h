@@ -462,6 +462,24 @@ int ivlm_llama_decode_attn_batch_split(const void *qkv, int64_t ldq, void *kcach
                                        const int32_t *pos_dev, float theta, float scale, const float *cos_tab,
                                        const float *sin_tab, ivlm_stream_t stream);
 
+/* Test hook: the argument check and the routing of ONE call of the decode-attention family, recorded instead of launched - nothing is
+ * launched, no GPU is needed.  form: 0 one block (ivlm_llama_decode_attn[_f16|_split]), 1 batched (.._batch[_f16|_split]), 2 split KV,
+ * 3 parts, 4 shared prefix, 5 verify (B = k), 6 fused attention + o_proj (cus = the compute units its grid must fit, > 0).  io_dtype,
+ * cache_f16, the strides, tmax, B, H, D and the host pos are the described call's (the one-sequence forms: B = 1, strides 0);
+ * `present` has one bit per pointer the call gives, from bit 0: qkv, kcache, vcache, o, pos_dev, prefix_len_dev, kcache_lo, vcache_lo,
+ * cos_tab, sin_tab, scratch, wo, x, x_out, step_dev, counter, status (a clear bit is a NULL pointer; the lo bits make a hi + lo cache);
+ * the scratch (split-KV scratch, parts buffer, prefix partials, the fused launch's attention row) is a 1 MiB-aligned dummy +
+ * scratch_skew bytes of scratch_bytes bytes; the split-KV and parts forms take their key ranges from the hooks
+ * ivlm_llama_decode_attn_splits / ivlm_decode_parts_tuning.  record (14 int32): [0] the code the call returns, [1] the number of
+ * launches (<= 2), then per launch (kernel, template flags, grid.x, grid.y, block size, byte offset of the partials in the scratch or
+ * -1) with kernel 0 one block, 1 split KV, 2 / 3 the shared and own phase of the prefix form, 4 verify, 5 fused, and flags 1 fp32 I/O,
+ * 2 lo planes, 4 fp16 cache, 8 parts, hidden / 512 << 8 (fused).  Returns IVLM_ERR_INVALID_ARG for no record / an unknown form. */
+int ivlm_llama_decode_attn_query(int form, int io_dtype, int cache_f16, int64_t ldq, int64_t ldo, int64_t cache_stride, int tmax, int B,
+                                 int H, int D, int pos, int present, int scratch_skew, int64_t scratch_bytes, int cus, int32_t *record);
+/* Whether ivlm_llama_attn_oproj has a kernel for hidden = H * D ({512, 1024, 4096, 5120}) whose grid (H + hidden / 32 blocks, one per
+ * compute unit) fits `cus` compute units: what the decode step and a caller that plans its launches ask.  Pure arithmetic. */
+int ivlm_llama_attn_oproj_fits(int H, int D, int cus);
+
 /* ---------------------------------------------------------------------------------------------
  * Stage-level entry points of the language path: C++ sequencers over the ops above, the same kernels in the same
  * order as interactvlm_amd/llava.py (bit-identical results).  Weights: a HOST array of per-layer DEVICE pointers, bf16, in the

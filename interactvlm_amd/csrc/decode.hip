@@ -9,6 +9,12 @@
 // The arithmetic itself - one query against a key range of a slab - lives in decode_attn.h (decode_attn_range, merge_ranges) and is
 // shared with decode_prefix.hip and decode_fused.hip; the kernels here are a prologue (position, past-the-slab zero row, the block's
 // range), the range call, and an epilogue (store, or publish + merge).
+//
+// Host side of the whole family (this file, decode_prefix.hip, verify.hip, decode_fused.hip): a call is a DecodeAttnArgs and a form
+// (kernels.h); decode_attn_check holds every argument rule, decode_attn routes a checked call to its kernel instantiation(s) through
+// the one cache-kind dispatch and the one launcher of decode_attn.h.  The C entry points only fill the struct.
+#include <climits>
+
 #include "decode_attn.h"
 
 namespace ivlm {
@@ -129,97 +135,109 @@ __global__ __launch_bounds__(splitkv::kT) void llama_decode_attn_splitkv_kernel(
 
 }  // namespace
 
-// the one dispatch of the one-block kernel over (io_f32, lo planes, cache_f16), on grid (H, B); arguments checked by the callers
-// (ivlm_launch: a plain launch unless the caller armed ivlm_profile_launches - then the timing events ride on the kernel)
-static int launch_decode_attn(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride, int tmax,
-                              void* o, int64_t ldo, int B, int H, int D, int pos, const int32_t* pos_dev, float theta, float scale,
-                              const float* cos_tab, const float* sin_tab, hipStream_t st, bf16_t* kcache_lo, bf16_t* vcache_lo,
-                              int cache_f16) {
-    if ((kcache_lo != nullptr) != (vcache_lo != nullptr) || (kcache_lo && !io_f32)) return IVLM_ERR_INVALID_ARG;
-    if (cache_f16 && (!io_f32 || kcache_lo)) return IVLM_ERR_INVALID_ARG;
-    auto go = [&](auto kfn) {
-        ivlm_launch(kfn, dim3(H, B), dim3(kDecThreads), 0, st, qkv, ldq, kcache, vcache, cache_stride, o, ldo, H, D, pos, theta, scale,
-                    cos_tab, sin_tab, pos_dev, tmax, kcache_lo, vcache_lo);
-    };
-    if (cache_f16) go(llama_decode_attn_kernel<true, false, true>);
-    else if (kcache_lo) go(llama_decode_attn_kernel<true, true, false>);
-    else if (io_f32) go(llama_decode_attn_kernel<true, false, false>);
-    else go(llama_decode_attn_kernel<false, false, false>);
-    return ivlm_launch_status();
-}
-
-int llama_decode_attn_batch(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,
-                            int tmax, void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev, float theta, float scale,
-                            const float* cos_tab, const float* sin_tab, hipStream_t st, bf16_t* kcache_lo, bf16_t* vcache_lo,
-                            int cache_f16) {
-    if (!qkv || !kcache || !vcache || !o || !pos_dev) return IVLM_ERR_INVALID_ARG;
-    if (B <= 0 || B > 65535 || H <= 0 || D <= 0 || D > kMaxD || (D & 15)) return IVLM_ERR_INVALID_ARG;
-    if (ldq < 3LL * H * D || ldo < (int64_t)H * D || cache_stride < (int64_t)H * D || ((ldq | ldo | cache_stride) & 7))
-        return IVLM_ERR_INVALID_ARG;  // 16-byte rows
-    if (tmax <= 0 || (int64_t)tmax * H * D > cache_stride) return IVLM_ERR_INVALID_ARG;
-    return launch_decode_attn(qkv, io_f32, ldq, kcache, vcache, cache_stride, tmax, o, ldo, B, H, D, 0, pos_dev, theta, scale, cos_tab,
-                              sin_tab, st, kcache_lo, vcache_lo, cache_f16);
-}
-
+// split-KV scratch: the per-head arrival counters, then (at this offset, a 256-byte boundary) the partials [H][kMaxSplits][D + 2] fp32
+static size_t splitkv_partials(int H) { return (((size_t)H * 4 + 255) / 256) * 256; }
 size_t llama_decode_attn_splitkv_scratch_bytes(int H, int D) {
-    if (H <= 0 || D <= 0) return 0;
-    return 256 + (((size_t)H * 4 + 255) / 256) * 256 + (size_t)H * kMaxSplits * (D + 2) * 4;
+    return H <= 0 || D <= 0 ? 0 : 256 + splitkv_partials(H) + (size_t)H * kMaxSplits * (D + 2) * 4;
 }
 
 int g_splitkv_splits = 8;  // A/B hook: ivlm_llama_decode_attn_splits
 
-// the PARTS form: S = g_decode_parts_S ranges, partials [H][S][decode_parts_stride(D)] fp32 for ivlm_gemv1_bf12m_parts
-int llama_decode_attn_parts(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* parts, int H, int D, int pos, float theta,
-                            float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
-                            int cache_f16) {
-    if (!qkv || !kcache || !vcache || !parts || H <= 0 || D <= 0 || D > kMaxD || (D & 15) || tmax <= 0) return IVLM_ERR_INVALID_ARG;
-    if (!pos_dev && (pos < 0 || pos >= kMaxT || pos >= tmax)) return IVLM_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(parts) & 15) return IVLM_ERR_INVALID_ARG;
-    const int S = g_decode_parts_S;
-    if (cache_f16)
-        llama_decode_attn_splitkv_kernel<true, true><<<dim3(H, S), splitkv::kT, 0, st>>>(qkv, kcache, vcache, nullptr, H, D, pos, theta, scale,
-                                                                                         cos_tab, sin_tab, pos_dev, tmax, parts, nullptr);
-    else
-        llama_decode_attn_splitkv_kernel<false, true><<<dim3(H, S), splitkv::kT, 0, st>>>(qkv, kcache, vcache, nullptr, H, D, pos, theta, scale,
-                                                                                          cos_tab, sin_tab, pos_dev, tmax, parts, nullptr);
-    return ivlm_launch_status();
+thread_local decattn::LaunchLog* decattn::t_launch_log = nullptr;
+
+DecodeAttnArgs decode_attn_args(const void* qkv, int io_f32, void* kcache, void* vcache, int cache_f16, int tmax, void* o, int H, int D, int pos,
+                                const int32_t* pos_dev, float theta, float scale, const float* cos_tab, const float* sin_tab) {
+    DecodeAttnArgs a;
+    a.qkv = qkv; a.io_f32 = io_f32; a.o = o; a.tmax = tmax; a.H = H; a.D = D; a.pos = pos; a.pos_dev = pos_dev;
+    a.kcache = static_cast<bf16_t*>(kcache); a.vcache = static_cast<bf16_t*>(vcache); a.cache_f16 = cache_f16;
+    a.theta = theta; a.scale = scale; a.cos_tab = cos_tab; a.sin_tab = sin_tab;
+    return a;
 }
 
-int llama_decode_attn_splitkv(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, int pos, float theta,
-                              float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
-                              int cache_f16, void* scratch, size_t scratch_bytes) {
-    if (!qkv || !kcache || !vcache || !o || !scratch || H <= 0 || D <= 0 || D > kMaxD || (D & 15) || tmax <= 0) return IVLM_ERR_INVALID_ARG;
-    if (!pos_dev && (pos < 0 || pos >= kMaxT || pos >= tmax)) return IVLM_ERR_INVALID_ARG;
-    if (scratch_bytes < llama_decode_attn_splitkv_scratch_bytes(H, D) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return IVLM_ERR_WORKSPACE;
-    int32_t* counters = static_cast<int32_t*>(scratch);
-    float* part = reinterpret_cast<float*>(static_cast<char*>(scratch) + (((size_t)H * 4 + 255) / 256) * 256);
-    const int S = g_splitkv_splits;
-    if (cache_f16)
-        llama_decode_attn_splitkv_kernel<true><<<dim3(H, S), splitkv::kT, 0, st>>>(qkv, kcache, vcache, o, H, D, pos, theta, scale, cos_tab,
-                                                                                   sin_tab, pos_dev, tmax, part, counters);
-    else
-        llama_decode_attn_splitkv_kernel<false><<<dim3(H, S), splitkv::kT, 0, st>>>(qkv, kcache, vcache, o, H, D, pos, theta, scale, cos_tab,
-                                                                                    sin_tab, pos_dev, tmax, part, counters);
-    return ivlm_launch_status();
+// What each form requires, in the order the codes are reported when two rules are violated: INVALID_ARG for pointers and shapes,
+// UNSUPPORTED for what the prefix and fused forms have no kernel for, INVALID_ARG for strides / positions / tables / cache kind (the
+// prefix form has always reported these after its UNSUPPORTED rules; so does the fused form's lone table), WORKSPACE last.
+int decode_attn_check(DecodeAttnForm form, const DecodeAttnArgs& a) {
+    const bool prefix = form == DA_PREFIX, fused = form == DA_FUSED, strided = form == DA_BATCHED || prefix;
+    const bool host_pos = form == DA_ONE_BLOCK || form == DA_SPLIT_KV || form == DA_PARTS;  // pos_dev may be null
+    const bool any_io = form == DA_ONE_BLOCK || form == DA_BATCHED;                         // bf16 I/O and lo planes exist
+    const bool own_scratch = form == DA_SPLIT_KV || form == DA_PARTS || fused;              // (a null one is reported at once)
+    const int max_b = form == DA_BATCHED ? 65535 : form == DA_VERIFY ? kVerifyMaxK : prefix ? INT_MAX : 1;  // (grid.y; k of verify)
+    const bool bad_d = a.D > kMaxD || (a.D & 15), misaligned = reinterpret_cast<uintptr_t>(a.scratch) & 15;
+    const int64_t hd = (int64_t)a.H * a.D;
+    if (!a.qkv || !a.kcache || !a.vcache || (!a.o && form != DA_PARTS && !fused) || (!a.pos_dev && !host_pos) ||
+        (prefix && !a.prefix_len_dev) || (own_scratch && !a.scratch) ||
+        (fused && (!a.wo || !a.x || !a.x_out || !a.step_dev || !a.counter || !a.status)))
+        return IVLM_ERR_INVALID_ARG;
+    if (a.B <= 0 || a.B > max_b || a.H <= 0 || (prefix && a.H > 65535) || a.D <= 0 || (!prefix && bad_d) || (!fused && a.tmax <= 0))
+        return IVLM_ERR_INVALID_ARG;
+    if (prefix && (!a.io_f32 || bad_d || a.B > kPrefixMaxB)) return IVLM_ERR_UNSUPPORTED;
+    if (fused && (a.tmax <= 0 || !attn_oproj_fits(a.H, a.D, a.cus ? a.cus : INT_MAX))) return IVLM_ERR_UNSUPPORTED;
+    if (!a.scratch && prefix) return IVLM_ERR_INVALID_ARG;
+    if (strided && (a.ldq < 3 * hd || a.ldo < hd || a.cache_stride < hd || ((a.ldq | a.ldo | a.cache_stride) & 7) ||  // 16-byte rows
+                    a.tmax * hd > a.cache_stride))                                                                      // tmax rows a slab
+        return IVLM_ERR_INVALID_ARG;
+    if (host_pos && !a.pos_dev && (a.pos < 0 || a.pos >= kMaxT || a.pos >= a.tmax)) return IVLM_ERR_INVALID_ARG;
+    if ((a.cos_tab != nullptr) != (a.sin_tab != nullptr) || (a.kcache_lo != nullptr) != (a.vcache_lo != nullptr)) return IVLM_ERR_INVALID_ARG;
+    if ((!a.io_f32 && (a.kcache_lo || a.cache_f16 || !any_io)) || (a.kcache_lo && (a.cache_f16 || !any_io)) || (a.cache_f16 && fused))
+        return IVLM_ERR_INVALID_ARG;
+    if (form == DA_PARTS && misaligned) return IVLM_ERR_INVALID_ARG;
+    if (form == DA_SPLIT_KV && (a.scratch_bytes < llama_decode_attn_splitkv_scratch_bytes(a.H, a.D) || misaligned)) return IVLM_ERR_WORKSPACE;
+    if (prefix && (a.scratch_bytes < llama_decode_attn_batch_prefix_scratch_bytes(a.B, a.H, a.D) || misaligned)) return IVLM_ERR_WORKSPACE;
+    return IVLM_OK;
 }
 
-int llama_decode_attn(const void* qkv, int io_f32, bf16_t* kcache, bf16_t* vcache, int tmax, void* o, int H, int D, int pos,
-                      float theta, float scale, hipStream_t st, const float* cos_tab, const float* sin_tab,
-                      const int32_t* pos_dev, bf16_t* kcache_lo, bf16_t* vcache_lo, int cache_f16) {
-    if (!qkv || !kcache || !vcache || !o || H <= 0 || D <= 0 || D > kMaxD || (D & 15) || tmax <= 0) return IVLM_ERR_INVALID_ARG;
-    if (!pos_dev && (pos < 0 || pos >= kMaxT || pos >= tmax)) return IVLM_ERR_INVALID_ARG;
-    return launch_decode_attn(qkv, io_f32, 0, kcache, vcache, 0, tmax, o, 0, 1, H, D, pos, pos_dev, theta, scale, cos_tab, sin_tab, st,
-                              kcache_lo, vcache_lo, cache_f16);
+// the one-block kernel on grid (H, B) - the one-sequence form is B = 1 on strides 0 - over (io_f32, lo planes, cache_f16)
+static void launch_one_block(const DecodeAttnArgs& a, hipStream_t st) {
+    auto go = [&](int flags, auto kfn) {
+        launch(K_ONE_BLOCK, flags, -1, kfn, dim3(a.H, a.B), dim3(kDecThreads), st, a.qkv, a.ldq, a.kcache, a.vcache, a.cache_stride, a.o, a.ldo,
+               a.H, a.D, a.pos, a.theta, a.scale, a.cos_tab, a.sin_tab, a.pos_dev, a.tmax, a.kcache_lo, a.vcache_lo);
+    };
+    if (a.cache_f16) go(kFlagF32IO | kFlagCF16, llama_decode_attn_kernel<true, false, true>);
+    else if (a.kcache_lo) go(kFlagF32IO | kFlagLO, llama_decode_attn_kernel<true, true, false>);
+    else if (a.io_f32) go(kFlagF32IO, llama_decode_attn_kernel<true, false, false>);
+    else go(0, llama_decode_attn_kernel<false, false, false>);
+}
+// the split-KV kernel on grid (H, S); PARTS: S = g_decode_parts_S ranges, the scratch is the parts buffer of ivlm_gemv1_bf12m_parts
+template <bool PARTS>
+static void launch_splitkv(const DecodeAttnArgs& a, hipStream_t st) {
+    const size_t part_off = PARTS ? 0 : splitkv_partials(a.H);
+    float* part = reinterpret_cast<float*>(static_cast<char*>(a.scratch) + part_off);
+    with_cache_f16(a, [&](int flags, auto cf) {
+        launch(K_SPLIT_KV, flags | (PARTS ? kFlagParts : 0), part_off, llama_decode_attn_splitkv_kernel<cf.value, PARTS>,
+               dim3(a.H, PARTS ? g_decode_parts_S : g_splitkv_splits), dim3(splitkv::kT), st, static_cast<const float*>(a.qkv), a.kcache, a.vcache,
+               PARTS ? nullptr : static_cast<float*>(a.o), a.H, a.D, a.pos, a.theta, a.scale, a.cos_tab, a.sin_tab, a.pos_dev, a.tmax, part,
+               PARTS ? nullptr : static_cast<int32_t*>(a.scratch));
+    });
+}
+
+int decode_attn(DecodeAttnForm form, const DecodeAttnArgs& a, hipStream_t st) {
+    if (const int rc = decode_attn_check(form, a)) return rc;
+    switch (form) {
+        case DA_ONE_BLOCK:
+        case DA_BATCHED: launch_one_block(a, st); break;
+        case DA_SPLIT_KV: launch_splitkv<false>(a, st); break;
+        case DA_PARTS: launch_splitkv<true>(a, st); break;
+        case DA_PREFIX: launch_prefix(a, st); break;
+        case DA_VERIFY: launch_verify(a, st); break;
+        default:
+            if (const int rc = launch_fused(a, st)) return rc;
+    }
+    return t_launch_log ? IVLM_OK : ivlm_launch_status();  // (a dry run made no launch and asks no runtime)
 }
 
 }  // namespace ivlm
+
+// ---- C ABI: each entry point fills DecodeAttnArgs (one sequence: B = 1 on strides 0) and names its form ---------------------------
+using ivlm::decode_attn;
+using ivlm::decode_attn_args;
 
 extern "C" int ivlm_llama_decode_attn(const void* qkv, int io_dtype, void* kcache, void* vcache, int tmax, void* o, int H, int D,
                                       int pos, const int32_t* pos_dev, float theta, float scale, const float* cos_tab,
                                       const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
-    return ivlm::llama_decode_attn(qkv, io_dtype == IVLM_F32, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o,
-                                   H, D, pos, theta, scale, ivlm_stream(stream), cos_tab, sin_tab, pos_dev);
+    return decode_attn(ivlm::DA_ONE_BLOCK, decode_attn_args(qkv, io_dtype == IVLM_F32, kcache, vcache, 0, tmax, o, H, D, pos, pos_dev,
+        theta, scale, cos_tab, sin_tab), ivlm_stream(stream));
 }
 
 // "parity" precision: K / V cached as hi + lo bf16 planes (fp32 qkv / o); kcache_lo / vcache_lo as the hi caches
@@ -228,9 +246,8 @@ extern "C" int ivlm_llama_decode_attn_split(const void* qkv, void* kcache, void*
                                             const float* cos_tab, const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
     if (!kcache_lo || !vcache_lo) return IVLM_ERR_INVALID_ARG;
-    return ivlm::llama_decode_attn(qkv, 1, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o, H, D, pos, theta,
-                                   scale, ivlm_stream(stream), cos_tab, sin_tab, pos_dev, static_cast<bf16_t*>(kcache_lo),
-                                   static_cast<bf16_t*>(vcache_lo));
+    return decode_attn(ivlm::DA_ONE_BLOCK, decode_attn_args(qkv, 1, kcache, vcache, 0, tmax, o, H, D, pos, pos_dev, theta, scale, cos_tab,
+        sin_tab).lo(kcache_lo, vcache_lo), ivlm_stream(stream));
 }
 
 extern "C" int ivlm_llama_decode_attn_batch_split(const void* qkv, int64_t ldq, void* kcache, void* kcache_lo, void* vcache,
@@ -239,9 +256,8 @@ extern "C" int ivlm_llama_decode_attn_batch_split(const void* qkv, int64_t ldq, 
                                                   const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
     if (!kcache_lo || !vcache_lo) return IVLM_ERR_INVALID_ARG;
-    return ivlm::llama_decode_attn_batch(qkv, 1, ldq, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), cache_stride, tmax,
-                                         o, ldo, B, H, D, pos_dev, theta, scale, cos_tab, sin_tab, ivlm_stream(stream),
-                                         static_cast<bf16_t*>(kcache_lo), static_cast<bf16_t*>(vcache_lo));
+    return decode_attn(ivlm::DA_BATCHED, decode_attn_args(qkv, 1, kcache, vcache, 0, tmax, o, H, D, 0, pos_dev, theta, scale, cos_tab,
+        sin_tab).rows(ldq, cache_stride, ldo, B).lo(kcache_lo, vcache_lo), ivlm_stream(stream));
 }
 
 extern "C" int ivlm_llama_decode_attn_batch(const void* qkv, int io_dtype, int64_t ldq, void* kcache, void* vcache,
@@ -249,9 +265,8 @@ extern "C" int ivlm_llama_decode_attn_batch(const void* qkv, int io_dtype, int64
                                             const int32_t* pos_dev, float theta, float scale, const float* cos_tab,
                                             const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
-    return ivlm::llama_decode_attn_batch(qkv, io_dtype == IVLM_F32, ldq, static_cast<bf16_t*>(kcache),
-                                         static_cast<bf16_t*>(vcache), cache_stride, tmax, o, ldo, B, H, D, pos_dev, theta, scale,
-                                         cos_tab, sin_tab, ivlm_stream(stream));
+    return decode_attn(ivlm::DA_BATCHED, decode_attn_args(qkv, io_dtype == IVLM_F32, kcache, vcache, 0, tmax, o, H, D, 0, pos_dev, theta,
+        scale, cos_tab, sin_tab).rows(ldq, cache_stride, ldo, B), ivlm_stream(stream));
 }
 
 // fp16 KV cache (the fp16-operand prefill appends IEEE halves): fp32 qkv / o, K / V rows appended as fp16 and read back as fp16
@@ -259,8 +274,8 @@ extern "C" int ivlm_llama_decode_attn_f16(const void* qkv, void* kcache, void* v
                                           const int32_t* pos_dev, float theta, float scale, const float* cos_tab,
                                           const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
-    return ivlm::llama_decode_attn(qkv, 1, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o, H, D, pos, theta,
-                                   scale, ivlm_stream(stream), cos_tab, sin_tab, pos_dev, nullptr, nullptr, 1);
+    return decode_attn(ivlm::DA_ONE_BLOCK, decode_attn_args(qkv, 1, kcache, vcache, 1, tmax, o, H, D, pos, pos_dev, theta, scale, cos_tab,
+        sin_tab), ivlm_stream(stream));
 }
 
 extern "C" int ivlm_llama_decode_attn_batch_f16(const void* qkv, int64_t ldq, void* kcache, void* vcache, int64_t cache_stride,
@@ -268,9 +283,8 @@ extern "C" int ivlm_llama_decode_attn_batch_f16(const void* qkv, int64_t ldq, vo
                                                 float theta, float scale, const float* cos_tab, const float* sin_tab,
                                                 ivlm_stream_t stream) {
     ivlm_enter();
-    return ivlm::llama_decode_attn_batch(qkv, 1, ldq, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), cache_stride, tmax,
-                                         o, ldo, B, H, D, pos_dev, theta, scale, cos_tab, sin_tab, ivlm_stream(stream), nullptr,
-                                         nullptr, 1);
+    return decode_attn(ivlm::DA_BATCHED, decode_attn_args(qkv, 1, kcache, vcache, 1, tmax, o, H, D, 0, pos_dev, theta, scale, cos_tab,
+        sin_tab).rows(ldq, cache_stride, ldo, B), ivlm_stream(stream));
 }
 
 // split-KV variant of ivlm_llama_decode_attn (fp32 qkv / o; cache_dtype IVLM_BF16 or IVLM_F16): H x S blocks, partials merged by the
@@ -283,9 +297,10 @@ extern "C" int ivlm_llama_decode_attn_splitkv(const float* qkv, int cache_dtype,
                                               const float* sin_tab, void* scratch, size_t scratch_bytes, ivlm_stream_t stream) {
     ivlm_enter();
     if (cache_dtype != IVLM_BF16 && cache_dtype != IVLM_F16) return IVLM_ERR_INVALID_ARG;
-    return ivlm::llama_decode_attn_splitkv(qkv, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o, H, D, pos, theta,
-                                           scale, ivlm_stream(stream), cos_tab, sin_tab, pos_dev, cache_dtype == IVLM_F16, scratch,
-                                           scratch_bytes);
+    ivlm::DecodeAttnArgs a = decode_attn_args(qkv, 1, kcache, vcache, cache_dtype == IVLM_F16, tmax, o, H, D, pos, pos_dev, theta, scale,
+        cos_tab, sin_tab);
+    a.scratch = scratch, a.scratch_bytes = scratch_bytes;
+    return decode_attn(ivlm::DA_SPLIT_KV, a, ivlm_stream(stream));
 }
 
 extern "C" int ivlm_llama_decode_attn_splits(int splits) {
@@ -302,6 +317,38 @@ extern "C" int ivlm_llama_decode_attn_parts(const float* qkv, int cache_dtype, v
                                             const float* sin_tab, ivlm_stream_t stream) {
     ivlm_enter();
     if (cache_dtype != IVLM_BF16 && cache_dtype != IVLM_F16) return IVLM_ERR_INVALID_ARG;
-    return ivlm::llama_decode_attn_parts(qkv, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, parts, H, D, pos, theta,
-                                         scale, ivlm_stream(stream), cos_tab, sin_tab, pos_dev, cache_dtype == IVLM_F16);
+    ivlm::DecodeAttnArgs a = decode_attn_args(qkv, 1, kcache, vcache, cache_dtype == IVLM_F16, tmax, nullptr, H, D, pos, pos_dev, theta,
+        scale, cos_tab, sin_tab);
+    a.scratch = parts;
+    return decode_attn(ivlm::DA_PARTS, a, ivlm_stream(stream));
 }
+
+// Test hook: the check and the routing of ONE described call of the family, recorded instead of launched (see ivlm_hip.h).  The
+// pointers are dummies of the alignment a caller's would have; nothing dereferences them on the host.
+extern "C" int ivlm_llama_decode_attn_query(int form, int io_dtype, int cache_f16, int64_t ldq, int64_t ldo, int64_t cache_stride, int tmax,
+                                            int B, int H, int D, int pos, int present, int scratch_skew, int64_t scratch_bytes, int cus,
+                                            int32_t* record) {
+    if (!record || form < 0 || form >= ivlm::DA_FORMS || (form == ivlm::DA_FUSED && cus <= 0)) return IVLM_ERR_INVALID_ARG;
+    int bit = 0;
+    const auto next = [&]() -> char* {  // the next pointer in the documented order of `present`: null when its bit is clear
+        ++bit;
+        return (present >> (bit - 1)) & 1 ? reinterpret_cast<char*>((uintptr_t)bit << 20) : nullptr;
+    };
+    char *qkv = next(), *kc = next(), *vc = next(), *o = next(), *pos_dev = next(), *plen = next(), *klo = next(), *vlo = next(), *ct = next(),
+         *st = next(), *scratch = next();
+    ivlm::DecodeAttnArgs a = decode_attn_args(qkv, io_dtype == IVLM_F32, kc, vc, cache_f16, tmax, o, H, D, pos,
+        reinterpret_cast<int32_t*>(pos_dev), 10000.0f, 1.0f, reinterpret_cast<float*>(ct), reinterpret_cast<float*>(st)).rows(ldq,
+        cache_stride, ldo, B).lo(klo, vlo);
+    a.prefix_len_dev = reinterpret_cast<int32_t*>(plen);
+    a.scratch = scratch ? scratch + scratch_skew : nullptr, a.scratch_bytes = (size_t)scratch_bytes, a.cus = cus;
+    a.wo = reinterpret_cast<bf16_t*>(next()), a.x = reinterpret_cast<float*>(next()), a.x_out = reinterpret_cast<float*>(next());
+    a.step_dev = reinterpret_cast<int32_t*>(next()), a.counter = reinterpret_cast<int32_t*>(next()), a.status = reinterpret_cast<int32_t*>(next());
+    for (int i = 0; i < 14; ++i) record[i] = 0;
+    ivlm::decattn::LaunchLog log{record + 2, 2, 0};
+    ivlm::decattn::t_launch_log = &log;
+    record[0] = decode_attn(static_cast<ivlm::DecodeAttnForm>(form), a, nullptr);
+    ivlm::decattn::t_launch_log = nullptr;
+    record[1] = log.n;
+    return IVLM_OK;
+}
+

@@ -4,6 +4,8 @@
 // (decode_prefix.hip) and the producer blocks of the fused attention + o_proj launch (decode_fused.hip); merge_ranges combines the
 // (o, max, sum) partials of several ranges.  verify.hip and the prefix kernel's shared phase take only rope_cos_sin.
 #pragma once
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace ivlm {
@@ -271,6 +273,46 @@ __device__ __forceinline__ float merge_ranges(const float (&pm)[kMaxSplits], con
     }
     return den > 0.0f ? num / den : 0.0f;
 }
+
+// ---- host side: what the four files of the family share under decode_attn (decode.hip) -------------------------------------------
+// kernel ids and template-flag bits of a launch record (ivlm_llama_decode_attn_query)
+enum Kernel : int { K_ONE_BLOCK = 0, K_SPLIT_KV, K_PREFIX_SHARED, K_PREFIX_OWN, K_VERIFY, K_FUSED };
+constexpr int kFlagF32IO = 1, kFlagLO = 2, kFlagCF16 = 4, kFlagParts = 8;  // (the fused kernel: NB << 8)
+
+// the fp32-only forms: f(record flags, CF16 as a std::bool_constant) for the call's cache kind
+template <class F>
+inline void with_cache_f16(const DecodeAttnArgs& a, F&& f) {
+    if (a.cache_f16) f(kFlagF32IO | kFlagCF16, std::true_type{});
+    else f(kFlagF32IO, std::false_type{});
+}
+
+// a dry run (ivlm_llama_decode_attn_query) points this at its record: launches are then noted instead of made
+struct LaunchLog {
+    int32_t* rec;  // 6 int32 per launch: kernel, flags, grid.x, grid.y, block, byte offset of the partials in the scratch (-1: none)
+    int cap, n;
+};
+extern thread_local LaunchLog* t_launch_log;
+
+// the one launcher of the family (ivlm_launch: a plain launch unless the caller armed ivlm_profile_launches - then the timing events
+// ride on the kernel).  args must have the kernel's parameter types.
+template <class K, class... A>
+inline void launch(Kernel id, int flags, int64_t part_off, K kfn, dim3 grid, dim3 block, hipStream_t st, A... args) {
+    if (LaunchLog* log = t_launch_log) {
+        if (log->n < log->cap) {
+            const int32_t v[6] = {id, flags, (int32_t)grid.x, (int32_t)grid.y, (int32_t)block.x, (int32_t)part_off};
+            for (int i = 0; i < 6; ++i) log->rec[6 * log->n + i] = v[i];
+        }
+        ++log->n;
+        return;
+    }
+    ivlm_launch(kfn, grid, block, 0, st, args...);
+}
+
+// the launches of a CHECKED call of the forms that live outside decode.hip
+void launch_prefix(const DecodeAttnArgs& a, hipStream_t st);  // decode_prefix.hip
+void launch_verify(const DecodeAttnArgs& a, hipStream_t st);  // verify.hip
+int launch_fused(const DecodeAttnArgs& a, hipStream_t st);    // decode_fused.hip (asks the runtime for the CUs when a.cus == 0)
+constexpr int kPrefixMaxB = 16, kVerifyMaxK = 16;
 
 }  // namespace decattn
 }  // namespace ivlm

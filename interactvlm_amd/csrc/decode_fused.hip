@@ -134,47 +134,51 @@ __global__ __launch_bounds__(kDecThreads) void attn_oproj_kernel(AttnOprojArgs a
 
 }  // namespace
 
-int llama_attn_oproj(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* attn_scratch, const bf16_t* wo,
-                     const float* x, float* x_out, int H, int D, float theta, float scale, const float* cos_tab,
-                     const float* sin_tab, const int32_t* pos_dev, const int32_t* step_dev, int32_t* counter, int32_t* status,
-                     hipStream_t st) {
-    if (!qkv || !kcache || !vcache || !attn_scratch || !wo || !x || !x_out || !pos_dev || !step_dev || !counter || !status)
-        return IVLM_ERR_INVALID_ARG;
-    if (H <= 0 || D <= 0 || D > kMaxD || (D & 15)) return IVLM_ERR_INVALID_ARG;
-    const int hidden = H * D;
-    if (hidden % 512 != 0 || hidden > 8192 || tmax <= 0) return IVLM_ERR_UNSUPPORTED;
-    AttnOprojArgs a;
-    a.qkv = qkv; a.kcache = kcache; a.vcache = vcache; a.attn = attn_scratch; a.wo = wo; a.x = x; a.x_out = x_out;
-    a.H = H; a.D = D; a.tmax = tmax; a.theta = theta; a.scale = scale; a.cos_tab = cos_tab; a.sin_tab = sin_tab;
-    a.pos_dev = pos_dev; a.step_dev = step_dev; a.counter = counter; a.status = status;
-    const int grid = H + (hidden + kRowsPerBlock - 1) / kRowsPerBlock;
-    {  // consumers wait for producers inside the launch: the whole grid must be resident (one block per CU)
+// the hidden sizes attn_oproj_kernel<hidden / 512> is instantiated for: 4096 (LLaMA-2 7B), 5120 (13B), 512 and 1024 (tests); consumers
+// wait for producers inside the launch, so the whole grid - kRowsPerBlock rows of W_o per consumer block - must be resident, one block per CU.
+// Callers that hold a model's hidden size pass (heads, hidden / heads): the configurations they accept have hidden % heads == 0 (cfg_ok).
+bool attn_oproj_fits(int H, int D, int cus) {
+    const int64_t hidden = (int64_t)H * D;
+    if (H <= 0 || D <= 0 || (hidden != 512 && hidden != 1024 && hidden != 4096 && hidden != 5120)) return false;
+    return H + hidden / kRowsPerBlock <= cus;
+}
+
+int decattn::launch_fused(const DecodeAttnArgs& d, hipStream_t st) {  // (a checked call: with d.cus given, the check applied the CU rule)
+    if (!d.cus) {
         static int cus = 0;  // queried once (never during a stream capture: the graph path warms up first)
         if (cus == 0) {
             int dev = 0;
             IVLM_HIP_TRY(hipGetDevice(&dev));
             IVLM_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         }
-        if (grid > cus) return IVLM_ERR_UNSUPPORTED;
+        if (!attn_oproj_fits(d.H, d.D, cus)) return IVLM_ERR_UNSUPPORTED;
     }
-    switch (hidden / 512) {
-        case 8: attn_oproj_kernel<8><<<grid, kDecThreads, 0, st>>>(a); break;    // 4096 (LLaMA-2 7B)
-        case 10: attn_oproj_kernel<10><<<grid, kDecThreads, 0, st>>>(a); break;  // 5120 (13B)
-        case 1: attn_oproj_kernel<1><<<grid, kDecThreads, 0, st>>>(a); break;    // 512  (tests)
-        case 2: attn_oproj_kernel<2><<<grid, kDecThreads, 0, st>>>(a); break;    // 1024 (tests)
-        default: return IVLM_ERR_UNSUPPORTED;
+    const AttnOprojArgs a{static_cast<const float*>(d.qkv), d.kcache, d.vcache, static_cast<float*>(d.scratch), d.wo, d.x, d.x_out, d.H, d.D,
+                          d.tmax, d.theta, d.scale, d.cos_tab, d.sin_tab, d.pos_dev, d.step_dev, d.counter, d.status};
+    const int hidden = d.H * d.D, nb = hidden / 512;
+    const dim3 grid(d.H + hidden / kRowsPerBlock), block(kDecThreads);
+    const int flags = kFlagF32IO | (nb << 8);
+    switch (nb) {
+        case 8: launch(K_FUSED, flags, -1, attn_oproj_kernel<8>, grid, block, st, a); break;
+        case 10: launch(K_FUSED, flags, -1, attn_oproj_kernel<10>, grid, block, st, a); break;
+        case 1: launch(K_FUSED, flags, -1, attn_oproj_kernel<1>, grid, block, st, a); break;
+        default: launch(K_FUSED, flags, -1, attn_oproj_kernel<2>, grid, block, st, a); break;
     }
-    return ivlm_launch_status();
+    return IVLM_OK;
 }
 
 }  // namespace ivlm
+
+extern "C" int ivlm_llama_attn_oproj_fits(int H, int D, int cus) { return ivlm::attn_oproj_fits(H, D, cus); }
 
 extern "C" int ivlm_llama_attn_oproj(const float* qkv, void* kcache, void* vcache, int tmax, float* attn_scratch, const void* wo,
                                      const float* x, float* x_out, int H, int D, float theta, float scale,
                                      const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
                                      const int32_t* step_dev, int32_t* counter, int32_t* status, ivlm_stream_t stream) {
     ivlm_enter();
-    return ivlm::llama_attn_oproj(qkv, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, attn_scratch,
-                                  static_cast<const bf16_t*>(wo), x, x_out, H, D, theta, scale, cos_tab, sin_tab, pos_dev, step_dev,
-                                  counter, status, ivlm_stream(stream));
+    ivlm::DecodeAttnArgs a =
+        ivlm::decode_attn_args(qkv, 1, kcache, vcache, 0, tmax, nullptr, H, D, 0, pos_dev, theta, scale, cos_tab, sin_tab);
+    a.scratch = attn_scratch; a.wo = static_cast<const bf16_t*>(wo); a.x = x; a.x_out = x_out;
+    a.step_dev = step_dev; a.counter = counter; a.status = status;
+    return ivlm::decode_attn(ivlm::DA_FUSED, a, ivlm_stream(stream));
 }

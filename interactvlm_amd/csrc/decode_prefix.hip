@@ -22,7 +22,7 @@ namespace {
 using namespace decattn;
 
 namespace prefix {
-constexpr int kT = 256, kChunk = 64, kMaxB = 16, kMinPer = 16;
+constexpr int kT = 256, kChunk = 64, kMaxB = kPrefixMaxB, kMinPer = 16;
 constexpr int kG = kT / 16;  // staging rows per sweep (16 lanes share a row)
 __host__ __device__ inline int clampP(int P, int tmax) {
     const int cap = tmax < kMaxT ? tmax : kMaxT;
@@ -242,39 +242,20 @@ size_t llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D) {
     return (size_t)H * prefix::splits(H) * B * decode_parts_stride(D) * sizeof(float);
 }
 
-int llama_decode_attn_batch_prefix(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,
-                                   int tmax, void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev,
-                                   const int32_t* prefix_len_dev, float theta, float scale, const float* cos_tab,
-                                   const float* sin_tab, int cache_f16, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    if (!qkv || !kcache || !vcache || !o || !pos_dev || !prefix_len_dev) return IVLM_ERR_INVALID_ARG;
-    if (B <= 0 || H <= 0 || H > 65535 || D <= 0 || tmax <= 0) return IVLM_ERR_INVALID_ARG;
-    if (!io_f32 || D > kMaxD || (D & 15) || B > prefix::kMaxB) return IVLM_ERR_UNSUPPORTED;
-    if (!scratch) return IVLM_ERR_INVALID_ARG;
-    if (ldq < 3LL * H * D || ldo < (int64_t)H * D || cache_stride < (int64_t)H * D || ((ldq | ldo | cache_stride) & 7))
-        return IVLM_ERR_INVALID_ARG;  // 16-byte rows
-    if ((int64_t)tmax * H * D > cache_stride) return IVLM_ERR_INVALID_ARG;
-    if ((cos_tab != nullptr) != (sin_tab != nullptr)) return IVLM_ERR_INVALID_ARG;
-    if (scratch_bytes < llama_decode_attn_batch_prefix_scratch_bytes(B, H, D) || (reinterpret_cast<uintptr_t>(scratch) & 15))
-        return IVLM_ERR_WORKSPACE;
-    const int S = prefix::splits(H);
-    float* part = static_cast<float*>(scratch);
-    const float* q = static_cast<const float*>(qkv);
-    float* out = static_cast<float*>(o);
-    // (ivlm_launch: with ivlm_profile_launches armed the start event rides on the first kernel, the stop event on the last)
-    const dim3 gs(H, S), go(H, B), blk(prefix::kT);
-    const bf16_t *k0 = kcache, *v0 = vcache;
-    if (cache_f16) {
-        ivlm_launch(llama_prefix_shared_kernel<true>, gs, blk, 0, st, q, ldq, k0, v0, B, H, D, theta, scale, cos_tab, sin_tab, pos_dev,
-                    prefix_len_dev, tmax, part);
-        ivlm_launch(llama_prefix_own_kernel<true>, go, blk, 0, st, q, ldq, kcache, vcache, cache_stride, out, ldo, H, D, theta, scale, cos_tab,
-                    sin_tab, pos_dev, prefix_len_dev, tmax, (const float*)part, S);
-    } else {
-        ivlm_launch(llama_prefix_shared_kernel<false>, gs, blk, 0, st, q, ldq, k0, v0, B, H, D, theta, scale, cos_tab, sin_tab, pos_dev,
-                    prefix_len_dev, tmax, part);
-        ivlm_launch(llama_prefix_own_kernel<false>, go, blk, 0, st, q, ldq, kcache, vcache, cache_stride, out, ldo, H, D, theta, scale, cos_tab,
-                    sin_tab, pos_dev, prefix_len_dev, tmax, (const float*)part, S);
-    }
-    return ivlm_launch_status();
+// the two launches of a checked call (with ivlm_profile_launches armed the start event rides on the first kernel, the stop event on
+// the last); the partials fill the scratch from its start
+void decattn::launch_prefix(const DecodeAttnArgs& a, hipStream_t st) {
+    const int S = prefix::splits(a.H);
+    float* part = static_cast<float*>(a.scratch);
+    const float* q = static_cast<const float*>(a.qkv);
+    with_cache_f16(a, [&](int flags, auto cf) {
+        launch(K_PREFIX_SHARED, flags, 0, llama_prefix_shared_kernel<cf.value>, dim3(a.H, S), dim3(prefix::kT), st, q, a.ldq,
+               (const bf16_t*)a.kcache, (const bf16_t*)a.vcache, a.B, a.H, a.D, a.theta, a.scale, a.cos_tab, a.sin_tab, a.pos_dev,
+               a.prefix_len_dev, a.tmax, part);
+        launch(K_PREFIX_OWN, flags, 0, llama_prefix_own_kernel<cf.value>, dim3(a.H, a.B), dim3(prefix::kT), st, q, a.ldq, a.kcache, a.vcache,
+               a.cache_stride, static_cast<float*>(a.o), a.ldo, a.H, a.D, a.theta, a.scale, a.cos_tab, a.sin_tab, a.pos_dev, a.prefix_len_dev,
+               a.tmax, (const float*)part, S);
+    });
 }
 
 }  // namespace ivlm
@@ -283,16 +264,23 @@ extern "C" size_t ivlm_llama_decode_attn_batch_prefix_scratch_bytes(int B, int H
     return ivlm::llama_decode_attn_batch_prefix_scratch_bytes(B, H, D);
 }
 
+static int prefix_entry(const void* qkv, int io_f32, int64_t ldq, void* kcache, void* vcache, int cache_f16, int64_t cache_stride, int tmax,
+                        void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev, const int32_t* prefix_len_dev, float theta,
+                        float scale, const float* cos_tab, const float* sin_tab, void* scratch, size_t scratch_bytes, ivlm_stream_t stream) {
+    ivlm_enter();
+    ivlm::DecodeAttnArgs a = ivlm::decode_attn_args(qkv, io_f32, kcache, vcache, cache_f16, tmax, o, H, D, 0, pos_dev, theta, scale,
+        cos_tab, sin_tab).rows(ldq, cache_stride, ldo, B);
+    a.prefix_len_dev = prefix_len_dev; a.scratch = scratch; a.scratch_bytes = scratch_bytes;
+    return ivlm::decode_attn(ivlm::DA_PREFIX, a, ivlm_stream(stream));
+}
+
 extern "C" int ivlm_llama_decode_attn_batch_prefix(const void* qkv, int io_dtype, int64_t ldq, void* kcache, void* vcache,
                                                    int64_t cache_stride, int tmax, void* o, int64_t ldo, int B, int H, int D,
                                                    const int32_t* pos_dev, const int32_t* prefix_len_dev, float theta, float scale,
                                                    const float* cos_tab, const float* sin_tab, void* scratch, size_t scratch_bytes,
                                                    ivlm_stream_t stream) {
-    ivlm_enter();
-    return ivlm::llama_decode_attn_batch_prefix(qkv, io_dtype == IVLM_F32, ldq, static_cast<bf16_t*>(kcache),
-                                                static_cast<bf16_t*>(vcache), cache_stride, tmax, o, ldo, B, H, D, pos_dev,
-                                                prefix_len_dev, theta, scale, cos_tab, sin_tab, 0, scratch, scratch_bytes,
-                                                ivlm_stream(stream));
+    return prefix_entry(qkv, io_dtype == IVLM_F32, ldq, kcache, vcache, 0, cache_stride, tmax, o, ldo, B, H, D, pos_dev, prefix_len_dev, theta,
+                        scale, cos_tab, sin_tab, scratch, scratch_bytes, stream);
 }
 
 extern "C" int ivlm_llama_decode_attn_batch_prefix_f16(const void* qkv, int64_t ldq, void* kcache, void* vcache, int64_t cache_stride,
@@ -300,8 +288,6 @@ extern "C" int ivlm_llama_decode_attn_batch_prefix_f16(const void* qkv, int64_t 
                                                        const int32_t* prefix_len_dev, float theta, float scale, const float* cos_tab,
                                                        const float* sin_tab, void* scratch, size_t scratch_bytes,
                                                        ivlm_stream_t stream) {
-    ivlm_enter();
-    return ivlm::llama_decode_attn_batch_prefix(qkv, 1, ldq, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), cache_stride,
-                                                tmax, o, ldo, B, H, D, pos_dev, prefix_len_dev, theta, scale, cos_tab, sin_tab, 1,
-                                                scratch, scratch_bytes, ivlm_stream(stream));
+    return prefix_entry(qkv, 1, ldq, kcache, vcache, 1, cache_stride, tmax, o, ldo, B, H, D, pos_dev, prefix_len_dev, theta, scale, cos_tab,
+                        sin_tab, scratch, scratch_bytes, stream);
 }

@@ -227,49 +227,65 @@ int phong_shade(const int32_t* p2v, const float* bary, const float* verts, const
                 const float* light3_host, const float* cam3_host, float ambient, float diffuse, float specular, float shininess,
                 const float* bg3_host, uint8_t* out, hipStream_t st);
 
-// ---- single-token decode (decode.hip) ---------------------------------------------------------------
-// qkv / o bf16 or fp32 (io_f32); tmax = rows of the cache slab (a position >= tmax is skipped, never appended)
-int llama_decode_attn(const void* qkv, int io_f32, bf16_t* kcache, bf16_t* vcache, int tmax, void* o, int H, int D, int pos,
-                      float theta, float scale, hipStream_t st, const float* cos_tab = nullptr, const float* sin_tab = nullptr,
-                      const int32_t* pos_dev = nullptr, bf16_t* kcache_lo = nullptr, bf16_t* vcache_lo = nullptr, int cache_f16 = 0);
-int llama_decode_attn_batch(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,
-                            int tmax, void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev, float theta, float scale,
-                            const float* cos_tab, const float* sin_tab, hipStream_t st, bf16_t* kcache_lo = nullptr,
-                            bf16_t* vcache_lo = nullptr, int cache_f16 = 0);
-
-// split-KV variant (fp32 qkv / o, no lo planes): grid H x S, scratch zeroed once by the caller (decode.hip)
+// ---- decode attention (decode.hip, decode_prefix.hip, verify.hip, decode_fused.hip) -------------------
+// One description of a call for every form of the family; a form reads the members it needs and decode_attn_check says which those are.
+enum DecodeAttnForm : int {
+    DA_ONE_BLOCK = 0,  // one sequence, one block per head; position from the host (pos) or the device (pos_dev)
+    DA_BATCHED,        // B sequences on grid (H, B): slab, qkv row, output row and pos_dev[b] per sequence
+    DA_SPLIT_KV,       // one sequence, grid H x S key ranges merged by the last block of a head; scratch zeroed once by the caller
+    DA_PARTS,          // ... without the merge: the partials go to scratch for the o_proj GEMV that merges them (layout below)
+    DA_PREFIX,         // B <= 16 sequences whose keys [0, *prefix_len_dev) are read from slab 0 once (two launches)
+    DA_VERIFY,         // speculative decoding: B = k <= 16 new rows of ONE sequence at positions pos_dev[0] .. +k-1
+    DA_FUSED,          // one sequence, attention and o_proj + residual in one launch
+    DA_FORMS
+};
+struct DecodeAttnArgs {
+    const void* qkv = nullptr;  // [B, 3*H*D], row stride ldq: bf16, or fp32 (io_f32; every form but the first two is fp32 only)
+    void* o = nullptr;          // [B, H*D] as qkv, row stride ldo
+    int io_f32 = 1;
+    int64_t ldq = 0, ldo = 0, cache_stride = 0;
+    bf16_t *kcache = nullptr, *vcache = nullptr;        // [tmax, H, D] per sequence, cache_stride elements apart
+    bf16_t *kcache_lo = nullptr, *vcache_lo = nullptr;  // "parity" precision: the lo planes of hi + lo bf16 rows (both or none)
+    int cache_f16 = 0;                                  // the slabs hold IEEE halves
+    int tmax = 0;  // rows of a slab: a position >= tmax is skipped, never appended
+    int B = 1, H = 0, D = 0;
+    int pos = 0;  // host position, read when pos_dev is null (forms that allow it)
+    const int32_t *pos_dev = nullptr, *prefix_len_dev = nullptr;  // [B] ([1] for the one-sequence forms and verify), [1]
+    float theta = 0.0f, scale = 0.0f;
+    const float *cos_tab = nullptr, *sin_tab = nullptr;  // both or none
+    void* scratch = nullptr;  // split-KV scratch, the parts buffer, the prefix partials, the fused launch's attention row
+    size_t scratch_bytes = 0;
+    // the fused launch: x_out = x + wo . attention; counter / status / step_dev as ivlm_llama_attn_oproj documents
+    const bf16_t* wo = nullptr;
+    const float* x = nullptr;
+    float* x_out = nullptr;
+    const int32_t* step_dev = nullptr;
+    int32_t *counter = nullptr, *status = nullptr;
+    int cus = 0;  // compute units the fused grid must fit; 0 = ask the runtime (once)
+    DecodeAttnArgs& rows(int64_t q, int64_t c, int64_t o_, int b) { return ldq = q, cache_stride = c, ldo = o_, B = b, *this; }  // B strided rows
+    DecodeAttnArgs& lo(void* k, void* v) { return kcache_lo = static_cast<bf16_t*>(k), vcache_lo = static_cast<bf16_t*>(v), *this; }
+};
+// what every form shares, as one sequence (B = 1 on strides 0); .rows() / .lo() and the caller add what the form adds
+DecodeAttnArgs decode_attn_args(const void* qkv, int io_f32, void* kcache, void* vcache, int cache_f16, int tmax, void* o, int H, int D, int pos,
+                                const int32_t* pos_dev, float theta, float scale, const float* cos_tab, const float* sin_tab);
+// IVLM_OK, or the code the call is rejected with (cus == 0: the fused form's CU rule is left to decode_attn)
+int decode_attn_check(DecodeAttnForm form, const DecodeAttnArgs& a);
+// check, choose the kernel instantiation(s), launch
+int decode_attn(DecodeAttnForm form, const DecodeAttnArgs& a, hipStream_t st);
+// hidden = H * D has an instantiation of the fused kernel and its grid (H + hidden / 32 blocks, one per CU) is resident at once
+bool attn_oproj_fits(int H, int D, int cus);
 size_t llama_decode_attn_splitkv_scratch_bytes(int H, int D);
-int llama_decode_attn_splitkv(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, int pos, float theta,
-                              float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
-                              int cache_f16, void* scratch, size_t scratch_bytes);
+size_t llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D);
 
 // the "parts" layout between the split-KV attention and the consumer that merges it (the packed o_proj GEMV, ivlm_gemv1_bf12m_parts):
 // parts[H][g_decode_parts_S][decode_parts_stride(D)] fp32, a row = o unnormalised [D] | max | sum | 2 pad (16-byte rows)
 extern int g_decode_parts_S;  // key ranges per head: 4, or 2 (A/B hook ivlm_decode_parts_tuning, gemv_p12.hip)
 constexpr int kDecodePartsMaxS = 4;
 __host__ __device__ constexpr int decode_parts_stride(int D) { return D + 4; }
-int llama_decode_attn_parts(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* parts, int H, int D, int pos, float theta,
-                            float scale, hipStream_t st, const float* cos_tab, const float* sin_tab, const int32_t* pos_dev,
-                            int cache_f16);
 
-// speculative decoding of one sequence (verify.hip): k <= 16 new tokens at positions pos_dev[0] .. +k-1 in one attention launch
-// (fp32 qkv [k, 3*H*D] / o [k, H*D]; bf16 or fp16 cache), and the accept step of a verify pass
-// shared-prefix batched decode attention (decode_prefix.hip): keys [0, *prefix_len_dev) read from slab 0 once for all B <= 16 queries
-size_t llama_decode_attn_batch_prefix_scratch_bytes(int B, int H, int D);
-int llama_decode_attn_batch_prefix(const void* qkv, int io_f32, int64_t ldq, bf16_t* kcache, bf16_t* vcache, int64_t cache_stride,
-                                   int tmax, void* o, int64_t ldo, int B, int H, int D, const int32_t* pos_dev,
-                                   const int32_t* prefix_len_dev, float theta, float scale, const float* cos_tab,
-                                   const float* sin_tab, int cache_f16, void* scratch, size_t scratch_bytes, hipStream_t st);
-int llama_verify_attn(const float* qkv, int k, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, const int32_t* pos_dev,
-                      float theta, float scale, const float* cos_tab, const float* sin_tab, int cache_f16, hipStream_t st);
+// the accept step of a speculative verify pass (verify.hip)
 int spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* nd_dev, int k, int32_t* n_acc, int32_t* tok, int32_t* pos,
                 hipStream_t st);
-
-// fused decode attention + o_proj (decode_fused.hip)
-int llama_attn_oproj(const float* qkv, bf16_t* kcache, bf16_t* vcache, int tmax, float* attn_scratch, const bf16_t* wo,
-                     const float* x, float* x_out, int H, int D, float theta, float scale, const float* cos_tab,
-                     const float* sin_tab, const int32_t* pos_dev, const int32_t* step_dev, int32_t* counter, int32_t* status,
-                     hipStream_t st);
 
 // ---- skinny GEMM (gemv.hip): M <= 8 rows of activations against streamed weights -------------------
 int gemv_bf16(const GemmArgs& g, hipStream_t st);

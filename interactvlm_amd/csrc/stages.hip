@@ -274,34 +274,37 @@ int decode_step(const ivlm_llama_cfg* c, const Layer* layers_host, const void* f
         IVLM_HIP_TRY(hipGetDevice(&dev));
         IVLM_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    const bool fused = !packed && !cache_f16 && c->fuse_attn_oproj && (Hd == 512 || Hd == 1024 || Hd == 4096 || Hd == 5120) &&
-                       H + Hd / 32 <= cus;
+    const bool fused = !packed && !cache_f16 && c->fuse_attn_oproj && attn_oproj_fits(H, D, cus);
     const bool split_kv = packed && !c->fuse_attn_oproj;
     const int64_t cache_layer = (int64_t)c->max_len * Hd;
-    const float scale = 1.0f / sqrtf((float)D);
+    // the attention of every layer: what changes per layer is the cache slab and, in the fused form, the operands of o_proj
+    DecodeAttnArgs at = decode_attn_args(b.qkv, 1, nullptr, nullptr, cache_f16, c->max_len, b.att, H, D, 0, pos_dev, c->theta,
+                                         1.0f / sqrtf((float)D), cos_tab, sin_tab);
+    at.scratch = b.parts;  // (split KV: the parts buffer)
+    at.step_dev = b.words + 1; at.status = b.words; at.cus = cus;
     const float* x = x_in;
     int rc = 0;
     for (int l = 0; l < c->layers; ++l) {
         const Layer& L = layers_host[l];
-        bf16_t* kc = static_cast<bf16_t*>(kcache) + l * cache_layer;
-        bf16_t* vc = static_cast<bf16_t*>(vcache) + l * cache_layer;
+        at.kcache = static_cast<bf16_t*>(kcache) + l * cache_layer;
+        at.vcache = static_cast<bf16_t*>(vcache) + l * cache_layer;
         if ((rc = dec_linear(c, x, L.qkv, b.qkv, nullptr, 3 * Hd, Hd, ACT_NONE, L.ln1, stream))) return rc;
         float* x1 = (x == b.xa) ? b.xb : b.xa;
         if (fused) {
-            if constexpr (!packed)
-                rc = llama_attn_oproj(b.qkv, kc, vc, c->max_len, b.scratch + (size_t)l * Hd, static_cast<const bf16_t*>(L.o), x, x1, H, D,
-                                      c->theta, scale, cos_tab, sin_tab, pos_dev, b.words + 1, b.counters + l * 32, b.words, st);
+            if constexpr (!packed) {
+                at.scratch = b.scratch + (size_t)l * Hd; at.wo = static_cast<const bf16_t*>(L.o); at.x = x; at.x_out = x1;
+                at.counter = b.counters + l * 32;
+                rc = decode_attn(DA_FUSED, at, st);
+            }
         } else if (split_kv) {
             if constexpr (packed) {
-                rc = llama_decode_attn_parts(b.qkv, kc, vc, c->max_len, b.parts, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev,
-                                             cache_f16);
+                rc = decode_attn(DA_PARTS, at, st);
                 if (!rc)
                     rc = ivlm_gemv1_bf12m_parts(b.parts, D, L.o.Pf, L.o.Ef, L.o.ebase, L.o.patch_ptr, L.o.patch_col, L.o.patch_val, x1,
                                                 nullptr, x, Hd, Hd, ACT_NONE, 1, IVLM_GEMM_RES_F32, stream);
             }
         } else {
-            rc = llama_decode_attn(b.qkv, 1, kc, vc, c->max_len, b.att, H, D, 0, c->theta, scale, st, cos_tab, sin_tab, pos_dev, nullptr,
-                                   nullptr, cache_f16);
+            rc = decode_attn(DA_ONE_BLOCK, at, st);
             if (!rc) rc = dec_linear(c, b.att, L.o, x1, x, Hd, Hd, ACT_NONE, nullptr, stream);
         }
         if (rc) return rc;

@@ -16,7 +16,7 @@
 namespace ivlm {
 namespace {
 
-constexpr int kVMaxK = 16, kVMaxD = 128, kVThreads = 1024, kVChunk = 256;
+constexpr int kVMaxK = decattn::kVerifyMaxK, kVMaxD = decattn::kMaxD, kVThreads = 1024, kVChunk = 256;
 
 template <bool CF16>
 __global__ __launch_bounds__(kVThreads) void llama_verify_attn_kernel(const float* __restrict__ qkv, int k, bf16_t* __restrict__ kcache,
@@ -225,18 +225,12 @@ __global__ void spec_accept_kernel(const int32_t* __restrict__ amax, const int32
 
 }  // namespace
 
-int llama_verify_attn(const float* qkv, int k, bf16_t* kcache, bf16_t* vcache, int tmax, float* o, int H, int D, const int32_t* pos_dev,
-                      float theta, float scale, const float* cos_tab, const float* sin_tab, int cache_f16, hipStream_t st) {
-    if (!qkv || !kcache || !vcache || !o || !pos_dev) return IVLM_ERR_INVALID_ARG;
-    if (k <= 0 || k > kVMaxK || H <= 0 || D <= 0 || D > kVMaxD || (D & 15) || tmax <= 0) return IVLM_ERR_INVALID_ARG;
-    if ((cos_tab != nullptr) != (sin_tab != nullptr)) return IVLM_ERR_INVALID_ARG;
-    if (cache_f16)
-        llama_verify_attn_kernel<true><<<H, kVThreads, 0, st>>>(qkv, k, kcache, vcache, o, H, D, theta, scale, cos_tab, sin_tab, pos_dev,
-                                                                tmax);
-    else
-        llama_verify_attn_kernel<false><<<H, kVThreads, 0, st>>>(qkv, k, kcache, vcache, o, H, D, theta, scale, cos_tab, sin_tab, pos_dev,
-                                                                 tmax);
-    return ivlm_launch_status();
+void decattn::launch_verify(const DecodeAttnArgs& a, hipStream_t st) {  // (a checked call: B = k rows)
+    with_cache_f16(a, [&](int flags, auto cf) {
+        launch(K_VERIFY, flags, -1, llama_verify_attn_kernel<cf.value>, dim3(a.H), dim3(kVThreads), st,
+               static_cast<const float*>(a.qkv), a.B, a.kcache, a.vcache, static_cast<float*>(a.o), a.H, a.D, a.theta, a.scale, a.cos_tab, a.sin_tab,
+               a.pos_dev, a.tmax);
+    });
 }
 
 int spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* nd_dev, int k, int32_t* n_acc, int32_t* tok, int32_t* pos,
@@ -248,20 +242,23 @@ int spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* nd_dev, 
 
 }  // namespace ivlm
 
+static int verify_entry(const float* qkv, int k, void* kcache, void* vcache, int cache_f16, int tmax, float* o, int H, int D,
+                        const int32_t* pos_dev, float theta, float scale, const float* cos_tab, const float* sin_tab, ivlm_stream_t stream) {
+    ivlm_enter();
+    return ivlm::decode_attn(ivlm::DA_VERIFY, ivlm::decode_attn_args(qkv, 1, kcache, vcache, cache_f16, tmax, o, H, D, 0, pos_dev, theta,
+        scale, cos_tab, sin_tab).rows(0, 0, 0, k), ivlm_stream(stream));
+}
+
 extern "C" int ivlm_llama_verify_attn(const float* qkv, int k, void* kcache, void* vcache, int tmax, float* o, int H, int D,
                                       const int32_t* pos_dev, float theta, float scale, const float* cos_tab, const float* sin_tab,
                                       ivlm_stream_t stream) {
-    ivlm_enter();
-    return ivlm::llama_verify_attn(qkv, k, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o, H, D, pos_dev, theta,
-                                   scale, cos_tab, sin_tab, 0, ivlm_stream(stream));
+    return verify_entry(qkv, k, kcache, vcache, 0, tmax, o, H, D, pos_dev, theta, scale, cos_tab, sin_tab, stream);
 }
 
 extern "C" int ivlm_llama_verify_attn_f16(const float* qkv, int k, void* kcache, void* vcache, int tmax, float* o, int H, int D,
                                           const int32_t* pos_dev, float theta, float scale, const float* cos_tab, const float* sin_tab,
                                           ivlm_stream_t stream) {
-    ivlm_enter();
-    return ivlm::llama_verify_attn(qkv, k, static_cast<bf16_t*>(kcache), static_cast<bf16_t*>(vcache), tmax, o, H, D, pos_dev, theta,
-                                   scale, cos_tab, sin_tab, 1, ivlm_stream(stream));
+    return verify_entry(qkv, k, kcache, vcache, 1, tmax, o, H, D, pos_dev, theta, scale, cos_tab, sin_tab, stream);
 }
 
 extern "C" int ivlm_spec_accept(const int32_t* amax, const int32_t* fed, const int32_t* n_draft, int k, int32_t* n_acc, int32_t* tok,

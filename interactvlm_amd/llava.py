@@ -486,9 +486,9 @@ class Llama:
         if batched:
             return _GraphKey(True, B, self.precision, self.decode_packed and self.decode_packed_batch and B > 1, self.fp8, False)
         c = self.cfg
-        # (every block of the fused launch must be resident at once: one 1024-thread block per CU)
-        fused = bool(self.fuse_attn_oproj and c.hidden in (512, 1024, 4096, 5120)
-                     and c.heads + c.hidden // 32 <= torch.cuda.get_device_properties(self.device).multi_processor_count)
+        # (every block of the fused launch must be resident at once: one 1024-thread block per CU; hidden % heads == 0, as everywhere here)
+        fused = bool(self.fuse_attn_oproj and _lib.load().ivlm_llama_attn_oproj_fits(
+            c.heads, c.hidden // c.heads, torch.cuda.get_device_properties(self.device).multi_processor_count))
         return _GraphKey(False, 1, self.precision, bool(self.decode_packed), self.fp8, fused)
 
     def _drop_graphs(self, pred):

@@ -1138,17 +1138,28 @@ def mask_dot(up, hyper, B, gh, gw):
     return low
 
 
+# ---- the decode-attention entry points: what their argument lists share ----------------------------------------------------------
+def _pos_pair(pos):
+    """(host position, device position pointer): one of the two is used"""
+    return (0, pos.data_ptr()) if isinstance(pos, torch.Tensor) else (int(pos), 0)
+
+
+def _rope_tail(theta, scale, table):
+    return float(theta), float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0
+
+
+def _cache_code(kcache):
+    return 4 if kcache.dtype == F16 else IVLM_BF16
+
+
 def llama_decode_attn_parts(qkv, kcache, vcache, H, D, pos, theta, scale, parts, table=None):
     """Split-KV decode attention WITHOUT the merge: RoPE + cache append + four key ranges per head -> parts fp32 [H, 4, D + 4] (o
     unnormalised | max | sum | pad) for ``linear_bf12(..., parts=)`` (the o_proj merges them while it stages its activation row)."""
     lib = _lib.load()
     assert qkv.dtype == F32 and qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
     assert parts.dtype == F32 and parts.is_contiguous() and parts.numel() >= H * 4 * (D + 4) and kcache.dtype in (BF16, F16)
-    dev_pos = isinstance(pos, torch.Tensor)
-    check(lib.ivlm_llama_decode_attn_parts(qkv.data_ptr(), 4 if kcache.dtype == F16 else IVLM_BF16, kcache.data_ptr(), vcache.data_ptr(),
-                                           kcache.shape[0], parts.data_ptr(), H, D, 0 if dev_pos else int(pos),
-                                           pos.data_ptr() if dev_pos else 0, float(theta), float(scale),
-                                           _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()),
+    check(lib.ivlm_llama_decode_attn_parts(qkv.data_ptr(), _cache_code(kcache), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0],
+                                           parts.data_ptr(), H, D, *_pos_pair(pos), *_rope_tail(theta, scale, table), _stream()),
           "llama_decode_attn_parts")
     return parts
 
@@ -1164,40 +1175,26 @@ def llama_decode_attn(qkv, kcache, vcache, H, D, pos, theta, scale, out=None, ta
     pos: python int, or an int32 device tensor [1] (read by the kernel: HIP-graph friendly).  kcache [Tmax, H, D].
     lo = (kcache_lo, vcache_lo): "parity" precision, K / V cached as hi + lo planes (fp32 qkv only).
     scratch (decode_attn_scratch; fp32 qkv, no lo planes): the split-KV kernel - H x S blocks instead of H."""
-    lib = _lib.load()
     assert qkv.dtype in (BF16, F32) and qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
     if out is None:
         out = torch.empty(1, H * D, dtype=qkv.dtype, device=qkv.device)
     dev_pos = isinstance(pos, torch.Tensor)
     if dev_pos:
         assert pos.dtype == torch.int32 and pos.is_cuda
+    lib, q, k, v = _lib.load(), qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
+    rest = (kcache.shape[0], out.data_ptr(), H, D, *_pos_pair(pos), *_rope_tail(theta, scale, table))
     if scratch is not None and lo is None and qkv.dtype == F32:
         assert kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
-        check(lib.ivlm_llama_decode_attn_splitkv(qkv.data_ptr(), 4 if kcache.dtype == F16 else IVLM_BF16,
-                                                 kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(), H, D,
-                                                 0 if dev_pos else int(pos), pos.data_ptr() if dev_pos else 0, float(theta),
-                                                 float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0,
-                                                 scratch.data_ptr(), scratch.numel(), _stream()), "llama_decode_attn_splitkv")
-        return out
-    if lo is not None:
+        check(lib.ivlm_llama_decode_attn_splitkv(q, _cache_code(kcache), k, v, *rest, scratch.data_ptr(), scratch.numel(), _stream()),
+              "llama_decode_attn_splitkv")
+    elif lo is not None:
         assert qkv.dtype == F32 and lo[0].is_contiguous() and lo[1].is_contiguous() and lo[0].shape == kcache.shape
-        check(lib.ivlm_llama_decode_attn_split(qkv.data_ptr(), kcache.data_ptr(), lo[0].data_ptr(), vcache.data_ptr(),
-                                               lo[1].data_ptr(), kcache.shape[0], out.data_ptr(), H, D,
-                                               0 if dev_pos else int(pos), pos.data_ptr() if dev_pos else 0, float(theta),
-                                               float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0,
-                                               _stream()), "llama_decode_attn_split")
-        return out
-    if kcache.dtype == F16:  # fp16 cache (the fp16-operand prefill): fp32 qkv / o
+        check(lib.ivlm_llama_decode_attn_split(q, k, lo[0].data_ptr(), v, lo[1].data_ptr(), *rest, _stream()), "llama_decode_attn_split")
+    elif kcache.dtype == F16:  # fp16 cache (the fp16-operand prefill): fp32 qkv / o
         assert qkv.dtype == F32 and vcache.dtype == F16
-        check(lib.ivlm_llama_decode_attn_f16(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(),
-                                             H, D, 0 if dev_pos else int(pos), pos.data_ptr() if dev_pos else 0, float(theta),
-                                             float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()),
-              "llama_decode_attn_f16")
-        return out
-    check(lib.ivlm_llama_decode_attn(qkv.data_ptr(), _dtc(qkv), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0],
-                                     out.data_ptr(), H, D, 0 if dev_pos else int(pos), pos.data_ptr() if dev_pos else 0,
-                                     float(theta), float(scale), _p(table[0]) if table else 0,
-                                     _p(table[1]) if table else 0, _stream()), "llama_decode_attn")
+        check(lib.ivlm_llama_decode_attn_f16(q, k, v, *rest, _stream()), "llama_decode_attn_f16")
+    else:
+        check(lib.ivlm_llama_decode_attn(q, _dtc(qkv), k, v, *rest, _stream()), "llama_decode_attn")
     return out
 
 
@@ -1205,32 +1202,23 @@ def llama_decode_attn_batch(qkv, kcache, vcache, H, D, pos_dev, theta, scale, ta
     """One decode step of B sequences: qkv bf16 | fp32 [B, 3*H*D], kcache/vcache bf16 [B, Tmax, H, D] (one slab per
     sequence), pos_dev int32 [B] on the device -> o [B, H*D].  A sequence whose position has reached Tmax is skipped: its
     output row is zero (written by the kernel)."""
-    lib = _lib.load()
     B = qkv.shape[0]
     assert qkv.dtype in (BF16, F32) and qkv.stride(1) == 1 and kcache.dim() == 4 and kcache.shape[0] == B
     assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
     assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() == B and pos_dev.is_contiguous()
     if out is None:
         out = torch.empty(B, H * D, dtype=qkv.dtype, device=qkv.device)
+    lib, q, k, v = _lib.load(), (qkv.data_ptr(), qkv.stride(0)), kcache.data_ptr(), vcache.data_ptr()
+    rest = (kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D, pos_dev.data_ptr(), *_rope_tail(theta, scale, table))
     if lo is not None:  # "parity" precision: hi + lo cache planes
         assert qkv.dtype == F32 and lo[0].stride() == kcache.stride() and lo[1].stride() == vcache.stride()
-        check(lib.ivlm_llama_decode_attn_batch_split(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), lo[0].data_ptr(),
-                                                     vcache.data_ptr(), lo[1].data_ptr(), kcache.stride(0), kcache.shape[1],
-                                                     out.data_ptr(), out.stride(0), B, H, D, pos_dev.data_ptr(), float(theta),
-                                                     float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0,
-                                                     _stream()), "llama_decode_attn_batch_split")
-        return out
-    if kcache.dtype == F16:
+        check(lib.ivlm_llama_decode_attn_batch_split(*q, k, lo[0].data_ptr(), v, lo[1].data_ptr(), *rest, _stream()),
+              "llama_decode_attn_batch_split")
+    elif kcache.dtype == F16:
         assert qkv.dtype == F32 and vcache.dtype == F16
-        check(lib.ivlm_llama_decode_attn_batch_f16(qkv.data_ptr(), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                                   kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D,
-                                                   pos_dev.data_ptr(), float(theta), float(scale), _p(table[0]) if table else 0,
-                                                   _p(table[1]) if table else 0, _stream()), "llama_decode_attn_batch_f16")
-        return out
-    check(lib.ivlm_llama_decode_attn_batch(qkv.data_ptr(), _dtc(qkv), qkv.stride(0), kcache.data_ptr(), vcache.data_ptr(),
-                                           kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D,
-                                           pos_dev.data_ptr(), float(theta), float(scale), _p(table[0]) if table else 0,
-                                           _p(table[1]) if table else 0, _stream()), "llama_decode_attn_batch")
+        check(lib.ivlm_llama_decode_attn_batch_f16(*q, k, v, *rest, _stream()), "llama_decode_attn_batch_f16")
+    else:
+        check(lib.ivlm_llama_decode_attn_batch(q[0], _dtc(qkv), q[1], k, v, *rest, _stream()), "llama_decode_attn_batch")
     return out
 
 
@@ -1263,8 +1251,7 @@ def llama_decode_attn_batch_prefix(qkv, kcache, vcache, H, D, pos_dev, prefix_de
     if scratch is None:
         scratch = decode_attn_prefix_scratch(B, H, D, qkv.device)
     args = (kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D,
-            pos_dev.data_ptr(), prefix_dev.data_ptr(), float(theta), float(scale), _p(table[0]) if table else 0,
-            _p(table[1]) if table else 0, scratch.data_ptr(), scratch.numel(), _stream())
+            pos_dev.data_ptr(), prefix_dev.data_ptr(), *_rope_tail(theta, scale, table), scratch.data_ptr(), scratch.numel(), _stream())
     if kcache.dtype == F16:
         check(lib.ivlm_llama_decode_attn_batch_prefix_f16(qkv.data_ptr(), qkv.stride(0), *args), "llama_decode_attn_batch_prefix_f16")
     else:
@@ -1288,7 +1275,7 @@ def llama_verify_attn(qkv, kcache, vcache, H, D, pos_dev, theta, scale, table=No
         out = torch.empty(k, H * D, dtype=F32, device=qkv.device)
     fn = lib.ivlm_llama_verify_attn_f16 if kcache.dtype == F16 else lib.ivlm_llama_verify_attn
     check(fn(qkv.data_ptr(), k, kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(), H, D, pos_dev.data_ptr(),
-             float(theta), float(scale), _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()), "llama_verify_attn")
+             *_rope_tail(theta, scale, table), _stream()), "llama_verify_attn")
     return out
 
 
