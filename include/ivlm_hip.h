@@ -201,7 +201,8 @@ int ivlm_gemm_bf16_panel(const void *A, int64_t lda, int64_t a_kstep, const void
  * *scale_w + bias) + residual on v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, fp32 accumulation, the tile kernels
  * of ivlm_gemm_bf16 (same tiles, DMA and epilogues; half the K tiles).  A [M,K] / W [N,K] are byte matrices (K, lda, ldw in
  * bytes, multiples of 16; K % 128 != 0 tails are zero-filled); per-tensor scales are device scalars (x = q * scale).
- * out_kind: IVLM_BF16, IVLM_F32, or 2 = e4m3 output act(...) / *scale_out (mlp1 -> mlp2).  act: none | GELU.  M > 16.
+ * out_kind: IVLM_BF16, IVLM_F32, or 2 = e4m3 output act(...) / *scale_out (mlp1 -> mlp2; N % 4 == 0 and ldc % 4 == 0: the bytes leave four
+ * at a time, anything else is IVLM_ERR_UNSUPPORTED / IVLM_ERR_INVALID_ARG).  act: none | GELU.  M > 16.
  * The reference has no counterpart (it is a bf16 model): an opt-in variant whose error is reported against the bf16 path. */
 int ivlm_gemm_fp8(const void *A, int64_t lda, const void *W, int64_t ldw, void *C, int64_t ldc, const void *bias,
                   const void *residual, int64_t ldr, int M, int N, int K, int act, int out_kind, const float *scale_a,

@@ -427,6 +427,7 @@ int gemm_bf16(const GemmArgs& g, hipStream_t st) {
     }
     if (g.fp8 && (!g.scale_a || !g.scale_w || (g.out_fp8 && (!g.scale_out || g.out_f32 || (g.ldc & 3))))) return IVLM_ERR_INVALID_ARG;
     if (g.out_fp8 && !g.fp8) return IVLM_ERR_UNSUPPORTED;
+    if (g.out_fp8 && (g.N & 3)) return IVLM_ERR_UNSUPPORTED;  // e4m3 leaves four bytes at a time: the scalar tail of a ragged N has no such store
     const GemmRoute r = gemm_route(g, g_gemm_switches);
     if (r.rc != IVLM_OK) return r.rc;
     if (route_logged(r.family, r.bm, r.bn, r.opk, r.out_f32, r.act, r.grid_x, r.grid_z, r.lds)) return IVLM_OK;

@@ -283,17 +283,29 @@ def test_gemm_fp32_residual_and_scatter_epilogue(hip_lib, cuda):
         assert got.shape == (M2, N2) and torch.allclose(got, ref, atol=2e-3, rtol=1e-4), (tile, M2, N2, K2)
 
 
-@pytest.mark.parametrize("M,N,K,act,f32res", [(16384, 1280, 1280, "none", True), (16384, 1280, 5120, "none", True),
+@pytest.mark.parametrize("M,N,K,act,f32res", [(8192, 2304, 2048, "none", True), (8192, 2304, 2048, "gelu", False),
+                                              (16384, 1280, 1280, "none", True), (16384, 1280, 5120, "none", True),
                                               (8192, 768, 512, "gelu", False), (4096, 1536, 256, "none", False)])
 def test_gemm_column_split_matches_unsplit(hip_lib, cuda, M, N, K, act, f32res):
-    """The column split of under-filled 256 x 256 rounds (SAM proj / mlp2: 320 tiles -> 256 on the 8-phase kernel + a strip
-    on 128 x 64 tiles) against the unsplit launch: same K order per output element on every tile kernel, so the two agree to
-    fp32 rounding of different MFMA groupings; both against fp32 torch."""
+    """The column split of under-filled 256 x 256 rounds (288 tiles -> 256 on the 8-phase kernel + a strip on 128 x 64 tiles)
+    against the unsplit launch: same K order per output element on every tile kernel, so the two agree to
+    fp32 rounding of different MFMA groupings; both against fp32 torch.  ivlm_gemm_route_query says whether the call splits: the
+    first two shapes do (two launches); the last four are the SAM shapes this test began with, which run as ONE launch with the hook
+    on or off (K < 2048, or whole rounds of 256 x 320 tiles) and stay as a check of that."""
+    import ctypes
+
     import torch
 
     from interactvlm_amd import _lib, ops
 
     lib = _lib.load()
+    splits = (M, N, K) == (8192, 2304, 2048)
+    rec = (ctypes.c_int32 * 72)()
+    n_launches = lib.ivlm_gemm_route_query(0, M, N, K, K, K, N, N, 0, 0, 0, ops.ACT[act], 1, 1, 1, 0, 1, ops.GEMM_RES_F32 if f32res else 0,
+                                           0, 0, 0, ctypes.cast(rec, ctypes.c_void_p), 8)
+    assert n_launches == (2 if splits else 1), list(rec[:18])
+    if splits:
+        assert tuple(rec[0:3]) == (1, 256, 256) and tuple(rec[9:12]) == (0, 128, 64)
     g = torch.Generator().manual_seed(M + N + K)
     x = _bf(torch.randn(M, K, generator=g)).to(cuda)
     w = _bf(torch.randn(N, K, generator=g) / K ** 0.5).to(cuda)
