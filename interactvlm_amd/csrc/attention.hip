@@ -16,13 +16,13 @@
 //     once the key order inside each 32-key step is permuted consistently for P and V.
 //   * LDS images are built for the hardware's lane groups (a ds_read_b128 is served 16 lanes at a time: {0-3,12-15,
 //     20-27}, {4-11,16-19,28-31}, ...; bank = dword address mod 64):
-//       K  [k-step][key][32 elements]: 64-byte rows, 16-byte chunk g of key r stored at chunk g ^ ((r >> 3 & 1) << 1) -
-//          every lane group then covers 16 distinct 16-byte bank slots (a padded row-major image is 2-way conflicted);
-//       V  [16-wide d tile][key][16 elements], row-major as it arrives from HBM (16-byte stores, no scatter): the
-//          V^T fragments of the second MFMA come from ds_read_b64_tr_b16 (4 keys x 16 d per 16-lane group, lane i
-//          receives column i), two reads per fragment in the permuted key order.
+//       K  [k-step][key][32 elements] with a chunk swizzle (k_chunk_off / k_frag_off below: conflict-free fragment reads);
+//       V  [16-wide d tile][key][16 elements], row-major as it arrives from HBM (v_chunk_off); the V^T fragments of the
+//          second MFMA come from ds_read_b64_tr_b16 (v_frag), two reads per fragment in the permuted key order.
 //     Both are double-buffered: one barrier per key tile.  Head dim 80 pads to 96 for QK^T (zero chunks).
 //   * the S x S score matrix is never materialised (the reference materialises [B*16,4096,4096]).
+// File order: the fragment helpers (LDS image addresses, V^T fragment, q * scale, rel-pos operands and table product, lo
+// probabilities, output store) that attn_kernel and the whole-window win_attn_kernel share, the two kernels, the dispatch.
 #include <algorithm>
 
 #include "kernels.h"
@@ -48,21 +48,11 @@ __device__ __forceinline__ f32x4_t mma16(const bf16x8_t a, const bf16x8_t b, con
     else
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-// two fp32 -> one packed 16-bit pair (RNE; fp16 overflows to inf), and back
+// two fp32 -> one packed 16-bit pair (RNE; fp16 overflows to inf); back with pair_lo_f32 / pair_hi_f32
 template <bool F16>
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
     if constexpr (F16) return pack_f16x2(lo, hi);
     else return pack_bf16x2(lo, hi);
-}
-template <bool F16>
-__device__ __forceinline__ float lo16(uint32_t u) {
-    if constexpr (F16) return (float)__builtin_bit_cast(ivlm_f16x2_t, u)[0];
-    else return __uint_as_float(u << 16);
-}
-template <bool F16>
-__device__ __forceinline__ float hi16(uint32_t u) {
-    if constexpr (F16) return (float)__builtin_bit_cast(ivlm_f16x2_t, u)[1];
-    else return __uint_as_float(u & 0xffff0000u);
 }
 
 constexpr int kQPerWave = 32, kWaves = 4, kQPerBlock = kQPerWave * kWaves, kKV = 64;
@@ -87,6 +77,165 @@ __device__ __forceinline__ float groups_sum(float x) {
 // Block barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. it would wait at EVERY key tile for the
 // global loads of the next tiles that were issued precisely so that they stay in flight across the barrier.
 __device__ __forceinline__ void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// ======================================================================================================================
+// Fragment helpers of attn_kernel and win_attn_kernel.  A lane is (l15, g) = (lane & 15, lane >> 4): row l15 of a 16-row tile
+// (a key of the A operand, a query of the B operand and of every accumulator), 16-byte chunk g of a 32-element k-step.
+
+// ---- the K and V images in LDS (element offsets inside one buffer; the plane strides KPL / VPL carry the pad row of AttnLds) ----
+// K [k-step][key][32 elements]: 64-byte rows, 16-byte chunk ch of key r stored at chunk ch ^ ((r >> 3 & 1) << 1) - every lane group
+// of a ds_read_b128 then covers 16 distinct 16-byte bank slots (a padded row-major image is 2-way conflicted).  The window
+// kernel's rel-pos table image uses the same layout (rows for keys).
+__device__ __forceinline__ int k_swz(int key, int ch) { return (ch & 3) ^ (((key >> 3) & 1) << 1); }
+__device__ __forceinline__ int k_chunk_off(int key, int dch, int KPL) {
+    const int phys = k_swz(key, dch);
+    return (dch >> 2) * KPL + key * 32 + phys * 8;
+}
+// read side: this lane's chunk inside the 64-byte row of key kt * 16 + l15 (add ks * KPL + (kt * 16 + l15) * 32)
+__device__ __forceinline__ int k_frag_off(int l15, int g) { return k_swz(l15, g) * 8; }
+// V [16-wide d tile][key][16 elements], row-major as it arrives from HBM (16-byte stores, no scatter)
+__device__ __forceinline__ int v_chunk_off(int key, int dch, int VPL) { return (dch >> 1) * VPL + key * 16 + (dch & 1) * 8; }
+// read side: the tr-read address of this lane inside a 16-key tile: key g*4 + l15/4, d-quad l15%4
+__device__ __forceinline__ int v_frag_off(int l15, int g) { return (g * 4 + (l15 >> 2)) * 16 + (l15 & 3) * 4; }
+// V^T fragment of one 32-key step (vp = plane + step * 32 * 16 + v_frag_off): ds_read_b64_tr_b16 hands lane i column i of 4 keys x 16 d
+// per 16-lane group, two reads (16 keys apart) give the 8 K-slots in the permuted key order of the P^T fragments
+__device__ __forceinline__ bf16x8_t v_frag(const bf16_t* vp) {
+    typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+    typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
+    typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp));
+    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp + 16 * 16));
+    return __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// ---- q * scale before the dot product (SAM, HF-CLIP), one fragment.  Single operand: rounded to 16 bits like the reference's bf16
+// model does; HILO (SPLIT: bf16 planes, QLO: IEEE halves): in fp32 on the hi + lo value, split again.
+template <bool HILO, bool F16>
+__device__ __forceinline__ void q_times_scale(bf16x8_t& hi, bf16x8_t& lo, const float sc) {
+    u32x4_t uh = __builtin_bit_cast(u32x4_t, hi);
+    if constexpr (HILO) {
+        u32x4_t ul = __builtin_bit_cast(u32x4_t, lo);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            uint32_t hh, ll;
+            split_16x2((pair_lo_f32<F16>(uh[e]) + pair_lo_f32<F16>(ul[e])) * sc, (pair_hi_f32<F16>(uh[e]) + pair_hi_f32<F16>(ul[e])) * sc, hh, ll, F16);
+            uh[e] = hh;
+            ul[e] = ll;
+        }
+        lo = __builtin_bit_cast(bf16x8_t, ul);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) uh[e] = pack2<F16>(pair_lo_f32<F16>(uh[e]) * sc, pair_hi_f32<F16>(uh[e]) * sc);
+    }
+    hi = __builtin_bit_cast(bf16x8_t, uh);
+}
+
+// ---- rel-pos terms as operands of the one-hot MFMAs: 8 fp32 bias values (features g*8 .. g*8+7 = [rel_h(KH) | rel_w(KW) | 0] of
+// this lane's query) packed into hi (default precision: the terms rounded to bf16, as the bf16 reference materialises them) and
+//   F16: lo - the terms ADD to the scores: an fp16 rounding of a bias of +-8 would be an absolute 2e-3 on the score, so they
+//        travel as hi + lo fp16 operands (22 bits) of two one-hot MFMAs;
+//   SPLIT: lo + lo2 - three bf16 terms carry all 24 bits of the fp32 value: the one-hot MFMAs add them exactly; a bias of +-20
+//        split in two would be off by 1e-4.
+template <bool SPLIT, bool F16>
+__device__ __forceinline__ void pack_rel_terms(const float (&f)[8], bf16x8_t& hi, bf16x8_t& lo, bf16x8_t& lo2) {
+    u32x4_t uh, ul, ul2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float f0 = f[2 * e], f1 = f[2 * e + 1];
+        uh[e] = pack2<F16>(f0, f1);
+        const float r0 = f0 - pair_lo_f32<F16>(uh[e]), r1 = f1 - pair_hi_f32<F16>(uh[e]);
+        if (SPLIT || F16) ul[e] = pack2<F16>(r0, r1);
+        if (SPLIT) ul2[e] = pack_bf16x2(r0 - pair_lo_f32<false>(ul[e]), r1 - pair_hi_f32<false>(ul[e]));
+    }
+    hi = __builtin_bit_cast(bf16x8_t, uh);
+    if (SPLIT || F16) lo = __builtin_bit_cast(bf16x8_t, ul);
+    if (SPLIT) lo2 = __builtin_bit_cast(bf16x8_t, ul2);
+}
+
+// the A operand that picks them: the one-hot (kh, rel_kh + kw) code of a key of a rel_kh x rel_kw grid, chunk g (exact, no VALU add)
+template <bool F16>
+__device__ __forceinline__ bf16x8_t one_hot_rel(int key, int rel_kh, int rel_kw, int g) {
+    constexpr uint32_t kOne16 = F16 ? 0x3C00u : 0x3F80u;  // 1.0 as a 16-bit operand
+    const int kh = key / rel_kw;
+    const int f1 = kh - g * 8, f2 = rel_kh + (key - kh * rel_kw) - g * 8;  // hot slots e
+    u32x4_t w;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = (f1 == 2 * j || f2 == 2 * j) ? kOne16 : 0u;
+        const uint32_t hi = (f1 == 2 * j + 1 || f2 == 2 * j + 1) ? (kOne16 << 16) : 0u;
+        w[j] = lo | hi;
+    }
+    return __builtin_bit_cast(bf16x8_t, w);
+}
+
+// ---- rel-pos terms of a square window from its table (REL 4 of attn_kernel, table mode of win_attn_kernel): the decomposed terms
+// computed in the attention kernel instead of by a kernel of their own (54 us and 120 MB of traffic per windowed block).
+// G^T = T . Q^T on the matrix cores - T = [rel_pos_h ; rel_pos_w ; 0] (64 rows; tab(ks, row) fetches this lane's A fragment of it), Q the
+// UNSCALED query fragments already in registers - lands in C layout (lane = query l15, rows g*4+r of each 16-row tile), goes through
+// the wave's LDS scratch Gw and comes back as the 2 * side Toeplitz picks of this lane's query qi:
+//   rel_h[q][kh] = G[q][qh - kh + side - 1],   rel_w[q][kw] = G[q][(2 side - 1) + qw - kw + side - 1].
+template <bool F16, bool QL, int KS, int NL, class Tab>
+__device__ __forceinline__ void rel_table_terms(Tab tab, const bf16x8_t (&qf)[KS], const bf16x8_t (&qfl)[NL], float* Gw, int l15, int g,
+                                                int qi, int side, float (&f)[8]) {
+    f32x4_t gacc[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) gacc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) {
+            const bf16x8_t tf = tab(ks, rt * 16 + l15);
+            gacc[rt] = mma16<F16>(tf, qf[ks], gacc[rt]);
+            if (QL) gacc[rt] = mma16<F16>(tf, qfl[QL ? ks : 0], gacc[rt]);
+        }
+    }
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Gw[l15 * 65 + rt * 16 + g * 4 + r] = gacc[rt][r];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const int qh = qi / side, qw = qi - qh * side;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int fi = g * 8 + e;
+        float v = 0.0f;
+        if (fi < side) v = Gw[l15 * 65 + qh - fi + side - 1];
+        else if (fi < 2 * side) v = Gw[l15 * 65 + (2 * side - 1) + qw - (fi - side) + side - 1];
+        f[e] = v;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();  // the scratch is reused by the wave's next query tile
+}
+
+// ---- lo halves of a P^T fragment, p - rnd16(p) of the 8 probabilities it was packed from (exactly representable differences, rounded
+// once): bf16 for SPLIT, fp16 for QLO.  (The hi packing stays with each kernel: they schedule differently.)
+template <bool F16>
+__device__ __forceinline__ bf16x8_t p_lo(const f32x4_t& sa, const f32x4_t& sb, const bf16x8_t pf) {
+    const u32x4_t u = __builtin_bit_cast(u32x4_t, pf);
+    u32x4_t ul;
+    ul[0] = pack2<F16>(sa[0] - pair_lo_f32<F16>(u[0]), sa[1] - pair_hi_f32<F16>(u[0]));
+    ul[1] = pack2<F16>(sa[2] - pair_lo_f32<F16>(u[1]), sa[3] - pair_hi_f32<F16>(u[1]));
+    ul[2] = pack2<F16>(sb[0] - pair_lo_f32<F16>(u[2]), sb[1] - pair_hi_f32<F16>(u[2]));
+    ul[3] = pack2<F16>(sb[2] - pair_lo_f32<F16>(u[3]), sb[3] - pair_hi_f32<F16>(u[3]));
+    return __builtin_bit_cast(bf16x8_t, ul);
+}
+
+// ---- normalise and store what a lane holds of output tile dt of its query qi: O[qi][d = dt*16 + g*4 + r] (O: the head's output, row
+// stride rs) as one 16-bit plane, or (SPLIT) as hi + lo planes (O_lo, same strides)
+template <bool SPLIT, bool F16>
+__device__ __forceinline__ void store_o(bf16_t* O, bf16_t* O_lo, int qi, int64_t rs, int dt, int g, const f32x4_t& o, const float inv) {
+    if constexpr (SPLIT) {
+        uint2 wh, wl;
+        split_bf16x2(o[0] * inv, o[1] * inv, wh.x, wl.x);
+        split_bf16x2(o[2] * inv, o[3] * inv, wh.y, wl.y);
+        *reinterpret_cast<uint2*>(O + (int64_t)qi * rs + dt * 16 + g * 4) = wh;
+        *reinterpret_cast<uint2*>(O_lo + (int64_t)qi * rs + dt * 16 + g * 4) = wl;
+    } else {
+        const uint2 w = make_uint2(pack2<F16>(o[0] * inv, o[1] * inv), pack2<F16>(o[2] * inv, o[3] * inv));
+        *reinterpret_cast<uint2*>(O + (int64_t)qi * rs + dt * 16 + g * 4) = w;
+    }
+}
 
 // LDS layout of attn_kernel's K / V tiles: the kernel takes its strides and pointers from it, the launcher the dynamic bytes.
 template <int DQK, int DV, int REL, bool SPLIT>
@@ -135,7 +284,6 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
     static_assert(REL != 5 || (!SPLIT && !PP && DV == 80), "REL 5: SAM's global grid, the 4-wave block");
     constexpr bool QLO = QLV == 2;
     constexpr bool R2 = REL == 2 || REL == 5;  // rel_w seeds the accumulators, rel_h is one value per (query, key tile)
-    constexpr uint32_t kOne16 = F16 ? 0x3C00u : 0x3F80u;  // 1.0 as a 16-bit operand
     // SPLIT: 8 waves of ONE 16-query tile each (the same 128 queries per block): two waves per SIMD to cover each other's LDS
     // and MFMA latencies - with two query tiles per wave the split kernel needs > 256 registers, i.e. one wave per SIMD (measured:
     // SAM global attention 1618 us, windows 302 us that way)
@@ -207,9 +355,8 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
             for (int i = tid; i < 2 * kKV * NPAD; i += NT) {
                 const int buf = i / (kKV * NPAD), r = i % (kKV * NPAD);
                 const int key = r / NPAD, ch = DCH + r % NPAD;
-                const int phys = (ch & 3) ^ (((key >> 3) & 1) << 1);
-                *reinterpret_cast<u32x4_t*>(&Ks(buf)[(ch >> 2) * KPL + key * 32 + phys * 8]) = u32x4_t{0u, 0u, 0u, 0u};
-                if (SPLIT) *reinterpret_cast<u32x4_t*>(&Ks(buf)[KBUF + (ch >> 2) * KPL + key * 32 + phys * 8]) = u32x4_t{0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4_t*>(&Ks(buf)[k_chunk_off(key, ch, KPL)]) = u32x4_t{0u, 0u, 0u, 0u};
+                if (SPLIT) *reinterpret_cast<u32x4_t*>(&Ks(buf)[KBUF + k_chunk_off(key, ch, KPL)]) = u32x4_t{0u, 0u, 0u, 0u};
             }
         }
     };
@@ -247,44 +394,14 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
             qf[qt][s] = *reinterpret_cast<bf16x8_t*>(&u);
         }
     }
-    // q * scale before the dot product (SAM, HF-CLIP).  Default precision: rounded to bf16 like the reference's bf16 model does;
-    // SPLIT: in fp32 on the hi + lo value, split again.  (REL 4 first needs the UNSCALED q for the rel-pos terms: applied below.)
+    // q * scale (REL 4 / 5 first need the UNSCALED q for the rel-pos terms: applied below)
     auto prescale = [&]() __attribute__((always_inline)) {
         if (!a.prescale_q) return;
         const float sc = a.scale;
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
-            for (int s_ = 0; s_ < KS; ++s_) {
-                u32x4_t uh = __builtin_bit_cast(u32x4_t, qf[qt][s_]);
-                if (SPLIT) {
-                    u32x4_t ul = __builtin_bit_cast(u32x4_t, qfl[qt][SPLIT ? s_ : 0]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float x0 = (__uint_as_float(uh[e] << 16) + __uint_as_float(ul[e] << 16)) * sc;
-                        const float x1 = (__uint_as_float(uh[e] & 0xffff0000u) + __uint_as_float(ul[e] & 0xffff0000u)) * sc;
-                        uint32_t hh, ll;
-                        split_bf16x2(x0, x1, hh, ll);
-                        uh[e] = hh;
-                        ul[e] = ll;
-                    }
-                    qfl[qt][SPLIT ? s_ : 0] = __builtin_bit_cast(bf16x8_t, ul);
-                } else if (QLO) {
-                    u32x4_t ul = __builtin_bit_cast(u32x4_t, qfl[qt][QLO ? s_ : 0]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        uint32_t hh, ll;
-                        split_16x2((lo16<true>(uh[e]) + lo16<true>(ul[e])) * sc, (hi16<true>(uh[e]) + hi16<true>(ul[e])) * sc, hh, ll, 1);
-                        uh[e] = hh;
-                        ul[e] = ll;
-                    }
-                    qfl[qt][QLO ? s_ : 0] = __builtin_bit_cast(bf16x8_t, ul);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) uh[e] = pack2<F16>(lo16<F16>(uh[e]) * sc, hi16<F16>(uh[e]) * sc);
-                }
-                qf[qt][s_] = __builtin_bit_cast(bf16x8_t, uh);
-            }
+            for (int s_ = 0; s_ < KS; ++s_) q_times_scale<SPLIT || QLO, F16>(qf[qt][s_], qfl[qt][(SPLIT || QLO) ? s_ : 0], sc);
     };
     if (REL != 4 && REL != 5) prescale();
 
@@ -319,6 +436,8 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
         ld_d[i] = (c % DCH) * 8;
     }
     const int last_key = a.Sk - 1;
+    // (gload_k / gload_v name K and V themselves instead of going through gload_lo's parameters: with one parameterised loader the
+    //  D = 128 kernels, which sit at their register limit, come out of the scheduler with another instruction order)
     auto gload_k = [&](u32x4_t (&kreg)[CPT], int t) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
@@ -339,21 +458,14 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int c = tid + i * NT;
-            if (c < NCH) {
-                const int key = c / DCH, dch = c % DCH;
-                const int phys = (dch & 3) ^ (((key >> 3) & 1) << 1);
-                *reinterpret_cast<u32x4_t*>(&Ks(buf)[plane_off + (dch >> 2) * KPL + key * 32 + phys * 8]) = kreg[i];
-            }
+            if (c < NCH) *reinterpret_cast<u32x4_t*>(&Ks(buf)[plane_off + k_chunk_off(c / DCH, c % DCH, KPL)]) = kreg[i];
         }
     };
     auto store_v = [&](const u32x4_t (&vreg)[CPT], int buf, int plane_off = 0) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < CPT; ++i) {
             const int c = tid + i * NT;
-            if (c < NCH) {
-                const int key = c / DCH, dch = c % DCH;
-                *reinterpret_cast<u32x4_t*>(&Vs(buf)[plane_off + (dch >> 1) * VPL + key * 16 + (dch & 1) * 8]) = vreg[i];
-            }
+            if (c < NCH) *reinterpret_cast<u32x4_t*>(&Vs(buf)[plane_off + v_chunk_off(c / DCH, c % DCH, VPL)]) = vreg[i];
         }
     };
     auto gload_lo = [&](u32x4_t (&reg)[CPT], const bf16_t* base, int64_t rs, int t) __attribute__((always_inline)) {
@@ -364,45 +476,13 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
             reg[i] = *reinterpret_cast<const u32x4_t*>(base + (int64_t)key * rs + ld_d[i]);
         }
     };
-    const int kswz = (g ^ ((l15 >> 3) << 1)) * 8;                       // this lane's K chunk inside a 64-byte row
-    const int voff = (g * 4 + (l15 >> 2)) * 16 + (l15 & 3) * 4;         // tr-read address: key g*4 + i/4, d-quad i%4
+    const int kswz = k_frag_off(l15, g), voff = v_frag_off(l15, g);
 
     // ---- rel-pos operands of this lane's two queries -------------------------------------------
-    bf16x8_t qrel[QT];       // REL 1: [rel_h(KH) | rel_w(KW) | 0] features g*8 .. g*8+7
-    bf16x8_t qrel_lo[QT];    //        (SPLIT: the fp32 bias values as hi + lo + lo2 operands - three bf16 terms carry all 24 bits:
-    bf16x8_t qrel_lo2[QT];   //         the one-hot MFMAs add them exactly; a bias of +-20 split in two would be off by 1e-4)
+    bf16x8_t qrel[QT], qrel_lo[QT], qrel_lo2[QT];  // REL 1 / 4: the operands of pack_rel_terms
     f32x4_t rwf[QT][4];      // REL 2: rel_w[q][kt*16 + g*4 + r]: tile-invariant, SEEDS the score accumulators (no add later)
     const float* rhp[QT] = {};
     const float* rwg[QT] = {};  // REL 3
-    // packs 8 fp32 bias values (features g*8 .. g*8+7 of this lane's query) into the one-hot MFMA operand(s)
-    auto pack_qrel = [&](const float (&f)[8], int qt) __attribute__((always_inline)) {
-        uint4 u = make_uint4(pack2<F16>(f[0], f[1]), pack2<F16>(f[2], f[3]), pack2<F16>(f[4], f[5]), pack2<F16>(f[6], f[7]));
-        if (F16) {  // the terms ADD to the scores: an fp16 rounding of a bias of +-8 would be an absolute 2e-3 on the score, so
-                    // they travel as hi + lo fp16 operands (22 bits) of two one-hot MFMAs
-            const uint32_t uu[4] = {u.x, u.y, u.z, u.w};
-            u32x4_t ul;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ul[e] = pack2<F16>(f[2 * e] - lo16<F16>(uu[e]), f[2 * e + 1] - hi16<F16>(uu[e]));
-            qrel_lo[qt] = __builtin_bit_cast(bf16x8_t, ul);
-        }
-        if (SPLIT) {
-            u32x4_t uh, ul, ul2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t hh, ll;
-                split_bf16x2(f[2 * e], f[2 * e + 1], hh, ll);
-                const float r0 = (f[2 * e] - __uint_as_float(hh << 16)) - __uint_as_float(ll << 16);
-                const float r1 = (f[2 * e + 1] - __uint_as_float(hh & 0xffff0000u)) - __uint_as_float(ll & 0xffff0000u);
-                uh[e] = hh;
-                ul[e] = ll;
-                ul2[e] = pack_bf16x2(r0, r1);
-            }
-            u = make_uint4(uh[0], uh[1], uh[2], uh[3]);
-            qrel_lo[qt] = __builtin_bit_cast(bf16x8_t, ul);
-            qrel_lo2[qt] = __builtin_bit_cast(bf16x8_t, ul2);
-        }
-        qrel[qt] = *reinterpret_cast<bf16x8_t*>(&u);
-    };
     if (REL == 5) {
         // T = a.rel_h: 16-bit [>= 254, DV] = [rel_pos_h (rows 0 .. 126) ; rel_pos_w (rows 127 .. 253)] of the 64 x 64 grid.  A wave's 32
         // queries lie in ONE grid row qh (32 | 64), at columns qw0 + 0 .. 31 (qw0 = 0 or 32):
@@ -463,53 +543,21 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
         __syncthreads();  // every wave is done with its scratch: the K buffers may be staged now
         zero_pads();
     } else if (REL == 4) {
-        // The decomposed rel-pos terms computed HERE instead of by a kernel of their own (54 us and 120 MB of traffic per
-        // windowed block): G^T = T . Q^T on the matrix cores - T = [rel_pos_h ; rel_pos_w ; 0] (64 rows, a.rel_h), Q the UNSCALED
-        // query fragments already in registers - lands in C layout (lane = query l15, rows g*4+r of each 16-row tile), goes through
-        // a per-wave LDS scratch and comes back as the 2 * side Toeplitz picks of this lane's query:
-        //   rel_h[q][kh] = G[q][qh - kh + side - 1],   rel_w[q][kw] = G[q][(2 side - 1) + qw - kw + side - 1].
+        // the table fragments come straight from global memory (T = a.rel_h, 16-bit [64, DV])
         const bf16_t* tab = reinterpret_cast<const bf16_t*>(a.rel_h);
-        const int side = a.rel_kh;
-        float* Gw = Gs + wave * kGW;
+        auto tab_frag = [&](int ks, int row) __attribute__((always_inline)) {
+            const int d0 = (ks * 4 + g) * 8;
+            u32x4_t t4 = u32x4_t{0u, 0u, 0u, 0u};
+            if (d0 < DV) t4 = *reinterpret_cast<const u32x4_t*>(tab + row * DV + d0);
+            return __builtin_bit_cast(bf16x8_t, t4);
+        };
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-            f32x4_t gacc[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) gacc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int d0 = (ks * 4 + g) * 8;
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
-                    u32x4_t t4 = u32x4_t{0u, 0u, 0u, 0u};
-                    if (d0 < DV) t4 = *reinterpret_cast<const u32x4_t*>(tab + (rt * 16 + l15) * DV + d0);
-                    const bf16x8_t tf = __builtin_bit_cast(bf16x8_t, t4);
-                    gacc[rt] = mma16<F16>(tf, qf[qt][ks], gacc[rt]);
-                    if (QL) gacc[rt] = mma16<F16>(tf, qfl[qt][QL ? ks : 0], gacc[rt]);
-                }
-            }
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Gw[l15 * 65 + rt * 16 + g * 4 + r] = gacc[rt][r];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
             int qi = q0 + qt * 16 + l15;
             qi = qi < a.Sq ? qi : a.Sq - 1;
-            const int qh = qi / side, qw = qi - qh * side;
             float f[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int fi = g * 8 + e;
-                float v = 0.0f;
-                if (fi < side) v = Gw[l15 * 65 + qh - fi + side - 1];
-                else if (fi < 2 * side) v = Gw[l15 * 65 + (2 * side - 1) + qw - (fi - side) + side - 1];
-                // default precision: the bf16 reference materialises the terms in bf16 (pack_qrel rounds); SPLIT keeps fp32
-                f[e] = v;
-            }
-            pack_qrel(f, qt);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();  // the scratch is reused by the next query tile
+            rel_table_terms<F16, QL>(tab_frag, qf[qt], qfl[qt], Gs + wave * kGW, l15, g, qi, a.rel_kh, f);
+            pack_rel_terms<SPLIT, F16>(f, qrel[qt], qrel_lo[qt], qrel_lo2[qt]);  // (default precision rounds the terms to bf16, SPLIT keeps fp32)
         }
         prescale();
     } else if (REL != 0) {
@@ -527,7 +575,7 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
                     const int fi = g * 8 + e;
                     f[e] = fi < a.rel_kh ? rh[fi] : (fi < a.rel_kh + a.rel_kw ? rw[fi - a.rel_kh] : 0.0f);
                 }
-                pack_qrel(f, qt);
+                pack_rel_terms<SPLIT, F16>(f, qrel[qt], qrel_lo[qt], qrel_lo2[qt]);
             } else if (REL == 3) {
                 rhp[qt] = rh;
                 rwg[qt] = rw;
@@ -582,18 +630,7 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
                 }
             }
             if (REL == 1 || REL == 4) {
-                const int key = t * kKV + kt * 16 + l15;
-                const int kh = key / a.rel_kw;
-                const int f1 = kh - g * 8, f2 = a.rel_kh + (key - kh * a.rel_kw) - g * 8;  // hot slots e
-                uint32_t w[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t lo = (f1 == 2 * j || f2 == 2 * j) ? kOne16 : 0u;
-                    const uint32_t hi = (f1 == 2 * j + 1 || f2 == 2 * j + 1) ? (kOne16 << 16) : 0u;
-                    w[j] = lo | hi;
-                }
-                uint4 u = make_uint4(w[0], w[1], w[2], w[3]);
-                const bf16x8_t hot = *reinterpret_cast<bf16x8_t*>(&u);
+                const bf16x8_t hot = one_hot_rel<F16>(t * kKV + kt * 16 + l15, a.rel_kh, a.rel_kw, g);
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     s[qt][kt] = mma16<F16>(hot, qrel[qt], s[qt][kt]);
@@ -703,26 +740,7 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
                     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(u.w) : "v"(s[qt][2 * s2 + 1][2]), "v"(s[qt][2 * s2 + 1][3]));
                 }
                 pf[qt][s2] = *reinterpret_cast<bf16x8_t*>(&u);
-                if (QLO) {  // lo halves: p - fp16(p)
-                    uint4 ul;
-                    const f32x4_t& sa = s[qt][2 * s2];
-                    const f32x4_t& sb = s[qt][2 * s2 + 1];
-                    ul.x = pack2<true>(sa[0] - lo16<true>(u.x), sa[1] - hi16<true>(u.x));
-                    ul.y = pack2<true>(sa[2] - lo16<true>(u.y), sa[3] - hi16<true>(u.y));
-                    ul.z = pack2<true>(sb[0] - lo16<true>(u.z), sb[1] - hi16<true>(u.z));
-                    ul.w = pack2<true>(sb[2] - lo16<true>(u.w), sb[3] - hi16<true>(u.w));
-                    pfl[qt][QLO ? s2 : 0] = *reinterpret_cast<bf16x8_t*>(&ul);
-                }
-                if (SPLIT) {  // lo halves: p - bf16(p), exactly representable differences rounded once
-                    uint4 ul;
-                    const f32x4_t& sa = s[qt][2 * s2];
-                    const f32x4_t& sb = s[qt][2 * s2 + 1];
-                    ul.x = pack_bf16x2(sa[0] - __uint_as_float(u.x << 16), sa[1] - __uint_as_float(u.x & 0xffff0000u));
-                    ul.y = pack_bf16x2(sa[2] - __uint_as_float(u.y << 16), sa[3] - __uint_as_float(u.y & 0xffff0000u));
-                    ul.z = pack_bf16x2(sb[0] - __uint_as_float(u.z << 16), sb[1] - __uint_as_float(u.z & 0xffff0000u));
-                    ul.w = pack_bf16x2(sb[2] - __uint_as_float(u.w << 16), sb[3] - __uint_as_float(u.w & 0xffff0000u));
-                    pfl[qt][s2] = *reinterpret_cast<bf16x8_t*>(&ul);
-                }
+                if (SPLIT || QLO) pfl[qt][(SPLIT || QLO) ? s2 : 0] = p_lo<F16>(s[qt][2 * s2], s[qt][2 * s2 + 1], pf[qt][s2]);
             }
 
     };
@@ -735,25 +753,15 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
             if (!R2 && 2 * s2 >= nkt) continue;  // all 32 keys of this step are past Sk (their P is 0)
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-                typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
                 const bf16_t* vp = Vb + dt * VPL + (2 * s2) * 16 * 16 + voff;
-                const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp));
-                const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp + 16 * 16));
-                typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-                const s16x8_t v8 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, v8);
+                const bf16x8_t vf = v_frag(vp);
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     o[qt][dt] = mma16<F16>(vf, pf[qt][s2], o[qt][dt]);
                     if (QLO) o[qt][dt] = mma16<F16>(vf, pfl[qt][QLO ? s2 : 0], o[qt][dt]);
                 }
                 if (SPLIT) {
-                    const bf16_t* vpl = vp + VBUF;
-                    const s16x4_t lo2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vpl));
-                    const s16x4_t hi2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vpl + 16 * 16));
-                    const s16x8_t v8l = __builtin_shufflevector(lo2, hi2, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const bf16x8_t vfl = __builtin_bit_cast(bf16x8_t, v8l);
+                    const bf16x8_t vfl = v_frag(vp + VBUF);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt) {
                         o[qt][dt] = mma16<F16>(vf, pfl[qt][s2], o[qt][dt]);
@@ -859,25 +867,14 @@ __global__ __launch_bounds__((PP || SPLIT) ? 512 : 256, (PP || SPLIT) ? 1 : 2) v
 
     // ---- normalise and store: lane holds O[query l15][d = dt*16 + g*4 + r] ---------------------
     bf16_t* __restrict__ O = a.o + b * a.o_bs + h * a.o_hs;
+    bf16_t* Ol = SPLIT ? a.o_lo + b * a.o_bs + h * a.o_hs : nullptr;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         const int qi = q0 + qt * 16 + l15;
         if (qi >= a.Sq) continue;
         const float inv = l_run[qt] > 0.0f ? 1.0f / l_run[qt] : 0.0f;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            if (SPLIT) {
-                uint2 wh, wl;
-                split_bf16x2(o[qt][dt][0] * inv, o[qt][dt][1] * inv, wh.x, wl.x);
-                split_bf16x2(o[qt][dt][2] * inv, o[qt][dt][3] * inv, wh.y, wl.y);
-                *reinterpret_cast<uint2*>(O + (int64_t)qi * a.o_rs + dt * 16 + g * 4) = wh;
-                *reinterpret_cast<uint2*>(a.o_lo + b * a.o_bs + h * a.o_hs + (int64_t)qi * a.o_rs + dt * 16 + g * 4) = wl;
-                continue;
-            }
-            const uint2 w = make_uint2(pack2<F16>(o[qt][dt][0] * inv, o[qt][dt][1] * inv),
-                                       pack2<F16>(o[qt][dt][2] * inv, o[qt][dt][3] * inv));
-            *reinterpret_cast<uint2*>(O + (int64_t)qi * a.o_rs + dt * 16 + g * 4) = w;
-        }
+        for (int dt = 0; dt < DT; ++dt) store_o<SPLIT, F16>(O, Ol, qi, a.o_rs, dt, g, o[qt][dt], inv);
     }
 }
 
@@ -924,7 +921,6 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
     static_assert(!QLV || F16, "QLV: q as hi + lo IEEE halves");
     constexpr bool QLO = QLV == 2;          // lo half in Q.K^T, split softmax weights
     constexpr bool QL = SPLIT || QLV != 0;  // a lo half of q is loaded
-    constexpr uint32_t kOne16 = F16 ? 0x3C00u : 0x3F80u;  // 1.0 as a 16-bit operand
     constexpr bool TAB = !SPLIT;
     // SPLIT: 8 waves (two per SIMD, 240 registers: held under 256 with scheduling barriers in the fragment loops), the 13 query tiles
     // in two rounds.  Default precision: 126 registers allow 16 waves (four per SIMD) - every query tile has a wave of its own (ONE
@@ -971,7 +967,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
     const bf16_t* __restrict__ Kl_g = SPLIT ? a.k_lo + b * a.k_bs + h * a.k_hs : nullptr;
     const bf16_t* __restrict__ Vl_g = SPLIT ? a.v_lo + b * a.v_bs + h * a.v_hs : nullptr;
 
-    // ---- stage the whole window: K planes [k-step][key][32] (chunk swizzle of attn_kernel), V planes [d tile][key][16];
+    // ---- stage the whole window: K planes [k-step][key][32] (k_chunk_off), V planes [d tile][key][16] (v_chunk_off);
     //      padded keys and the two pad chunks of K's third plane are zero -----------------------------------------------
     // (all global loads of the block are issued before the first LDS store: a load -> store loop serialises ~5 memory round trips)
     constexpr int NKC = (SPK * 12 + NT - 1) / NT, NVC = (SPV * DCH + NT - 1) / NT;
@@ -1002,8 +998,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
             if (c < SPK * 12) {
                 const int key = c / 12, dch = c % 12;
                 const bool ok = key < S && dch < DCH;
-                const int phys = (dch & 3) ^ (((key >> 3) & 1) << 1);
-                const int off = (dch >> 2) * KPL + key * 32 + phys * 8;
+                const int off = k_chunk_off(key, dch, KPL);
                 *reinterpret_cast<u32x4_t*>(&Kh[off]) = ok ? kr[i] : zero4;
                 if (SPLIT) *reinterpret_cast<u32x4_t*>(&Kl[off]) = ok ? krl[SPLIT ? i : 0] : zero4;
             }
@@ -1014,7 +1009,7 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
                 const int c = tid + i * NT;
                 if (c < SPV * DCH) {
                     const int key = c / DCH, dch = c % DCH;
-                    *reinterpret_cast<u32x4_t*>(&Vh[(dch >> 1) * VPL + key * 16 + (dch & 1) * 8]) = key < S ? vr[SPLIT ? 0 : i] : zero4;
+                    *reinterpret_cast<u32x4_t*>(&Vh[v_chunk_off(key, dch, VPL)]) = key < S ? vr[SPLIT ? 0 : i] : zero4;
                 }
             }
         }
@@ -1034,42 +1029,30 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
             const int c = tid + i * NT;
             if (c < SPV * DCH) {
                 const int key = c / DCH, dch = c % DCH;
-                const int off = (dch >> 1) * VPL + key * 16 + (dch & 1) * 8;
+                const int off = v_chunk_off(key, dch, VPL);
                 *reinterpret_cast<u32x4_t*>(&Vh[off]) = key < S ? vr[i] : zero4;
                 *reinterpret_cast<u32x4_t*>(&Vl[off]) = key < S ? vrl[i] : zero4;
             }
         }
     }
-    if (TAB) {  // [rel_pos_h ; rel_pos_w ; 0] (64 rows x 80) as three k-step planes [row][32], chunk swizzle as K: 12 KB
+    if (TAB) {  // [rel_pos_h ; rel_pos_w ; 0] (64 rows x 80) as three k-step planes [row][32] in the K image layout: 12 KB
         const bf16_t* tabg = reinterpret_cast<const bf16_t*>(a.rel_h);
         for (int c = tid; c < 64 * 12; c += NT) {
             const int row = c / 12, dch = c % 12;
             u32x4_t v4 = u32x4_t{0u, 0u, 0u, 0u};
             if (dch < DCH) v4 = *reinterpret_cast<const u32x4_t*>(tabg + row * DV + dch * 8);
-            const int phys = (dch & 3) ^ (((row >> 3) & 1) << 1);
-            *reinterpret_cast<u32x4_t*>(&Tb[(dch >> 2) * TPL + row * 32 + phys * 8]) = v4;
+            *reinterpret_cast<u32x4_t*>(&Tb[k_chunk_off(row, dch, TPL)]) = v4;
         }
     }
     // the one-hot (kh, side + kw) operand of every 16-key tile depends on the key alone: built once per block (13 KB), read back
     // as one 16-byte fragment per tile by every query tile
     for (int c = tid; c < (TAB ? KT * 64 : 0); c += NT) {  // (SPLIT: no LDS left - built per tile in registers)
         const int kt = c >> 6, ln = c & 63;
-        const int key = kt * 16 + (ln & 15), gg = ln >> 4;
-        const int kh = key / a.rel_kh;
-        const int f1 = kh - gg * 8, f2 = a.rel_kh + (key - kh * a.rel_kh) - gg * 8;
-        u32x4_t w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t lo = (f1 == 2 * j || f2 == 2 * j) ? kOne16 : 0u;
-            const uint32_t hi = (f1 == 2 * j + 1 || f2 == 2 * j + 1) ? (kOne16 << 16) : 0u;
-            w[j] = lo | hi;
-        }
-        Hot[c] = w;
+        Hot[c] = __builtin_bit_cast(u32x4_t, one_hot_rel<F16>(kt * 16 + (ln & 15), a.rel_kh, a.rel_kh, ln >> 4));
     }
     __syncthreads();
 
-    const int kswz = (g ^ ((l15 >> 3) << 1)) * 8;
-    const int voff = (g * 4 + (l15 >> 2)) * 16 + (l15 & 3) * 4;
+    const int kswz = k_frag_off(l15, g), voff = v_frag_off(l15, g);
     float* Gw = Gs + (wave < NGW ? wave : 0) * kGW;  // (waves without a query tile never touch it)
     const float sc = a.scale;
     const int nqt = (S + 15) >> 4;
@@ -1107,36 +1090,11 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
         constexpr bool ONE = NWV >= 13;
         if (!ONE && qtile + NWV < nqt) fetch_q(qtile + NWV);
         float f[8];
-        if (TAB) {
-            f32x4_t gacc[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) gacc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
-                    const bf16x8_t tf = *reinterpret_cast<const bf16x8_t*>(&Tb[ks * TPL + (rt * 16 + l15) * 32 + kswz]);
-                    gacc[rt] = mma16<F16>(tf, qf[ks], gacc[rt]);
-                    if (QLV) gacc[rt] = mma16<F16>(tf, qfl[QLV ? ks : 0], gacc[rt]);
-                }
-            }
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) Gw[l15 * 65 + rt * 16 + g * 4 + r] = gacc[rt][r];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            const int qh = qi / side, qw = qi - qh * side;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int fi = g * 8 + e;
-                float v = 0.0f;
-                if (fi < side) v = Gw[l15 * 65 + qh - fi + side - 1];
-                else if (fi < 2 * side) v = Gw[l15 * 65 + (2 * side - 1) + qw - (fi - side) + side - 1];
-                f[e] = v;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
+        if (TAB) {  // table mode: the table fragments come from its LDS image
+            auto tab_frag = [&](int ks, int row) __attribute__((always_inline)) {
+                return *reinterpret_cast<const bf16x8_t*>(&Tb[ks * TPL + row * 32 + kswz]);
+            };
+            rel_table_terms<F16, QLV != 0>(tab_frag, qf, qfl, Gw, l15, g, qi, side, f);
         } else {  // array mode: rel_h / rel_w f32 [B*H, S, side]
             const int64_t bq = ((int64_t)b * a.H + h) * S + qi;
             const float* rh = a.rel_h + bq * side;
@@ -1148,65 +1106,10 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
             }
         }
         bf16x8_t qrel, qrel_lo, qrel_lo2;
-        {
-            u32x4_t uh, ul, ul2;
+        pack_rel_terms<SPLIT, F16>(f, qrel, qrel_lo, qrel_lo2);
+        // ---- q * scale, now that the table product has seen the unscaled q ---------------------------------------------
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                uint32_t hh, ll = 0;
-                if constexpr (F16) {  // hi + lo fp16 operands (22 bits) of two one-hot MFMAs: see attn_kernel
-                    hh = pack_f16x2(f[2 * e], f[2 * e + 1]);
-                    ul[e] = pack_f16x2(f[2 * e] - lo16<true>(hh), f[2 * e + 1] - hi16<true>(hh));
-                } else {
-                    split_bf16x2(f[2 * e], f[2 * e + 1], hh, ll);
-                }
-                uh[e] = hh;
-                if (SPLIT) {
-                    const float r0 = (f[2 * e] - __uint_as_float(hh << 16)) - __uint_as_float(ll << 16);
-                    const float r1 = (f[2 * e + 1] - __uint_as_float(hh & 0xffff0000u)) - __uint_as_float(ll & 0xffff0000u);
-                    ul[e] = ll;
-                    ul2[e] = pack_bf16x2(r0, r1);
-                }
-            }
-            qrel = __builtin_bit_cast(bf16x8_t, uh);  // default precision: the terms rounded to bf16, as the bf16 reference holds them
-            if (F16) qrel_lo = __builtin_bit_cast(bf16x8_t, ul);
-            if (SPLIT) {
-                qrel_lo = __builtin_bit_cast(bf16x8_t, ul);
-                qrel_lo2 = __builtin_bit_cast(bf16x8_t, ul2);
-            }
-        }
-        // ---- q * scale (bf16-rounded in default precision like SAM's bf16 model; fp32 on hi + lo in SPLIT) --------------
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            u32x4_t uh = __builtin_bit_cast(u32x4_t, qf[ks]);
-            if (SPLIT) {
-                u32x4_t ul = __builtin_bit_cast(u32x4_t, qfl[SPLIT ? ks : 0]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float x0 = (__uint_as_float(uh[e] << 16) + __uint_as_float(ul[e] << 16)) * sc;
-                    const float x1 = (__uint_as_float(uh[e] & 0xffff0000u) + __uint_as_float(ul[e] & 0xffff0000u)) * sc;
-                    uint32_t hh, ll;
-                    split_bf16x2(x0, x1, hh, ll);
-                    uh[e] = hh;
-                    ul[e] = ll;
-                }
-                qfl[SPLIT ? ks : 0] = __builtin_bit_cast(bf16x8_t, ul);
-            } else if (QLO) {
-                u32x4_t ul = __builtin_bit_cast(u32x4_t, qfl[QLO ? ks : 0]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    uint32_t hh, ll;
-                    split_16x2((lo16<true>(uh[e]) + lo16<true>(ul[e])) * sc, (hi16<true>(uh[e]) + hi16<true>(ul[e])) * sc, hh, ll, 1);
-                    uh[e] = hh;
-                    ul[e] = ll;
-                }
-                qfl[QLO ? ks : 0] = __builtin_bit_cast(bf16x8_t, ul);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    uh[e] = pack2<F16>(lo16<F16>(uh[e]) * sc, hi16<F16>(uh[e]) * sc);
-            }
-            qf[ks] = __builtin_bit_cast(bf16x8_t, uh);
-        }
+        for (int ks = 0; ks < KS; ++ks) q_times_scale<SPLIT || QLO, F16>(qf[ks], qfl[(SPLIT || QLO) ? ks : 0], sc);
         // ---- S^T = K . Q^T + bias: s[kt] holds keys kt*16 + g*4 + r of query l15 -----------------------------------------
         f32x4_t s[KT];
 #pragma unroll
@@ -1224,21 +1127,8 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
                 }
             }
             bf16x8_t hot;
-            if (TAB) {
-                hot = __builtin_bit_cast(bf16x8_t, Hot[kt * 64 + lane]);
-            } else {
-                const int key = kt * 16 + l15;
-                const int kh = key / side;
-                const int f1 = kh - g * 8, f2 = side + (key - kh * side) - g * 8;
-                u32x4_t w;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t lo = (f1 == 2 * j || f2 == 2 * j) ? kOne16 : 0u;
-                    const uint32_t hi = (f1 == 2 * j + 1 || f2 == 2 * j + 1) ? (kOne16 << 16) : 0u;
-                    w[j] = lo | hi;
-                }
-                hot = __builtin_bit_cast(bf16x8_t, w);
-            }
+            if (TAB) hot = __builtin_bit_cast(bf16x8_t, Hot[kt * 64 + lane]);
+            else hot = one_hot_rel<F16>(kt * 16 + l15, side, side, g);
             s[kt] = mma16<F16>(hot, qrel, s[kt]);
             if (F16) s[kt] = mma16<F16>(hot, qrel_lo, s[kt]);
             if (SPLIT) {
@@ -1276,43 +1166,21 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
         for (int s2 = 0; s2 < VS; ++s2) {
             const f32x4_t sa = s[2 * s2];
             const f32x4_t sb = (2 * s2 + 1 < KT) ? s[(2 * s2 + 1 < KT) ? 2 * s2 + 1 : 0] : f32x4_t{0.f, 0.f, 0.f, 0.f};
-            u32x4_t u, ul;
+            u32x4_t u;  // (the compiler-visible conversion: attn_kernel's inline asm schedules differently here)
             u[0] = pack2<F16>(sa[0], sa[1]);
             u[1] = pack2<F16>(sa[2], sa[3]);
             u[2] = pack2<F16>(sb[0], sb[1]);
             u[3] = pack2<F16>(sb[2], sb[3]);
             const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, u);
             bf16x8_t pfl;
-            if (QLO) {
-                ul[0] = pack2<true>(sa[0] - lo16<true>(u[0]), sa[1] - hi16<true>(u[0]));
-                ul[1] = pack2<true>(sa[2] - lo16<true>(u[1]), sa[3] - hi16<true>(u[1]));
-                ul[2] = pack2<true>(sb[0] - lo16<true>(u[2]), sb[1] - hi16<true>(u[2]));
-                ul[3] = pack2<true>(sb[2] - lo16<true>(u[3]), sb[3] - hi16<true>(u[3]));
-                pfl = __builtin_bit_cast(bf16x8_t, ul);
-            }
-            if (SPLIT) {
-                ul[0] = pack_bf16x2(sa[0] - __uint_as_float(u[0] << 16), sa[1] - __uint_as_float(u[0] & 0xffff0000u));
-                ul[1] = pack_bf16x2(sa[2] - __uint_as_float(u[1] << 16), sa[3] - __uint_as_float(u[1] & 0xffff0000u));
-                ul[2] = pack_bf16x2(sb[0] - __uint_as_float(u[2] << 16), sb[1] - __uint_as_float(u[2] & 0xffff0000u));
-                ul[3] = pack_bf16x2(sb[2] - __uint_as_float(u[3] << 16), sb[3] - __uint_as_float(u[3] & 0xffff0000u));
-                pfl = __builtin_bit_cast(bf16x8_t, ul);
-            }
+            if (SPLIT || QLO) pfl = p_lo<F16>(sa, sb, pf);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-                typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-                typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-                typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-                const bf16_t* vp = Vh + dt * VPL + (2 * s2) * 16 * 16 + voff;
-                const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp));
-                const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vp + 16 * 16));
-                const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                const bf16x8_t vf = v_frag(Vh + dt * VPL + (2 * s2) * 16 * 16 + voff);
                 o[dt] = mma16<F16>(vf, pf, o[dt]);
                 if (QLO) o[dt] = mma16<F16>(vf, pfl, o[dt]);
                 if (SPLIT) {
-                    const bf16_t* vpl = Vl + dt * VPL + (2 * s2) * 16 * 16 + voff;
-                    const s16x4_t lo2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vpl));
-                    const s16x4_t hi2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(vpl + 16 * 16));
-                    const bf16x8_t vfl = __builtin_bit_cast(bf16x8_t, (s16x8_t)__builtin_shufflevector(lo2, hi2, 0, 1, 2, 3, 4, 5, 6, 7));
+                    const bf16x8_t vfl = v_frag(Vl + dt * VPL + (2 * s2) * 16 * 16 + voff);
                     o[dt] = mma16<F16>(vf, pfl, o[dt]);
                     o[dt] = mma16<F16>(vfl, pf, o[dt]);
                 }
@@ -1321,20 +1189,10 @@ __global__ __launch_bounds__(SPLIT ? 512 : 1024, 1) void win_attn_kernel(AttnArg
         }
         // ---- normalise and store: lane holds O[query l15][d = dt*16 + g*4 + r] ---------------------------------------------
         if (q_ok) {
-            bf16_t* __restrict__ O = a.o + b * a.o_bs + h * a.o_hs + (int64_t)qi * a.o_rs;
+            bf16_t* __restrict__ O = a.o + b * a.o_bs + h * a.o_hs;
+            bf16_t* Ol = SPLIT ? a.o_lo + b * a.o_bs + h * a.o_hs : nullptr;
 #pragma unroll
-            for (int dt = 0; dt < DT; ++dt) {
-                if (SPLIT) {
-                    uint2 wh, wl;
-                    split_bf16x2(o[dt][0] * inv, o[dt][1] * inv, wh.x, wl.x);
-                    split_bf16x2(o[dt][2] * inv, o[dt][3] * inv, wh.y, wl.y);
-                    *reinterpret_cast<uint2*>(O + dt * 16 + g * 4) = wh;
-                    *reinterpret_cast<uint2*>(a.o_lo + b * a.o_bs + h * a.o_hs + (int64_t)qi * a.o_rs + dt * 16 + g * 4) = wl;
-                } else {
-                    *reinterpret_cast<uint2*>(O + dt * 16 + g * 4) =
-                        make_uint2(pack2<F16>(o[dt][0] * inv, o[dt][1] * inv), pack2<F16>(o[dt][2] * inv, o[dt][3] * inv));
-                }
-            }
+            for (int dt = 0; dt < DT; ++dt) store_o<SPLIT, F16>(O, Ol, qi, a.o_rs, dt, g, o[dt], inv);
         }
         if (ONE) break;
     }
