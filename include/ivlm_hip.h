@@ -1013,6 +1013,68 @@ int ivlm_pose_transform_backward(const float *verts, const float *rot6d, const f
                                  float *grad_rot6d, float *grad_translation, float *grad_scale, void *workspace,
                                  size_t workspace_bytes, ivlm_stream_t stream);
 
+/* One iteration of the object-pose fit for B starts as one launch sequence (fit_step.hip): the transform, the silhouette and its
+ * two terms, the contact term, the total and its history row, every backward, Adam and the step counter, enqueued on the stream
+ * with no host read and no allocation.
+ *   total = ((0 + mask w_mask) + centroid_loss w_centroid) + contact w_contact over the terms of terms_on, in fp32, operation by
+ *   operation as torch evaluates ObjectPoseFit.forward; centroid_loss = d0 d0 + d1 d1, d = centroid - target_centroid.  The
+ *   silhouette is taken on obj + centroid_offset (a separate fp32 add), the contact term on the un-offset vertices.
+ *   history[t][b] = total, term_history[t][k][b] = term k (mask, centroid, contact; an exact 0 when off), t = *step (rows are written
+ *   while t < max_iter).  The vertex gradient is g_sil + w_contact g_pair (product rounded first).
+ *   Adam (amsgrad off, no weight decay), per element in fp64 with t = *step + 1, each of p, m, v rounded to fp32 once:
+ *     m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p = p - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   eps > 0 (else IVLM_ERR_INVALID_ARG), so that g = 0 with m = v = 0 leaves p bit-unchanged.  *step is advanced by a one-thread launch of its own, after its last reader.
+ * A term that is off launches nothing of its own: no silhouette kernels without IVLM_FIT_MASK | IVLM_FIT_CENTROID, no contact_pair
+ * without IVLM_FIT_CONTACT; at least one term and one of IVLM_FIT_POSE | IVLM_FIT_SCALE must be set.  The gradients of the last
+ * step stay in grad_*; a group that is not optimised is not read or written (its pointers may be NULL).  No floating-point atomics,
+ * fixed orders: the same bits every call and for a start whatever the batch around it.
+ * Sizes as the member kernels take them (B <= 65535, N, F <= 2^22, N, N_h <= 2^20, H, W <= 16384), else IVLM_ERR_UNSUPPORTED before
+ * any launch; ivlm_fit_step_workspace_bytes(B, N, F, H, W, N_h) = the three members' workspaces, IVLM_SILHOUETTE_TERMS_WORKSPACE,
+ * four [B,N,3] and two [B,H,W] fp32 arrays, [B,5] fp64 sums and 7 B floats, each rounded up to 256 bytes (0 for sizes that are not
+ * supported); the workspace is 256-byte aligned. */
+#define IVLM_FIT_MASK 1
+#define IVLM_FIT_CENTROID 2
+#define IVLM_FIT_CONTACT 4
+#define IVLM_FIT_POSE 1
+#define IVLM_FIT_SCALE 2
+typedef struct IvlmFitStepArgs {
+    /* the scene */
+    const float *obj_verts;            /* [N,3] */
+    const int32_t *faces;              /* [F,3] */
+    const int32_t *vert_face_offsets;  /* [N+1], as ivlm_soft_silhouette_backward takes it */
+    const int32_t *vert_face_list;     /* [3F] */
+    const float *human_verts;          /* [N_h,3] */
+    const void *obj_probs;             /* [N] of p_dtype */
+    const void *human_probs;           /* [N_h] of p_dtype */
+    const float *target;               /* [H,W] */
+    const float *target_centroid;      /* [2] (row, col) */
+    const float *centroid_offset;      /* [3] */
+    /* the state: parameters, Adam moments, the last gradients, the counter and the histories */
+    float *rotation, *translation, *scale;                /* [B,6], [B,3], [B] */
+    float *m_rotation, *m_translation, *m_scale;
+    float *v_rotation, *v_translation, *v_scale;
+    float *grad_rotation, *grad_translation, *grad_scale;
+    int32_t *step;                                        /* device: iterations done */
+    float *history;                                       /* [max_iter,B] */
+    float *term_history;                                  /* [max_iter,3,B] */
+    void *workspace;
+    size_t workspace_bytes;
+    double lr_rotation, lr_translation, lr_scale, beta1, beta2, eps;
+    int32_t B, N, F, H, W, N_h, p_dtype, max_iter;
+    int32_t terms_on;                                     /* IVLM_FIT_MASK | IVLM_FIT_CENTROID | IVLM_FIT_CONTACT */
+    int32_t optimise;                                     /* IVLM_FIT_POSE | IVLM_FIT_SCALE */
+    float fx, fy, px, py, sigma, blur_radius;
+    float w_mask, w_centroid, w_contact;
+} IvlmFitStepArgs;
+size_t ivlm_fit_step_workspace_bytes(int B, int N, int F, int H, int W, int N_h);
+int ivlm_fit_step(const IvlmFitStepArgs *args, ivlm_stream_t stream);
+/* The Adam update of ivlm_fit_step alone, with t = *step + 1 (the counter is read, not advanced).  A group whose gradient is NULL is
+ * not touched; not all three may be. */
+int ivlm_fit_adam(float *rotation, float *translation, float *scale, const float *grad_rotation, const float *grad_translation,
+                  const float *grad_scale, float *m_rotation, float *m_translation, float *m_scale, float *v_rotation,
+                  float *v_translation, float *v_scale, int B, const int32_t *step, double lr_rotation, double lr_translation,
+                  double lr_scale, double beta1, double beta2, double eps, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

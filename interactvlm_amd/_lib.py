@@ -17,8 +17,25 @@ _lib = None
 
 _CTYPES = {
     "int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float,
-    "ivlm_stream_t": C.c_void_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8,
+    "ivlm_stream_t": C.c_void_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8, "double": C.c_double,
 }
+
+FIT_MASK, FIT_CENTROID, FIT_CONTACT = 1, 2, 4  # IVLM_FIT_* of terms_on
+FIT_POSE, FIT_SCALE = 1, 2                     # IVLM_FIT_* of optimise
+
+
+class FitStepArgs(C.Structure):
+    """``IvlmFitStepArgs`` of include/ivlm_hip.h, field for field (tests/test_fit_device_cpu.py compares the two)"""
+    _fields_ = (
+        [(n, C.c_void_p) for n in (
+            "obj_verts", "faces", "vert_face_offsets", "vert_face_list", "human_verts", "obj_probs", "human_probs", "target",
+            "target_centroid", "centroid_offset", "rotation", "translation", "scale", "m_rotation", "m_translation", "m_scale",
+            "v_rotation", "v_translation", "v_scale", "grad_rotation", "grad_translation", "grad_scale", "step", "history",
+            "term_history", "workspace")]
+        + [("workspace_bytes", C.c_size_t)]
+        + [(n, C.c_double) for n in ("lr_rotation", "lr_translation", "lr_scale", "beta1", "beta2", "eps")]
+        + [(n, C.c_int32) for n in ("B", "N", "F", "H", "W", "N_h", "p_dtype", "max_iter", "terms_on", "optimise")]
+        + [(n, C.c_float) for n in ("fx", "fy", "px", "py", "sigma", "blur_radius", "w_mask", "w_centroid", "w_contact")])
 
 
 class IvlmError(RuntimeError):

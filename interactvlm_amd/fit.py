@@ -9,6 +9,8 @@ operations of a single-pose run, so that every start of a batch computes the bit
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -162,18 +164,212 @@ class ObjectPoseFit(nn.Module):
         return total, terms
 
 
+TERM_KEYS = ("mask_loss", "centroid_loss", "contact_loss")  # the rows of term_history, the bits of IVLM_FIT_MASK / CENTROID / CONTACT
+DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
+
+
+def fit_phases(loss_weights, max_iter):
+    """-> [(first iteration, end, bits)]: the runs of iterations over which the same terms count.  Bit k of ``bits`` is TERM_KEYS[k];
+    a term counts at iteration i when ``kick_in >= 0 and i >= kick_in`` (-1: never, 0: from the start, k: from iteration k on).
+    ``kick_in`` is a host number, so the phases are known before the loop: at most four of them."""
+    weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
+    kicks = [weights[k]["kick_in"] if k in weights else -1 for k in TERM_KEYS]
+
+    def bits(i):
+        return sum(1 << k for k, kick in enumerate(kicks) if kick >= 0 and i >= kick)
+
+    edges = sorted({0, max_iter} | {k for k in kicks if 0 < k < max_iter})
+    return [(lo, hi, bits(lo)) for lo, hi in zip(edges[:-1], edges[1:])]
+
+
+def adam_reference(p, g, m, v, t, lr, betas=(0.9, 0.999), eps=1e-8):
+    """One step of torch's Adam (amsgrad off, no weight decay) in fp64, as csrc/fit_step.hip evaluates it per element: t is the
+    1-based step.  -> (p, m, v) in fp64; the kernel stores each rounded to fp32 once."""
+    p, g, m, v = (x.detach().double() for x in (p, g, m, v))
+    beta1, beta2 = betas
+    m = beta1 * m + (1.0 - beta1) * g
+    v = beta2 * v + (1.0 - beta2) * (g * g)
+    bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
+    p = p - (lr / bc1) * m / (v.sqrt() / bc2 ** 0.5 + eps)
+    return p, m, v
+
+
+def _f32(x):
+    """a Python number rounded to fp32 the way torch rounds a scalar operand of an fp32 tensor"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+class DevicePoseFit:
+    """The loop of ``fit_object_pose`` on the device: one ``ivlm_fit_step`` (csrc/fit_step.hip) per iteration - the fused transform,
+    the silhouette and contact kernels, the loss arithmetic, every backward and Adam as one launch sequence without a host read or
+    an allocation; each phase (``fit_phases``) has its own launch sequence.  The launches are eager: replaying the sequence as
+    a HIP graph is NOT built (DESIGN 4.42 says what was tried and why it was taken out).  Iteration i computes the total, the
+    terms and the gradients of ``ObjectPoseFit(fused_transform=True)`` at step i bit for bit; the update is torch's Adam evaluated
+    in fp64 per element (``adam_reference``), so later iterations follow the torch loop within Adam's rounding, not bit for bit.
+
+    The constructor takes ``ObjectPoseFit``'s arguments (the transform is always fused) and loss_weights, max_iter, lrs = (rotation,
+    translation, scale), betas, eps > 0.  It owns rotation [B,6], translation [B,3], scale [B], the moments, the device step
+    counter, history [max_iter,B] (the total BEFORE update i), term_history [max_iter,3,B] (``TERM_KEYS``; an exact 0 for a term
+    that does not count), the workspace and the topology lists (from the silhouette module's cache: the one host read, here).
+    step() runs one iteration, run(n=None) the remaining ones (or n).  rotation_grad / translation_grad / scale_grad are the last
+    step's gradients."""
+
+    def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
+                 human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
+                 blur_radius=None, loss_weights=None, max_iter=250, lrs=DEFAULT_LRS, betas=(0.9, 0.999), eps=1e-8):
+        from . import _lib
+        from . import contact_pair as cp
+        from . import pose as pose_mod
+        from . import silhouette as sil
+
+        if not isinstance(max_iter, int) or isinstance(max_iter, bool) or max_iter < 1:
+            raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
+        if not set(vars):
+            raise ValueError("vars: nothing to optimise")
+        try:
+            lrs = tuple(float(x) for x in lrs)
+            betas = tuple(float(x) for x in betas)
+            eps = float(eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"lrs / betas / eps: expected numbers, got {lrs!r}, {betas!r}, {eps!r}") from None
+        if len(lrs) != 3 or len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas) or not eps > 0.0:
+            raise ValueError(f"expected three learning rates, two betas in [0, 1) and eps > 0, got {lrs}, {betas}, {eps}")
+        weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
+        self.phases = fit_phases(weights, max_iter)
+        for lo, _, bits in self.phases:
+            if bits == 0:
+                raise ValueError(f"loss_weights: no term counts at iteration {lo}: nothing to descend")
+        # validation of shapes, dtypes and devices by the modules whose kernels run, before the library loads
+        model = ObjectPoseFit(rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
+                              human_contact_probs, target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius,
+                              fused_transform=True)
+        if not isinstance(target_mask, torch.Tensor) or target_mask.dim() != 2:
+            raise ValueError("target_mask: expected [H,W]")
+        H, W = model.target_mask.shape
+        pose_mod._validate(model.obj_vertices, model.rotation.data, model.translation.data, model.scale.data)
+        cam = sil._validate(model.obj_vertices, model.obj_faces, focal, principal, (H, W), sigma, blur_radius)
+        cp._validate(model.obj_vertices, model.human_vertices, model.object_contact_probs, model.human_contact_probs)
+        sil._validate_terms(model.target_mask.new_empty(H, W), model.target_mask)
+        if model.hum_centroid_offset.shape != (3,):
+            raise ValueError(f"hum_centroid_offset: expected [3], got {tuple(model.hum_centroid_offset.shape)}")
+        self.model = model
+        self.max_iter, self.iteration = max_iter, 0
+        self.rotation, self.translation, self.scale = model.rotation.data, model.translation.data, model.scale.data
+        dev = self.rotation.device
+        B, N, F, N_h = self.rotation.shape[0], model.obj_vertices.shape[0], model.obj_faces.shape[0], model.human_vertices.shape[0]
+        self.sizes = (B, N, F, H, W, N_h)
+        lib = _lib.load()
+        nbytes = lib.ivlm_fit_step_workspace_bytes(B, N, F, H, W, N_h)
+        if nbytes == 0:
+            raise _lib.IvlmError(f"DevicePoseFit: sizes B={B}, N={N}, F={F}, H={H}, W={W}, N_h={N_h} are not supported")
+        p, q = model.object_contact_probs, model.human_contact_probs
+        if p.dtype != q.dtype:  # as contact_distance: a mixed pair goes in as fp32
+            p, q = p.float(), q.float()
+        optimise = (_lib.FIT_POSE if "pose" in vars else 0) | (_lib.FIT_SCALE if "scale" in vars else 0)
+        with torch.cuda.device(dev):
+            f32, offsets, slots = sil._topology_of(model.obj_faces, N)
+            zeros = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+            self._moments = [zeros(B, 6), zeros(B, 3), zeros(B), zeros(B, 6), zeros(B, 3), zeros(B)]
+            self._grads = [zeros(B, 6), zeros(B, 3), zeros(B)]
+            self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.history, self.term_history = zeros(max_iter, B), zeros(max_iter, 3, B)
+            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._keep = (f32, offsets, slots, p.contiguous(), q.contiguous(), model.obj_vertices.contiguous(),
+                      model.human_vertices.contiguous(), model.target_mask.contiguous(), model.target_mask_centroid.contiguous(),
+                      model.hum_centroid_offset.contiguous())
+        f32, offsets, slots, p, q, verts, hum, target, target_c, off = self._keep
+        a = _lib.FitStepArgs()
+        for name, t in (("obj_verts", verts), ("faces", f32), ("vert_face_offsets", offsets), ("vert_face_list", slots),
+                        ("human_verts", hum), ("obj_probs", p), ("human_probs", q), ("target", target), ("target_centroid", target_c),
+                        ("centroid_offset", off), ("rotation", self.rotation), ("translation", self.translation), ("scale", self.scale),
+                        ("step", self.counter), ("history", self.history), ("term_history", self.term_history),
+                        ("workspace", self.workspace)):
+            setattr(a, name, t.data_ptr())
+        for name, t in zip(("m_rotation", "m_translation", "m_scale", "v_rotation", "v_translation", "v_scale"), self._moments):
+            setattr(a, name, t.data_ptr())
+        for name, t in zip(("grad_rotation", "grad_translation", "grad_scale"), self._grads):
+            setattr(a, name, t.data_ptr())
+        a.workspace_bytes = nbytes
+        a.lr_rotation, a.lr_translation, a.lr_scale = lrs
+        a.beta1, a.beta2, a.eps = betas[0], betas[1], eps
+        a.B, a.N, a.F, a.H, a.W, a.N_h = self.sizes
+        a.p_dtype = cp.IVLM_BF16 if p.dtype == torch.bfloat16 else cp.IVLM_F32
+        a.max_iter, a.optimise = max_iter, optimise
+        a.fx, a.fy, a.px, a.py, _, _, a.sigma, a.blur_radius = cam
+        a.w_mask, a.w_centroid, a.w_contact = (_f32(weights[k]["w"]) if k in weights else 0.0 for k in TERM_KEYS)
+        self._args, self._lib = a, lib
+        self._vars = tuple(vars)
+
+    def _grad(self, k, name):
+        if name not in self._vars:
+            return None
+        return self._grads[k].detach()
+
+    rotation_grad = property(lambda self: self._grad(0, "pose"))
+    translation_grad = property(lambda self: self._grad(1, "pose"))
+    scale_grad = property(lambda self: self._grad(2, "scale"))
+
+    def _state(self):
+        return [self.rotation, self.translation, self.scale, *self._moments, *self._grads, self.counter, self.history, self.term_history]
+
+    def _launch(self, bits):
+        from ._lib import check
+
+        self._args.terms_on = bits
+        with torch.cuda.device(self.rotation.device):
+            check(self._lib.ivlm_fit_step(ctypes.byref(self._args), torch.cuda.current_stream().cuda_stream), "fit_step")
+
+    def step(self):
+        """one iteration: the total of the current parameters into history[i], then the update"""
+        i = self.iteration
+        if i >= self.max_iter:
+            raise RuntimeError(f"DevicePoseFit: all {self.max_iter} iterations have run")
+        bits = next(b for lo, hi, b in self.phases if lo <= i < hi)
+        self._launch(bits)
+        self.iteration = i + 1
+
+    def run(self, n=None):
+        """the remaining iterations, or n of them"""
+        left = self.max_iter - self.iteration
+        if n is not None and (not isinstance(n, int) or n < 0 or n > left):
+            raise ValueError(f"n: expected an integer in [0, {left}], got {n!r}")
+        for _ in range(left if n is None else n):
+            self.step()
+        return self
+
+    def result(self):
+        """-> the dict of ``fit_object_pose`` plus term_history, at the current parameters"""
+        with torch.no_grad():
+            verts = self.model.object_vertices()
+        done = self.iteration
+        return {"rotation": self.rotation, "translation": self.translation, "scale": self.scale, "object_vertices": verts,
+                "history": self.history[:done], "term_history": self.term_history[:done]}
+
+
+_UNSET = object()  # fused_transform was not passed: False for the torch loop, implied by device_loop
+
+
 def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                     init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250, early_stop=False,
-                    sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=False):
+                    sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
+                    device_loop=False):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
     init = (R6 [B,6], T [B,3], s number or [B]) gives the B starts; None takes one start from ``contact_icp`` between the object
     vertices of contact probability > icp_threshold[0] and the human vertices of probability > icp_threshold[1] (selecting them
     reads the device once, before the loop).  early_stop ends the loop when every start has |previous - current| < 1e-6: the only
-    host read of the loop, made only when asked for.  fused_transform: see ``ObjectPoseFit``.
+    host read of the loop, made only when asked for.  fused_transform: see ``ObjectPoseFit``.  device_loop=True runs the loop as
+    ``DevicePoseFit`` does (one launch sequence per iteration, Adam as a kernel): it implies the fused
+    transform, refuses early_stop (a host read per iteration) and adds term_history [iterations,3,B] to the result.
     -> dict(rotation [B,6], translation [B,3], scale [B], object_vertices [B,N,3], history [iterations,B] (device tensor))."""
     if not isinstance(max_iter, int) or max_iter < 1:
         raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
+    if device_loop:
+        if early_stop:
+            raise ValueError("early_stop: not available with device_loop=True (it reads the device every iteration)")
+        if fused_transform is not _UNSET and not fused_transform:
+            raise ValueError("fused_transform=False: not available with device_loop=True (the device loop runs the fused transform)")
+    fused_transform = bool(device_loop) if fused_transform is _UNSET else fused_transform
     if init is None:
         o_sel = obj_vertices[obj_contact_probs.float() > icp_threshold[0]]
         h_sel = human_vertices[human_contact_probs.float() > icp_threshold[1]]
@@ -181,6 +377,10 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
             raise ValueError("init=None needs contact vertices above icp_threshold on both meshes for contact_icp")
         icp = contact_icp(o_sel.float(), h_sel.float(), max_iterations=icp_max_iterations)
         init = (matrix_to_rot6d(icp.R), icp.T, 1.0)
+    if device_loop:
+        return DevicePoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
+                             target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, loss_weights,
+                             max_iter).run().result()
     model = ObjectPoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
                           target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform)
     groups = []
@@ -227,7 +427,8 @@ _SEARCH_FIT_KWARGS = ("hum_centroid_offset", "vars", "loss_weights", "max_iter",
 
 
 def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
-                       rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, **fit_kwargs):
+                       rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, device_loop=False,
+                       **fit_kwargs):
     """A multi-start ``fit_object_pose``: K starts around one pose, fitted in one loop with the fused transform, scored and ranked on
     the device.  NOT the reference's, which runs one start (optim/fit.py): contact patches and a silhouette leave rotational
     ambiguities that a local fit from one start does not resolve.
@@ -241,6 +442,9 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     vars, loss_weights, max_iter, sigma, blur_radius, icp_threshold, icp_max_iterations (early_stop is refused: it ends a loop
     when all of ITS starts have settled).  The score of a start is one more forward at its returned parameters, without gradients,
     with every configured term (kick_in >= 0) on; history[-1] is the total BEFORE the last update and is not the score.
+
+    device_loop=True runs every loop on the device (``fit_object_pose(device_loop=True)``, ``DevicePoseFit``) and adds term_history
+    [iterations,3,K]; the scoring stays the forward described above.
 
     chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
     computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
@@ -292,14 +496,14 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     parts, scores = [], []
     for lo in range(0, K, step):
         sel = slice(lo, min(lo + step, K))
-        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, **fit_kwargs)
+        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop, **fit_kwargs)
         final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], *scene, fit_kwargs.get("hum_centroid_offset"),
                               fit_kwargs.get("vars", ("pose",)), fit_kwargs.get("sigma", 1e-4), fit_kwargs.get("blur_radius"),
                               fused_transform=True)
         with torch.no_grad():
             scores.append(final(weights, step=every_term)[0])
         parts.append(out)
-    result = {k: torch.cat([p[k] for p in parts], dim=1 if k == "history" else 0) for k in parts[0]}
+    result = {k: torch.cat([p[k] for p in parts], dim={"history": 1, "term_history": 2}.get(k, 0)) for k in parts[0]}
     result["scores"] = torch.cat(scores)
     best = select_best(result["scores"])
     result["best_index"] = best

@@ -1,5 +1,7 @@
 """Time one ObjectPoseFit step (forward, total.sum().backward()) with the pose-by-pose torch transform and with the fused
-pose_transform, at B = 1, 8, 24 starts, and one whole search_object_pose (24 starts, 250 iterations).
+pose_transform, one whole iteration of the torch loop (that step plus torch.optim.Adam) and one of the device loop
+(fit.DevicePoseFit.step, whose last total is checked against the torch loop's after the same iterations), at B = 1, 8, 24 starts,
+and one whole search_object_pose (24 starts, 250 iterations) with the torch loop and with device_loop=True.
 
     python tools/bench_fit_search.py [--rounds 5] [--iters 20] [--out FILE.json] [--baseline PARENT.json] [--commit HASH]
     python tools/bench_fit_search.py --tree PATH --commit HASH --out PARENT.json    # the same steps with the package of another checkout
@@ -8,7 +10,8 @@ The method and the shapes are those of tools/bench_silhouette.py: a UV sphere of
 sigma 1e-4, (N, F, H, W) = (20002, 40000, 1024, 1024) and (2050, 4096, 512, 512), 6890 human vertices, 5 % contact on both sides;
 device events around `iters` steps, the median of `rounds` rounds (all rounds are kept in the output).  The baseline of "fused off" is
 the parent commit's step: run the tool with --tree on a checkout of the parent in the same session on the same machine (it times
-only what that package has), then pass its output with --baseline; the merged file is what profiles/fit_search_bench.json holds.
+only what that package has), then pass its output with --baseline; the merged file is what profiles/fit_search_bench.json holds
+(profiles/fit_device_loop_bench.json for the run that added the device loop, whose parent column is the parent's torch iteration).
 The whole search is wall time around a synchronised call, host reads included, beside the same 24 starts fitted by
 fit_object_pose with the torch transform.  Prints one JSON line per case.  Needs a GPU: there is no CPU path.
 """
@@ -53,6 +56,7 @@ def main():
         raise SystemExit("bench_fit_search needs a GPU (no CPU path)")
     dev = torch.device("cuda:0")
     has_fused = "fused_transform" in inspect.signature(fit.ObjectPoseFit.__init__).parameters
+    has_device = hasattr(fit, "DevicePoseFit")
     modes = (("off", False), ("on", True)) if has_fused else (("off", False),)
     gen = torch.Generator().manual_seed(0)
     cases, scene_small = [], None
@@ -84,6 +88,29 @@ def main():
                 for _ in range(3):
                     fit_step()
                 steps[name] = fit_step
+            if has_fused:  # a whole iteration of the torch loop: the fused step and torch.optim.Adam as fit_object_pose drives them
+                model = fit.ObjectPoseFit(fit.matrix_to_rot6d(torch.eye(3)).expand(B, 6).to(dev), (shift + 0.03).to(dev), 1.0, *scene,
+                                          fused_transform=True)
+                opt = torch.optim.Adam([{"params": [model.rotation], "lr": 5e-2}, {"params": [model.translation], "lr": 1e-2}])
+
+                last = {}
+
+                def torch_iteration(model=model, opt=opt, last=last):
+                    opt.zero_grad()
+                    total, _ = model(step=0)
+                    total.sum().backward()
+                    opt.step()
+                    last["total"] = total.detach()
+
+                for _ in range(3):
+                    torch_iteration()
+                steps["torch_loop"] = torch_iteration
+            if has_device:  # the same iteration as one C call
+                dfit = fit.DevicePoseFit(fit.matrix_to_rot6d(torch.eye(3)).expand(B, 6).to(dev), (shift + 0.03).to(dev), 1.0, *scene,
+                                         max_iter=3 + a.rounds * a.iters)
+                for _ in range(3):
+                    dfit.step()
+                steps["device_loop"] = dfit.step
             t = {name: [] for name in steps}
             for _ in range(a.rounds):  # the modes alternate inside a round, so that a drift of the machine reaches both
                 for name, step in steps.items():
@@ -92,6 +119,11 @@ def main():
             for name in steps:
                 r[f"step_{name}_us_rounds"] = t[name]
                 r[f"step_{name}_us_median"] = statistics.median(t[name])
+            if has_device:  # faster and different is not faster: both loops have run the same iterations from the same start
+                theirs, mine = last["total"], dfit.history[dfit.iteration - 1]
+                r["device_loop_iterations"] = dfit.iteration
+                r["device_loop_last_total_max_rel_diff_to_torch"] = float(((mine - theirs).abs() / theirs.abs()).max())
+                r["device_loop_last_total_finite"] = bool(torch.isfinite(mine).all())
             print(json.dumps(r), flush=True)
             cases.append(r)
     result = {"machine": f"{torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName})", "torch": torch.__version__,
@@ -111,7 +143,15 @@ def main():
             return fit.fit_object_pose(*scene_small, init=(r6, T, s), max_iter=a.max_iter)
 
         fit.search_object_pose(*scene_small, init=init, icp=True, max_iter=3)  # warm: the topology cache, the allocator
-        for name, call in (("search_ms_rounds", whole_search), ("unfused_fit_24_starts_ms_rounds", unfused_fit)):
+
+        def device_search():
+            return fit.search_object_pose(*scene_small, init=init, icp=True, max_iter=a.max_iter, device_loop=True)
+
+        calls = [("search_ms_rounds", whole_search), ("unfused_fit_24_starts_ms_rounds", unfused_fit)]
+        if has_device:
+            fit.search_object_pose(*scene_small, init=init, icp=True, max_iter=3, device_loop=True)
+            calls.insert(1, ("search_device_loop_ms_rounds", device_search))
+        for name, call in calls:
             times = []
             for _ in range(a.search_rounds):
                 torch.cuda.synchronize()
@@ -121,8 +161,8 @@ def main():
                 times.append((time.perf_counter() - t0) * 1e3)
             search[name] = times
             search[name.replace("_rounds", "_median")] = statistics.median(times)
-            if name.startswith("search"):
-                search["best_index"] = int(out["best_index"])
+            if name.startswith("search"):  # (best_index: the torch loop's; the device loop's beside it)
+                search["best_index" if name == "search_ms_rounds" else "device_loop_best_index"] = int(out["best_index"])
         print(json.dumps(search), flush=True)
         result["search"] = search
     if a.baseline:
@@ -134,6 +174,15 @@ def main():
             assert all(r[k] == p[k] for k in ("B", "N", "F", "H", "W"))
             r["parent_step_us_rounds"] = p["step_off_us_rounds"]
             r["parent_step_us_median"] = p["step_off_us_median"]
+            if "step_on_us_rounds" in p:  # the parent's step with the fused transform
+                r["parent_step_on_us_rounds"] = p["step_on_us_rounds"]
+                r["parent_step_on_us_median"] = p["step_on_us_median"]
+            if "step_torch_loop_us_rounds" in p:  # the parent's whole iteration with the fused transform
+                r["parent_torch_loop_us_rounds"] = p["step_torch_loop_us_rounds"]
+                r["parent_torch_loop_us_median"] = p["step_torch_loop_us_median"]
+        if "search" in base and "search" in result:
+            result["search"]["parent_search_ms_rounds"] = base["search"]["search_ms_rounds"]
+            result["search"]["parent_search_ms_median"] = base["search"]["search_ms_median"]
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
