@@ -1075,6 +1075,39 @@ int ivlm_fit_adam(float *rotation, float *translation, float *scale, const float
                   float *v_translation, float *v_scale, int B, const int32_t *step, double lr_rotation, double lr_translation,
                   double lr_scale, double beta1, double beta2, double eps, ivlm_stream_t stream);
 
+/* Signed distance to a closed, outward-oriented triangle mesh and the penetration term built on it (mesh_sdf.hip).  NOT the
+ * reference's: none of its three fit terms knows inside from outside.  vertices f32 [N_h,3], faces i32 [F,3], points f32 [B,N,3].
+ *   c(x) = the closest point of the surface (per face by Ericson's region classification), d(x) = |x - c(x)|
+ *   k(x) = a face that attains d(x); among faces whose fp32 squared distance compares equal, the lowest index
+ *   w(x) = (1 / 4 pi) sum_f Omega_f(x), Omega_f = 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|) with
+ *          a, b, c = v0 - x, v1 - x, v2 - x;  inside(x) <=> w(x) > 0.5;  sdf(x) = -d inside, +d outside
+ *   L    = (1 / N) sum_i inside(x_i) d(x_i)^2 per pose,  dL/dx_i = inside(x_i) 2 (x_i - c(x_i)) / N;  no gradient to the mesh
+ * A face of zero area (the fp32 cross product of its edges is exactly 0) contributes to neither sum; a face that names a vertex
+ * outside [0, N_h) is treated the same way (callers validate their faces: interactvlm_amd.mesh_sdf does).
+ * ivlm_mesh_sdf_prepare writes the plan once per mesh: a 256-byte header (face count, chunk count, the bounding box of the
+ * vertices) and one 48-byte record per face {v0, v1, v2, mark, 0, 0}; ivlm_mesh_sdf_plan_bytes(N_h, F) bytes, 16-byte aligned.
+ * ivlm_mesh_sdf_query: sdf [B,N], closest [B,N,3], face i32 [B,N], winding [B,N] for every point; any of the four may be NULL,
+ * not all.  ivlm_mesh_sdf_penetration: value [B] and grad [B,N,3] (may be NULL).  A point outside the bounding box is outside: it
+ * adds an exact 0, its gradient row is an exact 0 and it causes no face sweep; only points found inside get a closest-point sweep.
+ * The faces are swept IVLM_MESH_SDF_TILE at a time from LDS, in grid chunks of IVLM_MESH_SDF_CHUNK; the winding sum is fp32 within
+ * a chunk and fp64 across chunks, the sum of d^2 over the points fp64, rounded once.  No atomics, fixed orders: the same bits every
+ * call and for a pose whatever the batch around it.
+ * NULL or non-positive arguments: IVLM_ERR_INVALID_ARG before any launch.  N_h, F <= 2^22, N <= 2^20, B <= 65535, else
+ * IVLM_ERR_UNSUPPORTED (the size queries return 0).  workspace: ivlm_mesh_sdf_workspace_bytes(B, N, F) bytes, 16-byte aligned,
+ * 24 B N ceil(F / IVLM_MESH_SDF_CHUNK) bytes of chunk partials + 8 B N + O(B N / 256) and padding; nothing scales with N F.  The two
+ * calls are not told F (it is in the plan, on the device): they return IVLM_ERR_WORKSPACE for a workspace that holds no chunk at
+ * all; one that holds some chunks but fewer than the plan's runs no sweep and gives NaN (face -1), never an access out of bounds. */
+#define IVLM_MESH_SDF_TILE 128
+#define IVLM_MESH_SDF_CHUNK 512
+size_t ivlm_mesh_sdf_plan_bytes(int N_h, int F);
+int ivlm_mesh_sdf_prepare(const float *vertices, const int32_t *faces, int N_h, int F, void *plan, size_t plan_bytes,
+                          ivlm_stream_t stream);
+size_t ivlm_mesh_sdf_workspace_bytes(int B, int N, int F);
+int ivlm_mesh_sdf_query(const void *plan, const float *points, int B, int N, float *sdf, float *closest, int32_t *face,
+                        float *winding, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+int ivlm_mesh_sdf_penetration(const void *plan, const float *points, int B, int N, float *value, float *grad, void *workspace,
+                              size_t workspace_bytes, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

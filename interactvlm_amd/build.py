@@ -26,6 +26,9 @@ EXTRA = {
     "postprocess.hip": ["-ffp-contract=off"],
     "heads.hip": ["-ffp-contract=off"],
     "fit_step.hip": ["-ffp-contract=off"],  # the loss arithmetic repeats torch's operations one by one; Adam is plain IEEE fp64
+    # every fp32 operation is the one tests/_mesh_sdf_ref.py states in its fp32 mode, which is what the tests' tolerance constants
+    # were measured with
+    "mesh_sdf.hip": ["-ffp-contract=off"],
 }
 
 

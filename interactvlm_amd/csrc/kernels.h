@@ -176,6 +176,15 @@ int seg_iou_counts(const float* pred, const void* gt, int gt_dtype, int V, int H
 int afford_metrics(const float* gt, const float* pred, int B, int n, const float* thresholds, int T, float mae_div, float* out,
                    int32_t* valid, hipStream_t st);
 
+// ---- signed distance to a closed mesh and the penetration term (mesh_sdf.hip) ---------------------------
+size_t mesh_sdf_plan_bytes(int n_verts, int n_faces);
+int mesh_sdf_prepare(const float* verts, const int32_t* faces, int n_verts, int n_faces, void* plan, size_t plan_bytes, hipStream_t st);
+size_t mesh_sdf_workspace_bytes(int B, int N, int n_faces);
+int mesh_sdf_query(const void* plan, const float* points, int B, int N, float* sdf, float* closest, int32_t* face, float* winding,
+                   void* ws, size_t ws_bytes, hipStream_t st);
+int mesh_sdf_penetration(const void* plan, const float* points, int B, int N, float* value, float* grad, void* ws, size_t ws_bytes,
+                         hipStream_t st);
+
 // ---- contact-weighted human-object distance with both gradients (contact_pair.hip) ---------------------
 size_t contact_pair_workspace_bytes(int B, int n_o, int n_h);
 int contact_pair(const float* o, const float* h, const void* p, const void* q, int p_dtype, int B, int n_o, int n_h,

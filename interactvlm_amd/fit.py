@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from .contact_icp import contact_icp
 from .contact_pair import contact_distance
+from .mesh_sdf import MeshSDF
 from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_transform
 from .silhouette import silhouette_terms, soft_silhouette
 
@@ -26,6 +27,9 @@ DEFAULT_LOSS_WEIGHTS = {
     "centroid_loss": {"w": 1e-4, "kick_in": 0},
     "contact_loss": {"w": 10.0, "kick_in": 0},
 }
+# NOT the reference's and not in DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh.  A term of
+# ``ObjectPoseFit`` when loss_weights holds it and the model has human_faces; not a row of TERM_KEYS, not run by ivlm_fit_step.
+PENETRATION_KEY = "penetration_loss"
 
 
 def matrix_to_rot6d(matrix):
@@ -92,11 +96,14 @@ class ObjectPoseFit(nn.Module):
     ``soft_silhouette`` takes them.  ``vars`` selects what is optimised: "pose", "scale" or both.  fused_transform=True moves the
     object with ``pose.pose_transform`` (one launch for the batch, two for its backward) instead of the pose-by-pose torch
     operations of ``apply_transformation``: the same transform within the documented errors of that kernel, not the same bits.
+    human_faces [F_h,3] int32 (closed, outward) prepares one ``MeshSDF`` of the human and allows one more term, NOT the reference's:
+    "penetration_loss" = ``MeshSDF.penetration`` of the un-offset object vertices (the frame of the contact term), gated and weighted
+    like the others when loss_weights holds the key (``DEFAULT_LOSS_WEIGHTS`` does not); on without human_faces it raises.
     forward(loss_weights, step=None) -> (total [B], {term: [B]})."""
 
     def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
                  human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
-                 blur_radius=None, fused_transform=False):
+                 blur_radius=None, fused_transform=False, human_faces=None):
         super().__init__()
         unknown = set(vars) - {"pose", "scale"}
         if unknown:
@@ -130,6 +137,8 @@ class ObjectPoseFit(nn.Module):
         mask = (target_mask != 0).float()
         self.register_buffer("target_mask", mask)
         self.register_buffer("target_mask_centroid", mask_bbox_centre(mask))
+        # the penetration term's prepared mesh (one device read, here); a plain attribute: the plan belongs to this device
+        self.human_sdf = None if human_faces is None else MeshSDF(self.human_vertices, human_faces.detach())
 
     def object_vertices(self):
         if self.fused_transform:
@@ -157,6 +166,11 @@ class ObjectPoseFit(nn.Module):
                 terms["centroid_loss"] = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
         if on("contact_loss"):
             terms["contact_loss"] = contact_distance(obj, self.human_vertices, self.object_contact_probs, self.human_contact_probs)
+        if on(PENETRATION_KEY):
+            if self.human_sdf is None:
+                raise ValueError(f"{PENETRATION_KEY} is on, but the model was built without human_faces: the signed distance needs the "
+                                 "human's triangles")
+            terms[PENETRATION_KEY] = self.human_sdf.penetration(obj)
         total = torch.zeros(self.rotation.shape[0], dtype=torch.float32, device=self.rotation.device)
         for key, val in terms.items():
             total = total + val * weights[key]["w"]
@@ -166,6 +180,12 @@ class ObjectPoseFit(nn.Module):
 
 TERM_KEYS = ("mask_loss", "centroid_loss", "contact_loss")  # the rows of term_history, the bits of IVLM_FIT_MASK / CENTROID / CONTACT
 DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
+
+
+def _refuse_penetration_on_device(loss_weights):
+    if loss_weights is not None and PENETRATION_KEY in loss_weights and loss_weights[PENETRATION_KEY]["kick_in"] >= 0:
+        raise ValueError(f"{PENETRATION_KEY}: not available with device_loop=True (the device loop's launch sequence does not run the "
+                         "term; configure kick_in = -1 or use the torch loop)")
 
 
 def fit_phases(loss_weights, max_iter):
@@ -234,6 +254,7 @@ class DevicePoseFit:
             raise ValueError(f"lrs / betas / eps: expected numbers, got {lrs!r}, {betas!r}, {eps!r}") from None
         if len(lrs) != 3 or len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas) or not eps > 0.0:
             raise ValueError(f"expected three learning rates, two betas in [0, 1) and eps > 0, got {lrs}, {betas}, {eps}")
+        _refuse_penetration_on_device(loss_weights)
         weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
         self.phases = fit_phases(weights, max_iter)
         for lo, _, bits in self.phases:
@@ -352,7 +373,7 @@ _UNSET = object()  # fused_transform was not passed: False for the torch loop, i
 def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                     init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250, early_stop=False,
                     sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
-                    device_loop=False):
+                    device_loop=False, human_faces=None):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
     init = (R6 [B,6], T [B,3], s number or [B]) gives the B starts; None takes one start from ``contact_icp`` between the object
@@ -361,6 +382,8 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
     host read of the loop, made only when asked for.  fused_transform: see ``ObjectPoseFit``.  device_loop=True runs the loop as
     ``DevicePoseFit`` does (one launch sequence per iteration, Adam as a kernel): it implies the fused
     transform, refuses early_stop (a host read per iteration) and adds term_history [iterations,3,B] to the result.
+    human_faces [F_h,3] int32 (the human's triangles, closed and outward) is what the term "penetration_loss" of loss_weights needs
+    (``ObjectPoseFit``, ``mesh_sdf``: NOT the reference's); device_loop=True refuses that term when it is configured (kick_in >= 0).
     -> dict(rotation [B,6], translation [B,3], scale [B], object_vertices [B,N,3], history [iterations,B] (device tensor))."""
     if not isinstance(max_iter, int) or max_iter < 1:
         raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
@@ -369,6 +392,7 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
             raise ValueError("early_stop: not available with device_loop=True (it reads the device every iteration)")
         if fused_transform is not _UNSET and not fused_transform:
             raise ValueError("fused_transform=False: not available with device_loop=True (the device loop runs the fused transform)")
+        _refuse_penetration_on_device(loss_weights)
     fused_transform = bool(device_loop) if fused_transform is _UNSET else fused_transform
     if init is None:
         o_sel = obj_vertices[obj_contact_probs.float() > icp_threshold[0]]
@@ -382,7 +406,7 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
                              target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, loss_weights,
                              max_iter).run().result()
     model = ObjectPoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
-                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform)
+                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform, human_faces)
     groups = []
     if "pose" in vars:
         groups += [{"params": [model.rotation], "lr": 5e-2}, {"params": [model.translation], "lr": 1e-2}]
@@ -428,7 +452,7 @@ _SEARCH_FIT_KWARGS = ("hum_centroid_offset", "vars", "loss_weights", "max_iter",
 
 def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                        rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, device_loop=False,
-                       **fit_kwargs):
+                       human_faces=None, **fit_kwargs):
     """A multi-start ``fit_object_pose``: K starts around one pose, fitted in one loop with the fused transform, scored and ranked on
     the device.  NOT the reference's, which runs one start (optim/fit.py): contact patches and a silhouette leave rotational
     ambiguities that a local fit from one start does not resolve.
@@ -444,7 +468,8 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     with every configured term (kick_in >= 0) on; history[-1] is the total BEFORE the last update and is not the score.
 
     device_loop=True runs every loop on the device (``fit_object_pose(device_loop=True)``, ``DevicePoseFit``) and adds term_history
-    [iterations,3,K]; the scoring stays the forward described above.
+    [iterations,3,K]; the scoring stays the forward described above.  human_faces goes to every loop and to the scoring model, so
+    that the score holds "penetration_loss" whenever loss_weights configures it (device_loop=True refuses that, see ``fit_object_pose``).
 
     chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
     computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
@@ -455,6 +480,8 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     ``fit_object_pose`` and of the silhouette's topology cache, before the loop."""
     if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
         raise ValueError(f"chunk: expected None or an integer >= 1, got {chunk!r}")
+    if device_loop:
+        _refuse_penetration_on_device(fit_kwargs.get("loss_weights"))
     if "early_stop" in fit_kwargs:
         raise ValueError("early_stop: not available in search_object_pose (it would make a start's result depend on chunk)")
     unknown = sorted(set(fit_kwargs) - set(_SEARCH_FIT_KWARGS))
@@ -496,10 +523,11 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     parts, scores = [], []
     for lo in range(0, K, step):
         sel = slice(lo, min(lo + step, K))
-        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop, **fit_kwargs)
+        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop,
+                              human_faces=human_faces, **fit_kwargs)
         final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], *scene, fit_kwargs.get("hum_centroid_offset"),
                               fit_kwargs.get("vars", ("pose",)), fit_kwargs.get("sigma", 1e-4), fit_kwargs.get("blur_radius"),
-                              fused_transform=True)
+                              fused_transform=True, human_faces=human_faces)
         with torch.no_grad():
             scores.append(final(weights, step=every_term)[0])
         parts.append(out)
