@@ -96,6 +96,38 @@ def load():
     return lib
 
 
+def stream():
+    """the handle of torch's current stream, as an ``ivlm_stream_t``"""
+    import torch
+
+    return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(x):
+    """the device address of a tensor, 0 for None (an output or input the call does without)"""
+    return 0 if x is None else x.data_ptr()
+
+
+def require_gpu(named):
+    """named: (tensor, name) pairs, in the order their errors are reported"""
+    for t, name in named:
+        if not t.is_cuda:
+            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+
+
+def workspace(size_fn, what, device, **sizes):
+    """Ask ``size_fn(*sizes.values())`` (an ``ivlm_*_bytes`` query) and -> (uint8 tensor of that size on ``device``, nbytes); sizes the
+    library refuses (the query returns 0) raise.  device None: only the check, -> (None, nbytes)."""
+    nbytes = size_fn(*sizes.values())
+    if nbytes == 0:
+        raise IvlmError(f"{what}: sizes {', '.join(f'{k}={v}' for k, v in sizes.items())} are not supported")
+    if device is None:
+        return None, nbytes
+    import torch
+
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
 def check(rc: int, what: str = "") -> None:
     if rc != 0:
         lib = load()

@@ -22,7 +22,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
-from ._lib import IvlmError, check
+from ._lib import check
 
 ESTIMATE_SCALE, ALLOW_REFLECTION, REQUERY = 1, 2, 4  # IVLM_ICP_* of include/ivlm_hip.h
 
@@ -60,9 +60,7 @@ def _batch(named):
 
 
 def _check_devices(named):
-    for t, name, _ in named:
-        if not t.is_cuda:
-            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu((t, name) for t, name, _ in named)
     devs = {t.device for t, _, _ in named}
     if len(devs) != 1:
         raise ValueError(f"all tensors must be on one device, got {sorted(str(d) for d in devs)}")
@@ -83,10 +81,6 @@ def _side(t, rank):
     """-> (contiguous tensor with a batch axis, elements between poses or 0 for a side shared by the batch)"""
     t = (t if t.dim() == rank + 1 else t.unsqueeze(0)).contiguous()
     return t, (t[0].numel() if t.shape[0] > 1 else 0)
-
-
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
 
 
 def contact_nearest(queries, targets):
@@ -110,7 +104,7 @@ def contact_nearest(queries, targets):
         idx = torch.empty(B, n_o, dtype=torch.int32, device=q.device)
         d2 = torch.empty(B, n_o, dtype=torch.float32, device=q.device)
         check(lib.ivlm_contact_nearest(q.data_ptr(), t.data_ptr(), D, B, n_o, n_h, q_bs, t_bs, idx.data_ptr(), d2.data_ptr(),
-                                       torch.cuda.current_stream().cuda_stream), "contact_nearest")
+                                       _lib.stream()), "contact_nearest")
     return idx, d2
 
 
@@ -140,18 +134,15 @@ def align_points(X, Y, weights=None, estimate_scale=False, allow_reflection=Fals
     y, y_bs = _side(Y, 2)
     w, w_bs = _side(weights, 1) if weights is not None else (None, 0)
     n = x.shape[1]
-    nbytes = lib.ivlm_contact_icp_workspace_bytes(B, n)
-    if nbytes == 0:
-        raise IvlmError(f"align_points: sizes B={B}, N={n} are not supported")
     dev = x.device
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace(lib.ivlm_contact_icp_workspace_bytes, "align_points", dev, B=B, N=n)
         R = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
         T = torch.empty(B, 3, dtype=torch.float32, device=dev)
         s = torch.empty(B, dtype=torch.float32, device=dev)
         flags = (ESTIMATE_SCALE if estimate_scale else 0) | (ALLOW_REFLECTION if allow_reflection else 0)
-        check(lib.ivlm_points_align(x.data_ptr(), y.data_ptr(), _ptr(w), B, n, x_bs, y_bs, w_bs, flags, R.data_ptr(), T.data_ptr(),
-                                    s.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "points_align")
+        check(lib.ivlm_points_align(x.data_ptr(), y.data_ptr(), _lib.ptr(w), B, n, x_bs, y_bs, w_bs, flags, R.data_ptr(), T.data_ptr(),
+                                    s.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "points_align")
     return R, T, s
 
 
@@ -179,8 +170,7 @@ def contact_normal_filter(obj_normals, human_normals, angle_deg, angle_neg_deg=N
     with torch.cuda.device(o.device):
         keep = torch.empty(o.shape[0], dtype=torch.uint8, device=o.device)
         check(lib.ivlm_contact_normal_filter(o.data_ptr(), h.data_ptr(), o.shape[0], h.shape[0], c_pos, c_neg,
-                                             int(angle_neg_deg is not None), keep.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream), "contact_normal_filter")
+                                             int(angle_neg_deg is not None), keep.data_ptr(), _lib.stream()), "contact_normal_filter")
     return keep.bool()
 
 
@@ -258,24 +248,21 @@ def contact_icp(obj_pts, human_pts, obj_normals=None, human_normals=None, init=N
     iR = iT = i_s = None
     if init is not None:
         iR, iT, i_s = (t.contiguous().expand(B, *t.shape[1:]).contiguous() for t in init)
-    nbytes = lib.ivlm_contact_icp_workspace_bytes(B, n_o)
-    if nbytes == 0:
-        raise IvlmError(f"contact_icp: sizes B={B}, N_o={n_o} are not supported")
     flags = (ESTIMATE_SCALE if estimate_scale else 0) | (ALLOW_REFLECTION if allow_reflection else 0) | (REQUERY if requery else 0)
     with torch.cuda.device(dev):
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace(lib.ivlm_contact_icp_workspace_bytes, "contact_icp", dev, B=B, N_o=n_o)
         R, T, s, rmse = torch.empty(B, 3, 3, **f32), torch.empty(B, 3, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
         conv, iters, nn_idx = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(B, n_o, **i32)
         hR = torch.empty(max_iterations, B, 3, 3, **f32)
         hT = torch.empty(max_iterations, B, 3, **f32)
         hs = torch.empty(max_iterations, B, **f32)
-        check(lib.ivlm_contact_icp(x.data_ptr(), y.data_ptr(), _ptr(xn), _ptr(yn), _ptr(w), _ptr(iR), _ptr(iT), _ptr(i_s), B, n_o, n_h,
+        p = _lib.ptr
+        check(lib.ivlm_contact_icp(x.data_ptr(), y.data_ptr(), p(xn), p(yn), p(w), p(iR), p(iT), p(i_s), B, n_o, n_h,
                                    x_bs, y_bs, xn_bs, yn_bs, w_bs, max_iterations, float(relative_rmse_thr), flags, R.data_ptr(),
                                    T.data_ptr(), s.data_ptr(), rmse.data_ptr(), conv.data_ptr(), iters.data_ptr(), nn_idx.data_ptr(),
-                                   hR.data_ptr(), hT.data_ptr(), hs.data_ptr(), ws.data_ptr(), nbytes,
-                                   torch.cuda.current_stream().cuda_stream), "contact_icp")
+                                   hR.data_ptr(), hT.data_ptr(), hs.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "contact_icp")
         # s x R + T, elementwise and in place: no library GEMM whose summation could depend on the batch, no temporaries
         Xt = x[..., 0:1] * R[:, None, 0, :]
         Xt.addcmul_(x[..., 1:2], R[:, None, 1, :]).addcmul_(x[..., 2:3], R[:, None, 2, :])

@@ -12,7 +12,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import IvlmError, check
+from ._lib import check
 
 # The longest serial fp32 accumulation of the kernel (IVLM_CONTACT_PAIR_CHAIN of include/ivlm_hip.h: the vertices of one LDS
 # tile); what follows it is summed in fp64.  Tests derive their tolerance from it: (L_CHAIN + 8) * 2^-24 * sum |terms|.
@@ -50,9 +50,7 @@ def _validate(obj_verts, human_verts, obj_probs, human_probs):
     bh = human_verts.shape[0] if human_verts.dim() == 3 else 1
     if bo != bh and bo != 1 and bh != 1:
         raise ValueError(f"batch sizes {bo} (obj_verts) and {bh} (human_verts) do not broadcast")
-    for t, name in ((obj_verts, "obj_verts"), (human_verts, "human_verts"), (obj_probs, "obj_probs"), (human_probs, "human_probs")):
-        if not t.is_cuda:
-            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu(((obj_verts, "obj_verts"), (human_verts, "human_verts"), (obj_probs, "obj_probs"), (human_probs, "human_probs")))
     devs = {t.device for t in (obj_verts, human_verts, obj_probs, human_probs)}
     if len(devs) != 1:
         raise ValueError(f"all four tensors must be on one device, got {sorted(str(d) for d in devs)}")
@@ -68,19 +66,15 @@ def _launch(o, h, p, q, want_go, want_gh):
         p, q = p.float(), q.float()
     p, q = p.contiguous(), q.contiguous()
     dev = o.device
-    nbytes = lib.ivlm_contact_pair_workspace_bytes(B, n_o, n_h)
-    if nbytes == 0:
-        raise IvlmError(f"contact_distance: sizes B={B}, N_o={n_o}, N_h={n_h} are not supported")
     with torch.cuda.device(dev):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws, nbytes = _lib.workspace(lib.ivlm_contact_pair_workspace_bytes, "contact_distance", dev, B=B, N_o=n_o, N_h=n_h)
         value = torch.empty(B, dtype=torch.float32, device=dev)
         go = torch.empty(B, n_o, 3, dtype=torch.float32, device=dev) if want_go else None
         gh = torch.empty(B, n_h, 3, dtype=torch.float32, device=dev) if want_gh else None
         check(lib.ivlm_contact_pair(o.data_ptr(), h.data_ptr(), p.data_ptr(), q.data_ptr(),
                                     IVLM_BF16 if p.dtype == torch.bfloat16 else IVLM_F32, B, n_o, n_h,
                                     n_o * 3 if o.shape[0] > 1 else 0, n_h * 3 if h.shape[0] > 1 else 0, value.data_ptr(),
-                                    0 if go is None else go.data_ptr(), 0 if gh is None else gh.data_ptr(), ws.data_ptr(), nbytes,
-                                    torch.cuda.current_stream().cuda_stream), "contact_pair")
+                                    _lib.ptr(go), _lib.ptr(gh), ws.data_ptr(), nbytes, _lib.stream()), "contact_pair")
     return value, go, gh
 
 

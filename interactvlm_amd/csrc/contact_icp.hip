@@ -9,7 +9,7 @@
 //                   is kept with a strict < over ascending j, so the lowest index wins an exact tie whatever the tiling.  Then
 //                   each thread fetches its neighbours and forms the weighted moments in fp64 from the fp32 coordinates - of the
 //                   ORIGINAL object point x, as the reference aligns obj_init - and the block reduces them in a fixed order
-//                   (wave butterfly, then wave 0 + wave 1) into one fp64 partial of kMom values.  A second entry mode takes the
+//                   (wave_sum, then wave 0 + wave 1) into one fp64 partial of kMom values.  A second entry mode takes the
 //                   correspondences as given and skips the sweep (points_align); a third stops after the sweep (contact_nearest).
 //   icp_solve       one wave per pose: the block partials folded in block order in fp64, then one lane forms the centroids and
 //                   the covariance exactly as the reference does,
@@ -30,7 +30,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
@@ -202,11 +202,9 @@ __global__ __launch_bounds__(kThreads) void icp_nn_moments_kernel(IcpArgs a) {
             }
         }
     }
+    // NOT block4_sum's order: two waves, wave 0 + wave 1 - only the butterfly is the shared one
 #pragma unroll
-    for (int k = 0; k < kMom; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m[k] += __shfl_xor(m[k], o, 64);
-    }
+    for (int k = 0; k < kMom; ++k) m[k] = wave_sum(m[k]);
     if (t == 64) {
 #pragma unroll
         for (int k = 0; k < kMom; ++k) red[k] = m[k];
@@ -466,19 +464,14 @@ struct IcpLayout {
 
 IcpLayout icp_layout(int B, int n_o) {
     IcpLayout l;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    Carve c;
     l.nblk = (n_o + kStat - 1) / kStat;
-    l.part = take((size_t)B * l.nblk * kMom * 8);
-    l.xf = take((size_t)B * kXf * 8);
-    l.prev = take((size_t)B * 8);
-    l.done = take((size_t)B * 4);
-    l.d2 = take((size_t)B * n_o * 4);
-    l.total = off;
+    l.part = c.take((size_t)B * l.nblk * kMom * 8);
+    l.xf = c.take((size_t)B * kXf * 8);
+    l.prev = c.take((size_t)B * 8);
+    l.done = c.take((size_t)B * 4);
+    l.d2 = c.take((size_t)B * n_o * 4);
+    l.total = c.off;
     return l;
 }
 
@@ -508,16 +501,17 @@ int contact_icp(const float* x, const float* y, const float* xn, const float* yn
         return IVLM_ERR_INVALID_ARG;
     if (!sizes_ok(B, n_o, n_h)) return IVLM_ERR_UNSUPPORTED;
     const IcpLayout l = icp_layout(B, n_o);
-    if (ws_bytes < l.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
-    char* base = static_cast<char*>(ws);
+    if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
+    double* xf = ws_at<double>(ws, l.xf);
+    int32_t* done = ws_at<int32_t>(ws, l.done);
     IcpArgs a = {};
     a.x = x;
     a.xn = xn;
     a.y = y;
     a.yn = yn;
     a.w = w;
-    a.xf = reinterpret_cast<double*>(base + l.xf);
-    a.done = reinterpret_cast<int32_t*>(base + l.done);
+    a.xf = xf;
+    a.done = done;
     a.x_bs = x_bs;
     a.xn_bs = xn_bs;
     a.y_bs = y_bs;
@@ -530,8 +524,8 @@ int contact_icp(const float* x, const float* y, const float* xn, const float* yn
     a.n_h = n_h;
     a.nblk = l.nblk;
     a.nn_idx = nn_idx;
-    a.nn_d2 = reinterpret_cast<float*>(base + l.d2);
-    a.part = reinterpret_cast<double*>(base + l.part);
+    a.nn_d2 = ws_at<float>(ws, l.d2);
+    a.part = ws_at<double>(ws, l.part);
     SolveArgs sa = {};
     sa.part = a.part;
     sa.x = x;
@@ -542,9 +536,9 @@ int contact_icp(const float* x, const float* y, const float* xn, const float* yn
     sa.flags = flags;
     sa.B = B;
     sa.thr = (double)relative_rmse_thr;
-    sa.xf = reinterpret_cast<double*>(base + l.xf);
-    sa.prev = reinterpret_cast<double*>(base + l.prev);
-    sa.done = reinterpret_cast<int32_t*>(base + l.done);
+    sa.xf = xf;
+    sa.prev = ws_at<double>(ws, l.prev);
+    sa.done = done;
     sa.R = R;
     sa.T = T;
     sa.s = s;
@@ -571,8 +565,7 @@ int points_align(const float* X, const float* Y, const float* w, int B, int n, i
         return IVLM_ERR_INVALID_ARG;
     if (!sizes_ok(B, n, 1)) return IVLM_ERR_UNSUPPORTED;
     const IcpLayout l = icp_layout(B, n);
-    if (ws_bytes < l.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
-    char* base = static_cast<char*>(ws);
+    if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     IcpArgs a = {};
     a.x = X;
     a.yg = Y;
@@ -583,7 +576,7 @@ int points_align(const float* X, const float* Y, const float* w, int B, int n, i
     a.x_rs = 3;
     a.n_o = n;
     a.nblk = l.nblk;
-    a.part = reinterpret_cast<double*>(base + l.part);
+    a.part = ws_at<double>(ws, l.part);
     launch_nn(a, B, false, st);
     SolveArgs sa = {};
     sa.part = a.part;

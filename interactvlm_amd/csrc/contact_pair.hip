@@ -5,10 +5,10 @@
 //   dL/do_i = (p_i / S) sum_j q_j (o_i - h_j) / d_ij        dL/dh_j = (q_j / S) sum_i p_i (h_j - o_i) / d_ij
 //
 // Four launches, no atomics, every sum in a fixed order (the same bits every call):
-//   pair_compact   one block per side: the indices of the non-zero probabilities in order, their fp32 values and the fp64
-//                  sum of those.  Everything after it walks the COMPACTED lists only, so rows and columns of probability 0
-//                  cost nothing and change no bit of the result: tiling and summation order are functions of the non-zero
-//                  entries alone.
+//   pair_compact   one block per side: block_compact (fit_common.h) keeps the indices of the non-zero probabilities in order
+//                  and their fp32 values; then the fp64 sum of those.  Everything after it walks the COMPACTED lists only, so
+//                  rows and columns of probability 0 cost nothing and change no bit of the result: tiling and summation order
+//                  are functions of the non-zero entries alone.
 //   pair_sweep     the hot kernel.  A block keeps kStat "stationary" vertices in registers (kRows per thread) and sweeps one
 //                  tile of kTile vertices of the other side, staged as {x, y, z, weight} float4 in LDS and read by all lanes
 //                  at one address (a broadcast ds_read_b128: 4 LDS cycles per wave and entry, against ~60 VALU cycles).  The
@@ -18,8 +18,8 @@
 //                  kRows = 2, and a fitter that moves the object only (the reference's case) launches no human role at all.
 //                  Per (stationary vertex, tile) one float4 partial {gx, gy, gz, value} goes to the workspace.
 //   pair_fold      per stationary vertex: the tile partials summed in tile order in fp64, scaled by 1 / S, scattered to the
-//                  vertex's original index; per block of object vertices the fp64 sum of their value partials.
-//   pair_value     per pose: the block sums in a fixed order, divided by S.
+//                  vertex's original index; per block of object vertices the fp64 sum of their value partials (block4_sum).
+//   pair_value     per pose: the block sums by wave_fold, divided by S.
 //
 // Longest serial fp32 accumulation chain: the kTile = IVLM_CONTACT_PAIR_CHAIN terms one thread adds in the sweep.  The folds
 // after it are fp64 and round to fp32 once.  Outside the chain a term carries at most 8 roundings of 2^-24 (to first order):
@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
@@ -46,7 +46,7 @@ struct PairHeader {
     double sum[2];  // their sums
 };
 
-// workspace carve, shared by the size query and the launcher (offsets in bytes, 256-byte aligned)
+// workspace carve, shared by the size query and the launcher
 struct PairLayout {
     size_t hdr, idx[2], wt[2], part[2], blockval, total;
     int cb[2];  // tiles of side s when it is the swept side
@@ -57,23 +57,18 @@ struct PairLayout {
 PairLayout pair_layout(int B, int n_o, int n_h) {
     PairLayout l;
     const int n[2] = {n_o, n_h};
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    l.hdr = take(sizeof(PairHeader));
+    Carve c;
+    l.hdr = c.take(sizeof(PairHeader));
     for (int s = 0; s < 2; ++s) {
         l.cb[s] = (n[s] + kTile - 1) / kTile;
         l.sb[s] = (n[s] + kStat - 1) / kStat;
-        l.idx[s] = take((size_t)n[s] * 4);
-        l.wt[s] = take((size_t)n[s] * 4);
+        l.idx[s] = c.take((size_t)n[s] * 4);
+        l.wt[s] = c.take((size_t)n[s] * 4);
     }
-    for (int s = 0; s < 2; ++s) l.part[s] = take((size_t)B * l.cb[1 - s] * n[s] * 16);
+    for (int s = 0; s < 2; ++s) l.part[s] = c.take((size_t)B * l.cb[1 - s] * n[s] * 16);
     l.fb = (n_o + kFold - 1) / kFold;
-    l.blockval = take((size_t)B * l.fb * 8);
-    l.total = off;
+    l.blockval = c.take((size_t)B * l.fb * 8);
+    l.total = c.off;
     return l;
 }
 
@@ -95,37 +90,21 @@ __global__ __launch_bounds__(1024) void pair_compact_kernel(const void* __restri
     const int n = side ? n_h : n_o;
     int32_t* idx = side ? idx_h : idx_o;
     float* wt = side ? wt_h : wt_o;
-    const int seg = (n + 1023) / 1024;
-    const int i0 = min(t * seg, n), i1 = min(i0 + seg, n);
-    int c = 0;
-    for (int i = i0; i < i1; ++i) c += load_prob<BF16>(w, i) != 0.0f;
-    cnt[t] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // inclusive scan
-        const int v = t >= off ? cnt[t - off] : 0;
-        __syncthreads();
-        cnt[t] += v;
-        __syncthreads();
-    }
-    int k = cnt[t] - c;
-    const int m = cnt[1023];
-    for (int i = i0; i < i1; ++i) {
-        const float v = load_prob<BF16>(w, i);
-        if (v != 0.0f) {
+    const int m = block_compact(
+        n, cnt, [&](int i) { return load_prob<BF16>(w, i) != 0.0f; },
+        [&](int k, int i) {
             idx[k] = i;
-            wt[k] = v;
-            ++k;
-        }
-    }
+            wt[k] = load_prob<BF16>(w, i);
+        });
     __syncthreads();
     // the sum walks the compacted list, so that it is a function of the non-zero entries alone
     double s = 0.0;
     for (int j = t; j < m; j += 1024) s += (double)wt[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     if ((t & 63) == 0) red[t >> 6] = s;
     __syncthreads();
     if (t == 0) {
+        // NOT block4_sum's order: 16 waves, added one after the other from 0.0 - only the butterfly is the shared one
         double a = 0.0;
         for (int v = 0; v < 16; ++v) a += red[v];
         hdr->m[side] = m;
@@ -218,7 +197,8 @@ __global__ __launch_bounds__(kThreads) void pair_sweep_kernel(PairArgs a) {
 // them: human vertices (launched only with grad_h).  Gradients of zero-probability vertices were zeroed by the launcher.
 __global__ __launch_bounds__(kFold) void pair_fold_kernel(PairArgs a, int fb_o, float* __restrict__ grad_o, float* __restrict__ grad_h,
                                                           double* __restrict__ blockval) {
-    __shared__ double red[kFold / 64];
+    __shared__ double red[4][1];
+    static_assert(kFold == 256, "block4_sum: four waves");
     const int b = blockIdx.y, t = threadIdx.x;
     const int S = (int)blockIdx.x >= fb_o, W = 1 - S;
     const int k = ((int)blockIdx.x - (S ? fb_o : 0)) * kFold + t;
@@ -243,25 +223,20 @@ __global__ __launch_bounds__(kFold) void pair_fold_kernel(PairArgs a, int fb_o, 
         }
     }
     if (S == 0) {  // block-uniform
-        double s = g[3];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if ((t & 63) == 0) red[t >> 6] = s;
-        __syncthreads();
-        if (t == 0) blockval[(int64_t)b * fb_o + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        double s[1] = {g[3]};
+        block4_sum(s, red);
+        if (t == 0) blockval[(int64_t)b * fb_o + blockIdx.x] = s[0];
     }
 }
 
-// one wave per pose: the block sums of the compacted object vertices in a fixed order
+// one wave per pose: the block sums of the compacted object vertices
 __global__ __launch_bounds__(64) void pair_value_kernel(const PairHeader* __restrict__ hdr, const double* __restrict__ blockval, int fb_o,
                                                         float* __restrict__ value) {
     const int b = blockIdx.x;
     const int nb = (hdr->m[0] + kFold - 1) / kFold;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < nb; j += 64) s += blockval[(int64_t)b * fb_o + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (threadIdx.x == 0) value[b] = (float)(s / (hdr->sum[0] * hdr->sum[1]));
+    double s[1];
+    wave_fold(blockval + (int64_t)b * fb_o, nb, s);
+    if (threadIdx.x == 0) value[b] = (float)(s[0] / (hdr->sum[0] * hdr->sum[1]));
 }
 
 }  // namespace
@@ -278,41 +253,38 @@ int contact_pair(const float* o, const float* h, const void* p, const void* q, i
         return IVLM_ERR_INVALID_ARG;
     if ((p_dtype != IVLM_F32 && p_dtype != IVLM_BF16) || n_o > kMaxN || n_h > kMaxN || B > 65535) return IVLM_ERR_UNSUPPORTED;
     const PairLayout l = pair_layout(B, n_o, n_h);
-    if (ws_bytes < l.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
-    char* base = static_cast<char*>(ws);
+    if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
+    PairHeader* hdr = ws_at<PairHeader>(ws, l.hdr);
+    int32_t* idx[2] = {ws_at<int32_t>(ws, l.idx[0]), ws_at<int32_t>(ws, l.idx[1])};
+    float* wt[2] = {ws_at<float>(ws, l.wt[0]), ws_at<float>(ws, l.wt[1])};
+    double* blockval = ws_at<double>(ws, l.blockval);
     PairArgs a;
     a.verts[0] = o;
     a.verts[1] = h;
     a.bstride[0] = o_bstride;
     a.bstride[1] = h_bstride;
-    a.hdr = reinterpret_cast<PairHeader*>(base + l.hdr);
+    a.hdr = hdr;
     a.n[0] = n_o;
     a.n[1] = n_h;
     for (int s = 0; s < 2; ++s) {
-        a.idx[s] = reinterpret_cast<int32_t*>(base + l.idx[s]);
-        a.wt[s] = reinterpret_cast<float*>(base + l.wt[s]);
-        a.part[s] = reinterpret_cast<float4*>(base + l.part[s]);
+        a.idx[s] = idx[s];
+        a.wt[s] = wt[s];
+        a.part[s] = ws_at<float4>(ws, l.part[s]);
         a.cb[s] = l.cb[s];
         a.sb[s] = l.sb[s];
     }
     a.role_blocks0 = l.sb[0] * l.cb[1];
     a.grad_o = grad_o != nullptr;
     const int role_blocks1 = grad_h ? l.sb[1] * l.cb[0] : 0;
-    double* blockval = reinterpret_cast<double*>(base + l.blockval);
-    PairHeader* hdr = reinterpret_cast<PairHeader*>(base + l.hdr);
-    int32_t* idx_o = reinterpret_cast<int32_t*>(base + l.idx[0]);
-    int32_t* idx_h = reinterpret_cast<int32_t*>(base + l.idx[1]);
-    float* wt_o = reinterpret_cast<float*>(base + l.wt[0]);
-    float* wt_h = reinterpret_cast<float*>(base + l.wt[1]);
 
     if (grad_o) IVLM_HIP_TRY(hipMemsetAsync(grad_o, 0, (size_t)B * n_o * 12, st));
     if (grad_h) IVLM_HIP_TRY(hipMemsetAsync(grad_h, 0, (size_t)B * n_h * 12, st));
-    if (p_dtype == IVLM_BF16) pair_compact_kernel<true><<<2, 1024, 0, st>>>(p, q, n_o, n_h, hdr, idx_o, wt_o, idx_h, wt_h);
-    else pair_compact_kernel<false><<<2, 1024, 0, st>>>(p, q, n_o, n_h, hdr, idx_o, wt_o, idx_h, wt_h);
+    if (p_dtype == IVLM_BF16) pair_compact_kernel<true><<<2, 1024, 0, st>>>(p, q, n_o, n_h, hdr, idx[0], wt[0], idx[1], wt[1]);
+    else pair_compact_kernel<false><<<2, 1024, 0, st>>>(p, q, n_o, n_h, hdr, idx[0], wt[0], idx[1], wt[1]);
     pair_sweep_kernel<<<dim3(a.role_blocks0 + role_blocks1, B), kThreads, 0, st>>>(a);
     const int fb_h = grad_h ? (n_h + kFold - 1) / kFold : 0;
     pair_fold_kernel<<<dim3(l.fb + fb_h, B), kFold, 0, st>>>(a, l.fb, grad_o, grad_h, blockval);
-    pair_value_kernel<<<B, 64, 0, st>>>(a.hdr, blockval, l.fb, value);
+    pair_value_kernel<<<B, 64, 0, st>>>(hdr, blockval, l.fb, value);
     return ivlm_launch_status();
 }
 

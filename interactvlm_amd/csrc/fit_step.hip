@@ -26,15 +26,13 @@
 #include <cmath>
 #include <cstdint>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kParams = 10;  // elements per start: rot6d 6, translation 3, scale 1
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __global__ __launch_bounds__(kThreads) void fit_offset_kernel(const float* __restrict__ moved, const float* __restrict__ off, int64_t total,
                                                               float* __restrict__ out) {
@@ -146,25 +144,20 @@ FitLayout fit_layout(int B, int N, int F, int H, int W, int N_h) {
     if (!l.pose_bytes || !l.sil_bytes || !l.pair_bytes) return l;
     l.terms_bytes = IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H);
     const size_t verts = (size_t)B * N * 3 * sizeof(float), image = (size_t)B * H * W * sizeof(float);
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += align256(bytes);
-        return here;
-    };
-    l.pose = take(l.pose_bytes);
-    l.sil = take(l.sil_bytes);
-    l.terms = take(l.terms_bytes);
-    l.pair = take(l.pair_bytes);
-    l.moved = take(verts);
-    l.moved_off = take(verts);
-    l.alpha = take(image);
-    l.galpha = take(image);
-    l.g_sil = take(verts);
-    l.g_pair = take(verts);
-    l.sums = take((size_t)B * 5 * sizeof(double));
-    l.small = take((size_t)B * 7 * sizeof(float));  // loss 1, centroid 2, contact 1, g_loss 1, g_centroid 2
-    l.total = at;
+    Carve c;
+    l.pose = c.take(l.pose_bytes);
+    l.sil = c.take(l.sil_bytes);
+    l.terms = c.take(l.terms_bytes);
+    l.pair = c.take(l.pair_bytes);
+    l.moved = c.take(verts);
+    l.moved_off = c.take(verts);
+    l.alpha = c.take(image);
+    l.galpha = c.take(image);
+    l.g_sil = c.take(verts);
+    l.g_pair = c.take(verts);
+    l.sums = c.take((size_t)B * 5 * sizeof(double));
+    l.small = c.take((size_t)B * 7 * sizeof(float));  // loss 1, centroid 2, contact 1, g_loss 1, g_centroid 2
+    l.total = c.off;
     return l;
 }
 
@@ -207,17 +200,17 @@ int fit_step(const IvlmFitStepArgs& x, hipStream_t st) {
         return IVLM_ERR_UNSUPPORTED;
     const FitLayout l = fit_layout(B, N, F, H, W, N_h);
     if (!l.total) return IVLM_ERR_UNSUPPORTED;
-    if (x.workspace_bytes < l.total || (reinterpret_cast<uintptr_t>(x.workspace) & 255)) return IVLM_ERR_WORKSPACE;
+    void* ws = x.workspace;
+    if (!workspace_ok(ws, x.workspace_bytes, l.total, 256)) return IVLM_ERR_WORKSPACE;
 
-    char* base = static_cast<char*>(x.workspace);
-    float* moved = reinterpret_cast<float*>(base + l.moved);
-    float* moved_off = reinterpret_cast<float*>(base + l.moved_off);
-    float* alpha = reinterpret_cast<float*>(base + l.alpha);
-    float* galpha = reinterpret_cast<float*>(base + l.galpha);
-    float* g_sil = reinterpret_cast<float*>(base + l.g_sil);
-    float* g_pair = reinterpret_cast<float*>(base + l.g_pair);
-    double* sums = reinterpret_cast<double*>(base + l.sums);
-    float* loss = reinterpret_cast<float*>(base + l.small);
+    float* moved = ws_at<float>(ws, l.moved);
+    float* moved_off = ws_at<float>(ws, l.moved_off);
+    float* alpha = ws_at<float>(ws, l.alpha);
+    float* galpha = ws_at<float>(ws, l.galpha);
+    float* g_sil = ws_at<float>(ws, l.g_sil);
+    float* g_pair = ws_at<float>(ws, l.g_pair);
+    double* sums = ws_at<double>(ws, l.sums);
+    float* loss = ws_at<float>(ws, l.small);
     float* centroid = loss + B;
     float* value = loss + 3 * (size_t)B;
     float* g_loss = loss + 4 * (size_t)B;
@@ -237,13 +230,13 @@ int fit_step(const IvlmFitStepArgs& x, hipStream_t st) {
         fit_offset_kernel<<<vblocks, kThreads, 0, st>>>(moved, x.centroid_offset, nv, moved_off);
         FIT_TRY(ivlm_launch_status());
         FIT_TRY(soft_silhouette_forward(moved_off, x.faces, B, N, F, H, W, x.fx, x.fy, x.px, x.py, x.sigma, x.blur_radius, alpha,
-                                        base + l.sil, l.sil_bytes, st));
-        FIT_TRY(silhouette_terms(alpha, x.target, 0, B, H, W, loss, centroid, sums, nullptr, nullptr, nullptr, base + l.terms,
+                                        ws_at<char>(ws, l.sil), l.sil_bytes, st));
+        FIT_TRY(silhouette_terms(alpha, x.target, 0, B, H, W, loss, centroid, sums, nullptr, nullptr, nullptr, ws_at<char>(ws, l.terms),
                                  l.terms_bytes, st));
     }
     if (contact)
         FIT_TRY(contact_pair(moved, x.human_verts, x.obj_probs, x.human_probs, x.p_dtype, B, N, N_h, (int64_t)N * 3, 0, value, g_pair,
-                             nullptr, base + l.pair, l.pair_bytes, st));
+                             nullptr, ws_at<char>(ws, l.pair), l.pair_bytes, st));
     fit_combine_kernel<<<(B + kThreads - 1) / kThreads, kThreads, 0, st>>>(loss, centroid, value, x.target_centroid, x.w_mask,
                                                                            x.w_centroid, x.w_contact, on, B, x.max_iter, x.step,
                                                                            x.history, x.term_history, g_loss, g_centroid);
@@ -251,7 +244,7 @@ int fit_step(const IvlmFitStepArgs& x, hipStream_t st) {
     if (image) {
         FIT_TRY(silhouette_terms(nullptr, x.target, 0, B, H, W, nullptr, nullptr, sums, g_loss, g_centroid, galpha, nullptr, 0, st));
         FIT_TRY(soft_silhouette_backward(moved_off, x.vert_face_offsets, x.vert_face_list, galpha, B, N, F, H, W, x.fx, x.fy, x.px,
-                                         x.py, x.sigma, x.blur_radius, g_sil, base + l.sil, l.sil_bytes, st));
+                                         x.py, x.sigma, x.blur_radius, g_sil, ws_at<char>(ws, l.sil), l.sil_bytes, st));
     }
     const float* g = g_sil;
     if (contact) {
@@ -260,7 +253,7 @@ int fit_step(const IvlmFitStepArgs& x, hipStream_t st) {
         g = g_pair;
     }
     FIT_TRY(pose_transform_backward(x.obj_verts, x.rotation, x.scale, g, B, N, pose ? x.grad_rotation : nullptr,
-                                    pose ? x.grad_translation : nullptr, scale ? x.grad_scale : nullptr, base + l.pose, l.pose_bytes,
+                                    pose ? x.grad_translation : nullptr, scale ? x.grad_scale : nullptr, ws_at<char>(ws, l.pose), l.pose_bytes,
                                     st));
     a.p[0] = x.rotation, a.p[1] = x.translation, a.p[2] = x.scale;
     a.m[0] = x.m_rotation, a.m[1] = x.m_translation, a.m[2] = x.m_scale;

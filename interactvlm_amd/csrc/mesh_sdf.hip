@@ -18,11 +18,11 @@
 //                  (point, chunk) it writes {q = c - x, |q|^2} , the face and the fp32 sum of atan2 over the chunk.
 //   sdf_query_fold per point: the chunk partials in chunk order - strict '<' keeps the lower face on equal d^2, the winding sum
 //                  in fp64 - and the four outputs.
-//   penetration    sdf_compact<0>: the points inside the bounding box, in index order, per pose;  sdf_sweep<1,0> over them;
-//                  sdf_compact<1>: folds their winding sums and keeps the inside ones;  sdf_sweep<0,1> over those;
-//                  sdf_pen_fold: the gradient rows and the fp64 sum of d^2 per block of 256;  sdf_pen_value: the block sums in
-//                  order, / N, rounded once.  The gradient is zeroed first, so every other row is an exact 0; a pose with no
-//                  point in the box runs no sweep (all its blocks leave at once).
+//   penetration    sdf_compact<0>: the points inside the bounding box, in index order, per pose (block_compact of fit_common.h);
+//                  sdf_sweep<1,0> over them;  sdf_compact<1>: folds their winding sums and keeps the inside ones;  sdf_sweep<0,1>
+//                  over those;  sdf_pen_fold: the gradient rows and the fp64 sum of d^2 per block of 256 (block4_sum);
+//                  sdf_pen_value: the block sums by wave_fold, / N, rounded once.  The gradient is zeroed first, so every other
+//                  row is an exact 0; a pose with no point in the box runs no sweep (all its blocks leave at once).
 //
 // The query and penetration calls are not told F: it lives in the plan, on the device.  The host derives from workspace_bytes
 // how many chunks the workspace holds (Cw), sizes the grid by it and lays the partials out by it; the kernels read the plan's
@@ -35,7 +35,7 @@
 #include <cfloat>
 #include <cmath>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
@@ -56,7 +56,7 @@ struct SdfHeader {  // 256 bytes at the head of the plan
 };
 static_assert(sizeof(SdfHeader) == 256, "plan header");
 
-// workspace carve for a capacity of C chunks (offsets in bytes, 256-byte aligned)
+// workspace carve for a capacity of C chunks
 struct SdfLayout {
     size_t cnt, list[2], blockval, p4, pf, pw, total;
     int nb;  // fold blocks per pose
@@ -64,21 +64,16 @@ struct SdfLayout {
 
 SdfLayout sdf_layout(int B, int N, int C) {
     SdfLayout l;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    Carve c;
     l.nb = (N + kFold - 1) / kFold;
-    l.cnt = take((size_t)2 * B * 4);
-    l.list[0] = take((size_t)B * N * 4);
-    l.list[1] = take((size_t)B * N * 4);
-    l.blockval = take((size_t)B * l.nb * 8);
-    l.p4 = take((size_t)C * B * N * 16);
-    l.pf = take((size_t)C * B * N * 4);
-    l.pw = take((size_t)C * B * N * 4);
-    l.total = off;
+    l.cnt = c.take((size_t)2 * B * 4);
+    l.list[0] = c.take((size_t)B * N * 4);
+    l.list[1] = c.take((size_t)B * N * 4);
+    l.blockval = c.take((size_t)B * l.nb * 8);
+    l.p4 = c.take((size_t)C * B * N * 16);
+    l.pf = c.take((size_t)C * B * N * 4);
+    l.pw = c.take((size_t)C * B * N * 4);
+    l.total = c.off;
     return l;
 }
 
@@ -321,40 +316,28 @@ __global__ __launch_bounds__(1024) void sdf_compact_kernel(SweepArgs s, const in
             return fold_winding(s, C, b, k) > 0.5f;
         }
     };
-    const int seg = (n + 1023) / 1024;
-    const int k0 = min(t * seg, n), k1 = min(k0 + seg, n);
-    int c = 0;
-    for (int k = k0; k < k1; ++k) c += keep(k) ? 1 : 0;
-    cnt[t] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {  // inclusive scan
-        const int v = t >= off ? cnt[t - off] : 0;
-        __syncthreads();
-        cnt[t] += v;
-        __syncthreads();
-    }
-    int at = cnt[t] - c;
-    for (int k = k0; k < k1; ++k) {
-        if (keep(k)) out_list[(int64_t)b * s.N + at++] = MODE == 0 ? k : in_list[(int64_t)b * s.N + k];
-    }
-    if (t == 1023) out_count[b] = cnt[1023];
+    const int m = block_compact(n, cnt, keep, [&](int at, int k) {
+        out_list[(int64_t)b * s.N + at] = MODE == 0 ? k : in_list[(int64_t)b * s.N + k];
+    });
+    if (t == 1023) out_count[b] = m;
 }
 
 // per inside point (list 1): the gradient row, and per block the fp64 sum of d^2
 __global__ __launch_bounds__(kFold) void sdf_pen_fold_kernel(SweepArgs s, float* __restrict__ grad, double* __restrict__ blockval, int nb) {
-    __shared__ double red[kFold / 64];
+    __shared__ double red[4][1];
+    static_assert(kFold == 256, "block4_sum: four waves");
     const int b = blockIdx.y, t = threadIdx.x, k = blockIdx.x * kFold + t;
     const int C = s.hdr->n_chunks;
     if (C > s.Cw) return;
     const int m = s.count[b];
     if ((int)blockIdx.x * kFold >= m) return;  // block-uniform
-    double d2 = 0.0;
+    double d2[1] = {0.0};
     if (k < m) {
         float4 q;
         int fc;
         fold_closest(s, C, b, k, q, fc);
         if (fc >= 0) {
-            d2 = (double)q.w;
+            d2[0] = (double)q.w;
             if (grad) {
                 const float sc = 2.0f / (float)s.N;
                 float* g = grad + ((int64_t)b * s.N + s.list[(int64_t)b * s.N + k]) * 3;
@@ -364,14 +347,11 @@ __global__ __launch_bounds__(kFold) void sdf_pen_fold_kernel(SweepArgs s, float*
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d2 += __shfl_xor(d2, o, 64);
-    if ((t & 63) == 0) red[t >> 6] = d2;
-    __syncthreads();
-    if (t == 0) blockval[(int64_t)b * nb + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    block4_sum(d2, red);
+    if (t == 0) blockval[(int64_t)b * nb + blockIdx.x] = d2[0];
 }
 
-// one wave per pose: the block sums in a fixed order, / N, rounded once
+// one wave per pose: the block sums, / N, rounded once
 __global__ __launch_bounds__(64) void sdf_pen_value_kernel(SweepArgs s, const double* __restrict__ blockval, int nb, float* __restrict__ value) {
     const int b = blockIdx.x;
     if (s.hdr->n_chunks > s.Cw) {
@@ -379,11 +359,9 @@ __global__ __launch_bounds__(64) void sdf_pen_value_kernel(SweepArgs s, const do
         return;
     }
     const int used = (s.count[b] + kFold - 1) / kFold;
-    double v = 0.0;
-    for (int j = threadIdx.x; j < used; j += 64) v += blockval[(int64_t)b * nb + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (threadIdx.x == 0) value[b] = (float)(v / (double)s.N);
+    double v[1];
+    wave_fold(blockval + (int64_t)b * nb, used, v);
+    if (threadIdx.x == 0) value[b] = (float)(v[0] / (double)s.N);
 }
 
 bool sizes_ok(int B, int N) { return B > 0 && N > 0 && B <= 65535 && N <= kMaxN; }
@@ -423,19 +401,18 @@ SweepArgs sweep_args(const void* plan, const float* points, int B, int N, void* 
         *rc = IVLM_ERR_UNSUPPORTED;
         return s;
     }
-    const int Cw = sdf_capacity(B, N, ws_bytes);
-    if (Cw < 1 || (reinterpret_cast<uintptr_t>(ws) & 15)) {
+    if (!workspace_ok(ws, ws_bytes, sdf_layout(B, N, 1).total, 16)) {  // not even one chunk
         *rc = IVLM_ERR_WORKSPACE;
         return s;
     }
+    const int Cw = sdf_capacity(B, N, ws_bytes);
     *l = sdf_layout(B, N, Cw);
-    char* base = static_cast<char*>(ws);
     s.hdr = static_cast<const SdfHeader*>(plan);
     s.rec = reinterpret_cast<const float4*>(s.hdr + 1);
     s.points = points;
-    s.p4 = reinterpret_cast<float4*>(base + l->p4);
-    s.pf = reinterpret_cast<int32_t*>(base + l->pf);
-    s.pw = reinterpret_cast<float*>(base + l->pw);
+    s.p4 = ws_at<float4>(ws, l->p4);
+    s.pf = ws_at<int32_t>(ws, l->pf);
+    s.pw = ws_at<float>(ws, l->pw);
     s.N = N;
     s.Cw = Cw;
     return s;
@@ -461,11 +438,10 @@ int mesh_sdf_penetration(const void* plan, const float* points, int B, int N, fl
     int rc;
     SweepArgs s = sweep_args(plan, points, B, N, ws, ws_bytes, &l, &rc);
     if (rc != IVLM_OK) return rc;
-    char* base = static_cast<char*>(ws);
-    int32_t* cnt = reinterpret_cast<int32_t*>(base + l.cnt);
-    int32_t* list0 = reinterpret_cast<int32_t*>(base + l.list[0]);
-    int32_t* list1 = reinterpret_cast<int32_t*>(base + l.list[1]);
-    double* blockval = reinterpret_cast<double*>(base + l.blockval);
+    int32_t* cnt = ws_at<int32_t>(ws, l.cnt);
+    int32_t* list0 = ws_at<int32_t>(ws, l.list[0]);
+    int32_t* list1 = ws_at<int32_t>(ws, l.list[1]);
+    double* blockval = ws_at<double>(ws, l.blockval);
     const dim3 grid((N + kWave - 1) / kWave, s.Cw, B);
     if (grad) IVLM_HIP_TRY(hipMemsetAsync(grad, 0, (size_t)B * N * 12, st));
     sdf_compact_kernel<0><<<B, 1024, 0, st>>>(s, nullptr, nullptr, list0, cnt);

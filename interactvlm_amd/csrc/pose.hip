@@ -11,14 +11,14 @@
 //   pose_partial   grid (vertex chunk, pose), IVLM_POSE_CHUNK vertices per block.  The backward's reduction does not depend on the
 //                  pose: per (chunk, pose) the twelve sums G = sum_n v_n^T g_n (3 x 3) and sum_n g_n.  Every product v_i g_j of two
 //                  floats is exact in fp64 and is added in fp64 from the first term (the fp32 chain is IVLM_POSE_CHAIN = 1): per
-//                  lane its kPerThread vertices in ascending order, then the 64 lanes by xor folds (32, 16, .. 1), then the waves
-//                  in order.  A vertex past N adds exact zeros.
+//                  lane its kPerThread vertices in ascending order, then the 64 lanes by wave_sum, then the waves in order.  A
+//                  vertex past N adds exact zeros.
 //   pose_finish    one wave per pose: lanes 0..11 add the partials of one sum each in ascending chunk order; lane 0 chains
 //                  dL/dR = s G through the Gram-Schmidt analytically, all in fp64, and rounds each result to fp32 once.
 //                  dL/dt = sum g;  dL/ds = sum_ij R_ij G_ij.
 #include <cstdint>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
@@ -133,15 +133,13 @@ __global__ __launch_bounds__(kThreads) void pose_partial_kernel(const float* __r
         }
     }
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
-    }
+    for (int k = 0; k < 12; ++k) acc[k] = wave_sum(acc[k]);
     if ((t & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) red[t >> 6][k] = acc[k];
     }
     __syncthreads();
+    // NOT block4_sum's order: the waves are added one after the other, ((w0 + w1) + w2) + w3 - only the butterfly is the shared one
     if (t < 12) {
         double s = red[0][t];
 #pragma unroll
@@ -219,7 +217,9 @@ inline bool pose_sizes_ok(int B, int N) { return B > 0 && N > 0 && B <= 65535 &&
 size_t pose_transform_workspace_bytes(int B, int N) {
     if (!pose_sizes_ok(B, N)) return 0;
     const size_t chunks = (size_t)(N + kChunk - 1) / kChunk;
-    return (((size_t)B * chunks * 12 * sizeof(double)) + 255) & ~(size_t)255;
+    Carve c;
+    c.take((size_t)B * chunks * 12 * sizeof(double));
+    return c.off;
 }
 
 int pose_transform_forward(const float* verts, const float* rot6d, const float* trans, const float* scale, int B, int N, float* out,
@@ -236,7 +236,7 @@ int pose_transform_backward(const float* verts, const float* rot6d, const float*
     if (!verts || !rot6d || !scale || !grad_out || !ws || B <= 0 || N <= 0 || (!grad_r6 && !grad_t && !grad_s))
         return IVLM_ERR_INVALID_ARG;
     if (!pose_sizes_ok(B, N)) return IVLM_ERR_UNSUPPORTED;
-    if (ws_bytes < pose_transform_workspace_bytes(B, N) || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
+    if (!workspace_ok(ws, ws_bytes, pose_transform_workspace_bytes(B, N), 16)) return IVLM_ERR_WORKSPACE;
     const int chunks = (N + kChunk - 1) / kChunk;
     double* part = static_cast<double*>(ws);
     pose_partial_kernel<<<dim3(chunks, B), kThreads, 0, st>>>(verts, grad_out, N, part);

@@ -26,17 +26,17 @@
 //   sil_backward  face-stationary (the two-roles-instead-of-atomics choice of contact_pair.hip): one wave per face walks the pixels
 //                 of its grown box 64 at a time, reads g_alpha (1 - alpha), recomputes p_k and the distance's derivative and
 //                 accumulates the six screen-space vertex gradients: IVLM_SILHOUETTE_CHAIN fp32 additions per lane, then fp64,
-//                 a fixed fp64 butterfly across the lanes, one [3, 2] fp32 record per face.  A box of very many pixels (one huge
+//                 wave_sum's fp64 butterfly across the lanes, one [3, 2] fp32 record per face.  A box of very many pixels (one huge
 //                 triangle) is walked by that one wave: correct, and its latency is accepted.
 //   sil_gather    per vertex: the records of its incident faces in ascending face order (incidence lists are inputs, built once per
 //                 topology by the caller), summed in fp64, chained through the projection to dL/d(X, Y, Z).
-//   terms_rows / terms_final / terms_grad   one fp64 reduction of (sum alpha, sum alpha t, sum t, sum i alpha, sum j alpha) per pose,
-//                 mask_loss = 1 - sum(alpha t) / (sum alpha + sum t), centroid = (sum i alpha, sum j alpha) / sum alpha, and their
-//                 analytic d / d alpha image.
+//   terms_rows / terms_final / terms_grad   one fp64 reduction of (sum alpha, sum alpha t, sum t, sum i alpha, sum j alpha) per pose
+//                 (per row block4_sum, then the rows by wave_fold: fit_common.h), mask_loss = 1 - sum(alpha t) / (sum alpha + sum t),
+//                 centroid = (sum i alpha, sum j alpha) / sum alpha, and their analytic d / d alpha image.
 #include <algorithm>
 #include <cmath>
 
-#include "kernels.h"
+#include "fit_common.h"
 
 namespace ivlm {
 namespace {
@@ -79,26 +79,21 @@ SilParams sil_params(int N, int F, int H, int W, float fx, float fy, float px, f
     return p;
 }
 
-// workspace carve, shared by the size query and both launchers (offsets in bytes, 256-byte aligned)
+// workspace carve, shared by the size query and both launchers
 struct SilLayout {
     size_t uv, tri, box, uni, oma, frec, total;
 };
 
 SilLayout sil_layout(int B, int N, int F, int H, int W) {
     SilLayout l;
-    size_t off = 0;
-    auto take = [&off](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    l.uv = take((size_t)B * N * 8);
-    l.tri = take((size_t)B * F * 32);
-    l.box = take((size_t)B * F * 16);
-    l.uni = take((size_t)B * 16);
-    l.oma = take((size_t)B * H * W * 4);
-    l.frec = take((size_t)B * F * 24);
-    l.total = off;
+    Carve c;
+    l.uv = c.take((size_t)B * N * 8);
+    l.tri = c.take((size_t)B * F * 32);
+    l.box = c.take((size_t)B * F * 16);
+    l.uni = c.take((size_t)B * 16);
+    l.oma = c.take((size_t)B * H * W * 4);
+    l.frec = c.take((size_t)B * F * 24);
+    l.total = c.off;
     return l;
 }
 
@@ -260,12 +255,6 @@ __global__ __launch_bounds__(kChunk) void sil_forward_kernel(const float4* __res
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void sil_backward_kernel(const float4* __restrict__ tri, const int4* __restrict__ box,
                                                            const float* __restrict__ oma, const float* __restrict__ galpha,
                                                            float* __restrict__ frec, SilParams p) {
@@ -357,37 +346,23 @@ __global__ __launch_bounds__(256) void terms_rows_kernel(const float* __restrict
         s[2] += tv;
         s[3] += av * (double)j;
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = wave_sum(s[k]);
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) red[t >> 6][k] = s[k];
-    }
-    __syncthreads();
+    block4_sum(s, red);
     if (t == 0) {
-        double r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
         double* out = rowsum + ((int64_t)b * H + i) * 5;
-        out[0] = r[0];
-        out[1] = r[1];
-        out[2] = r[2];
-        out[3] = r[0] * (double)i;
-        out[4] = r[3];
+        out[0] = s[0];
+        out[1] = s[1];
+        out[2] = s[2];
+        out[3] = s[0] * (double)i;
+        out[4] = s[3];
     }
 }
 
-// one wave per pose: the rows in a fixed order -> sums f64 [5], mask_loss, centroid (row, col)
+// one wave per pose: the rows by wave_fold -> sums f64 [5], mask_loss, centroid (row, col)
 __global__ __launch_bounds__(64) void terms_final_kernel(const double* __restrict__ rowsum, double* __restrict__ sums,
                                                          float* __restrict__ loss, float* __restrict__ centroid, int H, int W) {
     const int b = blockIdx.x;
-    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < H; i += 64) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) s[k] += rowsum[((int64_t)b * H + i) * 5 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) s[k] = wave_sum(s[k]);
+    double s[5];
+    wave_fold(rowsum + (int64_t)b * H * 5, H, s);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) sums[(int64_t)b * 5 + k] = s[k];
@@ -432,14 +407,13 @@ int soft_silhouette_forward(const float* verts, const int32_t* faces, int B, int
     if (!verts || !faces || !alpha || !ws) return IVLM_ERR_INVALID_ARG;
     if (!sil_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
     const SilLayout l = sil_layout(B, N, F, H, W);
-    if (ws_bytes < l.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
+    if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     const SilParams p = sil_params(N, F, H, W, fx, fy, px, py, sigma, blur);
-    char* base = static_cast<char*>(ws);
-    float2* uv = reinterpret_cast<float2*>(base + l.uv);
-    float4* tri = reinterpret_cast<float4*>(base + l.tri);
-    int4* box = reinterpret_cast<int4*>(base + l.box);
-    int4* uni = reinterpret_cast<int4*>(base + l.uni);
-    float* oma = reinterpret_cast<float*>(base + l.oma);
+    float2* uv = ws_at<float2>(ws, l.uv);
+    float4* tri = ws_at<float4>(ws, l.tri);
+    int4* box = ws_at<int4>(ws, l.box);
+    int4* uni = ws_at<int4>(ws, l.uni);
+    float* oma = ws_at<float>(ws, l.oma);
     sil_project_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, uv, uni, p);
     sil_faces_kernel<<<dim3((F + 255) / 256, B), 256, 0, st>>>(verts, faces, uv, tri, box, uni, p);
     sil_forward_kernel<<<dim3((W + kTile - 1) / kTile, (H + kTile - 1) / kTile, B), kChunk, 0, st>>>(tri, box, uni, alpha, oma, p);
@@ -452,13 +426,12 @@ int soft_silhouette_backward(const float* verts, const int32_t* vf_off, const in
     if (!verts || !vf_off || !vf_list || !galpha || !gverts || !ws) return IVLM_ERR_INVALID_ARG;
     if (!sil_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
     const SilLayout l = sil_layout(B, N, F, H, W);
-    if (ws_bytes < l.total || (reinterpret_cast<uintptr_t>(ws) & 15)) return IVLM_ERR_WORKSPACE;
+    if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     const SilParams p = sil_params(N, F, H, W, fx, fy, px, py, sigma, blur);
-    char* base = static_cast<char*>(ws);
-    const float4* tri = reinterpret_cast<const float4*>(base + l.tri);
-    const int4* box = reinterpret_cast<const int4*>(base + l.box);
-    const float* oma = reinterpret_cast<const float*>(base + l.oma);
-    float* frec = reinterpret_cast<float*>(base + l.frec);
+    const float4* tri = ws_at<float4>(ws, l.tri);
+    const int4* box = ws_at<int4>(ws, l.box);
+    const float* oma = ws_at<float>(ws, l.oma);
+    float* frec = ws_at<float>(ws, l.frec);
     sil_backward_kernel<<<dim3((F + 3) / 4, B), 256, 0, st>>>(tri, box, oma, galpha, frec, p);
     sil_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, frec, vf_off, vf_list, gverts, p);
     return ivlm_launch_status();
@@ -475,7 +448,7 @@ int silhouette_terms(const float* alpha, const float* target, int64_t t_bstride,
         return ivlm_launch_status();
     }
     if (!alpha || !loss || !centroid || !ws) return IVLM_ERR_INVALID_ARG;
-    if (ws_bytes < IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H) || (reinterpret_cast<uintptr_t>(ws) & 7)) return IVLM_ERR_WORKSPACE;
+    if (!workspace_ok(ws, ws_bytes, IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H), 8)) return IVLM_ERR_WORKSPACE;
     double* rowsum = static_cast<double*>(ws);
     terms_rows_kernel<<<dim3(H, B), 256, 0, st>>>(alpha, target, t_bstride, rowsum, H, W);
     terms_final_kernel<<<B, 64, 0, st>>>(rowsum, sums, loss, centroid, H, W);

@@ -280,21 +280,19 @@ class DevicePoseFit:
         B, N, F, N_h = self.rotation.shape[0], model.obj_vertices.shape[0], model.obj_faces.shape[0], model.human_vertices.shape[0]
         self.sizes = (B, N, F, H, W, N_h)
         lib = _lib.load()
-        nbytes = lib.ivlm_fit_step_workspace_bytes(B, N, F, H, W, N_h)
-        if nbytes == 0:
-            raise _lib.IvlmError(f"DevicePoseFit: sizes B={B}, N={N}, F={F}, H={H}, W={W}, N_h={N_h} are not supported")
         p, q = model.object_contact_probs, model.human_contact_probs
         if p.dtype != q.dtype:  # as contact_distance: a mixed pair goes in as fp32
             p, q = p.float(), q.float()
         optimise = (_lib.FIT_POSE if "pose" in vars else 0) | (_lib.FIT_SCALE if "scale" in vars else 0)
         with torch.cuda.device(dev):
+            self.workspace, nbytes = _lib.workspace(lib.ivlm_fit_step_workspace_bytes, "DevicePoseFit", dev,
+                                                    B=B, N=N, F=F, H=H, W=W, N_h=N_h)
             f32, offsets, slots = sil._topology_of(model.obj_faces, N)
             zeros = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
             self._moments = [zeros(B, 6), zeros(B, 3), zeros(B), zeros(B, 6), zeros(B, 3), zeros(B)]
             self._grads = [zeros(B, 6), zeros(B, 3), zeros(B)]
             self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
             self.history, self.term_history = zeros(max_iter, B), zeros(max_iter, 3, B)
-            self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._keep = (f32, offsets, slots, p.contiguous(), q.contiguous(), model.obj_vertices.contiguous(),
                       model.human_vertices.contiguous(), model.target_mask.contiguous(), model.target_mask_centroid.contiguous(),
                       model.hum_centroid_offset.contiguous())
@@ -334,11 +332,11 @@ class DevicePoseFit:
         return [self.rotation, self.translation, self.scale, *self._moments, *self._grads, self.counter, self.history, self.term_history]
 
     def _launch(self, bits):
-        from ._lib import check
+        from ._lib import check, stream
 
         self._args.terms_on = bits
         with torch.cuda.device(self.rotation.device):
-            check(self._lib.ivlm_fit_step(ctypes.byref(self._args), torch.cuda.current_stream().cuda_stream), "fit_step")
+            check(self._lib.ivlm_fit_step(ctypes.byref(self._args), stream()), "fit_step")
 
     def step(self):
         """one iteration: the total of the current parameters into history[i], then the update"""

@@ -41,8 +41,7 @@ def _check_points(points):
         raise ValueError(f"points: expected [N,3] or [B,N,3] with N >= 1, got {tuple(points.shape)}")
     if points.dtype != torch.float32:
         raise ValueError(f"points: expected float32, got {points.dtype}")
-    if not points.is_cuda:
-        raise IvlmError("points: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu(((points, "points"),))
     return points.dim() == 3
 
 
@@ -64,9 +63,7 @@ class MeshSDF:
             raise ValueError(f"faces: expected int32, got {faces.dtype}")
         if vertices.requires_grad:
             raise ValueError("vertices: requires_grad is set, and no gradient flows to the mesh (detach it: the human is a constant)")
-        for t, name in ((vertices, "vertices"), (faces, "faces")):
-            if not t.is_cuda:
-                raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+        _lib.require_gpu(((vertices, "vertices"), (faces, "faces")))
         if vertices.device != faces.device:
             raise ValueError(f"vertices and faces must be on one device, got {vertices.device} and {faces.device}")
         n_h, n_f = vertices.shape[0], faces.shape[0]
@@ -74,24 +71,18 @@ class MeshSDF:
         if lo < 0 or hi >= n_h:
             raise ValueError(f"faces: indices must lie in [0, {n_h}), got [{lo}, {hi}]")
         lib = _lib.load()
-        nbytes = lib.ivlm_mesh_sdf_plan_bytes(n_h, n_f)
-        if nbytes == 0:
-            raise IvlmError(f"MeshSDF: sizes N_h={n_h}, F={n_f} are not supported")
         self.device = vertices.device
         self.num_vertices, self.num_faces = n_h, n_f
         v, f = vertices.detach().contiguous(), faces.contiguous()
         with torch.cuda.device(self.device):
-            self.plan = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            check(lib.ivlm_mesh_sdf_prepare(v.data_ptr(), f.data_ptr(), n_h, n_f, self.plan.data_ptr(), nbytes,
-                                            torch.cuda.current_stream().cuda_stream), "mesh_sdf_prepare")
+            self.plan, nbytes = _lib.workspace(lib.ivlm_mesh_sdf_plan_bytes, "MeshSDF", self.device, N_h=n_h, F=n_f)
+            check(lib.ivlm_mesh_sdf_prepare(v.data_ptr(), f.data_ptr(), n_h, n_f, self.plan.data_ptr(), nbytes, _lib.stream()),
+                  "mesh_sdf_prepare")
 
     def _workspace(self, lib, points, B, N):
         if points.device != self.device:
             raise ValueError(f"points: expected a tensor on {self.device}, got {points.device}")
-        nbytes = lib.ivlm_mesh_sdf_workspace_bytes(B, N, self.num_faces)
-        if nbytes == 0:
-            raise IvlmError(f"mesh_sdf: sizes B={B}, N={N}, F={self.num_faces} are not supported")
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes
+        return _lib.workspace(lib.ivlm_mesh_sdf_workspace_bytes, "mesh_sdf", self.device, B=B, N=N, F=self.num_faces)
 
     def query(self, points):
         """points [N,3] or [B,N,3] (fp32, GPU) -> (sdf [..,N] fp32, closest [..,N,3] fp32, face [..,N] int32, winding [..,N] fp32).
@@ -107,8 +98,7 @@ class MeshSDF:
             face = torch.empty(B, N, dtype=torch.int32, device=self.device)
             winding = torch.empty(B, N, dtype=torch.float32, device=self.device)
             check(lib.ivlm_mesh_sdf_query(self.plan.data_ptr(), p.data_ptr(), B, N, sdf.data_ptr(), closest.data_ptr(), face.data_ptr(),
-                                          winding.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream),
-                  "mesh_sdf_query")
+                                          winding.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "mesh_sdf_query")
         out = (sdf, closest, face, winding)
         return out if batched else tuple(t[0] for t in out)
 
@@ -120,9 +110,8 @@ class MeshSDF:
             ws, nbytes = self._workspace(lib, p, B, N)
             value = torch.empty(B, dtype=torch.float32, device=self.device)
             grad = torch.empty(B, N, 3, dtype=torch.float32, device=self.device) if want_grad else None
-            check(lib.ivlm_mesh_sdf_penetration(self.plan.data_ptr(), p.data_ptr(), B, N, value.data_ptr(),
-                                                0 if grad is None else grad.data_ptr(), ws.data_ptr(), nbytes,
-                                                torch.cuda.current_stream().cuda_stream), "mesh_sdf_penetration")
+            check(lib.ivlm_mesh_sdf_penetration(self.plan.data_ptr(), p.data_ptr(), B, N, value.data_ptr(), _lib.ptr(grad),
+                                                ws.data_ptr(), nbytes, _lib.stream()), "mesh_sdf_penetration")
         return value, grad
 
     def penetration(self, points):

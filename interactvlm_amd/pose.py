@@ -17,7 +17,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import IvlmError, check
+from ._lib import check
 
 # Error model of the kernels, in units of 2^-24 (IVLM_POSE_* of include/ivlm_hip.h); tests derive their bounds from these.
 POSE_CHUNK = 1024  # vertices per block of the backward's partial sums (IVLM_POSE_CHUNK): a function of nothing but the build
@@ -97,9 +97,7 @@ def _validate(vertices, rot6d, translation, scaling):
             raise ValueError(f"scaling: expected a number or a tensor, got {scaling!r}") from None
         if not ok:
             raise ValueError(f"scaling: expected a finite number, got {scaling!r}")
-    for t, name in named:
-        if not t.is_cuda:
-            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu(named)
     devs = {t.device for t, _ in named}
     if len(devs) != 1:
         raise ValueError(f"all tensors must be on one device, got {sorted(str(d) for d in devs)}")
@@ -112,13 +110,12 @@ class _PoseTransform(torch.autograd.Function):
         lib = _lib.load()
         v, r6, t, s = verts.contiguous(), rot6d.contiguous(), trans.contiguous(), scale.contiguous()
         B, N = r6.shape[0], v.shape[0]
-        if lib.ivlm_pose_transform_workspace_bytes(B, N) == 0:
-            raise IvlmError(f"pose_transform: sizes B={B}, N={N} are not supported")
+        _lib.workspace(lib.ivlm_pose_transform_workspace_bytes, "pose_transform", None, B=B, N=N)  # (the forward needs none: the check)
         dev = v.device
         with torch.cuda.device(dev):
             out = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
             check(lib.ivlm_pose_transform_forward(v.data_ptr(), r6.data_ptr(), t.data_ptr(), s.data_ptr(), B, N, out.data_ptr(),
-                                                  torch.cuda.current_stream().cuda_stream), "pose_transform_forward")
+                                                  _lib.stream()), "pose_transform_forward")
         ctx.save_for_backward(v, r6, s)
         return out
 
@@ -133,16 +130,14 @@ class _PoseTransform(torch.autograd.Function):
         B, N = r6.shape[0], v.shape[0]
         g = grad_out.to(torch.float32).contiguous()
         dev = v.device
-        nbytes = lib.ivlm_pose_transform_workspace_bytes(B, N)
         with torch.cuda.device(dev):
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws, nbytes = _lib.workspace(lib.ivlm_pose_transform_workspace_bytes, "pose_transform", dev, B=B, N=N)
             g_r = torch.empty(B, 6, dtype=torch.float32, device=dev) if need_r else None
             g_t = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_t else None
             g_s = torch.empty(B, dtype=torch.float32, device=dev) if need_s else None
-            p = lambda x: 0 if x is None else x.data_ptr()  # noqa: E731
+            p = _lib.ptr
             check(lib.ivlm_pose_transform_backward(v.data_ptr(), r6.data_ptr(), s.data_ptr(), g.data_ptr(), B, N, p(g_r), p(g_t), p(g_s),
-                                                   ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream),
-                  "pose_transform_backward")
+                                                   ws.data_ptr(), nbytes, _lib.stream()), "pose_transform_backward")
         return None, g_r, g_t, g_s
 
 

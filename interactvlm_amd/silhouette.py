@@ -19,7 +19,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import IvlmError, check
+from ._lib import check
 
 # Error model of the kernels, in units of 2^-24 (IVLM_SILHOUETTE_* of include/ivlm_hip.h); tests derive their bounds from these.
 # With M = the largest of H, W, |u|, |v|, |u - px|, |v - py| over a face's vertices:
@@ -78,9 +78,7 @@ def _validate(verts, faces, focal, principal, image_size, sigma, blur_radius):
     blur_radius = default_blur_radius(sigma) if blur_radius is None else float(blur_radius)
     if not (blur_radius >= 0 and math.isfinite(blur_radius)):
         raise ValueError(f"blur_radius: expected a finite number >= 0, got {blur_radius}")
-    for t, name in ((verts, "verts"), (faces, "faces")):
-        if not t.is_cuda:
-            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu(((verts, "verts"), (faces, "faces")))
     if verts.device != faces.device:
         raise ValueError(f"all tensors must be on one device, got {sorted((str(verts.device), str(faces.device)))}")
     return fx, fy, px, py, H, W, sigma, blur_radius
@@ -121,16 +119,12 @@ class _SoftSilhouette(torch.autograd.Function):
         B, N = v.shape[0], v.shape[1]
         f32, offsets, slots = _topology_of(faces, N)
         F = f32.shape[0]
-        nbytes = lib.ivlm_soft_silhouette_workspace_bytes(B, N, F, H, W)
-        if nbytes == 0:
-            raise IvlmError(f"soft_silhouette: sizes B={B}, N={N}, F={F}, H={H}, W={W} are not supported")
         dev = v.device
         with torch.cuda.device(dev):
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws, nbytes = _lib.workspace(lib.ivlm_soft_silhouette_workspace_bytes, "soft_silhouette", dev, B=B, N=N, F=F, H=H, W=W)
             alpha = torch.empty(B, H, W, dtype=torch.float32, device=dev)
             check(lib.ivlm_soft_silhouette_forward(v.data_ptr(), f32.data_ptr(), B, N, F, H, W, fx, fy, px, py, sigma, blur,
-                                                   alpha.data_ptr(), ws.data_ptr(), nbytes,
-                                                   torch.cuda.current_stream().cuda_stream), "soft_silhouette_forward")
+                                                   alpha.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "soft_silhouette_forward")
         # the workspace keeps 1 - alpha and the projected faces for the backward; verts through save_for_backward, so that an
         # in-place change of them before the backward raises instead of chaining through other coordinates
         ctx.save_for_backward(verts, offsets, slots, ws)  # (the input itself, not the view of it made here)
@@ -152,8 +146,8 @@ class _SoftSilhouette(torch.autograd.Function):
         with torch.cuda.device(v.device):
             gv = torch.empty(B, N, 3, dtype=torch.float32, device=v.device)
             check(lib.ivlm_soft_silhouette_backward(v.data_ptr(), offsets.data_ptr(), slots.data_ptr(), g.data_ptr(), B, N, F, H, W,
-                                                    fx, fy, px, py, sigma, blur, gv.data_ptr(), ws.data_ptr(), nbytes,
-                                                    torch.cuda.current_stream().cuda_stream), "soft_silhouette_backward")
+                                                    fx, fy, px, py, sigma, blur, gv.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
+                  "soft_silhouette_backward")
         return gv.reshape(ctx.shape), None, None
 
 
@@ -188,9 +182,7 @@ def _validate_terms(alpha, target_mask):
     bt = target_mask.shape[0] if target_mask.dim() == 3 else 1
     if bt not in (1, ba):
         raise ValueError(f"target_mask: batch size {bt} does not broadcast with {ba}")
-    for t, name in ((alpha, "alpha"), (target_mask, "target_mask")):
-        if not t.is_cuda:
-            raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    _lib.require_gpu(((alpha, "alpha"), (target_mask, "target_mask")))
     if alpha.device != target_mask.device:
         raise ValueError(f"all tensors must be on one device, got {sorted((str(alpha.device), str(target_mask.device)))}")
 
@@ -198,10 +190,10 @@ def _validate_terms(alpha, target_mask):
 def _terms_call(lib, shape, a, t, sums, loss, centroid, g_loss, g_centroid, g_alpha, ws):
     """the forward (g_alpha None) or the backward (a, loss, centroid, ws None) of ivlm_silhouette_terms"""
     B, H, W = shape
-    p = lambda x: 0 if x is None else x.data_ptr()  # noqa: E731
+    p = _lib.ptr
     check(lib.ivlm_silhouette_terms(p(a), t.data_ptr(), H * W if t.shape[0] > 1 else 0, B, H, W, p(loss), p(centroid), sums.data_ptr(),
-                                    p(g_loss), p(g_centroid), p(g_alpha), p(ws), 0 if ws is None else ws.numel(),
-                                    torch.cuda.current_stream().cuda_stream), "silhouette_terms")
+                                    p(g_loss), p(g_centroid), p(g_alpha), p(ws), 0 if ws is None else ws.numel(), _lib.stream()),
+          "silhouette_terms")
 
 
 class _SilhouetteTerms(torch.autograd.Function):

@@ -36,13 +36,18 @@ def make_inputs(n_o, n_h, seed=0, batch_o=None, batch_h=None, density=0.1):
     o = torch.randn(*([batch_o] if batch_o else []), n_o, 3, generator=g)
     h = torch.randn(*([batch_h] if batch_h else []), n_h, 3, generator=g)
 
-    def probs(n):
+    def probs(n, side):
+        if isinstance(density, tuple):  # (m_o, m_h): exactly m non-zero entries - the last vertex, from m = 2 on the first, the rest anywhere
+            keep = torch.zeros(n, dtype=torch.bool)
+            keep[[0, n - 1][-density[side]:]] = True
+            keep[1 + torch.randperm(max(n - 2, 0), generator=g)[:max(density[side] - 2, 0)]] = True
+            return (0.05 + torch.rand(n, generator=g)) * keep
         p = torch.rand(n, generator=g) * (torch.rand(n, generator=g) < density)
         if not bool((p > 0).any()):  # S == 0 is NaN by definition and not a case here: keep one contact vertex
             p[int(torch.randint(n, (1,), generator=g))] = 0.5
         return p
 
-    return o, h, probs(n_o), probs(n_h)
+    return o, h, probs(n_o, 0), probs(n_h, 1)
 
 
 def definition64(o, h, p, q):
@@ -71,8 +76,14 @@ def case(n_o, n_h, density=0.1):
 #   (1025, 1024)  object: 5 stationary blocks, 5 fold blocks, 3 tiles with a tail of 1; human: exactly 2 full tiles
 #   (257, 6890)   human: 14 tiles, 27 stationary blocks; object: a stationary block of 1
 #   (512, 513) and (513, 512)  one full tile exactly, and one full tile followed by a 1-entry tail, on either side
+#
+# The compaction itself (one block of 1024 threads per side, a segment of ceil(N / 1024) vertices per thread) has its edges in N:
+# 1 (one thread has work; (1, 1) above), 1023 (segments of 1, the last thread idle), 1025 (segments of 2, half the threads idle).  A
+# density (m_o, m_h) asks for exactly that many non-zero probabilities, the first and the last vertex among them (a single one is the
+# last): m = 1, and 256 / 257 = one fold block of object vertices exactly and one more.
 SHAPES = [(70, 33, 0.1), (257, 6890, 0.1), (1, 1, 0.1), (1025, 1024, 0.1),
-          (1025, 1024, 1.0), (257, 6890, 1.0), (512, 513, 1.0), (513, 512, 1.0)]
+          (1025, 1024, 1.0), (257, 6890, 1.0), (512, 513, 1.0), (513, 512, 1.0),
+          (1023, 1025, (256, 257)), (1025, 1023, (257, 256)), (1023, 1025, (1, 1)), (1, 1023, (1, 257))]
 
 
 def run(dev, o, h, p, q, grads=True):
@@ -97,6 +108,9 @@ def test_value_and_both_gradients(hip_lib, cuda, n_o, n_h, density):
     (o, h, p, q), (L64, go64, gh64, Ao, Ah) = case(n_o, n_h, density)
     if density == 1.0:  # the compacted counts are the shape itself: the boundaries named above are really reached
         assert int((p != 0).sum()) == n_o and int((q != 0).sum()) == n_h
+    if isinstance(density, tuple):
+        assert (int((p != 0).sum()), int((q != 0).sum())) == density and bool(p[-1] != 0) and bool(q[-1] != 0)
+        assert all(bool(w[0] != 0) for w, m in ((p, density[0]), (q, density[1])) if m >= 2)
     L, go, gh = run(cuda, o, h, p, q)
     assert L.shape == () and go.shape == (n_o, 3) and gh.shape == (n_h, 3)
     assert_within(L, L64, C * U * L64, "L")

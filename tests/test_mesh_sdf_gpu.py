@@ -36,6 +36,13 @@ K_D, K_W, K_L, K_G = 452.0, 382.0, 4489.0, 2492.0
 MESHES = ref.mesh_names(ms.TILE, ms.CHUNK)
 CASES = [(m, n, b) for m in MESHES for n in ref.POINT_COUNTS for b in ref.BATCHES]
 FULL = ("body_82_84", 256, 2)
+# The edges of the penetration's compaction (one block of 1024 threads per pose, a segment of ceil(N / 1024) points per thread) and of
+# its fold blocks of 256: N = 1 (one thread has work), 1023 (segments of 1, the last thread idle), 1025 (segments of 2, half the
+# threads idle) with exactly 0, 1, 256 and 257 points of a pose inside the bounding box ('box': inside and outside points mixed as
+# the pool has them) or inside the mesh ('in': the kept list of the second compaction and the fold's count sit on 256 / 257).  The
+# counted points are spread evenly from the first index to the last; a single one is the last.  name@kind:count of pose 0,of pose 1
+PEN_EDGE_CASES = [("body_12_11@box:0,1", 1, 2), ("body_12_11@box:1,0", 1023, 2), ("body_12_11@box:256,257", 1023, 2),
+                  ("body_12_11@box:0,1", 1025, 2), ("body_12_11@box:257,256", 1025, 2), ("body_12_11@in:256,257", 1025, 2)]
 
 
 @pytest.fixture(autouse=True)
@@ -59,6 +66,8 @@ def test_the_meshes_sit_on_the_tile_and_chunk_boundaries():
 @functools.lru_cache(maxsize=None)
 def case(name, n, b):
     """(vertices, faces, points [b,n,3] f32, the fp64 results per pose): computed once, shared by the tests, never modified"""
+    if "@" in name:
+        return edge_case(name, n, b)
     v, f = ref.named_mesh(name)
     pts, r64 = ref.make_points(v, f, n * b, ref.case_seed(name, n, b), spare=1.5 if name == FULL[0] else 3.0)
     poses = [{k: val[p * n:(p + 1) * n] for k, val in r64.items()} for p in range(b)]
@@ -66,8 +75,52 @@ def case(name, n, b):
 
 
 @functools.lru_cache(maxsize=None)
-def mesh_on(name, dev):
+def edge_pool(name):
+    """4000 points of ``make_points`` for the mesh, their fp64 results, and which lie in the bounding box of the fp32 vertices (the
+    comparison the kernel makes: fp32 against fp32, exact): what the cases of PEN_EDGE_CASES draw from"""
     v, f = ref.named_mesh(name)
+    pts, r64 = ref.make_points(v, f, 4000, ref.case_seed(name, 4000, 1))
+    return v, f, pts, r64, ((pts >= v.min(0)) & (pts <= v.max(0))).all(1)
+
+
+def edge_case(name, n, b):
+    """``case`` for a name of PEN_EDGE_CASES: pose p has exactly counts[p] points in the box (kind 'box') or in the mesh ('in'), at
+    evenly spread indices from 0 to n - 1 (one alone: at n - 1); every other point lies outside the box"""
+    mesh, _, spec = name.partition("@")
+    kind, _, counts = spec.partition(":")
+    counts = [int(c) for c in counts.split(",")]
+    assert len(counts) == b and kind in ("box", "in")
+    v, f, pool, r64, box = edge_pool(mesh)
+    counted = np.nonzero(box & r64["inside"] if kind == "in" else box)[0]
+    rest = np.nonzero(~box)[0]
+    assert len(counted) >= sum(counts) and len(rest) >= n
+    idx = np.empty((b, n), dtype=np.int64)
+    for p, c in enumerate(counts):
+        at = np.zeros(n, dtype=bool)
+        at[[n - 1] if c == 1 else np.linspace(0, n - 1, c).round().astype(np.int64)] = True
+        assert int(at.sum()) == c
+        idx[p, at] = counted[sum(counts[:p]):sum(counts[:p]) + c]
+        idx[p, ~at] = np.roll(rest, -37 * p)[:n - c]
+    return v, f, pool[idx], [{k: val[idx[p]] for k, val in r64.items()} for p in range(b)]
+
+
+def assert_edge_counts(name, v, pts, poses):
+    """on the CPU, from the numpy reference alone: the poses of an edge case have the in-box / inside counts its name states"""
+    kind, _, counts = name.partition("@")[2].partition(":")
+    for p, c in enumerate(int(c) for c in counts.split(",")):
+        box = ((pts[p] >= v.min(0)) & (pts[p] <= v.max(0))).all(1)
+        ins = poses[p]["inside"]
+        assert not (ins & ~box).any()
+        assert int((ins if kind == "in" else box).sum()) == c
+        if kind == "in":
+            assert int(box.sum()) == c
+        if c >= 2:
+            assert box[0] and box[-1]
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_on(name, dev):
+    v, f = ref.named_mesh(name.partition("@")[0])
     return ms.MeshSDF(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev))
 
 
@@ -96,6 +149,8 @@ def check_query(name, n, b, dev):
 
 def check_penetration(name, n, b, dev):
     v, f, pts, poses = case(name, n, b)
+    if "@" in name:
+        assert_edge_counts(name, v, pts, poses)
     mesh = mesh_on(name, dev)
     x = torch.from_numpy(pts).to(dev).requires_grad_(True)
     L = mesh.penetration(x)
@@ -124,7 +179,7 @@ def test_query_against_fp64(hip_lib, cuda, name, n, b):
     check_query(name, n, b, cuda)
 
 
-@pytest.mark.parametrize("name,n,b", CASES)
+@pytest.mark.parametrize("name,n,b", CASES + PEN_EDGE_CASES)
 def test_penetration_against_fp64(hip_lib, cuda, name, n, b):
     check_penetration(name, n, b, cuda)
 
