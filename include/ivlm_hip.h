@@ -1118,7 +1118,9 @@ int ivlm_mesh_sdf_penetration(const void *plan, const float *points, int B, int 
  * ------------------------------------------------------------------------------------------- */
 size_t ivlm_raster_workspace_bytes(int n_verts_or_points, int H, int W);
 /* verts f32 [Nv,3], faces i32 [Nf,3] -> p2v i32 [H,W,3] (-1 background), bary f32 [H,W,3] (-1 background),
- * pix_to_face i32 [H,W] (may be NULL) */
+ * pix_to_face i32 [H,W] (may be NULL).  Face indices are not validated: every one must lie in [0, nv).  Each image axis runs
+ * over [-1, 1] across its own size (pytorch3d scales the longer axis of a non-square image: non-square output follows this
+ * project's convention only).  A face with a corner at or behind the camera plane while another is in front draws nothing. */
 int ivlm_rasterize_mesh(const float *verts, int nv, const int32_t *faces, int nf, const float *cam12_host,
                         float fov_deg, int H, int W, int32_t *p2v, float *bary, int32_t *pix_to_face,
                         void *workspace, size_t workspace_bytes, ivlm_stream_t stream);

@@ -6,7 +6,11 @@
 // pytorch3d (un-vendored, unpinned "@stable") is restated from its published conventions: row-vector cameras
 // X_view = X_world.R + T, FoV 60 deg, NDC +X left / +Y up, pixel centres at 1-(2i+1)/H, view-space z as depth,
 // strict inside test on the un-corrected barycentrics, perspective-correct barycentrics as output, nearest z wins,
-// equal z -> lower face index.
+// equal z -> lower face index.  Each axis runs over [-1, 1] across its own size: pytorch3d scales the longer axis of a
+// non-square image, so non-square output here follows the project's convention only.
+// The perspective-corrected barycentrics must be positive as well.  For a face in front of the camera that is the same test;
+// a face that straddles the camera plane (a corner with z <= 0) therefore draws nothing: what its projection covers is an
+// artefact in pytorch3d too, and without the test it wrote barycentrics of ~1e8 that do not sum to 1.
 //
 // Design: one thread per primitive walks its screen bounding box and takes the per-pixel minimum of a packed
 // 64-bit key (float-ordered z << 32 | primitive index) with atomicMin (L2 atomics); a resolve pass turns the
@@ -78,6 +82,9 @@ __global__ void raster_faces_kernel(const float* __restrict__ sv /*[Nv,3] screen
             if (!(b0 > 0.0f && b1 > 0.0f && b2 > 0.0f)) continue;  // blur_radius = 0: strictly inside
             // perspective-correct barycentrics, then depth
             const float t0 = b0 * z1 * z2, t1 = z0 * b1 * z2, t2 = z0 * z1 * b2;
+            // ... and inside by the corrected ones too.  They differ in sign only when a corner of the face lies behind the
+            // camera plane: there the 1/z weights cancel in den, the clamp takes over and barycentrics of ~1e8 would be written
+            if (!(t0 > 0.0f && t1 > 0.0f && t2 > 0.0f)) continue;
             const float den = fmaxf(t0 + t1 + t2, kEps);
             const float pz = (t0 * z0 + t1 * z1 + t2 * z2) / den;
             if (pz < 0.0f) continue;

@@ -9,6 +9,10 @@ Second witness [r6]: `oracle/raycast.py` computes pix_to_face + barycentrics by 
 same conventions; `tests/test_raster.py::test_oracle_raster_agrees_with_an_independent_fp64_ray_caster` holds the two (and the
 HIP kernel) together on the four HUMAN_VIEW_DICT cameras.  That guards against a slip in THIS restatement; it is not a pin to
 pytorch3d, and the label above stays.
+Third witness: `tests/_raster_ref.py` names, per pixel, the set of answers fp32 arithmetic may give (fp64 with a forward error band);
+`tests/test_raster_ref_cpu.py` holds this file inside those sets at every pixel of non-square scenes, and
+`tests/test_raster_exact_gpu.py` holds the HIP kernel there.  Each axis runs over [-1, 1] across its own size; pytorch3d scales the
+longer axis of a non-square image, so non-square output follows the project's convention only.
 """
 from __future__ import annotations
 
@@ -77,6 +81,9 @@ def rasterize_mesh(verts, faces, R, T, H, W, fov_deg=60.0):
         if not inside.any():
             continue
         t0, t1, t2 = b0 * z1 * z2, z0 * b1 * z2, z0 * z1 * b2
+        # inside by the corrected barycentrics too: the same test for a face in front of the camera; a face with a corner behind the
+        # camera plane draws nothing (its 1/z weights cancel in den, the clamp takes over and barycentrics of ~1e8 came out)
+        inside &= (t0 > 0) & (t1 > 0) & (t2 > 0)
         den = np.maximum(t0 + t1 + t2, EPS)
         pz = (t0 * z0 + t1 * z1 + t2 * z2) / den
         sub_z = zbest[np.ix_(ii, jj)]
