@@ -1107,6 +1107,24 @@ int ivlm_mesh_sdf_query(const void *plan, const float *points, int B, int N, flo
                         float *winding, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 int ivlm_mesh_sdf_penetration(const void *plan, const float *points, int B, int N, float *value, float *grad, void *workspace,
                               size_t workspace_bytes, ivlm_stream_t stream);
+/* The intrusion term: the other direction of the penetration term.  The plan is the OBJECT's mesh (closed, outward, constant) and
+ * points f32 [N,3] are the human's vertices, shared by the B poses (rot6d [B,6], translation [B,3], scale [B]; y = (s v) R + t, row
+ * vectors, R the Gram-Schmidt of ivlm_pose_transform_*).  Per pose and point:
+ *   x = ((h - t) R^T) / s   the point in the object's canonical frame: fp32, u = h - t, x_i = ((u_0 R_i0 + u_1 R_i1) + u_2 R_i2) / s
+ *   c, d, inside            the query of the plan at x;  e = s (x - c) R, the world-frame vector from the object's surface to h
+ *   L = (1 / N) sum_j inside_j |e_j|^2 = (1 / N) sum_j inside_j (s d_j)^2     -> value [B]
+ *   dL/dt = -(2 / N) sum inside e;  dL/ds = -(2 / N) sum inside e . (c R);  dL/dR_ik = -(2 s / N) sum inside c_i e_k, chained to rot6d
+ * (c is a constant of the derivative: the envelope theorem).  grad_rot6d [B,6], grad_translation [B,3], grad_scale [B]: each may be
+ * NULL.  No gradient to the points or to the mesh.  Sums in fp64 in a fixed order, each output rounded once; at the identity pose
+ * x == h and value == ivlm_mesh_sdf_penetration's bit for bit.  A pose whose scale is not > 0 (0, negative, NaN) gets NaN in its
+ * value and gradients; the other poses keep their bits.  Arguments, limits and a short workspace: as ivlm_mesh_sdf_penetration
+ * (IVLM_ERR_WORKSPACE for a workspace that holds no chunk; NaN in every output for one that holds fewer chunks than the plan has).
+ * workspace: ivlm_mesh_sdf_intrusion_workspace_bytes(B, N, F) = ivlm_mesh_sdf_workspace_bytes(B, N, F) + 12 B N for x
+ * + 112 B ceil(N / 256) for the block partials, each region padded to 256 bytes. */
+size_t ivlm_mesh_sdf_intrusion_workspace_bytes(int B, int N, int F);
+int ivlm_mesh_sdf_intrusion(const void *plan, const float *points, const float *rot6d, const float *translation, const float *scale,
+                            int B, int N, float *value, float *grad_rot6d, float *grad_translation, float *grad_scale,
+                            void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.

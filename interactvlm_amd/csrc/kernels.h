@@ -184,6 +184,9 @@ int mesh_sdf_query(const void* plan, const float* points, int B, int N, float* s
                    void* ws, size_t ws_bytes, hipStream_t st);
 int mesh_sdf_penetration(const void* plan, const float* points, int B, int N, float* value, float* grad, void* ws, size_t ws_bytes,
                          hipStream_t st);
+size_t mesh_sdf_intrusion_workspace_bytes(int B, int N, int n_faces);
+int mesh_sdf_intrusion(const void* plan, const float* points, const float* rot6d, const float* trans, const float* scale, int B, int N,
+                       float* value, float* grad_r6, float* grad_t, float* grad_s, void* ws, size_t ws_bytes, hipStream_t st);
 
 // ---- contact-weighted human-object distance with both gradients (contact_pair.hip) ---------------------
 size_t contact_pair_workspace_bytes(int B, int n_o, int n_h);

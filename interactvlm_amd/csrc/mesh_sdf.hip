@@ -24,10 +24,20 @@
 //                  sdf_pen_value: the block sums by wave_fold, / N, rounded once.  The gradient is zeroed first, so every other
 //                  row is an exact 0; a pose with no point in the box runs no sweep (all its blocks leave at once).
 //
-// The query and penetration calls are not told F: it lives in the plan, on the device.  The host derives from workspace_bytes
-// how many chunks the workspace holds (Cw), sizes the grid by it and lays the partials out by it; the kernels read the plan's
-// chunk count C and sweep only when C <= Cw; otherwise the folds write NaN (face -1) and nothing is read or written past the
-// workspace.  A workspace of ivlm_mesh_sdf_workspace_bytes(B, N, F) gives Cw == C.
+//   intrusion      the other direction: the plan is the OBJECT, the points are the human's vertices h [N,3], shared by B poses
+//                  (rot6d, t, s), y = (s v) R + t.  sdf_unpose: R by rot6d.h's Gram-Schmidt in fp64, rounded to fp32 once, then per
+//                  point in fp32 u = h - t, x_i = ((u_0 R_i0 + u_1 R_i1) + u_2 R_i2) / s -> x [B,N,3] in the workspace;  the four
+//                  kernels of the penetration, unchanged, with x as the points;  sdf_intrusion_fold: per inside point, in fp64,
+//                  c = x + q, e = -s (q R) (from q: h - (s c R + t) cancels) and the 14 sums {s^2 dd, e, e.(c R), c_i e_k} per block
+//                  of 256 (block4_sum);  sdf_intrusion_finish: one wave per pose, wave_fold over the blocks, the factors
+//                  dL/dt = -(2/N) sum e, dL/ds = -(2/N) sum e.(cR), dL/dR_ik = -(2 s/N) sum c_i e_k and rot6d.h's chain, each
+//                  output rounded once.  The value's sum has the order of sdf_pen_fold / sdf_pen_value: at the identity pose x == h
+//                  and the value is the penetration's bit for bit.  A pose with s not > 0 gets NaN (its x is NaN: no sweep).
+//
+// The query, penetration and intrusion calls are not told F: it lives in the plan, on the device.  The host derives from
+// workspace_bytes how many chunks the workspace holds (Cw), sizes the grid by it and lays the partials out by it; the kernels read
+// the plan's chunk count C and sweep only when C <= Cw; otherwise the folds write NaN (face -1) and nothing is read or written past
+// the workspace.  A workspace of ivlm_mesh_sdf_workspace_bytes(B, N, F) gives Cw == C.
 //
 // Built with -ffp-contract=off: each fp32 operation is the one tests/_mesh_sdf_ref.py states, so the tolerance constants measured
 // with its fp32 mode describe this arithmetic, apart from the device's sqrt / atan2 and the order of the winding sum.
@@ -36,6 +46,7 @@
 #include <cmath>
 
 #include "fit_common.h"
+#include "rot6d.h"
 
 namespace ivlm {
 namespace {
@@ -364,6 +375,139 @@ __global__ __launch_bounds__(64) void sdf_pen_value_kernel(SweepArgs s, const do
     if (threadIdx.x == 0) value[b] = (float)(v[0] / (double)s.N);
 }
 
+// ---- intrusion ------------------------------------------------------------------------------------------------------------------
+constexpr int kIntr = 14;  // sums per pose: s^2 dd, e[3], e.(c R), c_i e_k [9]
+
+// x = ((h - t) R^T) / s per pose and point; a pose whose s is not > 0 gets NaN (outside every bounding box: no sweep)
+__global__ __launch_bounds__(kFold) void sdf_unpose_kernel(const float* __restrict__ h, const float* __restrict__ rot6d,
+                                                           const float* __restrict__ trans, const float* __restrict__ scale, int N,
+                                                           float* __restrict__ x) {
+    __shared__ float pose[13];  // R row-major, t, s
+    const int b = blockIdx.y, t = threadIdx.x;
+    if (t == 0) {
+        const Frame f = gram_schmidt(rot6d + (int64_t)b * 6);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            pose[i * 3 + 0] = (float)f.b1[i];
+            pose[i * 3 + 1] = (float)f.b2[i];
+            pose[i * 3 + 2] = (float)f.b3[i];
+            pose[9 + i] = trans[(int64_t)b * 3 + i];
+        }
+        pose[12] = scale[b];
+    }
+    __syncthreads();
+    const int n = blockIdx.x * kFold + t;
+    if (n >= N) return;
+    const float s = pose[12];
+    const float u0 = h[(int64_t)n * 3] - pose[9], u1 = h[(int64_t)n * 3 + 1] - pose[10], u2 = h[(int64_t)n * 3 + 2] - pose[11];
+    float* o = x + ((int64_t)b * N + n) * 3;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = s > 0.0f ? ((u0 * pose[3 * i] + u1 * pose[3 * i + 1]) + u2 * pose[3 * i + 2]) / s : NAN;
+}
+
+// per inside point (list 1), all in fp64: the 14 sums of its block into part[(b nb + block) 14 + k]
+__global__ __launch_bounds__(kFold) void sdf_intrusion_fold_kernel(SweepArgs s, const float* __restrict__ rot6d, const float* __restrict__ scale,
+                                                                   double* __restrict__ part, int nb) {
+    __shared__ double red[4][kIntr];
+    __shared__ double pose[10];  // R row-major, s
+    static_assert(kFold == 256, "block4_sum: four waves");
+    const int b = blockIdx.y, t = threadIdx.x, k = blockIdx.x * kFold + t;
+    const int C = s.hdr->n_chunks;
+    if (C > s.Cw) return;
+    const int m = s.count[b];
+    if ((int)blockIdx.x * kFold >= m) return;  // block-uniform
+    if (t == 0) {
+        const Frame f = gram_schmidt(rot6d + (int64_t)b * 6);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            pose[i * 3 + 0] = f.b1[i];
+            pose[i * 3 + 1] = f.b2[i];
+            pose[i * 3 + 2] = f.b3[i];
+        }
+        pose[9] = (double)scale[b];
+    }
+    __syncthreads();
+    double acc[kIntr];
+#pragma unroll
+    for (int j = 0; j < kIntr; ++j) acc[j] = 0.0;
+    if (k < m) {
+        float4 q;
+        int fc;
+        fold_closest(s, C, b, k, q, fc);
+        if (fc >= 0) {
+            const double sc = pose[9];
+            const float* xp = s.points + ((int64_t)b * s.N + s.list[(int64_t)b * s.N + k]) * 3;
+            const double qd[3] = {(double)q.x, (double)q.y, (double)q.z};
+            const double c[3] = {(double)xp[0] + qd[0], (double)xp[1] + qd[1], (double)xp[2] + qd[2]};
+            double e[3], cr[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                e[j] = -sc * ((qd[0] * pose[j] + qd[1] * pose[3 + j]) + qd[2] * pose[6 + j]);
+                cr[j] = (c[0] * pose[j] + c[1] * pose[3 + j]) + c[2] * pose[6 + j];
+            }
+            acc[0] = (sc * sc) * (double)q.w;
+            acc[4] = (e[0] * cr[0] + e[1] * cr[1]) + e[2] * cr[2];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                acc[1 + i] = e[i];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc[5 + 3 * i + j] = c[i] * e[j];
+            }
+        }
+    }
+    block4_sum(acc, red);
+    if (t == 0) {
+#pragma unroll
+        for (int j = 0; j < kIntr; ++j) part[((int64_t)b * nb + blockIdx.x) * kIntr + j] = acc[j];
+    }
+}
+
+// one wave per pose: the block sums, the factors, the chain to rot6d; each output rounded once
+__global__ __launch_bounds__(64) void sdf_intrusion_finish_kernel(SweepArgs s, const float* __restrict__ rot6d, const float* __restrict__ scale,
+                                                                  const double* __restrict__ part, int nb, float* __restrict__ value,
+                                                                  float* __restrict__ grad_r6, float* __restrict__ grad_t,
+                                                                  float* __restrict__ grad_s) {
+    const int b = blockIdx.x;
+    const double sc = (double)scale[b];
+    const bool bad = s.hdr->n_chunks > s.Cw || !(sc > 0.0);  // block-uniform
+    double v[kIntr];
+    if (!bad) wave_fold(part + (int64_t)b * nb * kIntr, (s.count[b] + kFold - 1) / kFold, v);
+    if (threadIdx.x != 0) return;
+    if (bad) {
+        value[b] = NAN;
+        if (grad_t) grad_t[(int64_t)b * 3] = grad_t[(int64_t)b * 3 + 1] = grad_t[(int64_t)b * 3 + 2] = NAN;
+        if (grad_s) grad_s[b] = NAN;
+        if (grad_r6) {
+            for (int i = 0; i < 6; ++i) grad_r6[(int64_t)b * 6 + i] = NAN;
+        }
+        return;
+    }
+    const double n = (double)s.N;
+    value[b] = (float)(v[0] / n);
+    const double w = -2.0 / n;
+    if (grad_t) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) grad_t[(int64_t)b * 3 + j] = (float)(w * v[1 + j]);
+    }
+    if (grad_s) grad_s[b] = (float)(w * v[4]);
+    if (!grad_r6) return;
+    const Frame f = gram_schmidt(rot6d + (int64_t)b * 6);
+    const double ws = w * sc;
+    double gb1[3], gb2[3], gb3[3], ga1[3], ga2[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // dL/dR_ik = -(2 s / N) sum c_i e_k, by columns
+        gb1[i] = ws * v[5 + 3 * i];
+        gb2[i] = ws * v[5 + 3 * i + 1];
+        gb3[i] = ws * v[5 + 3 * i + 2];
+    }
+    gram_schmidt_backward(f, gb1, gb2, gb3, ga1, ga2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        grad_r6[(int64_t)b * 6 + 2 * i] = (float)ga1[i];
+        grad_r6[(int64_t)b * 6 + 2 * i + 1] = (float)ga2[i];
+    }
+}
+
 bool sizes_ok(int B, int N) { return B > 0 && N > 0 && B <= 65535 && N <= kMaxN; }
 
 }  // namespace
@@ -389,8 +533,24 @@ size_t mesh_sdf_workspace_bytes(int B, int N, int n_faces) {
 }
 
 namespace {
+// what the intrusion call keeps behind the penetration's layout: x [B,N,3] and the block partials [B,nb,14]
+struct IntrusionExtra {
+    size_t x, part, total;
+};
+
+IntrusionExtra intrusion_extra(int B, int N) {
+    IntrusionExtra e;
+    Carve c;
+    e.x = c.take((size_t)B * N * 12);
+    e.part = c.take((size_t)B * ((N + kFold - 1) / kFold) * kIntr * 8);
+    e.total = c.off;
+    return e;
+}
+
 // -> the sweep arguments over a checked workspace, or an error code in *rc
-SweepArgs sweep_args(const void* plan, const float* points, int B, int N, void* ws, size_t ws_bytes, SdfLayout* l, int* rc) {
+// extra: bytes the caller keeps for itself behind the layout (the chunk capacity is derived from what is left)
+SweepArgs sweep_args(const void* plan, const float* points, int B, int N, void* ws, size_t ws_bytes, SdfLayout* l, int* rc,
+                     size_t extra = 0) {
     SweepArgs s = {};
     *rc = IVLM_OK;
     if (!plan || !points || !ws || B <= 0 || N <= 0 || (reinterpret_cast<uintptr_t>(plan) & 15)) {
@@ -401,11 +561,11 @@ SweepArgs sweep_args(const void* plan, const float* points, int B, int N, void* 
         *rc = IVLM_ERR_UNSUPPORTED;
         return s;
     }
-    if (!workspace_ok(ws, ws_bytes, sdf_layout(B, N, 1).total, 16)) {  // not even one chunk
+    if (!workspace_ok(ws, ws_bytes, sdf_layout(B, N, 1).total + extra, 16)) {  // not even one chunk
         *rc = IVLM_ERR_WORKSPACE;
         return s;
     }
-    const int Cw = sdf_capacity(B, N, ws_bytes);
+    const int Cw = sdf_capacity(B, N, ws_bytes - extra);
     *l = sdf_layout(B, N, Cw);
     s.hdr = static_cast<const SdfHeader*>(plan);
     s.rec = reinterpret_cast<const float4*>(s.hdr + 1);
@@ -457,6 +617,40 @@ int mesh_sdf_penetration(const void* plan, const float* points, int B, int N, fl
     return ivlm_launch_status();
 }
 
+size_t mesh_sdf_intrusion_workspace_bytes(int B, int N, int n_faces) {
+    const size_t base = mesh_sdf_workspace_bytes(B, N, n_faces);
+    return base ? base + intrusion_extra(B, N).total : 0;
+}
+
+int mesh_sdf_intrusion(const void* plan, const float* points, const float* rot6d, const float* trans, const float* scale, int B, int N,
+                       float* value, float* grad_r6, float* grad_t, float* grad_s, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!value || !rot6d || !trans || !scale) return IVLM_ERR_INVALID_ARG;
+    SdfLayout l;
+    int rc;
+    const IntrusionExtra ex = sizes_ok(B, N) ? intrusion_extra(B, N) : IntrusionExtra{};
+    SweepArgs s = sweep_args(plan, points, B, N, ws, ws_bytes, &l, &rc, ex.total);
+    if (rc != IVLM_OK) return rc;
+    int32_t* cnt = ws_at<int32_t>(ws, l.cnt);
+    int32_t* list0 = ws_at<int32_t>(ws, l.list[0]);
+    int32_t* list1 = ws_at<int32_t>(ws, l.list[1]);
+    float* x = ws_at<float>(ws, l.total + ex.x);
+    double* part = ws_at<double>(ws, l.total + ex.part);
+    const dim3 grid((N + kWave - 1) / kWave, s.Cw, B);
+    sdf_unpose_kernel<<<dim3(l.nb, B), kFold, 0, st>>>(points, rot6d, trans, scale, N, x);
+    s.points = x;
+    sdf_compact_kernel<0><<<B, 1024, 0, st>>>(s, nullptr, nullptr, list0, cnt);
+    s.list = list0;
+    s.count = cnt;
+    sdf_sweep_kernel<true, false><<<grid, kWave, 0, st>>>(s);
+    sdf_compact_kernel<1><<<B, 1024, 0, st>>>(s, list0, cnt, list1, cnt + B);
+    s.list = list1;
+    s.count = cnt + B;
+    sdf_sweep_kernel<false, true><<<grid, kWave, 0, st>>>(s);
+    sdf_intrusion_fold_kernel<<<dim3(l.nb, B), kFold, 0, st>>>(s, rot6d, scale, part, l.nb);
+    sdf_intrusion_finish_kernel<<<B, 64, 0, st>>>(s, rot6d, scale, part, l.nb, value, grad_r6, grad_t, grad_s);
+    return ivlm_launch_status();
+}
+
 }  // namespace ivlm
 
 extern "C" {
@@ -475,5 +669,13 @@ int ivlm_mesh_sdf_penetration(const void* plan, const float* points, int B, int 
                               size_t workspace_bytes, ivlm_stream_t s) {
     ivlm_enter();
     return ivlm::mesh_sdf_penetration(plan, points, B, N, value, grad, workspace, workspace_bytes, ivlm_stream(s));
+}
+size_t ivlm_mesh_sdf_intrusion_workspace_bytes(int B, int N, int F) { return ivlm::mesh_sdf_intrusion_workspace_bytes(B, N, F); }
+int ivlm_mesh_sdf_intrusion(const void* plan, const float* points, const float* rot6d, const float* translation, const float* scale, int B,
+                            int N, float* value, float* grad_rot6d, float* grad_translation, float* grad_scale, void* workspace,
+                            size_t workspace_bytes, ivlm_stream_t s) {
+    ivlm_enter();
+    return ivlm::mesh_sdf_intrusion(plan, points, rot6d, translation, scale, B, N, value, grad_rot6d, grad_translation, grad_scale,
+                                    workspace, workspace_bytes, ivlm_stream(s));
 }
 }

@@ -16,9 +16,11 @@
 //   pose_finish    one wave per pose: lanes 0..11 add the partials of one sum each in ascending chunk order; lane 0 chains
 //                  dL/dR = s G through the Gram-Schmidt analytically, all in fp64, and rounds each result to fp32 once.
 //                  dL/dt = sum g;  dL/ds = sum_ij R_ij G_ij.
+// The Gram-Schmidt and its chain are rot6d.h's (shared with mesh_sdf.hip).
 #include <cstdint>
 
 #include "fit_common.h"
+#include "rot6d.h"
 
 namespace ivlm {
 namespace {
@@ -28,47 +30,7 @@ constexpr int kThreads = 256;
 constexpr int kPerThread = kChunk / kThreads;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxN = 1 << 22;
-constexpr double kEps = 1e-12;  // F.normalize's clamp of the norm
 static_assert(kChunk % kThreads == 0, "a chunk is a whole number of vertices per thread");
-
-struct Frame {
-    double b1[3], b2[3], b3[3];  // the columns of R
-    double a2[3], d, n1, n2;     // what the chain back to the six numbers needs
-    bool clamp1, clamp2;         // the norm was clamped: the normalisation is a division by the constant
-};
-
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ Frame gram_schmidt(const float* __restrict__ r6) {
-    Frame f;
-    double a1[3], u2[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        a1[i] = (double)r6[2 * i];
-        f.a2[i] = (double)r6[2 * i + 1];
-    }
-    const double l1 = sqrt(dot3(a1, a1));
-    f.clamp1 = !(l1 > kEps);
-    f.n1 = f.clamp1 ? kEps : l1;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) f.b1[i] = a1[i] / f.n1;
-    f.d = dot3(f.b1, f.a2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u2[i] = f.a2[i] - f.d * f.b1[i];
-    const double l2 = sqrt(dot3(u2, u2));
-    f.clamp2 = !(l2 > kEps);
-    f.n2 = f.clamp2 ? kEps : l2;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) f.b2[i] = u2[i] / f.n2;
-    cross3(f.b1, f.b2, f.b3);
-    return f;
-}
 
 __global__ __launch_bounds__(kThreads) void pose_forward_kernel(const float* __restrict__ verts, const float* __restrict__ rot6d,
                                                                 const float* __restrict__ trans, const float* __restrict__ scale, int N,
@@ -174,35 +136,14 @@ __global__ __launch_bounds__(64) void pose_finish_kernel(const float* __restrict
     }
     if (!grad_r6) return;
     const double s = (double)scale[b];
-    double gb1[3], gb2[3], gb3[3], c[3], gu2[3], ga1[3], ga2[3];
+    double gb1[3], gb2[3], gb3[3], ga1[3], ga2[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {  // dL/dR = s G, by columns
         gb1[i] = s * sums[3 * i];
         gb2[i] = s * sums[3 * i + 1];
         gb3[i] = s * sums[3 * i + 2];
     }
-    // b3 = b1 x b2
-    cross3(f.b2, gb3, c);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gb1[i] += c[i];
-    cross3(gb3, f.b1, c);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gb2[i] += c[i];
-    // b2 = u2 / n2
-    const double p2 = f.clamp2 ? 0.0 : dot3(f.b2, gb2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gu2[i] = (gb2[i] - f.b2[i] * p2) / f.n2;
-    // u2 = a2 - d b1,  d = b1 . a2
-    const double gd = -dot3(f.b1, gu2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        gb1[i] += gd * f.a2[i] - f.d * gu2[i];
-        ga2[i] = gu2[i] + gd * f.b1[i];
-    }
-    // b1 = a1 / n1
-    const double p1 = f.clamp1 ? 0.0 : dot3(f.b1, gb1);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ga1[i] = (gb1[i] - f.b1[i] * p1) / f.n1;
+    gram_schmidt_backward(f, gb1, gb2, gb3, ga1, ga2);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         grad_r6[(int64_t)b * 6 + 2 * i] = (float)ga1[i];

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from .contact_icp import contact_icp
 from .contact_pair import contact_distance
-from .mesh_sdf import MeshSDF
+from .mesh_sdf import MeshSDF, check_closed
 from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_transform
 from .silhouette import silhouette_terms, soft_silhouette
 
@@ -30,6 +30,10 @@ DEFAULT_LOSS_WEIGHTS = {
 # NOT the reference's and not in DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh.  A term of
 # ``ObjectPoseFit`` when loss_weights holds it and the model has human_faces; not a row of TERM_KEYS, not run by ivlm_fit_step.
 PENETRATION_KEY = "penetration_loss"
+# The other direction, under the same rules (NOT the reference's, not in DEFAULT_LOSS_WEIGHTS, not a row of TERM_KEYS): mesh_sdf's
+# intrusion of the human vertices into the posed object.  A term of ``ObjectPoseFit`` when loss_weights holds it and the model was
+# built with intrusion=True.
+INTRUSION_KEY = "intrusion_loss"
 
 
 def matrix_to_rot6d(matrix):
@@ -99,11 +103,16 @@ class ObjectPoseFit(nn.Module):
     human_faces [F_h,3] int32 (closed, outward) prepares one ``MeshSDF`` of the human and allows one more term, NOT the reference's:
     "penetration_loss" = ``MeshSDF.penetration`` of the un-offset object vertices (the frame of the contact term), gated and weighted
     like the others when loss_weights holds the key (``DEFAULT_LOSS_WEIGHTS`` does not); on without human_faces it raises.
+    intrusion=True checks that the object is closed and outward (``mesh_sdf.check_closed``, on a host copy) and prepares one
+    ``MeshSDF`` of it (its one device read; both here, before any loop) for the term "intrusion_loss" = ``MeshSDF.intrusion`` of the
+    un-offset human vertices under the B poses: the penetration term's other direction, for a coarse object none of whose vertices
+    lies inside the body while a limb passes through one of its faces.  Gated and weighted like the others, not in
+    ``DEFAULT_LOSS_WEIGHTS`` either; on without intrusion=True it raises.
     forward(loss_weights, step=None) -> (total [B], {term: [B]})."""
 
     def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
                  human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
-                 blur_radius=None, fused_transform=False, human_faces=None):
+                 blur_radius=None, fused_transform=False, intrusion=False, human_faces=None):
         super().__init__()
         unknown = set(vars) - {"pose", "scale"}
         if unknown:
@@ -139,6 +148,11 @@ class ObjectPoseFit(nn.Module):
         self.register_buffer("target_mask_centroid", mask_bbox_centre(mask))
         # the penetration term's prepared mesh (one device read, here); a plain attribute: the plan belongs to this device
         self.human_sdf = None if human_faces is None else MeshSDF(self.human_vertices, human_faces.detach())
+        # the intrusion term's prepared mesh: the object in its canonical frame, checked closed and outward on a host copy first
+        self.object_sdf = None
+        if intrusion:
+            check_closed(self.obj_vertices, self.obj_faces)
+            self.object_sdf = MeshSDF(self.obj_vertices, self.obj_faces.to(torch.int32))
 
     def object_vertices(self):
         if self.fused_transform:
@@ -171,6 +185,11 @@ class ObjectPoseFit(nn.Module):
                 raise ValueError(f"{PENETRATION_KEY} is on, but the model was built without human_faces: the signed distance needs the "
                                  "human's triangles")
             terms[PENETRATION_KEY] = self.human_sdf.penetration(obj)
+        if on(INTRUSION_KEY):
+            if self.object_sdf is None:
+                raise ValueError(f"{INTRUSION_KEY} is on, but the model was built without intrusion=True: the term needs the object "
+                                 "checked closed and prepared as a MeshSDF")
+            terms[INTRUSION_KEY] = self.object_sdf.intrusion(self.human_vertices, self.rotation, self.translation, self.scale)
         total = torch.zeros(self.rotation.shape[0], dtype=torch.float32, device=self.rotation.device)
         for key, val in terms.items():
             total = total + val * weights[key]["w"]
@@ -183,9 +202,10 @@ DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
 
 
 def _refuse_penetration_on_device(loss_weights):
-    if loss_weights is not None and PENETRATION_KEY in loss_weights and loss_weights[PENETRATION_KEY]["kick_in"] >= 0:
-        raise ValueError(f"{PENETRATION_KEY}: not available with device_loop=True (the device loop's launch sequence does not run the "
-                         "term; configure kick_in = -1 or use the torch loop)")
+    for key in (PENETRATION_KEY, INTRUSION_KEY):
+        if loss_weights is not None and key in loss_weights and loss_weights[key]["kick_in"] >= 0:
+            raise ValueError(f"{key}: not available with device_loop=True (the device loop's launch sequence does not run the "
+                             "term; configure kick_in = -1 or use the torch loop)")
 
 
 def fit_phases(loss_weights, max_iter):
@@ -371,7 +391,7 @@ _UNSET = object()  # fused_transform was not passed: False for the torch loop, i
 def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                     init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250, early_stop=False,
                     sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
-                    device_loop=False, human_faces=None):
+                    device_loop=False, intrusion=False, human_faces=None):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
     init = (R6 [B,6], T [B,3], s number or [B]) gives the B starts; None takes one start from ``contact_icp`` between the object
@@ -382,6 +402,8 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
     transform, refuses early_stop (a host read per iteration) and adds term_history [iterations,3,B] to the result.
     human_faces [F_h,3] int32 (the human's triangles, closed and outward) is what the term "penetration_loss" of loss_weights needs
     (``ObjectPoseFit``, ``mesh_sdf``: NOT the reference's); device_loop=True refuses that term when it is configured (kick_in >= 0).
+    intrusion=True is what the term "intrusion_loss" needs (``ObjectPoseFit``: the object is checked closed and prepared once, before
+    the loop); device_loop=True refuses that term in the same way.
     -> dict(rotation [B,6], translation [B,3], scale [B], object_vertices [B,N,3], history [iterations,B] (device tensor))."""
     if not isinstance(max_iter, int) or max_iter < 1:
         raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
@@ -404,7 +426,8 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
                              target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, loss_weights,
                              max_iter).run().result()
     model = ObjectPoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
-                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform, human_faces)
+                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform, intrusion=intrusion,
+                          human_faces=human_faces)
     groups = []
     if "pose" in vars:
         groups += [{"params": [model.rotation], "lr": 5e-2}, {"params": [model.translation], "lr": 1e-2}]
@@ -450,7 +473,7 @@ _SEARCH_FIT_KWARGS = ("hum_centroid_offset", "vars", "loss_weights", "max_iter",
 
 def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                        rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, device_loop=False,
-                       human_faces=None, **fit_kwargs):
+                       intrusion=False, human_faces=None, **fit_kwargs):
     """A multi-start ``fit_object_pose``: K starts around one pose, fitted in one loop with the fused transform, scored and ranked on
     the device.  NOT the reference's, which runs one start (optim/fit.py): contact patches and a silhouette leave rotational
     ambiguities that a local fit from one start does not resolve.
@@ -468,6 +491,7 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     device_loop=True runs every loop on the device (``fit_object_pose(device_loop=True)``, ``DevicePoseFit``) and adds term_history
     [iterations,3,K]; the scoring stays the forward described above.  human_faces goes to every loop and to the scoring model, so
     that the score holds "penetration_loss" whenever loss_weights configures it (device_loop=True refuses that, see ``fit_object_pose``).
+    intrusion goes the same way, for "intrusion_loss".
 
     chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
     computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
@@ -522,10 +546,10 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     for lo in range(0, K, step):
         sel = slice(lo, min(lo + step, K))
         out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop,
-                              human_faces=human_faces, **fit_kwargs)
+                              human_faces=human_faces, intrusion=intrusion, **fit_kwargs)
         final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], *scene, fit_kwargs.get("hum_centroid_offset"),
                               fit_kwargs.get("vars", ("pose",)), fit_kwargs.get("sigma", 1e-4), fit_kwargs.get("blur_radius"),
-                              fused_transform=True, human_faces=human_faces)
+                              fused_transform=True, human_faces=human_faces, intrusion=intrusion)
         with torch.no_grad():
             scores.append(final(weights, step=every_term)[0])
         parts.append(out)

@@ -7,6 +7,16 @@
             a, b, c = v0 - x, v1 - x, v2 - x;  inside(x) <=> w(x) > 0.5;  sdf(x) = -d inside, +d outside
     L     = (1 / N) sum_i inside(x_i) d(x_i)^2,  dL/dx_i = inside(x_i) 2 (x_i - c(x_i)) / N  (exact almost everywhere)
 
+The other direction, ``MeshSDF.intrusion``: the prepared mesh is the OBJECT (closed, outward, constant; ``check_closed``) under B poses
+(rot6d, t, s), y = (s v) R + t, and the points are the human's vertices h_j [N,3], shared by the batch:
+
+    x_j = ((h_j - t) R^T) / s   the human vertex in the object's canonical frame;  c_j, d_j, inside_j = the query at x_j
+    e_j = s (x_j - c_j) R       the world-frame vector from the object's surface to h_j
+    L   = (1 / N) sum_j inside_j |e_j|^2 = (1 / N) sum_j inside_j (s d_j)^2
+    dL/dt = -(2 / N) sum inside e;  dL/ds = -(2 / N) sum inside e . (c R);  dL/dR_ik = -(2 s / N) sum inside c_i e_k, then to rot6d
+
+(c_j is a constant of the derivative, by the envelope theorem.)  13 fp64 sums per pose; no [B, N, 3] gradient array exists.
+
 The mesh is closed and consistently oriented, outward, where a sign is wanted; a face of zero area contributes to neither sum;
 no gradient flows to the mesh vertices (the human is a constant of the fit, as in the reference).  No [N, F] array exists
 anywhere.  The same bits every call, and for a pose whatever the batch around it.  There is no CPU fallback.
@@ -15,11 +25,13 @@ from __future__ import annotations
 
 import re
 
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import IvlmError, check
+from .pose import _validate as _validate_pose
 
 
 def _header_constant(name):
@@ -45,8 +57,47 @@ def _check_points(points):
     return points.dim() == 3
 
 
+def check_closed(vertices, faces):
+    """A one-time host check that (vertices [N_v,3], faces [F,3]) is a closed, consistently oriented, outward mesh - what a signed
+    distance to it means anything for.  Tensors (copied to the host: one device read) or arrays.  Raises ValueError naming the first
+    defect, in this order: an index outside [0, N_v); a face with a repeated index; a directed edge that occurs twice (two
+    neighbours wound against each other); a directed edge whose reverse does not occur exactly once (a hole, or an edge of three
+    faces); a signed volume <= 0 (inward).  Pure numpy: usable without a GPU."""
+    v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
+    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1:
+        raise ValueError(f"vertices: expected [N_v,3] with at least one row, got {tuple(v.shape)}")
+    if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.kind not in "iu":
+        raise ValueError(f"faces: expected integers [F,3] with at least one row, got {f.dtype} {tuple(f.shape)}")
+    v, f = v.astype(np.float64), f.astype(np.int64)
+    if f.min() < 0 or f.max() >= v.shape[0]:
+        raise ValueError(f"faces: indices must lie in [0, {v.shape[0]}), got [{int(f.min())}, {int(f.max())}]")
+    repeated = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
+    if repeated.any():
+        k = int(np.nonzero(repeated)[0][0])
+        raise ValueError(f"faces: face {k} = {f[k].tolist()} repeats an index (a zero-area face: the mesh is not a closed surface)")
+    n = v.shape[0]
+    a, b = f.reshape(-1), f[:, (1, 2, 0)].reshape(-1)  # the directed edges a -> b, three per face, in face order
+    key, rev = a * n + b, b * n + a
+    uniq, first, count = np.unique(key, return_index=True, return_counts=True)
+    if (count > 1).any():
+        e = int(first[count > 1].min())
+        raise ValueError(f"faces: the directed edge {int(a[e])} -> {int(b[e])} (face {e // 3}) occurs {int(count[uniq == key[e]][0])} times: "
+                         "two faces are wound against each other (or the edge has more than two faces)")
+    at = np.searchsorted(uniq, rev)
+    found = (at < len(uniq)) & (uniq[np.minimum(at, len(uniq) - 1)] == rev)
+    if not found.all():
+        e = int(np.nonzero(~found)[0][0])
+        raise ValueError(f"faces: the directed edge {int(a[e])} -> {int(b[e])} (face {e // 3}) has no reverse {int(b[e])} -> {int(a[e])}: "
+                         "the mesh is open there")
+    v0, v1, v2 = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    volume = float((v0 * np.cross(v1, v2)).sum() / 6.0)
+    if not volume > 0.0:
+        raise ValueError(f"faces: the signed volume is {volume:.6g}, not > 0: the faces are wound inward (flip them)")
+
+
 class MeshSDF:
-    """A mesh prepared for ``query`` and ``penetration``: vertices [N_h,3] fp32, faces [F,3] int32, on the GPU.  The constructor
+    """A mesh prepared for ``query``, ``penetration`` and ``intrusion``: vertices [N_h,3] fp32, faces [F,3] int32, on the GPU.  The constructor
     validates shapes and dtypes and that faces lies within [0, N_h) - ONE device read, here and before any loop, the convention
     of ``fit_object_pose``'s own one-time reads - refuses vertices.requires_grad (no gradient flows to the mesh), and writes the
     plan (per-face records, the zero-area marks, the bounding box) with one launch sequence.  The plan is reused by every call."""
@@ -121,6 +172,65 @@ class MeshSDF:
         batched = _check_points(points)
         value = _Penetration.apply(points, self)
         return value if batched else value[0]
+
+
+    def _intrusion(self, h, r6, t, s, need):
+        """h [N,3], r6 [B,6], t [B,3], s [B], contiguous -> (L [B], dL/drot6d | None, dL/dt | None, dL/ds | None)"""
+        lib = _lib.load()
+        B, N = r6.shape[0], h.shape[0]
+        dev = self.device
+        with torch.cuda.device(dev):
+            ws, nbytes = _lib.workspace(lib.ivlm_mesh_sdf_intrusion_workspace_bytes, "mesh_sdf_intrusion", dev, B=B, N=N, F=self.num_faces)
+            value = torch.empty(B, dtype=torch.float32, device=dev)
+            grads = [torch.empty(*shape, dtype=torch.float32, device=dev) if want else None
+                     for want, shape in zip(need, ((B, 6), (B, 3), (B,)))]
+            check(lib.ivlm_mesh_sdf_intrusion(self.plan.data_ptr(), h.data_ptr(), r6.data_ptr(), t.data_ptr(), s.data_ptr(), B, N,
+                                              value.data_ptr(), _lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(grads[2]),
+                                              ws.data_ptr(), nbytes, _lib.stream()), "mesh_sdf_intrusion")
+        return (value, *grads)
+
+    def intrusion(self, points, rot6d, translation, scaling=1.0):
+        """This mesh is the object, posed B times by (rot6d [B,6], translation [B,3], scaling a number, [B] or [B,1]) as
+        ``pose.pose_transform`` poses it (or one pose: [6], [3], a scalar); points [N,3] (fp32, GPU) are the human's vertices, shared
+        by the batch and constant (requires_grad is refused).  -> L = mean over the points of inside (s d)^2 with d the distance of
+        the un-posed point to this mesh, shape [B] or [].  Differentiable in rot6d, translation and a tensor scaling, once: the
+        forward launch computes the gradients that are needed and saves them as constants, so a double backward raises.  A pose
+        whose scaling is not > 0 gets NaN.  The mesh must be closed and outward (``check_closed``)."""
+        if not isinstance(points, torch.Tensor):
+            raise ValueError(f"points: expected a tensor, got {type(points).__name__}")
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise ValueError(f"points: expected [N,3] with N >= 1 (shared by the batch), got {tuple(points.shape)}")
+        if points.dtype != torch.float32:
+            raise ValueError(f"points: expected float32, got {points.dtype}")
+        if points.requires_grad:
+            raise ValueError("points: requires_grad is set, and no gradient flows to the points of intrusion (detach them: the human "
+                             "is a constant)")
+        B, batched = _validate_pose(points, rot6d, translation, scaling)
+        if points.device != self.device:
+            raise ValueError(f"points: expected a tensor on {self.device}, got {points.device}")
+        r6 = rot6d if batched else rot6d.unsqueeze(0)
+        t = translation if batched else translation.unsqueeze(0)
+        if isinstance(scaling, torch.Tensor):
+            s = scaling.reshape(-1).expand(B)
+        else:
+            s = torch.full((B,), float(scaling), dtype=torch.float32, device=self.device)
+        value = _Intrusion.apply(points, r6, t, s, self)
+        return value if batched else value[0]
+
+
+class _Intrusion(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, rot6d, trans, scale, mesh):
+        value, *ctx.grads = mesh._intrusion(points.contiguous(), rot6d.contiguous(), trans.contiguous(), scale.contiguous(),
+                                            ctx.needs_input_grad[1:4])
+        return value
+
+    @staticmethod
+    @once_differentiable  # the saved gradients are constants: a double backward raises instead of returning wrong second derivatives
+    def backward(ctx, grad_value):
+        g_r, g_t, g_s = ctx.grads
+        return (None, None if g_r is None else grad_value.reshape(-1, 1) * g_r, None if g_t is None else grad_value.reshape(-1, 1) * g_t,
+                None if g_s is None else grad_value * g_s, None)
 
 
 class _Penetration(torch.autograd.Function):
