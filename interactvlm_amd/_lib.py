@@ -20,8 +20,26 @@ _CTYPES = {
     "ivlm_stream_t": C.c_void_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "uint8_t": C.c_uint8, "double": C.c_double,
 }
 
-FIT_MASK, FIT_CENTROID, FIT_CONTACT = 1, 2, 4  # IVLM_FIT_* of terms_on
-FIT_POSE, FIT_SCALE = 1, 2                     # IVLM_FIT_* of optimise
+class IvlmError(RuntimeError):
+    pass
+
+
+_constants = None
+
+
+def header_constant(name):
+    """the value of ``#define <name> <integer>`` in include/ivlm_hip.h: the ABI's numbers are read, not retyped (every such line of the
+    header is parsed once)"""
+    global _constants
+    if _constants is None:
+        _constants = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define[ \t]+(IVLM_\w+)[ \t]+(\d+)\b", open(HEADER_PATH).read(), flags=re.M)}
+    if name not in _constants:
+        raise IvlmError(f"include/ivlm_hip.h does not define {name} as an integer")
+    return _constants[name]
+
+
+FIT_MASK, FIT_CENTROID, FIT_CONTACT = (header_constant(f"IVLM_FIT_{k}") for k in ("MASK", "CENTROID", "CONTACT"))  # bits of terms_on
+FIT_POSE, FIT_SCALE = header_constant("IVLM_FIT_POSE"), header_constant("IVLM_FIT_SCALE")                      # bits of optimise
 
 
 class FitStepArgs(C.Structure):
@@ -36,10 +54,6 @@ class FitStepArgs(C.Structure):
         + [(n, C.c_double) for n in ("lr_rotation", "lr_translation", "lr_scale", "beta1", "beta2", "eps")]
         + [(n, C.c_int32) for n in ("B", "N", "F", "H", "W", "N_h", "p_dtype", "max_iter", "terms_on", "optimise")]
         + [(n, C.c_float) for n in ("fx", "fy", "px", "py", "sigma", "blur_radius", "w_mask", "w_centroid", "w_contact")])
-
-
-class IvlmError(RuntimeError):
-    pass
 
 
 def header_prototypes(path: str = HEADER_PATH):
@@ -109,8 +123,8 @@ def ptr(x):
 
 
 def require_gpu(named):
-    """named: (tensor, name) pairs, in the order their errors are reported"""
-    for t, name in named:
+    """named: (tensor, name) pairs (or ``_args``' triples), in the order their errors are reported"""
+    for t, name, *_ in named:
         if not t.is_cuda:
             raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
 

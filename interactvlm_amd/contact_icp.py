@@ -22,9 +22,11 @@ from typing import NamedTuple
 import torch
 
 from . import _lib
+from ._args import batch_size, check_devices, check_points, check_vector, side
 from ._lib import check
 
-ESTIMATE_SCALE, ALLOW_REFLECTION, REQUERY = 1, 2, 4  # IVLM_ICP_* of include/ivlm_hip.h
+ESTIMATE_SCALE, ALLOW_REFLECTION, REQUERY = (_lib.header_constant(f"IVLM_ICP_{k}")
+                                             for k in ("ESTIMATE_SCALE", "ALLOW_REFLECTION", "REQUERY"))
 
 
 class ICPResult(NamedTuple):
@@ -39,48 +41,10 @@ class ICPResult(NamedTuple):
     history: tuple            # (R [max_iterations, B, 3, 3], T [max_iterations, B, 3], s [max_iterations, B])
 
 
-def _check_points(v, name, dims=(3,)):
-    if not isinstance(v, torch.Tensor):
-        raise ValueError(f"{name}: expected a tensor, got {type(v).__name__}")
-    if v.dim() not in (2, 3) or v.shape[-1] not in dims or v.shape[-2] < 1 or v.shape[0] < 1:
-        raise ValueError(f"{name}: expected [N,D] or [B,N,D] with N >= 1 and D in {tuple(dims)}, got {tuple(v.shape)}")
-    if v.dtype != torch.float32:
-        raise ValueError(f"{name}: expected float32, got {v.dtype}")
-
-
-def _batch(named):
-    """named: [(tensor, name, unbatched rank)] -> B; raises when the batch sizes do not broadcast"""
-    B = 1
-    for t, name, rank in named:
-        b = t.shape[0] if t.dim() == rank + 1 else 1
-        if b != 1 and B != 1 and b != B:
-            raise ValueError(f"{name}: batch size {b} does not broadcast with {B}")
-        B = max(B, b)
-    return B
-
-
-def _check_devices(named):
-    _lib.require_gpu((t, name) for t, name, _ in named)
-    devs = {t.device for t, _, _ in named}
-    if len(devs) != 1:
-        raise ValueError(f"all tensors must be on one device, got {sorted(str(d) for d in devs)}")
-
-
 def _check_weights(w, n, name="weights"):
-    if not isinstance(w, torch.Tensor):
-        raise ValueError(f"{name}: expected a tensor, got {type(w).__name__}")
-    if w.dim() not in (1, 2) or w.shape[-1] != n or w.shape[0] < 1:
-        raise ValueError(f"{name}: expected [{n}] or [B,{n}], got {tuple(w.shape)}")
-    if w.dtype != torch.float32:
-        raise ValueError(f"{name}: expected float32, got {w.dtype}")
+    check_vector(w, n, name, batch=True)
     if bool((w < 0).any()):
         raise ValueError(f"{name}: expected non-negative weights")
-
-
-def _side(t, rank):
-    """-> (contiguous tensor with a batch axis, elements between poses or 0 for a side shared by the batch)"""
-    t = (t if t.dim() == rank + 1 else t.unsqueeze(0)).contiguous()
-    return t, (t[0].numel() if t.shape[0] > 1 else 0)
 
 
 def contact_nearest(queries, targets):
@@ -89,16 +53,16 @@ def contact_nearest(queries, targets):
     queries [N_o,D] or [B,N_o,D], targets [N_h,D] or [B,N_h,D] (fp32, GPU, D = 3 or 6; an unbatched side is shared by the batch)
     -> (idx int32 [B,N_o], d2 fp32 [B,N_o]).  d^2 is the direct fp32 sum of squared differences, relative error <= 8 * 2^-24;
     the lowest index wins an exact tie, so the result does not depend on the kernel's tiling."""
-    _check_points(queries, "queries", (3, 6))
-    _check_points(targets, "targets", (3, 6))
+    check_points(queries, "queries", (3, 6))
+    check_points(targets, "targets", (3, 6))
     if queries.shape[-1] != targets.shape[-1]:
         raise ValueError(f"queries have D = {queries.shape[-1]}, targets D = {targets.shape[-1]}")
     named = [(queries, "queries", 2), (targets, "targets", 2)]
-    B = _batch(named)
-    _check_devices(named)
+    B = batch_size(named)
+    check_devices(named)
     lib = _lib.load()
-    q, q_bs = _side(queries, 2)
-    t, t_bs = _side(targets, 2)
+    q, q_bs = side(queries, 2)
+    t, t_bs = side(targets, 2)
     n_o, n_h, D = q.shape[1], t.shape[1], q.shape[2]
     with torch.cuda.device(q.device):
         idx = torch.empty(B, n_o, dtype=torch.int32, device=q.device)
@@ -119,20 +83,20 @@ def align_points(X, Y, weights=None, estimate_scale=False, allow_reflection=Fals
     X, Y [N,3] or [B,N,3] (fp32, GPU), weights [N] or [B,N] >= 0 or None -> (R [B,3,3], T [B,3], s [B]).  Moments, the 3x3 Jacobi
     SVD and the solve are fp64, rounded once to fp32.  A degenerate covariance (collinear or coincident points, one point) still
     gives a finite orthonormal R, of determinant +1 unless allow_reflection."""
-    _check_points(X, "X")
-    _check_points(Y, "Y")
+    check_points(X, "X")
+    check_points(Y, "Y")
     if X.shape[-2] != Y.shape[-2]:
         raise ValueError(f"X has {X.shape[-2]} points, Y {Y.shape[-2]}")
     named = [(X, "X", 2), (Y, "Y", 2)]
     if weights is not None:
         _check_weights(weights, X.shape[-2])
         named.append((weights, "weights", 1))
-    B = _batch(named)
-    _check_devices(named)
+    B = batch_size(named)
+    check_devices(named)
     lib = _lib.load()
-    x, x_bs = _side(X, 2)
-    y, y_bs = _side(Y, 2)
-    w, w_bs = _side(weights, 1) if weights is not None else (None, 0)
+    x, x_bs = side(X, 2)
+    y, y_bs = side(Y, 2)
+    w, w_bs = side(weights, 1) if weights is not None else (None, 0)
     n = x.shape[1]
     dev = x.device
     with torch.cuda.device(dev):
@@ -155,10 +119,8 @@ def contact_normal_filter(obj_normals, human_normals, angle_deg, angle_neg_deg=N
     The thresholds are computed as the reference computes them, in fp32: cos(deg2rad(90)) is -4.37e-8, not 0, so (90, -90) keeps
     every row that has any d_ij > -4.37e-8 or < -4.37e-8."""
     for v, name in ((obj_normals, "obj_normals"), (human_normals, "human_normals")):
-        _check_points(v, name)
-        if v.dim() != 2:
-            raise ValueError(f"{name}: expected [N,3], got {tuple(v.shape)}")
-    _check_devices([(obj_normals, "obj_normals", 2), (human_normals, "human_normals", 2)])
+        check_points(v, name, batch=False)
+    check_devices([(obj_normals, "obj_normals", 2), (human_normals, "human_normals", 2)])
 
     def cosine(a):
         return float(torch.cos(torch.deg2rad(torch.tensor(a, dtype=torch.float32))))
@@ -176,14 +138,14 @@ def contact_normal_filter(obj_normals, human_normals, angle_deg, angle_neg_deg=N
 
 def _validate_icp(obj_pts, human_pts, obj_normals, human_normals, init, weights, max_iterations):
     """-> B: raises before anything touches the library"""
-    _check_points(obj_pts, "obj_pts")
-    _check_points(human_pts, "human_pts")
+    check_points(obj_pts, "obj_pts")
+    check_points(human_pts, "human_pts")
     named = [(obj_pts, "obj_pts", 2), (human_pts, "human_pts", 2)]
     if (obj_normals is None) != (human_normals is None):
         raise ValueError("normals must be given for both sides or for neither")
     if obj_normals is not None:
-        _check_points(obj_normals, "obj_normals")
-        _check_points(human_normals, "human_normals")
+        check_points(obj_normals, "obj_normals")
+        check_points(human_normals, "human_normals")
         if obj_normals.shape[-2] != obj_pts.shape[-2] or human_normals.shape[-2] != human_pts.shape[-2]:
             raise ValueError("normals: expected one normal per point")
         named += [(obj_normals, "obj_normals", 2), (human_normals, "human_normals", 2)]
@@ -206,8 +168,8 @@ def _validate_icp(obj_pts, human_pts, obj_normals, human_normals, init, weights,
         if not (R.shape[0] == T.shape[0] == s.shape[0]):
             raise ValueError(f"init: batch sizes {R.shape[0]}, {T.shape[0]}, {s.shape[0]} differ")
         named += [(R, "init R", 2), (T, "init T", 1), (s, "init s", 0)]
-    B = _batch(named)
-    _check_devices(named)
+    B = batch_size(named)
+    check_devices(named)
     return B
 
 
@@ -238,11 +200,11 @@ def contact_icp(obj_pts, human_pts, obj_normals=None, human_normals=None, init=N
     Not supported (optim/fit.py passes neither): Pointclouds objects or per-cloud lengths, min_scale / scale_penalty."""
     B = _validate_icp(obj_pts, human_pts, obj_normals, human_normals, init, weights, max_iterations)
     lib = _lib.load()
-    x, x_bs = _side(obj_pts, 2)
-    y, y_bs = _side(human_pts, 2)
-    xn, xn_bs = _side(obj_normals, 2) if obj_normals is not None else (None, 0)
-    yn, yn_bs = _side(human_normals, 2) if human_normals is not None else (None, 0)
-    w, w_bs = _side(weights, 1) if weights is not None else (None, 0)
+    x, x_bs = side(obj_pts, 2)
+    y, y_bs = side(human_pts, 2)
+    xn, xn_bs = side(obj_normals, 2) if obj_normals is not None else (None, 0)
+    yn, yn_bs = side(human_normals, 2) if human_normals is not None else (None, 0)
+    w, w_bs = side(weights, 1) if weights is not None else (None, 0)
     n_o, n_h = x.shape[1], y.shape[1]
     dev = x.device
     iR = iT = i_s = None

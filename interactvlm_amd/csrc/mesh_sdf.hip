@@ -577,6 +577,23 @@ SweepArgs sweep_args(const void* plan, const float* points, int B, int N, void* 
     s.Cw = Cw;
     return s;
 }
+
+// What penetration and intrusion share: the points of s.points inside the bounding box (list 0), their winding sums, the inside ones
+// among them (list 1), their closest points.  Leaves s on list 1 for the caller's fold.
+void sweep_inside(SweepArgs& s, const SdfLayout& l, void* ws, int B, hipStream_t st) {
+    int32_t* cnt = ws_at<int32_t>(ws, l.cnt);
+    int32_t* list0 = ws_at<int32_t>(ws, l.list[0]);
+    int32_t* list1 = ws_at<int32_t>(ws, l.list[1]);
+    const dim3 grid((s.N + kWave - 1) / kWave, s.Cw, B);
+    sdf_compact_kernel<0><<<B, 1024, 0, st>>>(s, nullptr, nullptr, list0, cnt);
+    s.list = list0;
+    s.count = cnt;
+    sdf_sweep_kernel<true, false><<<grid, kWave, 0, st>>>(s);
+    sdf_compact_kernel<1><<<B, 1024, 0, st>>>(s, list0, cnt, list1, cnt + B);
+    s.list = list1;
+    s.count = cnt + B;
+    sdf_sweep_kernel<false, true><<<grid, kWave, 0, st>>>(s);
+}
 }  // namespace
 
 int mesh_sdf_query(const void* plan, const float* points, int B, int N, float* sdf, float* closest, int32_t* face, float* winding,
@@ -598,20 +615,9 @@ int mesh_sdf_penetration(const void* plan, const float* points, int B, int N, fl
     int rc;
     SweepArgs s = sweep_args(plan, points, B, N, ws, ws_bytes, &l, &rc);
     if (rc != IVLM_OK) return rc;
-    int32_t* cnt = ws_at<int32_t>(ws, l.cnt);
-    int32_t* list0 = ws_at<int32_t>(ws, l.list[0]);
-    int32_t* list1 = ws_at<int32_t>(ws, l.list[1]);
     double* blockval = ws_at<double>(ws, l.blockval);
-    const dim3 grid((N + kWave - 1) / kWave, s.Cw, B);
     if (grad) IVLM_HIP_TRY(hipMemsetAsync(grad, 0, (size_t)B * N * 12, st));
-    sdf_compact_kernel<0><<<B, 1024, 0, st>>>(s, nullptr, nullptr, list0, cnt);
-    s.list = list0;
-    s.count = cnt;
-    sdf_sweep_kernel<true, false><<<grid, kWave, 0, st>>>(s);
-    sdf_compact_kernel<1><<<B, 1024, 0, st>>>(s, list0, cnt, list1, cnt + B);
-    s.list = list1;
-    s.count = cnt + B;
-    sdf_sweep_kernel<false, true><<<grid, kWave, 0, st>>>(s);
+    sweep_inside(s, l, ws, B, st);
     sdf_pen_fold_kernel<<<dim3(l.nb, B), kFold, 0, st>>>(s, grad, blockval, l.nb);
     sdf_pen_value_kernel<<<B, 64, 0, st>>>(s, blockval, l.nb, value);
     return ivlm_launch_status();
@@ -630,22 +636,11 @@ int mesh_sdf_intrusion(const void* plan, const float* points, const float* rot6d
     const IntrusionExtra ex = sizes_ok(B, N) ? intrusion_extra(B, N) : IntrusionExtra{};
     SweepArgs s = sweep_args(plan, points, B, N, ws, ws_bytes, &l, &rc, ex.total);
     if (rc != IVLM_OK) return rc;
-    int32_t* cnt = ws_at<int32_t>(ws, l.cnt);
-    int32_t* list0 = ws_at<int32_t>(ws, l.list[0]);
-    int32_t* list1 = ws_at<int32_t>(ws, l.list[1]);
     float* x = ws_at<float>(ws, l.total + ex.x);
     double* part = ws_at<double>(ws, l.total + ex.part);
-    const dim3 grid((N + kWave - 1) / kWave, s.Cw, B);
     sdf_unpose_kernel<<<dim3(l.nb, B), kFold, 0, st>>>(points, rot6d, trans, scale, N, x);
     s.points = x;
-    sdf_compact_kernel<0><<<B, 1024, 0, st>>>(s, nullptr, nullptr, list0, cnt);
-    s.list = list0;
-    s.count = cnt;
-    sdf_sweep_kernel<true, false><<<grid, kWave, 0, st>>>(s);
-    sdf_compact_kernel<1><<<B, 1024, 0, st>>>(s, list0, cnt, list1, cnt + B);
-    s.list = list1;
-    s.count = cnt + B;
-    sdf_sweep_kernel<false, true><<<grid, kWave, 0, st>>>(s);
+    sweep_inside(s, l, ws, B, st);
     sdf_intrusion_fold_kernel<<<dim3(l.nb, B), kFold, 0, st>>>(s, rot6d, scale, part, l.nb);
     sdf_intrusion_finish_kernel<<<B, 64, 0, st>>>(s, rot6d, scale, part, l.nb, value, grad_r6, grad_t, grad_s);
     return ivlm_launch_status();

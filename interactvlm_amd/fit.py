@@ -15,10 +15,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib, contact_pair, silhouette
 from .contact_icp import contact_icp
 from .contact_pair import contact_distance
 from .mesh_sdf import MeshSDF, check_closed
-from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_transform
+from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_arguments, pose_transform
 from .silhouette import silhouette_terms, soft_silhouette
 
 # optim/cfg/fit.yaml
@@ -27,13 +28,25 @@ DEFAULT_LOSS_WEIGHTS = {
     "centroid_loss": {"w": 1e-4, "kick_in": 0},
     "contact_loss": {"w": 10.0, "kick_in": 0},
 }
-# NOT the reference's and not in DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh.  A term of
-# ``ObjectPoseFit`` when loss_weights holds it and the model has human_faces; not a row of TERM_KEYS, not run by ivlm_fit_step.
-PENETRATION_KEY = "penetration_loss"
-# The other direction, under the same rules (NOT the reference's, not in DEFAULT_LOSS_WEIGHTS, not a row of TERM_KEYS): mesh_sdf's
-# intrusion of the human vertices into the posed object.  A term of ``ObjectPoseFit`` when loss_weights holds it and the model was
-# built with intrusion=True.
-INTRUSION_KEY = "intrusion_loss"
+# Every term of ``ObjectPoseFit``, in the order they are added up: key -> its bit of ivlm_fit_step's terms_on (a row of term_history),
+# or None for a term that the device loop's launch sequence does not run.  The two None terms are NOT the reference's and not in
+# DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh (the model needs human_faces) and, the other
+# direction, mesh_sdf's intrusion of the human vertices into the posed object (the model needs intrusion=True).
+TERMS = {"mask_loss": _lib.FIT_MASK, "centroid_loss": _lib.FIT_CENTROID, "contact_loss": _lib.FIT_CONTACT,
+         "penetration_loss": None, "intrusion_loss": None}
+TERM_KEYS = tuple(k for k, bit in TERMS.items() if bit is not None)
+PENETRATION_KEY, INTRUSION_KEY = (k for k, bit in TERMS.items() if bit is None)
+DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
+
+
+def term_configured(key, weights):
+    """weights holds the term and does not switch it off (kick_in = -1: never)"""
+    return key in weights and weights[key]["kick_in"] >= 0
+
+
+def term_counts(key, weights, i):
+    """the term counts at iteration i: configured, and i >= kick_in (0: from the start, k: from iteration k on)"""
+    return key in weights and 0 <= weights[key]["kick_in"] <= i
 
 
 def matrix_to_rot6d(matrix):
@@ -90,12 +103,70 @@ def mask_bbox_centre(mask):
     return torch.stack(out)
 
 
+class FitScene:
+    """The constants of a fit, prepared once and shared by every model and loop over them: the float, detached buffers, the binarised
+    target and the centre of its bounding box, the camera, sigma and blur radius, the centroid offset, with human_faces the human's
+    ``MeshSDF`` and with intrusion=True the object checked closed (``mesh_sdf.check_closed``, on a host copy) and prepared as a
+    ``MeshSDF`` - every host read of a fit's preparation but the silhouette's topology cache, which is keyed by the tensor object
+    ``obj_faces`` kept here and so hits after the first use.  The arguments are ``ObjectPoseFit``'s."""
+
+    def __init__(self, obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
+                 hum_centroid_offset=None, sigma=1e-4, blur_radius=None, intrusion=False, human_faces=None):
+        if not isinstance(target_mask, torch.Tensor) or target_mask.dim() != 2:
+            raise ValueError("target_mask: expected [H,W]")
+        self.camera = (focal, principal)
+        self.sigma, self.blur_radius = sigma, blur_radius
+        self.obj_vertices = obj_vertices.detach().float()
+        self.obj_faces = obj_faces.detach()
+        self.human_vertices = human_vertices.detach().float()
+        self.object_contact_probs = obj_contact_probs.detach()
+        self.human_contact_probs = human_contact_probs.detach()
+        off = torch.zeros(3) if hum_centroid_offset is None else hum_centroid_offset.detach().float()
+        self.hum_centroid_offset = off.to(obj_vertices.device)
+        self.target_mask = (target_mask != 0).float()
+        self.target_mask_centroid = mask_bbox_centre(self.target_mask)
+        # the penetration term's prepared mesh (one device read, here); the plan belongs to this device
+        self.human_sdf = None if human_faces is None else MeshSDF(self.human_vertices, human_faces.detach())
+        # the intrusion term's prepared mesh: the object in its canonical frame, checked closed and outward on a host copy first
+        self.object_sdf = None
+        if intrusion:
+            check_closed(self.obj_vertices, self.obj_faces)
+            self.object_sdf = MeshSDF(self.obj_vertices, self.obj_faces.to(torch.int32))
+
+    BUFFERS = ("obj_vertices", "obj_faces", "human_vertices", "object_contact_probs", "human_contact_probs", "hum_centroid_offset",
+               "target_mask", "target_mask_centroid")
+    _DEFAULTS = (None,) * 8 + (1e-4, None, False, None)  # of the arguments after obj_vertices
+
+    @classmethod
+    def of(cls, first, *rest):
+        """``first`` when it is a scene given in place of obj_vertices (nothing else of a scene may come with it), else the scene of
+        the arguments"""
+        if not isinstance(first, cls):
+            return cls(first, *rest)
+        if not all(v is d or (not isinstance(v, torch.Tensor) and v == d) for v, d in zip(rest, cls._DEFAULTS)):
+            raise ValueError("obj_vertices is a FitScene: no other argument of the scene may be given with it")
+        return first
+
+    def validate(self, rotation, translation, scale):
+        """What ``DevicePoseFit`` checks before the library loads, by the modules whose kernels run: shapes, dtypes and devices of the
+        scene with the pose parameters rotation [B,6], translation [B,3], scale [B] -> the camera tuple of ``silhouette.validate``"""
+        H, W = self.target_mask.shape
+        pose_arguments(self.obj_vertices, rotation, translation, scale)
+        cam = silhouette.validate(self.obj_vertices, self.obj_faces, *self.camera, (H, W), self.sigma, self.blur_radius)
+        contact_pair.validate(self.obj_vertices, self.human_vertices, self.object_contact_probs, self.human_contact_probs)
+        silhouette.validate_terms(self.target_mask.new_empty(H, W), self.target_mask)
+        if self.hum_centroid_offset.shape != (3,):
+            raise ValueError(f"hum_centroid_offset: expected [3], got {tuple(self.hum_centroid_offset.shape)}")
+        return cam
+
+
 class ObjectPoseFit(nn.Module):
     """The terms of ``ObjPose_Opt.forward`` for B starts at once, with its quirks: the silhouette is rendered on the object moved by
     ``hum_centroid_offset`` while the contact term is taken on the un-offset vertices; the target centroid is the centre of the
     target mask's bounding box; a term counts when ``kick_in >= 0 and step >= kick_in``.
 
-    rotation_init [B,6] (or [6]), translation_init [B,3], scaling_init a number or [B]; obj_vertices [N,3], obj_faces [F,3],
+    rotation_init [B,6] (or [6]), translation_init [B,3], scaling_init a number or [B]; obj_vertices [N,3] (or a ``FitScene``
+    in its place, and then none of the scene's other arguments), obj_faces [F,3],
     human_vertices [N_h,3], obj_contact_probs [N], human_contact_probs [N_h], target_mask [H,W]; focal / principal as
     ``soft_silhouette`` takes them.  ``vars`` selects what is optimised: "pose", "scale" or both.  fused_transform=True moves the
     object with ``pose.pose_transform`` (one launch for the batch, two for its backward) instead of the pose-by-pose torch
@@ -110,9 +181,9 @@ class ObjectPoseFit(nn.Module):
     ``DEFAULT_LOSS_WEIGHTS`` either; on without intrusion=True it raises.
     forward(loss_weights, step=None) -> (total [B], {term: [B]})."""
 
-    def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
-                 human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
-                 blur_radius=None, fused_transform=False, intrusion=False, human_faces=None):
+    def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces=None, human_vertices=None,
+                 obj_contact_probs=None, human_contact_probs=None, target_mask=None, focal=None, principal=None, hum_centroid_offset=None,
+                 vars=("pose",), sigma=1e-4, blur_radius=None, fused_transform=False, intrusion=False, human_faces=None):
         super().__init__()
         unknown = set(vars) - {"pose", "scale"}
         if unknown:
@@ -134,25 +205,12 @@ class ObjectPoseFit(nn.Module):
             self.register_buffer("scale", scale)
         self.step = 0
         self.fused_transform = bool(fused_transform)
-        self.camera = (focal, principal)
-        self.sigma, self.blur_radius = sigma, blur_radius
-        self.register_buffer("obj_vertices", obj_vertices.detach().float())
-        self.register_buffer("obj_faces", obj_faces.detach())
-        self.register_buffer("human_vertices", human_vertices.detach().float())
-        self.register_buffer("object_contact_probs", obj_contact_probs.detach())
-        self.register_buffer("human_contact_probs", human_contact_probs.detach())
-        off = torch.zeros(3) if hum_centroid_offset is None else hum_centroid_offset.detach().float()
-        self.register_buffer("hum_centroid_offset", off.to(obj_vertices.device))
-        mask = (target_mask != 0).float()
-        self.register_buffer("target_mask", mask)
-        self.register_buffer("target_mask_centroid", mask_bbox_centre(mask))
-        # the penetration term's prepared mesh (one device read, here); a plain attribute: the plan belongs to this device
-        self.human_sdf = None if human_faces is None else MeshSDF(self.human_vertices, human_faces.detach())
-        # the intrusion term's prepared mesh: the object in its canonical frame, checked closed and outward on a host copy first
-        self.object_sdf = None
-        if intrusion:
-            check_closed(self.obj_vertices, self.obj_faces)
-            self.object_sdf = MeshSDF(self.obj_vertices, self.obj_faces.to(torch.int32))
+        self.scene = scene = FitScene.of(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask,
+                                         focal, principal, hum_centroid_offset, sigma, blur_radius, intrusion, human_faces)
+        self.camera, self.sigma, self.blur_radius = scene.camera, scene.sigma, scene.blur_radius
+        for name in FitScene.BUFFERS:  # the scene's own tensor objects
+            self.register_buffer(name, getattr(scene, name))
+        self.human_sdf, self.object_sdf = scene.human_sdf, scene.object_sdf  # plain attributes: a plan belongs to its device
 
     def object_vertices(self):
         if self.fused_transform:
@@ -164,7 +222,7 @@ class ObjectPoseFit(nn.Module):
         step = self.step if step is None else step
 
         def on(key):
-            return key in weights and weights[key]["kick_in"] >= 0 and step >= weights[key]["kick_in"]
+            return term_counts(key, weights, step)
 
         obj = self.object_vertices()
         terms = {}
@@ -197,29 +255,20 @@ class ObjectPoseFit(nn.Module):
         return total, terms
 
 
-TERM_KEYS = ("mask_loss", "centroid_loss", "contact_loss")  # the rows of term_history, the bits of IVLM_FIT_MASK / CENTROID / CONTACT
-DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
-
-
-def _refuse_penetration_on_device(loss_weights):
-    for key in (PENETRATION_KEY, INTRUSION_KEY):
-        if loss_weights is not None and key in loss_weights and loss_weights[key]["kick_in"] >= 0:
+def refuse_terms_the_device_loop_lacks(loss_weights):
+    for key, bit in TERMS.items():
+        if bit is None and loss_weights is not None and term_configured(key, loss_weights):
             raise ValueError(f"{key}: not available with device_loop=True (the device loop's launch sequence does not run the "
                              "term; configure kick_in = -1 or use the torch loop)")
 
 
 def fit_phases(loss_weights, max_iter):
-    """-> [(first iteration, end, bits)]: the runs of iterations over which the same terms count.  Bit k of ``bits`` is TERM_KEYS[k];
-    a term counts at iteration i when ``kick_in >= 0 and i >= kick_in`` (-1: never, 0: from the start, k: from iteration k on).
-    ``kick_in`` is a host number, so the phases are known before the loop: at most four of them."""
+    """-> [(first iteration, end, bits)]: the runs of iterations over which the same terms count (``term_counts``).  ``bits`` holds
+    the ``TERMS`` bit of each of them.  ``kick_in`` is a host number, so the phases are known before the loop: at most four of them."""
     weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
-    kicks = [weights[k]["kick_in"] if k in weights else -1 for k in TERM_KEYS]
-
-    def bits(i):
-        return sum(1 << k for k, kick in enumerate(kicks) if kick >= 0 and i >= kick)
-
+    kicks = {weights[k]["kick_in"] for k in TERM_KEYS if term_configured(k, weights)}
     edges = sorted({0, max_iter} | {k for k in kicks if 0 < k < max_iter})
-    return [(lo, hi, bits(lo)) for lo, hi in zip(edges[:-1], edges[1:])]
+    return [(lo, hi, sum(TERMS[k] for k in TERM_KEYS if term_counts(k, weights, lo))) for lo, hi in zip(edges[:-1], edges[1:])]
 
 
 def adam_reference(p, g, m, v, t, lr, betas=(0.9, 0.999), eps=1e-8):
@@ -247,21 +296,17 @@ class DevicePoseFit:
     terms and the gradients of ``ObjectPoseFit(fused_transform=True)`` at step i bit for bit; the update is torch's Adam evaluated
     in fp64 per element (``adam_reference``), so later iterations follow the torch loop within Adam's rounding, not bit for bit.
 
-    The constructor takes ``ObjectPoseFit``'s arguments (the transform is always fused) and loss_weights, max_iter, lrs = (rotation,
-    translation, scale), betas, eps > 0.  It owns rotation [B,6], translation [B,3], scale [B], the moments, the device step
+    The constructor takes ``ObjectPoseFit``'s arguments (a ``FitScene`` too; the transform is always fused) and loss_weights, max_iter,
+    lrs = (rotation, translation, scale), betas, eps > 0.  It owns rotation [B,6], translation [B,3], scale [B], the moments, the device step
     counter, history [max_iter,B] (the total BEFORE update i), term_history [max_iter,3,B] (``TERM_KEYS``; an exact 0 for a term
     that does not count), the workspace and the topology lists (from the silhouette module's cache: the one host read, here).
     step() runs one iteration, run(n=None) the remaining ones (or n).  rotation_grad / translation_grad / scale_grad are the last
     step's gradients."""
 
-    def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
-                 human_contact_probs, target_mask, focal, principal, hum_centroid_offset=None, vars=("pose",), sigma=1e-4,
-                 blur_radius=None, loss_weights=None, max_iter=250, lrs=DEFAULT_LRS, betas=(0.9, 0.999), eps=1e-8):
-        from . import _lib
-        from . import contact_pair as cp
-        from . import pose as pose_mod
-        from . import silhouette as sil
-
+    def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces=None, human_vertices=None,
+                 obj_contact_probs=None, human_contact_probs=None, target_mask=None, focal=None, principal=None, hum_centroid_offset=None,
+                 vars=("pose",), sigma=1e-4, blur_radius=None, loss_weights=None, max_iter=250, lrs=DEFAULT_LRS, betas=(0.9, 0.999),
+                 eps=1e-8):
         if not isinstance(max_iter, int) or isinstance(max_iter, bool) or max_iter < 1:
             raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
         if not set(vars):
@@ -274,48 +319,36 @@ class DevicePoseFit:
             raise ValueError(f"lrs / betas / eps: expected numbers, got {lrs!r}, {betas!r}, {eps!r}") from None
         if len(lrs) != 3 or len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas) or not eps > 0.0:
             raise ValueError(f"expected three learning rates, two betas in [0, 1) and eps > 0, got {lrs}, {betas}, {eps}")
-        _refuse_penetration_on_device(loss_weights)
+        refuse_terms_the_device_loop_lacks(loss_weights)
         weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
         self.phases = fit_phases(weights, max_iter)
         for lo, _, bits in self.phases:
             if bits == 0:
                 raise ValueError(f"loss_weights: no term counts at iteration {lo}: nothing to descend")
-        # validation of shapes, dtypes and devices by the modules whose kernels run, before the library loads
-        model = ObjectPoseFit(rotation_init, translation_init, scaling_init, obj_vertices, obj_faces, human_vertices, obj_contact_probs,
-                              human_contact_probs, target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius,
-                              fused_transform=True)
-        if not isinstance(target_mask, torch.Tensor) or target_mask.dim() != 2:
-            raise ValueError("target_mask: expected [H,W]")
-        H, W = model.target_mask.shape
-        pose_mod._validate(model.obj_vertices, model.rotation.data, model.translation.data, model.scale.data)
-        cam = sil._validate(model.obj_vertices, model.obj_faces, focal, principal, (H, W), sigma, blur_radius)
-        cp._validate(model.obj_vertices, model.human_vertices, model.object_contact_probs, model.human_contact_probs)
-        sil._validate_terms(model.target_mask.new_empty(H, W), model.target_mask)
-        if model.hum_centroid_offset.shape != (3,):
-            raise ValueError(f"hum_centroid_offset: expected [3], got {tuple(model.hum_centroid_offset.shape)}")
-        self.model = model
-        self.max_iter, self.iteration = max_iter, 0
+        self.scene = scene = FitScene.of(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask,
+                                         focal, principal, hum_centroid_offset, sigma, blur_radius)
+        self.model = model = ObjectPoseFit(rotation_init, translation_init, scaling_init, scene, vars=vars, fused_transform=True)
         self.rotation, self.translation, self.scale = model.rotation.data, model.translation.data, model.scale.data
+        cam = scene.validate(self.rotation, self.translation, self.scale)  # before the library loads
+        self.max_iter, self.iteration = max_iter, 0
         dev = self.rotation.device
-        B, N, F, N_h = self.rotation.shape[0], model.obj_vertices.shape[0], model.obj_faces.shape[0], model.human_vertices.shape[0]
+        (H, W), B = scene.target_mask.shape, self.rotation.shape[0]
+        N, F, N_h = scene.obj_vertices.shape[0], scene.obj_faces.shape[0], scene.human_vertices.shape[0]
         self.sizes = (B, N, F, H, W, N_h)
         lib = _lib.load()
-        p, q = model.object_contact_probs, model.human_contact_probs
-        if p.dtype != q.dtype:  # as contact_distance: a mixed pair goes in as fp32
-            p, q = p.float(), q.float()
+        p, q, p_dtype = contact_pair.one_dtype(scene.object_contact_probs, scene.human_contact_probs)
         optimise = (_lib.FIT_POSE if "pose" in vars else 0) | (_lib.FIT_SCALE if "scale" in vars else 0)
         with torch.cuda.device(dev):
             self.workspace, nbytes = _lib.workspace(lib.ivlm_fit_step_workspace_bytes, "DevicePoseFit", dev,
                                                     B=B, N=N, F=F, H=H, W=W, N_h=N_h)
-            f32, offsets, slots = sil._topology_of(model.obj_faces, N)
+            f32, offsets, slots = silhouette.topology_of(scene.obj_faces, N)
             zeros = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
             self._moments = [zeros(B, 6), zeros(B, 3), zeros(B), zeros(B, 6), zeros(B, 3), zeros(B)]
             self._grads = [zeros(B, 6), zeros(B, 3), zeros(B)]
             self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
             self.history, self.term_history = zeros(max_iter, B), zeros(max_iter, 3, B)
-        self._keep = (f32, offsets, slots, p.contiguous(), q.contiguous(), model.obj_vertices.contiguous(),
-                      model.human_vertices.contiguous(), model.target_mask.contiguous(), model.target_mask_centroid.contiguous(),
-                      model.hum_centroid_offset.contiguous())
+        self._keep = (f32, offsets, slots, p, q, scene.obj_vertices.contiguous(), scene.human_vertices.contiguous(),
+                      scene.target_mask.contiguous(), scene.target_mask_centroid.contiguous(), scene.hum_centroid_offset.contiguous())
         f32, offsets, slots, p, q, verts, hum, target, target_c, off = self._keep
         a = _lib.FitStepArgs()
         for name, t in (("obj_verts", verts), ("faces", f32), ("vert_face_offsets", offsets), ("vert_face_list", slots),
@@ -332,7 +365,7 @@ class DevicePoseFit:
         a.lr_rotation, a.lr_translation, a.lr_scale = lrs
         a.beta1, a.beta2, a.eps = betas[0], betas[1], eps
         a.B, a.N, a.F, a.H, a.W, a.N_h = self.sizes
-        a.p_dtype = cp.IVLM_BF16 if p.dtype == torch.bfloat16 else cp.IVLM_F32
+        a.p_dtype = p_dtype
         a.max_iter, a.optimise = max_iter, optimise
         a.fx, a.fy, a.px, a.py, _, _, a.sigma, a.blur_radius = cam
         a.w_mask, a.w_centroid, a.w_contact = (_f32(weights[k]["w"]) if k in weights else 0.0 for k in TERM_KEYS)
@@ -352,11 +385,9 @@ class DevicePoseFit:
         return [self.rotation, self.translation, self.scale, *self._moments, *self._grads, self.counter, self.history, self.term_history]
 
     def _launch(self, bits):
-        from ._lib import check, stream
-
         self._args.terms_on = bits
         with torch.cuda.device(self.rotation.device):
-            check(self._lib.ivlm_fit_step(ctypes.byref(self._args), stream()), "fit_step")
+            _lib.check(self._lib.ivlm_fit_step(ctypes.byref(self._args), _lib.stream()), "fit_step")
 
     def step(self):
         """one iteration: the total of the current parameters into history[i], then the update"""
@@ -388,12 +419,13 @@ class DevicePoseFit:
 _UNSET = object()  # fused_transform was not passed: False for the torch loop, implied by device_loop
 
 
-def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
-                    init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250, early_stop=False,
-                    sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
+def fit_object_pose(obj_vertices, obj_faces=None, human_vertices=None, obj_contact_probs=None, human_contact_probs=None, target_mask=None,
+                    focal=None, principal=None, init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250,
+                    early_stop=False, sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
                     device_loop=False, intrusion=False, human_faces=None):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
+    The scene is ``ObjectPoseFit``'s (obj_vertices may be a ``FitScene``); it is prepared once, before the loop.
     init = (R6 [B,6], T [B,3], s number or [B]) gives the B starts; None takes one start from ``contact_icp`` between the object
     vertices of contact probability > icp_threshold[0] and the human vertices of probability > icp_threshold[1] (selecting them
     reads the device once, before the loop).  early_stop ends the loop when every start has |previous - current| < 1e-6: the only
@@ -412,22 +444,21 @@ def fit_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, 
             raise ValueError("early_stop: not available with device_loop=True (it reads the device every iteration)")
         if fused_transform is not _UNSET and not fused_transform:
             raise ValueError("fused_transform=False: not available with device_loop=True (the device loop runs the fused transform)")
-        _refuse_penetration_on_device(loss_weights)
+        refuse_terms_the_device_loop_lacks(loss_weights)
     fused_transform = bool(device_loop) if fused_transform is _UNSET else fused_transform
+    # (the device loop runs neither extra term, so a scene made here for it prepares neither mesh)
+    scene = FitScene.of(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
+                        hum_centroid_offset, sigma, blur_radius, intrusion and not device_loop, None if device_loop else human_faces)
     if init is None:
-        o_sel = obj_vertices[obj_contact_probs.float() > icp_threshold[0]]
-        h_sel = human_vertices[human_contact_probs.float() > icp_threshold[1]]
+        o_sel = scene.obj_vertices[scene.object_contact_probs.float() > icp_threshold[0]]
+        h_sel = scene.human_vertices[scene.human_contact_probs.float() > icp_threshold[1]]
         if o_sel.shape[0] < 1 or h_sel.shape[0] < 1:
             raise ValueError("init=None needs contact vertices above icp_threshold on both meshes for contact_icp")
-        icp = contact_icp(o_sel.float(), h_sel.float(), max_iterations=icp_max_iterations)
+        icp = contact_icp(o_sel, h_sel, max_iterations=icp_max_iterations)
         init = (matrix_to_rot6d(icp.R), icp.T, 1.0)
     if device_loop:
-        return DevicePoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
-                             target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, loss_weights,
-                             max_iter).run().result()
-    model = ObjectPoseFit(init[0], init[1], init[2], obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs,
-                          target_mask, focal, principal, hum_centroid_offset, vars, sigma, blur_radius, fused_transform, intrusion=intrusion,
-                          human_faces=human_faces)
+        return DevicePoseFit(*init, scene, vars=vars, loss_weights=loss_weights, max_iter=max_iter).run().result()
+    model = ObjectPoseFit(*init, scene, vars=vars, fused_transform=fused_transform)
     groups = []
     if "pose" in vars:
         groups += [{"params": [model.rotation], "lr": 5e-2}, {"params": [model.translation], "lr": 1e-2}]
@@ -489,21 +520,22 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     with every configured term (kick_in >= 0) on; history[-1] is the total BEFORE the last update and is not the score.
 
     device_loop=True runs every loop on the device (``fit_object_pose(device_loop=True)``, ``DevicePoseFit``) and adds term_history
-    [iterations,3,K]; the scoring stays the forward described above.  human_faces goes to every loop and to the scoring model, so
-    that the score holds "penetration_loss" whenever loss_weights configures it (device_loop=True refuses that, see ``fit_object_pose``).
-    intrusion goes the same way, for "intrusion_loss".
+    [iterations,3,K]; the scoring stays the forward described above.  One ``FitScene`` is prepared with human_faces and intrusion and
+    serves every loop and every scoring model, so that the score holds "penetration_loss" and "intrusion_loss" whenever loss_weights
+    configures them (device_loop=True refuses that, see ``fit_object_pose``).
 
     chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
     computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
 
     -> the dict of ``fit_object_pose`` for all K starts (rotation [K,6], translation [K,3], scale [K], object_vertices [K,N,3],
     history [iterations,K]) plus scores [K], best_index (0-dim int64 device tensor, ``select_best``) and best = {rotation [6],
-    translation [3], scale [], object_vertices [N,3]} gathered with index_select.  The only host reads are those of
-    ``fit_object_pose`` and of the silhouette's topology cache, before the loop."""
+    translation [3], scale [], object_vertices [N,3]} gathered with index_select.  The only host reads are made once per search,
+    before the first loop: the contact selection for icp, the ``FitScene`` (the closedness check and the two ``MeshSDF`` when asked
+    for) and the silhouette's topology cache at the first step."""
     if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
         raise ValueError(f"chunk: expected None or an integer >= 1, got {chunk!r}")
     if device_loop:
-        _refuse_penetration_on_device(fit_kwargs.get("loss_weights"))
+        refuse_terms_the_device_loop_lacks(fit_kwargs.get("loss_weights"))
     if "early_stop" in fit_kwargs:
         raise ValueError("early_stop: not available in search_object_pose (it would make a start's result depend on chunk)")
     unknown = sorted(set(fit_kwargs) - set(_SEARCH_FIT_KWARGS))
@@ -539,17 +571,18 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
         R, T = found.R, found.T
     R6 = matrix_to_rot6d(R)
     weights = fit_kwargs.get("loss_weights")
-    every_term = max([0] + [v["kick_in"] for v in (DEFAULT_LOSS_WEIGHTS if weights is None else weights).values()])
-    scene = (obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal)
+    configured = DEFAULT_LOSS_WEIGHTS if weights is None else weights
+    every_term = max([0] + [configured[k]["kick_in"] for k in configured if term_configured(k, configured)])  # every key that is held
+    scene = FitScene(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
+                     fit_kwargs.pop("hum_centroid_offset", None), fit_kwargs.pop("sigma", 1e-4), fit_kwargs.pop("blur_radius", None),
+                     intrusion, human_faces)
     step = K if chunk is None else chunk
     parts, scores = [], []
     for lo in range(0, K, step):
         sel = slice(lo, min(lo + step, K))
-        out = fit_object_pose(*scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop,
-                              human_faces=human_faces, intrusion=intrusion, **fit_kwargs)
-        final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], *scene, fit_kwargs.get("hum_centroid_offset"),
-                              fit_kwargs.get("vars", ("pose",)), fit_kwargs.get("sigma", 1e-4), fit_kwargs.get("blur_radius"),
-                              fused_transform=True, human_faces=human_faces, intrusion=intrusion)
+        out = fit_object_pose(scene, init=(R6[sel], T[sel], s[sel]), fused_transform=True, device_loop=device_loop, **fit_kwargs)
+        final = ObjectPoseFit(out["rotation"], out["translation"], out["scale"], scene, vars=fit_kwargs.get("vars", ("pose",)),
+                              fused_transform=True)
         with torch.no_grad():
             scores.append(final(weights, step=every_term)[0])
         parts.append(out)

@@ -23,37 +23,24 @@ anywhere.  The same bits every call, and for a pose whatever the batch around it
 """
 from __future__ import annotations
 
-import re
+import functools
 
 import numpy as np
 import torch
-from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import IvlmError, check
-from .pose import _validate as _validate_pose
+from ._args import ValueWithGradients, check_devices, check_points, side
+from ._lib import check, header_constant
+from .pose import pose_arguments
 
-
-def _header_constant(name):
-    m = re.search(rf"#define\s+{name}\s+(\d+)", open(_lib.HEADER_PATH).read())
-    if not m:
-        raise IvlmError(f"include/ivlm_hip.h does not define {name}")
-    return int(m.group(1))
-
-
-TILE = _header_constant("IVLM_MESH_SDF_TILE")    # faces per LDS tile
-CHUNK = _header_constant("IVLM_MESH_SDF_CHUNK")  # faces per grid chunk: the longest serial fp32 accumulation of the winding sum
+TILE = header_constant("IVLM_MESH_SDF_TILE")    # faces per LDS tile
+CHUNK = header_constant("IVLM_MESH_SDF_CHUNK")  # faces per grid chunk: the longest serial fp32 accumulation of the winding sum
 
 
 def _check_points(points):
     """-> batched; raises before anything touches the library"""
-    if not isinstance(points, torch.Tensor):
-        raise ValueError(f"points: expected a tensor, got {type(points).__name__}")
-    if points.dim() not in (2, 3) or points.shape[-1] != 3 or points.shape[-2] < 1 or points.shape[0] < 1:
-        raise ValueError(f"points: expected [N,3] or [B,N,3] with N >= 1, got {tuple(points.shape)}")
-    if points.dtype != torch.float32:
-        raise ValueError(f"points: expected float32, got {points.dtype}")
-    _lib.require_gpu(((points, "points"),))
+    check_points(points, "points")
+    check_devices([(points, "points", 2)])
     return points.dim() == 3
 
 
@@ -140,7 +127,7 @@ class MeshSDF:
         No autograd: the outputs are constants."""
         batched = _check_points(points)
         lib = _lib.load()
-        p = (points if batched else points.unsqueeze(0)).detach().contiguous()
+        p, _ = side(points.detach(), 2)
         B, N = p.shape[0], p.shape[1]
         with torch.cuda.device(self.device):
             ws, nbytes = self._workspace(lib, p, B, N)
@@ -153,14 +140,15 @@ class MeshSDF:
         out = (sdf, closest, face, winding)
         return out if batched else tuple(t[0] for t in out)
 
-    def _penetration(self, p, want_grad):
-        """p [B,N,3] contiguous -> (L [B], dL/dp [B,N,3] | None)"""
+    def _penetration(self, points, need):
+        """-> (L [B], dL/dpoints per pose [B,N,3] | None)"""
         lib = _lib.load()
+        p, _ = side(points, 2)
         B, N = p.shape[0], p.shape[1]
         with torch.cuda.device(self.device):
             ws, nbytes = self._workspace(lib, p, B, N)
             value = torch.empty(B, dtype=torch.float32, device=self.device)
-            grad = torch.empty(B, N, 3, dtype=torch.float32, device=self.device) if want_grad else None
+            grad = torch.empty(B, N, 3, dtype=torch.float32, device=self.device) if need[0] else None
             check(lib.ivlm_mesh_sdf_penetration(self.plan.data_ptr(), p.data_ptr(), B, N, value.data_ptr(), _lib.ptr(grad),
                                                 ws.data_ptr(), nbytes, _lib.stream()), "mesh_sdf_penetration")
         return value, grad
@@ -170,13 +158,13 @@ class MeshSDF:
         points, once: the forward launch computes dL/dpoints when points requires grad and saves it as a constant, so a double
         backward (create_graph=True) raises.  Points outside the mesh's bounding box cost no face sweep and get an exact zero row."""
         batched = _check_points(points)
-        value = _Penetration.apply(points, self)
+        value = ValueWithGradients.apply(self._penetration, points)
         return value if batched else value[0]
 
-
     def _intrusion(self, h, r6, t, s, need):
-        """h [N,3], r6 [B,6], t [B,3], s [B], contiguous -> (L [B], dL/drot6d | None, dL/dt | None, dL/ds | None)"""
+        """h [N,3] contiguous, r6 [B,6], t [B,3], s [B] -> (L [B], dL/drot6d | None, dL/dt | None, dL/ds | None)"""
         lib = _lib.load()
+        r6, t, s = r6.contiguous(), t.contiguous(), s.contiguous()
         B, N = r6.shape[0], h.shape[0]
         dev = self.device
         with torch.cuda.device(dev):
@@ -196,58 +184,11 @@ class MeshSDF:
         the un-posed point to this mesh, shape [B] or [].  Differentiable in rot6d, translation and a tensor scaling, once: the
         forward launch computes the gradients that are needed and saves them as constants, so a double backward raises.  A pose
         whose scaling is not > 0 gets NaN.  The mesh must be closed and outward (``check_closed``)."""
-        if not isinstance(points, torch.Tensor):
-            raise ValueError(f"points: expected a tensor, got {type(points).__name__}")
-        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
-            raise ValueError(f"points: expected [N,3] with N >= 1 (shared by the batch), got {tuple(points.shape)}")
-        if points.dtype != torch.float32:
-            raise ValueError(f"points: expected float32, got {points.dtype}")
-        if points.requires_grad:
-            raise ValueError("points: requires_grad is set, and no gradient flows to the points of intrusion (detach them: the human "
-                             "is a constant)")
-        B, batched = _validate_pose(points, rot6d, translation, scaling)
+        r6, t, s, batched = pose_arguments(points, rot6d, translation, scaling, name="points")
         if points.device != self.device:
             raise ValueError(f"points: expected a tensor on {self.device}, got {points.device}")
-        r6 = rot6d if batched else rot6d.unsqueeze(0)
-        t = translation if batched else translation.unsqueeze(0)
-        if isinstance(scaling, torch.Tensor):
-            s = scaling.reshape(-1).expand(B)
-        else:
-            s = torch.full((B,), float(scaling), dtype=torch.float32, device=self.device)
-        value = _Intrusion.apply(points, r6, t, s, self)
+        value = ValueWithGradients.apply(functools.partial(self._intrusion, points.contiguous()), r6, t, s)
         return value if batched else value[0]
-
-
-class _Intrusion(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, points, rot6d, trans, scale, mesh):
-        value, *ctx.grads = mesh._intrusion(points.contiguous(), rot6d.contiguous(), trans.contiguous(), scale.contiguous(),
-                                            ctx.needs_input_grad[1:4])
-        return value
-
-    @staticmethod
-    @once_differentiable  # the saved gradients are constants: a double backward raises instead of returning wrong second derivatives
-    def backward(ctx, grad_value):
-        g_r, g_t, g_s = ctx.grads
-        return (None, None if g_r is None else grad_value.reshape(-1, 1) * g_r, None if g_t is None else grad_value.reshape(-1, 1) * g_t,
-                None if g_s is None else grad_value * g_s, None)
-
-
-class _Penetration(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, points, mesh):
-        p = (points if points.dim() == 3 else points.unsqueeze(0)).contiguous()
-        value, grad = mesh._penetration(p, ctx.needs_input_grad[0])
-        ctx.grad = grad  # dL/dpoints per pose: backward only scales it
-        ctx.shape = tuple(points.shape)
-        return value
-
-    @staticmethod
-    @once_differentiable  # the saved gradient is a constant: a double backward raises instead of returning wrong second derivatives
-    def backward(ctx, grad_value):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        return (grad_value.reshape(-1, 1, 1) * ctx.grad).reshape(ctx.shape), None
 
 
 def mesh_signed_distance(points, vertices, faces):

@@ -17,13 +17,14 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import check
+from ._args import check_devices, check_points
+from ._lib import check, header_constant
 
 # Error model of the kernels, in units of 2^-24 (IVLM_POSE_* of include/ivlm_hip.h); tests derive their bounds from these.
-POSE_CHUNK = 1024  # vertices per block of the backward's partial sums (IVLM_POSE_CHUNK): a function of nothing but the build
-L_CHAIN = 1        # every term is converted to fp64 before it is added (IVLM_POSE_CHAIN)
-FWD_ULPS = 6       # |delta y_nj| <= FWD_ULPS 2^-24 (s sum_i |v_ni| |R_ij| + |t_j|)
-GRAD_ULPS = 16     # |delta dL/dtheta| <= GRAD_ULPS 2^-24 sum_n |d y_n / d theta| |g_n|
+POSE_CHUNK = header_constant("IVLM_POSE_CHUNK")     # vertices per block of the backward's partial sums: a function of nothing but the build
+L_CHAIN = header_constant("IVLM_POSE_CHAIN")        # every term is converted to fp64 before it is added
+FWD_ULPS = header_constant("IVLM_POSE_FWD_ULPS")    # |delta y_nj| <= FWD_ULPS 2^-24 (s sum_i |v_ni| |R_ij| + |t_j|)
+GRAD_ULPS = header_constant("IVLM_POSE_GRAD_ULPS")  # |delta dL/dtheta| <= GRAD_ULPS 2^-24 sum_n |d y_n / d theta| |g_n|
 
 
 def gram_schmidt_backward(rot6d, grad_R):
@@ -58,16 +59,13 @@ def gram_schmidt_backward(rot6d, grad_R):
     return torch.stack((ga1, ga2), dim=-1).reshape(6)
 
 
-def _validate(vertices, rot6d, translation, scaling):
-    """-> (B, batched): raises before anything touches the library"""
-    if not isinstance(vertices, torch.Tensor):
-        raise ValueError(f"vertices: expected a tensor, got {type(vertices).__name__}")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1:
-        raise ValueError(f"vertices: expected [N,3] with N >= 1 (one mesh shared by the batch), got {tuple(vertices.shape)}")
-    if vertices.dtype != torch.float32:
-        raise ValueError(f"vertices: expected float32, got {vertices.dtype}")
+def pose_arguments(vertices, rot6d, translation, scaling, name="vertices"):
+    """The arguments of a call that poses ``vertices`` [N,3] (a constant: it must not require grad) B times: rot6d [B,6] with
+    translation [B,3] and scaling a number, [B] or [B,1], or one pose ([6], [3], a scalar).  Raises before anything touches the
+    library; -> (r6 [B,6], t [B,3], s [B], batched)."""
+    check_points(vertices, name, batch=False)
     if vertices.requires_grad:
-        raise ValueError("vertices: the mesh is a constant of pose_transform, it must not require grad")
+        raise ValueError(f"{name}: requires_grad is set, and it is a constant of this call: it must not require grad (detach it)")
     if not isinstance(rot6d, torch.Tensor):
         raise ValueError(f"rot6d: expected a tensor, got {type(rot6d).__name__}")
     if rot6d.dim() not in (1, 2) or rot6d.shape[-1] != 6 or rot6d.shape[0] < 1:
@@ -83,13 +81,13 @@ def _validate(vertices, rot6d, translation, scaling):
         raise ValueError(f"translation: expected {list(want)} (one per pose of rot6d), got {tuple(translation.shape)}")
     if translation.dtype != torch.float32:
         raise ValueError(f"translation: expected float32, got {translation.dtype}")
-    named = [(vertices, "vertices"), (rot6d, "rot6d"), (translation, "translation")]
+    named = [(vertices, name, 2), (rot6d, "rot6d", 1), (translation, "translation", 1)]
     if isinstance(scaling, torch.Tensor):
         if scaling.numel() not in (1, B) or scaling.dim() > 2 or (scaling.dim() == 2 and scaling.shape[1] != 1):
             raise ValueError(f"scaling: expected a number, [{B}] or [{B},1], got {tuple(scaling.shape)}")
         if scaling.dtype != torch.float32:
             raise ValueError(f"scaling: expected float32, got {scaling.dtype}")
-        named.append((scaling, "scaling"))
+        named.append((scaling, "scaling", 0))
     else:
         try:
             ok = math.isfinite(float(scaling))
@@ -97,11 +95,12 @@ def _validate(vertices, rot6d, translation, scaling):
             raise ValueError(f"scaling: expected a number or a tensor, got {scaling!r}") from None
         if not ok:
             raise ValueError(f"scaling: expected a finite number, got {scaling!r}")
-    _lib.require_gpu(named)
-    devs = {t.device for t, _ in named}
-    if len(devs) != 1:
-        raise ValueError(f"all tensors must be on one device, got {sorted(str(d) for d in devs)}")
-    return B, batched
+    check_devices(named)
+    if isinstance(scaling, torch.Tensor):
+        s = scaling.reshape(-1).expand(B)
+    else:
+        s = torch.full((B,), float(scaling), dtype=torch.float32, device=vertices.device)
+    return (rot6d, translation, s, True) if batched else (rot6d.unsqueeze(0), translation.unsqueeze(0), s, False)
 
 
 class _PoseTransform(torch.autograd.Function):
@@ -150,13 +149,7 @@ def pose_transform(vertices, rot6d, translation, scaling=1.0):
     small block per pose that adds them in order and chains through the Gram-Schmidt, ``gram_schmidt_backward``); a parameter that
     does not require grad is not computed.  No atomics and no host read: the same bits every call, for a pose whatever the batch
     around it and its place in it.  Documented errors: ``FWD_ULPS`` and ``GRAD_ULPS``."""
-    B, batched = _validate(vertices, rot6d, translation, scaling)
-    r6 = rot6d if batched else rot6d.unsqueeze(0)
-    t = translation if batched else translation.unsqueeze(0)
-    if isinstance(scaling, torch.Tensor):
-        s = scaling.reshape(-1).expand(B)
-    else:
-        s = torch.full((B,), float(scaling), dtype=torch.float32, device=vertices.device)
+    r6, t, s, batched = pose_arguments(vertices, rot6d, translation, scaling)
     out = _PoseTransform.apply(vertices, r6, t, s)
     return out if batched else out.view(vertices.shape[0], 3)
 

@@ -19,16 +19,17 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import check
+from ._args import check_devices, check_points, side
+from ._lib import check, header_constant
 
 # Error model of the kernels, in units of 2^-24 (IVLM_SILHOUETTE_* of include/ivlm_hip.h); tests derive their bounds from these.
 # With M = the largest of H, W, |u|, |v|, |u - px|, |v - py| over a face's vertices:
-POS_ULPS = 12    # |delta sqrt(d_k)| <= POS_ULPS 2^-24 M
-REL_ULPS = 6     # plus a relative REL_ULPS 2^-24 on d_k
-EXP_ULPS = 3     # plus an absolute EXP_ULPS 2^-24 on the exponent argument s_k / sigma
-T_ULPS = 8       # |delta t| <= T_ULPS 2^-24 |p - a| / |b - a| (gradients only)
-L_CHAIN = 32     # fp32 additions per lane of the backward before fp64 takes over (IVLM_SILHOUETTE_CHAIN)
-TERMS_CHAIN = 1  # silhouette_terms converts every element to fp64 before it is added (IVLM_SILHOUETTE_TERMS_CHAIN)
+POS_ULPS = header_constant("IVLM_SILHOUETTE_POS_ULPS")        # |delta sqrt(d_k)| <= POS_ULPS 2^-24 M
+REL_ULPS = header_constant("IVLM_SILHOUETTE_REL_ULPS")        # plus a relative REL_ULPS 2^-24 on d_k
+EXP_ULPS = header_constant("IVLM_SILHOUETTE_EXP_ULPS")        # plus an absolute EXP_ULPS 2^-24 on the exponent argument s_k / sigma
+T_ULPS = header_constant("IVLM_SILHOUETTE_T_ULPS")            # |delta t| <= T_ULPS 2^-24 |p - a| / |b - a| (gradients only)
+L_CHAIN = header_constant("IVLM_SILHOUETTE_CHAIN")            # fp32 additions per lane of the backward before fp64 takes over
+TERMS_CHAIN = header_constant("IVLM_SILHOUETTE_TERMS_CHAIN")  # silhouette_terms converts every element to fp64 before it is added
 TERMS_WORKSPACE_ROW_BYTES = 40  # IVLM_SILHOUETTE_TERMS_WORKSPACE(B, H) = B H x this: five fp64 sums per image row
 
 # id(faces tensor) -> (weak reference to that tensor, its version, N, (faces int32, vertex -> face-slot offsets, slots)).  An entry
@@ -43,14 +44,9 @@ def default_blur_radius(sigma):
     return float(sigma) * math.log(1.0 / 1e-4 - 1.0)
 
 
-def _validate(verts, faces, focal, principal, image_size, sigma, blur_radius):
+def validate(verts, faces, focal, principal, image_size, sigma, blur_radius):
     """-> (fx, fy, px, py, H, W, sigma, blur_radius): raises before anything touches the library"""
-    if not isinstance(verts, torch.Tensor):
-        raise ValueError(f"verts: expected a tensor, got {type(verts).__name__}")
-    if verts.dim() not in (2, 3) or verts.shape[-1] != 3 or verts.shape[-2] < 1 or verts.shape[0] < 1:
-        raise ValueError(f"verts: expected [N,3] or [B,N,3] with N >= 1, got {tuple(verts.shape)}")
-    if verts.dtype != torch.float32:
-        raise ValueError(f"verts: expected float32 vertices, got {verts.dtype}")
+    check_points(verts, "verts")
     if not isinstance(faces, torch.Tensor):
         raise ValueError(f"faces: expected a tensor, got {type(faces).__name__}")
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
@@ -78,13 +74,11 @@ def _validate(verts, faces, focal, principal, image_size, sigma, blur_radius):
     blur_radius = default_blur_radius(sigma) if blur_radius is None else float(blur_radius)
     if not (blur_radius >= 0 and math.isfinite(blur_radius)):
         raise ValueError(f"blur_radius: expected a finite number >= 0, got {blur_radius}")
-    _lib.require_gpu(((verts, "verts"), (faces, "faces")))
-    if verts.device != faces.device:
-        raise ValueError(f"all tensors must be on one device, got {sorted((str(verts.device), str(faces.device)))}")
+    check_devices([(verts, "verts", 2), (faces, "faces", 2)])
     return fx, fy, px, py, H, W, sigma, blur_radius
 
 
-def _topology_of(faces, n):
+def topology_of(faces, n):
     """faces [F,3] -> (faces int32 contiguous, offsets int32 [N+1], slots int32 [3F]): per vertex the slots (face * 3 + corner) of
     its incident faces in ascending order.  Built once per faces tensor (this is where the indices are range-checked, the one host
     read) and kept while that tensor object lives and its version counter stands (a write that autograd's counter does not see,
@@ -110,14 +104,17 @@ def _topology_of(faces, n):
     return value
 
 
+_topology_of = topology_of  # its name before fit.DevicePoseFit became a caller from outside this module
+
+
 class _SoftSilhouette(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces, cam):
         fx, fy, px, py, H, W, sigma, blur = cam
         lib = _lib.load()
-        v = (verts if verts.dim() == 3 else verts.unsqueeze(0)).contiguous()
+        v, _ = side(verts, 2)
         B, N = v.shape[0], v.shape[1]
-        f32, offsets, slots = _topology_of(faces, N)
+        f32, offsets, slots = topology_of(faces, N)
         F = f32.shape[0]
         dev = v.device
         with torch.cuda.device(dev):
@@ -138,7 +135,7 @@ class _SoftSilhouette(torch.autograd.Function):
     def backward(ctx, grad_alpha):
         fx, fy, px, py, H, W, sigma, blur = ctx.cam
         verts, offsets, slots, ws = ctx.saved_tensors
-        v = (verts if verts.dim() == 3 else verts.unsqueeze(0)).contiguous()
+        v, _ = side(verts, 2)
         nbytes, F = ctx.sizes
         lib = _lib.load()
         B, N = v.shape[0], v.shape[1]
@@ -160,11 +157,11 @@ def soft_silhouette(verts, faces, focal, principal, image_size, sigma=1e-4, blur
     backward raises.  The vertex-to-face incidence lists of a faces tensor are built (and its indices range-checked, one host read)
     on first use and reused while that tensor object lives unmodified; everything else is enqueued on the current stream without host
     synchronisation.  The same bits every call, for a pose whatever the batch around it."""
-    cam = _validate(verts, faces, focal, principal, image_size, sigma, blur_radius)
+    cam = validate(verts, faces, focal, principal, image_size, sigma, blur_radius)
     return _SoftSilhouette.apply(verts, faces, cam)
 
 
-def _validate_terms(alpha, target_mask):
+def validate_terms(alpha, target_mask):
     if not isinstance(alpha, torch.Tensor):
         raise ValueError(f"alpha: expected a tensor, got {type(alpha).__name__}")
     if alpha.dim() not in (2, 3) or min(alpha.shape) < 1:
@@ -180,11 +177,9 @@ def _validate_terms(alpha, target_mask):
         raise ValueError(f"target_mask: expected float32, bool or uint8, got {target_mask.dtype}")
     ba = alpha.shape[0] if alpha.dim() == 3 else 1
     bt = target_mask.shape[0] if target_mask.dim() == 3 else 1
-    if bt not in (1, ba):
+    if bt not in (1, ba):  # (not batch_size: a batch of targets does not make a batch of one alpha)
         raise ValueError(f"target_mask: batch size {bt} does not broadcast with {ba}")
-    _lib.require_gpu(((alpha, "alpha"), (target_mask, "target_mask")))
-    if alpha.device != target_mask.device:
-        raise ValueError(f"all tensors must be on one device, got {sorted((str(alpha.device), str(target_mask.device)))}")
+    check_devices([(alpha, "alpha", 2), (target_mask, "target_mask", 2)])
 
 
 def _terms_call(lib, shape, a, t, sums, loss, centroid, g_loss, g_centroid, g_alpha, ws):
@@ -200,7 +195,7 @@ class _SilhouetteTerms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, alpha, target):
         lib = _lib.load()
-        a = (alpha if alpha.dim() == 3 else alpha.unsqueeze(0)).contiguous()
+        a, _ = side(alpha, 2)
         B, H, W = a.shape
         dev = a.device
         with torch.cuda.device(dev):
@@ -235,8 +230,7 @@ def silhouette_terms(alpha, target_mask):
     is mirrored; it is 1 when both images are empty.  centroid [2] or [B,2] = (sum i alpha, sum j alpha) / sum alpha in integer
     (row, col) index units as ``calculate_centroid`` has it; the image centre (H / 2, W / 2) with zero gradient when sum alpha ==
     0.  Sums are fp64 in a fixed order; no ``nonzero``, no host synchronisation.  Differentiable in alpha, once."""
-    _validate_terms(alpha, target_mask)
-    t = target_mask.detach()
-    t = (t if t.dim() == 3 else t.unsqueeze(0)).to(torch.float32).contiguous()
+    validate_terms(alpha, target_mask)
+    t, _ = side(target_mask.detach().to(torch.float32), 2)
     loss, centroid, _ = _SilhouetteTerms.apply(alpha, t)
     return (loss, centroid) if alpha.dim() == 3 else (loss[0], centroid[0])

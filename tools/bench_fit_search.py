@@ -177,12 +177,15 @@ def main():
             if "step_on_us_rounds" in p:  # the parent's step with the fused transform
                 r["parent_step_on_us_rounds"] = p["step_on_us_rounds"]
                 r["parent_step_on_us_median"] = p["step_on_us_median"]
-            if "step_torch_loop_us_rounds" in p:  # the parent's whole iteration with the fused transform
-                r["parent_torch_loop_us_rounds"] = p["step_torch_loop_us_rounds"]
-                r["parent_torch_loop_us_median"] = p["step_torch_loop_us_median"]
+            for mode in ("torch_loop", "device_loop"):  # the parent's whole iteration with the fused transform, in either loop
+                if f"step_{mode}_us_rounds" in p:
+                    r[f"parent_{mode}_us_rounds"] = p[f"step_{mode}_us_rounds"]
+                    r[f"parent_{mode}_us_median"] = p[f"step_{mode}_us_median"]
         if "search" in base and "search" in result:
-            result["search"]["parent_search_ms_rounds"] = base["search"]["search_ms_rounds"]
-            result["search"]["parent_search_ms_median"] = base["search"]["search_ms_median"]
+            for name in ("search", "search_device_loop"):
+                if f"{name}_ms_rounds" in base["search"]:
+                    result["search"][f"parent_{name}_ms_rounds"] = base["search"][f"{name}_ms_rounds"]
+                    result["search"][f"parent_{name}_ms_median"] = base["search"][f"{name}_ms_median"]
     if a.out:
         with open(a.out, "w") as f:
             json.dump(result, f, indent=1)
