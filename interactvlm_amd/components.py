@@ -33,6 +33,43 @@ def _stack_views(seg_maps: Sequence[torch.Tensor]) -> torch.Tensor:
     return t.to(torch.float32).contiguous()
 
 
+class _PlanCache:
+    """The policy of the predictors whose tables come from files: a table set seen for the first time is streamed and nothing of
+    it kept; one that comes back is inverted once into a lift plan, and the plan kept - the ``capacity`` most recently used ones
+    (~40 MB of HBM per mesh plan).  The record of sets seen once is bounded too (oldest first)."""
+
+    def __init__(self, capacity, seen_capacity=4096):
+        self.capacity, self.seen_capacity = capacity, seen_capacity
+        self._plans = collections.OrderedDict()
+        self._seen_once = collections.OrderedDict()
+
+    def __len__(self):
+        return len(self._plans)
+
+    def get(self, key):
+        """the kept plan of ``key`` (now the most recently used) or None"""
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+        return plan
+
+    def plan_for(self, key, build):
+        """-> the plan to gather through - kept, or (second sight of ``key``) made by ``build()`` now and kept - or None: stream
+        (first sight, or key None: tables without an identity)"""
+        if key is None:
+            return None
+        plan = self.get(key)
+        if plan is None and self._seen_once.pop(key, False):
+            plan = self._plans[key] = build()
+            while len(self._plans) > self.capacity:
+                self._plans.popitem(last=False)
+        elif plan is None:
+            self._seen_once[key] = True
+            while len(self._seen_once) > self.seen_capacity:
+                self._seen_once.popitem(last=False)
+        return plan
+
+
 class HumanContact3DPredictor(torch.nn.Module):
     """Soft bary-weighted multi-view vote onto the 6890 SMPL-topology vertices (components.py:195-277)."""
 
@@ -100,9 +137,7 @@ class ObjectMeshContact3DPredictor(torch.nn.Module):
         # lift plans of lift2d_dict.pkl files seen at least TWICE, least-recently-used first (a dataset evaluation visits one
         # pkl per object: a single-use table goes through the streaming dense kernel and is never inverted or kept; ~40 MB of
         # HBM per cached plan, bounded)
-        self._plans = collections.OrderedDict()
-        self._seen_once = collections.OrderedDict()
-        self.max_plans = 8
+        self._plans = _PlanCache(8)
         # record_lift (set by the caller for the span of a call): last_lift = ("plan", plan, logits) or ("dense", None, None) says
         # how the last lift ran, for the band census of the pixels it selected from (model.evaluate(exact_sets=...))
         self.record_lift = False
@@ -132,26 +167,16 @@ class ObjectMeshContact3DPredictor(torch.nn.Module):
         dtype = seg_maps[0].dtype
         logits = _stack_views(seg_maps)[:, : self.multiview_channels].contiguous()
         V = logits.shape[1]
-        plan = self._plans.get(cache_key) if cache_key is not None else None
+
+        def tables_on_device():
+            return (torch.as_tensor(vid_np[:V]).to(device=device, dtype=torch.int32).contiguous(),
+                    torch.as_tensor(bary_np[:V]).to(device=device, dtype=torch.float32).contiguous())
+
+        plan = self._plans.plan_for(cache_key, lambda: ops.LiftPlan(*tables_on_device(), nv))
         if plan is not None:
-            self._plans.move_to_end(cache_key)
             out = ops.lift_mesh_plan(logits, plan, mode=1, param=self.threshold)
-        else:
-            vid = torch.as_tensor(vid_np[:V]).to(device=device, dtype=torch.int32).contiguous()
-            bary = torch.as_tensor(bary_np[:V]).to(device=device, dtype=torch.float32).contiguous()
-            if cache_key is not None and cache_key in self._seen_once:  # the file came back: invert once, reuse from now on
-                del self._seen_once[cache_key]
-                plan = ops.LiftPlan(vid, bary, nv)
-                self._plans[cache_key] = plan
-                while len(self._plans) > self.max_plans:
-                    self._plans.popitem(last=False)
-                out = ops.lift_mesh_plan(logits, plan, mode=1, param=self.threshold)
-            else:  # first sight (or no file identity): stream the dense tables once, keep nothing on the device
-                if cache_key is not None:
-                    self._seen_once[cache_key] = True
-                    while len(self._seen_once) > 4096:
-                        self._seen_once.popitem(last=False)
-                out = ops.lift_mesh_dense(logits, vid, bary, nv, mode=1, param=self.threshold)
+        else:  # first sight (or no file identity): stream the dense tables once, keep nothing on the device
+            out = ops.lift_mesh_dense(logits, *tables_on_device(), nv, mode=1, param=self.threshold)
         if self.record_lift:
             self.last_lift = ("plan", plan, logits) if plan is not None else ("dense", None, None)
         return out.to(dtype)
@@ -159,8 +184,9 @@ class ObjectMeshContact3DPredictor(torch.nn.Module):
     def forward_inference(self, seg_maps, device, dtype, ds_names=None, lift2d_dict_path=None):
         st = os.stat(lift2d_dict_path)
         key = ("lift2d", os.path.abspath(lift2d_dict_path), st.st_mtime_ns, st.st_size)
-        if key in self._plans:
-            return self._lift(seg_maps, (None, None, self._plans[key].num_vertices), cache_key=key)
+        plan = self._plans.get(key)
+        if plan is not None:  # (no need to read the file again)
+            return self._lift(seg_maps, (None, None, plan.num_vertices), cache_key=key)
         tables = self._load_lift2d(lift2d_dict_path)
         print(f"Num vertices: {tables[2]}")
         return self._lift(seg_maps, tables, cache_key=key)
@@ -196,8 +222,7 @@ class ObjectPCAfford3DPredictor(torch.nn.Module):
         self._map_cache = {}
         # a p2pmap set that comes back (second sight of the same files) is inverted once into a point-major plan and kept (LRU of
         # 16): the plan gather is deterministic and moves ~1/10 of the bytes of the streaming kernel; single-use maps stream
-        self._plans = {}
-        self._seen = {}
+        self._plans = _PlanCache(16)
 
     def _maps_for(self, mask_paths, device):
         key = tuple(mask_paths[: self.multiview_channels])
@@ -222,15 +247,8 @@ class ObjectPCAfford3DPredictor(torch.nn.Module):
             keys = [tuple(mask_paths_list[b][: self.multiview_channels]) for b in idx]
             stream_rows = []
             for r, (b, key) in enumerate(zip(idx, keys)):
-                plan = self._plans.get(key)
-                if plan is None and self._seen.get(key, 0) >= 1:  # second sight: invert once
-                    plan = ops.LiftPlan.from_points(self._maps_for(mask_paths_list[b], device), self.num_points)
-                    if len(self._plans) >= 16:
-                        self._plans.pop(next(iter(self._plans)))
-                    self._plans[key] = plan
-                self._seen[key] = self._seen.get(key, 0) + 1
-                if len(self._seen) > 4096:
-                    self._seen.clear()
+                plan = self._plans.plan_for(key, lambda: ops.LiftPlan.from_points(self._maps_for(mask_paths_list[b], device),
+                                                                                  self.num_points))
                 if plan is not None:
                     out[b] = ops.lift_points_plan(probs[r: r + 1], plan)[0]
                 else:

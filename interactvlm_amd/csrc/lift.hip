@@ -13,6 +13,8 @@
 //   * "dense" (pixel-major streaming): for single-use tables. 16-byte coalesced loads of
 //     logits/ids/weights, votes privatised in LDS (2*Nv floats <= 160 KB), one flush per block.
 // Both are HBM/L2-bound byte shuffles: no MFMA here by design.
+#include <type_traits>
+
 #include "bilinear.h"
 
 namespace {
@@ -310,27 +312,47 @@ __global__ __launch_bounds__(kBlock) void lift_plan_lowres_kernel(const T* __res
 // dense streaming variant
 // =============================================================================================
 // grid (chunks, V, B); each thread walks groups of 4 consecutive pixels (16-byte loads).
+//
+// The frame of both streaming kernels: where block (chunk, v, b) votes and where its votes end up.
+// USE_LDS: the block votes into an LDS table [2][n] (votes, then weights), owns a slab [2][n] of the workspace ([B,V,chunks,2,n]) and
+// writes the table there with plain stores; the finalize kernel sums the slabs in chunk order.  (Device-scope float atomics execute
+// on the memory side of the 8 XCDs: flushing through them cost ~4 us per block-per-CU - tools/sweep_lift_blocks.py - and needed a
+// memset launch.)
+// !USE_LDS (2 n floats do not fit the LDS): one zeroed slab per (b, v) - the workspace is [B,V,2,n] - and global atomics into it.
+template <bool USE_LDS>
+struct VoteSlab {
+    float *votes, *cnt;  // what the vote loop adds to (atomicAdd)
+    float* slab;
+    int n;
+
+    __device__ __forceinline__ VoteSlab(float* __restrict__ ws, int V, int n_, unsigned char* smem) : n(n_) {
+        const int v = blockIdx.y, b = blockIdx.z;
+        slab = ws + ((((int64_t)b * V + v) * (USE_LDS ? gridDim.x : 1) + (USE_LDS ? blockIdx.x : 0)) * 2) * n;
+        votes = USE_LDS ? reinterpret_cast<float*>(smem) : slab;
+        cnt = votes + n;
+        if (USE_LDS) {
+            for (int i = threadIdx.x; i < 2 * n; i += kStream) votes[i] = 0.0f;
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ void write_out() const {  // by every thread of the block, after its last vote
+        if (USE_LDS) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < 2 * n; i += kStream) slab[i] = votes[i];
+        }
+    }
+};
+
 template <int MODE, bool USE_LDS>
 __global__ __launch_bounds__(kStream) void lift_dense_kernel(const float* __restrict__ logits,
                                                             const int32_t* __restrict__ vid,
                                                             const float* __restrict__ bary, int V, int64_t HW, int nv,
-                                                            float param, float* __restrict__ ws /*[B,V,2,nv]*/) {
+                                                            float param, float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* s_votes = reinterpret_cast<float*>(smem);
-    float* s_cnt = s_votes + nv;
     const int v = blockIdx.y, b = blockIdx.z;
-    // USE_LDS: every block owns a slab [2][nv] of the workspace ([B,V,chunks,2,nv]) and writes its LDS table there with plain
-    // stores; the finalize kernel sums the slabs in chunk order.  (Device-scope float atomics execute on the memory side of the 8
-    // XCDs: flushing through them cost ~4 us per block-per-CU - tools/sweep_lift_blocks.py - and needed a memset launch.)
-    // !USE_LDS (2 nv floats do not fit the LDS): one zeroed slab per (b, v), global atomics.
-    float* g_votes = ws + ((((int64_t)b * V + v) * (USE_LDS ? gridDim.x : 1) + (USE_LDS ? blockIdx.x : 0)) * 2) * nv;
-    float* g_cnt = g_votes + nv;
-    if (USE_LDS) {
-        for (int i = threadIdx.x; i < 2 * nv; i += kStream) s_votes[i] = 0.0f;
-        __syncthreads();
-    }
-    float* votes = USE_LDS ? s_votes : g_votes;
-    float* cnt = USE_LDS ? s_cnt : g_cnt;
+    const VoteSlab<USE_LDS> table(ws, V, nv, smem);
+    float* const votes = table.votes;
+    float* const cnt = table.cnt;
 
     const float* lg = logits + ((int64_t)b * V + v) * HW;
     const int32_t* vd = vid + (int64_t)v * HW * 3;
@@ -395,10 +417,7 @@ __global__ __launch_bounds__(kStream) void lift_dense_kernel(const float* __rest
         }
         flush();
     }
-    if (USE_LDS) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * nv; i += kStream) g_votes[i] = s_votes[i];
-    }
+    table.write_out();
 }
 
 // The votes of an (image, view) arrive as `chunks` slabs [2][n] (one per block of the streaming kernel).  Block = 32 consecutive
@@ -453,17 +472,10 @@ __global__ __launch_bounds__(kStream) void lift_points_kernel(const float* __res
                                                              const int32_t* __restrict__ pid, int pid_batched, int V,
                                                              int64_t HW, int np, float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* s_votes = reinterpret_cast<float*>(smem);
-    float* s_cnt = s_votes + np;
     const int v = blockIdx.y, b = blockIdx.z;
-    float* g_votes = ws + ((((int64_t)b * V + v) * (USE_LDS ? gridDim.x : 1) + (USE_LDS ? blockIdx.x : 0)) * 2) * np;  // (see lift_dense_kernel)
-    float* g_cnt = g_votes + np;
-    if (USE_LDS) {
-        for (int i = threadIdx.x; i < 2 * np; i += kStream) s_votes[i] = 0.0f;
-        __syncthreads();
-    }
-    float* votes = USE_LDS ? s_votes : g_votes;
-    float* cnt = USE_LDS ? s_cnt : g_cnt;
+    const VoteSlab<USE_LDS> table(ws, V, np, smem);
+    float* const votes = table.votes;
+    float* const cnt = table.cnt;
     const float* pr = probs + ((int64_t)b * V + v) * HW;
     const int32_t* mp = pid + ((int64_t)(pid_batched ? b : 0) * V + v) * HW;
     const int64_t ngroups = HW >> 2;
@@ -513,32 +525,95 @@ __global__ __launch_bounds__(kStream) void lift_points_kernel(const float* __res
             atomicAdd(&cnt[cur], rc);
         }
     }
-    if (USE_LDS) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * np; i += kStream) g_votes[i] = s_votes[i];
-    }
+    table.write_out();
 }
+
+// =============================================================================================
+// host side
+// =============================================================================================
+// f(std::integral_constant<int, m>) for the one m of MODES that equals `mode` (the entry points have checked that there is one)
+template <int... MODES, typename F>
+inline void with_mode(int mode, F f) {
+    (void)((mode == MODES && (f(std::integral_constant<int, MODES>{}), true)) || ...);
+}
+
+// memset, count, scan, fill, sort: the inversion of ids [V,HW,SLOTS] (and bary, SLOTS = 3; none for SLOTS = 1) into N rows per view
+template <int SLOTS>
+int plan_build(const int32_t* ids, const float* bary, int V, int64_t HW, int N, int32_t* row_ptr, int32_t* ent_pix, float* ent_w,
+               int64_t cap, int32_t* nnz_out, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
+    if (workspace_bytes < ivlm_lift_plan_workspace_bytes(V, HW, N)) return IVLM_ERR_WORKSPACE;
+    hipStream_t st = ivlm_stream(stream);
+    ivlm_enter();
+    const int R = V * N;
+    int32_t* row_cnt = static_cast<int32_t*>(workspace);
+    uint32_t* ent_key = reinterpret_cast<uint32_t*>(ent_pix);
+    IVLM_HIP_TRY(hipMemsetAsync(row_cnt, 0, sizeof(int32_t) * (size_t)R, st));
+    const int64_t n = (int64_t)V * HW;
+    const int grid = (int)((n + kBlock - 1) / kBlock < 4096 ? (n + kBlock - 1) / kBlock : 4096);
+    plan_count_kernel<SLOTS><<<grid, kBlock, 0, st>>>(ids, V, HW, N, row_cnt);
+    plan_scan_kernel<<<1, 1024, 0, st>>>(row_cnt, R, row_ptr, nnz_out);
+    plan_fill_kernel<SLOTS><<<grid, kBlock, 0, st>>>(ids, bary, V, HW, N, row_ptr, row_cnt, ent_key, ent_w, cap);
+    const size_t lds = (sizeof(uint32_t) + sizeof(float)) * kSortLdsMax;
+    plan_sort_kernel<<<R < 8192 ? R : 8192, kBlock, lds, st>>>(row_ptr, R, ent_key, ent_w);
+    return ivlm_launch_status();
+}
+
+// grid of the plan gather kernels: one block per (vertex, image), the vertex count rounded up to the 8 XCDs (lift_plan_body)
+inline dim3 plan_grid(int Nv, int B) { return dim3(8 * ((Nv + 7) / 8), B); }
 
 constexpr size_t kLdsBudget = 160 * 1024;
+constexpr size_t kStreamLdsCap = kLdsBudget - 1024;  // the largest vote table [2][n] kept in LDS, and the cap the kernels are given
+constexpr int kMaxChunksPerView = 256;               // bound of the slab count the workspace is sized for
+constexpr int kMaxBpc = 4;                           // largest blocks-per-CU setting the workspace is sized for
 
 static int g_lift_bpc = 1;  // blocks per CU of the streaming kernels (benchmark hook: ivlm_lift_stream_blocks_per_cu)
-constexpr int kMaxChunksPerView = 256;  // bound of the slab count the workspace is sized for
 
-inline int dense_chunks(int B, int V, int64_t HW, int bpc = 0) {
-    // ~bpc blocks per CU over the whole launch, at least 1, at most one block per 1024 pixels
-    int64_t want = ((bpc > 0 ? bpc : g_lift_bpc) * 256 + (int64_t)B * V - 1) / ((int64_t)B * V);
-    int64_t maxc = (HW / 4 + kStream - 1) / kStream;
+// blocks (= slabs) per (image, view) of a streaming launch: ~bpc blocks per CU over the whole launch, at least 1, at most one
+// block per 1024 groups of 4 pixels
+inline int stream_chunks(int B, int V, int64_t HW, int bpc) {
+    int64_t want = ((int64_t)bpc * 256 + (int64_t)B * V - 1) / ((int64_t)B * V);
+    const int64_t maxc = (HW / 4 + kStream - 1) / kStream;
     if (want > maxc) want = maxc;
     if (want > kMaxChunksPerView) want = kMaxChunksPerView;
-    if (want < 1) want = 1;
-    return (int)want;
+    return (int)(want < 1 ? 1 : want);
 }
 
-// slabs per (image, view) the workspace must hold: the largest chunk count dense_chunks can pick for this B * V (any HW, bpc <= 4)
-inline size_t ws_chunks(int B, int V) {
-    int64_t want = (4 * 256 + (int64_t)B * V - 1) / ((int64_t)B * V);
-    if (want > kMaxChunksPerView) want = kMaxChunksPerView;
-    return (size_t)(want < 1 ? 1 : want);
+// slabs per (image, view) the workspace holds: the most stream_chunks picks for this B * V (any HW, bpc <= kMaxBpc)
+inline int ws_chunks(int B, int V) { return stream_chunks(B, V, INT64_MAX, kMaxBpc); }
+
+inline size_t stream_workspace_bytes(int B, int V, int n) {
+    if (B <= 0 || V <= 0 || n <= 0) return 0;
+    return sizeof(float) * 2 * (size_t)B * V * n * ws_chunks(B, V);  // one [2][n] slab per block of an (image, view)
+}
+
+// a streaming kernel on `grid`; lds > 0: the USE_LDS instantiation with its vote table.  (Both forms go through ivlm_launch - the
+// cap helper does - so a caller that armed ivlm_profile_launches gets its events attached to the vote kernel; none does today.)
+template <auto KFN, typename... A>
+inline void stream_launch(dim3 grid, size_t lds, hipStream_t st, A... args) {
+    if (lds) ivlm_launch_lds_cap<KFN>((int)kStreamLdsCap, grid, dim3(kStream), lds, st, args...);
+    else ivlm_launch(KFN, grid, dim3(kStream), 0, st, args...);
+}
+
+// The host sequence of both streaming entry points: workspace check, LDS or atomics, chunk count, the zero fill of the atomics path,
+// the vote kernel - launch(std::bool_constant<use_lds>, grid, lds bytes, ws) - and lift_finalize_kernel<FMODE> over its slabs.
+template <typename Launch>
+int stream_lift(int B, int V, int64_t HW, int n, int fmode, float* out, float* nviews, void* workspace, size_t workspace_bytes,
+                hipStream_t st, Launch launch) {
+    if (workspace_bytes < stream_workspace_bytes(B, V, n)) return IVLM_ERR_WORKSPACE;
+    ivlm_enter();
+    float* ws = static_cast<float*>(workspace);
+    const size_t lds = sizeof(float) * 2 * (size_t)n;
+    const bool use_lds = lds <= kStreamLdsCap;
+    int chunks = stream_chunks(B, V, HW, g_lift_bpc);
+    if (chunks > ws_chunks(B, V)) chunks = ws_chunks(B, V);  // (the benchmark hook set above kMaxBpc)
+    if (!use_lds) IVLM_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(float) * 2 * (size_t)B * V * n, st));  // (atomics path: one slab per view)
+    const dim3 grid(chunks, V, B);
+    if (use_lds) launch(std::true_type{}, grid, lds, ws);
+    else launch(std::false_type{}, grid, (size_t)0, ws);
+    with_mode<0, 1>(fmode, [&](auto m) {
+        lift_finalize_kernel<decltype(m)::value><<<dim3((n + 31) / 32, B), kBlock, 0, st>>>(ws, V, n, use_lds ? chunks : 1, out, nviews);
+    });
+    return ivlm_launch_status();
 }
 
 }  // namespace
@@ -559,22 +634,7 @@ int ivlm_lift_plan_build(const int32_t* vid, const float* bary, int V, int64_t H
     IVLM_CHECK_ARG(vid && bary && row_ptr && ent_pix && ent_w && workspace);
     IVLM_CHECK_ARG(V > 0 && HW > 0 && Nv > 0 && HW < (1ll << 30) && cap > 0);
     IVLM_CHECK_ARG((int64_t)V * Nv < (1ll << 31) - 2 && (int64_t)V * HW * 3 < (1ll << 31));
-    if (workspace_bytes < ivlm_lift_plan_workspace_bytes(V, HW, Nv)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    ivlm_enter();
-    const int R = V * Nv;
-    int32_t* row_cnt = static_cast<int32_t*>(workspace);
-    IVLM_HIP_TRY(hipMemsetAsync(row_cnt, 0, sizeof(int32_t) * (size_t)R, st));
-    const int64_t n = (int64_t)V * HW;
-    const int grid = (int)((n + kBlock - 1) / kBlock < 4096 ? (n + kBlock - 1) / kBlock : 4096);
-    plan_count_kernel<3><<<grid, kBlock, 0, st>>>(vid, V, HW, Nv, row_cnt);
-    plan_scan_kernel<<<1, 1024, 0, st>>>(row_cnt, R, row_ptr, nnz_out);
-    plan_fill_kernel<3><<<grid, kBlock, 0, st>>>(vid, bary, V, HW, Nv, row_ptr, row_cnt,
-                                                 reinterpret_cast<uint32_t*>(ent_pix), ent_w, cap);
-    const size_t lds = (sizeof(uint32_t) + sizeof(float)) * kSortLdsMax;
-    plan_sort_kernel<<<R < 8192 ? R : 8192, kBlock, lds, st>>>(row_ptr, R, reinterpret_cast<uint32_t*>(ent_pix),
-                                                              ent_w);
-    return ivlm_launch_status();
+    return plan_build<3>(vid, bary, V, HW, Nv, row_ptr, ent_pix, ent_w, cap, nnz_out, workspace, workspace_bytes, stream);
 }
 
 // point-major plan of a pixel -> point map (pid int32 [V,HW], -1 / out of range = no point): rows sorted by pixel, weights 1;
@@ -584,20 +644,7 @@ int ivlm_lift_points_plan_build(const int32_t* pid, int V, int64_t HW, int Np, i
     IVLM_CHECK_ARG(pid && row_ptr && ent_pix && ent_w && workspace);
     IVLM_CHECK_ARG(V > 0 && HW > 0 && Np > 0 && HW < (1ll << 30) && cap > 0);
     IVLM_CHECK_ARG((int64_t)V * Np < (1ll << 31) - 2 && (int64_t)V * HW < (1ll << 31));
-    if (workspace_bytes < ivlm_lift_plan_workspace_bytes(V, HW, Np)) return IVLM_ERR_WORKSPACE;
-    hipStream_t st = ivlm_stream(stream);
-    ivlm_enter();
-    const int R = V * Np;
-    int32_t* row_cnt = static_cast<int32_t*>(workspace);
-    IVLM_HIP_TRY(hipMemsetAsync(row_cnt, 0, sizeof(int32_t) * (size_t)R, st));
-    const int64_t n = (int64_t)V * HW;
-    const int grid = (int)((n + kBlock - 1) / kBlock < 4096 ? (n + kBlock - 1) / kBlock : 4096);
-    plan_count_kernel<1><<<grid, kBlock, 0, st>>>(pid, V, HW, Np, row_cnt);
-    plan_scan_kernel<<<1, 1024, 0, st>>>(row_cnt, R, row_ptr, nnz_out);
-    plan_fill_kernel<1><<<grid, kBlock, 0, st>>>(pid, nullptr, V, HW, Np, row_ptr, row_cnt, reinterpret_cast<uint32_t*>(ent_pix), ent_w, cap);
-    const size_t lds = (sizeof(uint32_t) + sizeof(float)) * kSortLdsMax;
-    plan_sort_kernel<<<R < 8192 ? R : 8192, kBlock, lds, st>>>(row_ptr, R, reinterpret_cast<uint32_t*>(ent_pix), ent_w);
-    return ivlm_launch_status();
+    return plan_build<1>(pid, nullptr, V, HW, Np, row_ptr, ent_pix, ent_w, cap, nnz_out, workspace, workspace_bytes, stream);
 }
 
 int ivlm_lift_mesh_plan(const float* logits, const int32_t* row_ptr, const int32_t* ent_pix, const float* ent_w,
@@ -605,15 +652,11 @@ int ivlm_lift_mesh_plan(const float* logits, const int32_t* row_ptr, const int32
                         ivlm_stream_t stream) {
     IVLM_CHECK_ARG(logits && row_ptr && ent_pix && ent_w && out);
     IVLM_CHECK_ARG(B > 0 && V > 0 && HW > 0 && Nv > 0 && B <= 65535 && (mode == 0 || mode == 1 || mode == 2));
-    dim3 grid(8 * ((Nv + 7) / 8), B);
-    hipStream_t st = ivlm_stream(stream);
     ivlm_enter();
-    if (mode == 0)
-        ivlm_launch(lift_plan_kernel<0>, dim3(grid), dim3(kBlock), 0, st, logits, row_ptr, ent_pix, ent_w, V, HW, Nv, param, out, nviews);
-    else if (mode == 2)
-        ivlm_launch(lift_plan_kernel<2>, dim3(grid), dim3(kBlock), 0, st, logits, row_ptr, ent_pix, ent_w, V, HW, Nv, param, out, nviews);
-    else
-        ivlm_launch(lift_plan_kernel<1>, dim3(grid), dim3(kBlock), 0, st, logits, row_ptr, ent_pix, ent_w, V, HW, Nv, param, out, nviews);
+    with_mode<0, 1, 2>(mode, [&](auto m) {
+        ivlm_launch(lift_plan_kernel<decltype(m)::value>, plan_grid(Nv, B), dim3(kBlock), 0, ivlm_stream(stream), logits, row_ptr,
+                    ent_pix, ent_w, V, HW, Nv, param, out, nviews);
+    });
     return ivlm_launch_status();
 }
 
@@ -623,27 +666,21 @@ int ivlm_lift_mesh_plan_lowres(const void* low, int dtype, int lh, int lw, int i
     IVLM_CHECK_ARG(low && row_ptr && ent_pix && ent_w && out);
     IVLM_CHECK_ARG(B > 0 && V > 0 && Nv > 0 && B <= 65535 && (mode == 0 || mode == 1));
     IVLM_CHECK_ARG(lh > 0 && lw > 0 && img > 0 && in_h > 0 && in_w > 0 && in_h <= img && in_w <= img && oh > 0 && ow > 0);
-    dim3 grid(8 * ((Nv + 7) / 8), B);
-    hipStream_t st = ivlm_stream(stream);
     ivlm_enter();
-#define IVLM_LL(MODE, T)                                                                                          \
-    lift_plan_lowres_kernel<MODE, T><<<grid, kBlock, 0, st>>>(static_cast<const T*>(low), lh, lw, img, in_h, in_w, oh, \
-                                                              ow, row_ptr, ent_pix, ent_w, V, Nv, param, out, nviews)
-    if (dtype == IVLM_F32) {
-        if (mode == 0) IVLM_LL(0, float); else IVLM_LL(1, float);
-    } else if (dtype == IVLM_BF16) {
-        if (mode == 0) IVLM_LL(0, bf16_t); else IVLM_LL(1, bf16_t);
-    } else {
-        return IVLM_ERR_UNSUPPORTED;
-    }
-#undef IVLM_LL
+    if (dtype != IVLM_F32 && dtype != IVLM_BF16) return IVLM_ERR_UNSUPPORTED;
+    with_mode<0, 1>(mode, [&](auto m) {
+        auto launch = [&](auto t) {
+            using T = decltype(t);
+            lift_plan_lowres_kernel<decltype(m)::value, T><<<plan_grid(Nv, B), kBlock, 0, ivlm_stream(stream)>>>(
+                static_cast<const T*>(low), lh, lw, img, in_h, in_w, oh, ow, row_ptr, ent_pix, ent_w, V, Nv, param, out, nviews);
+        };
+        if (dtype == IVLM_F32) launch(float{});
+        else launch(bf16_t{});
+    });
     return ivlm_launch_status();
 }
 
-size_t ivlm_lift_mesh_dense_workspace_bytes(int B, int V, int Nv) {
-    if (B <= 0 || V <= 0 || Nv <= 0) return 0;
-    return sizeof(float) * 2 * (size_t)B * V * Nv * ws_chunks(B, V);  // one [2][Nv] slab per block of an (image, view)
-}
+size_t ivlm_lift_mesh_dense_workspace_bytes(int B, int V, int Nv) { return stream_workspace_bytes(B, V, Nv); }
 
 int ivlm_lift_mesh_dense(const float* logits, const int32_t* vid, const float* bary, int B, int V, int64_t HW,
                          int Nv, int mode, float param, float* out, float* nviews, void* workspace,
@@ -651,37 +688,12 @@ int ivlm_lift_mesh_dense(const float* logits, const int32_t* vid, const float* b
     IVLM_CHECK_ARG(logits && vid && bary && out && workspace);
     IVLM_CHECK_ARG(B > 0 && V > 0 && HW > 0 && Nv > 0 && (mode == 0 || mode == 1));
     IVLM_CHECK_ARG(HW % 4 == 0 && B <= 65535 && V <= 65535);
-    const size_t need = ivlm_lift_mesh_dense_workspace_bytes(B, V, Nv);
-    if (workspace_bytes < need) return IVLM_ERR_WORKSPACE;
     hipStream_t st = ivlm_stream(stream);
-    ivlm_enter();
-    float* ws = static_cast<float*>(workspace);
-    const size_t lds = sizeof(float) * 2 * (size_t)Nv;
-    const bool use_lds = lds <= kLdsBudget - 1024;
-    int chunks = dense_chunks(B, V, HW);
-    if ((size_t)chunks > ws_chunks(B, V)) chunks = (int)ws_chunks(B, V);
-    if (!use_lds) IVLM_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(float) * 2 * (size_t)B * V * Nv, st));  // (atomics path: one slab per view)
-    dim3 grid(chunks, V, B);
-#define IVLM_LAUNCH_DENSE(MODE, LDS)                                                                        \
-    do {                                                                                                    \
-        auto kfn = lift_dense_kernel<MODE, LDS>;                                                            \
-        if (LDS && lds > 64 * 1024)                                                                         \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn),                                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-        kfn<<<grid, kStream, LDS ? lds : 0, st>>>(logits, vid, bary, V, HW, Nv, param, ws);                   \
-    } while (0)
-    if (mode == 0) {
-        if (use_lds) IVLM_LAUNCH_DENSE(0, true); else IVLM_LAUNCH_DENSE(0, false);
-    } else {
-        if (use_lds) IVLM_LAUNCH_DENSE(1, true); else IVLM_LAUNCH_DENSE(1, false);
-    }
-#undef IVLM_LAUNCH_DENSE
-    dim3 fgrid((Nv + 31) / 32, B);
-    if (mode == 0)
-        lift_finalize_kernel<0><<<fgrid, kBlock, 0, st>>>(ws, V, Nv, use_lds ? chunks : 1, out, nviews);
-    else
-        lift_finalize_kernel<1><<<fgrid, kBlock, 0, st>>>(ws, V, Nv, use_lds ? chunks : 1, out, nviews);
-    return ivlm_launch_status();
+    return stream_lift(B, V, HW, Nv, mode, out, nviews, workspace, workspace_bytes, st, [&](auto in_lds, dim3 grid, size_t lds, float* ws) {
+        with_mode<0, 1>(mode, [&](auto m) {
+            stream_launch<lift_dense_kernel<decltype(m)::value, decltype(in_lds)::value>>(grid, lds, st, logits, vid, bary, V, HW, Nv, param, ws);
+        });
+    });
 }
 
 int ivlm_lift_stream_blocks_per_cu(int bpc) {  // benchmark hook; returns the previous value
@@ -690,38 +702,17 @@ int ivlm_lift_stream_blocks_per_cu(int bpc) {  // benchmark hook; returns the pr
     return prev;
 }
 
-size_t ivlm_lift_points_workspace_bytes(int B, int V, int Np) {
-    if (B <= 0 || V <= 0 || Np <= 0) return 0;
-    return sizeof(float) * 2 * (size_t)B * V * Np * ws_chunks(B, V);
-}
+size_t ivlm_lift_points_workspace_bytes(int B, int V, int Np) { return stream_workspace_bytes(B, V, Np); }
 
 int ivlm_lift_points(const float* probs, const int32_t* pid, int pid_batched, int B, int V, int64_t HW, int Np,
                      float* out, float* nviews, void* workspace, size_t workspace_bytes, ivlm_stream_t stream) {
     IVLM_CHECK_ARG(probs && pid && out && workspace);
     IVLM_CHECK_ARG(B > 0 && V > 0 && HW > 0 && Np > 0 && HW % 4 == 0 && B <= 65535 && V <= 65535);
-    const size_t need = ivlm_lift_points_workspace_bytes(B, V, Np);
-    if (workspace_bytes < need) return IVLM_ERR_WORKSPACE;
     hipStream_t st = ivlm_stream(stream);
-    ivlm_enter();
-    float* ws = static_cast<float*>(workspace);
-    const size_t lds = sizeof(float) * 2 * (size_t)Np;
-    const bool use_lds = lds <= kLdsBudget - 1024;
-    int chunks = dense_chunks(B, V, HW);
-    if ((size_t)chunks > ws_chunks(B, V)) chunks = (int)ws_chunks(B, V);
-    if (!use_lds) IVLM_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(float) * 2 * (size_t)B * V * Np, st));
-    dim3 grid(chunks, V, B);
-    if (use_lds) {
-        auto kfn = lift_points_kernel<true>;
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds);
-        kfn<<<grid, kStream, lds, st>>>(probs, pid, pid_batched, V, HW, Np, ws);
-    } else {
-        lift_points_kernel<false><<<grid, kStream, 0, st>>>(probs, pid, pid_batched, V, HW, Np, ws);
-    }
-    dim3 fgrid((Np + 31) / 32, B);
-    lift_finalize_kernel<1><<<fgrid, kBlock, 0, st>>>(ws, V, Np, use_lds ? chunks : 1, out, nviews);  // MODE 1: no clamp
-    return ivlm_launch_status();
+    // (finalize MODE 1: the mean of the per-view means is not clamped)
+    return stream_lift(B, V, HW, Np, 1, out, nviews, workspace, workspace_bytes, st, [&](auto in_lds, dim3 grid, size_t lds, float* ws) {
+        stream_launch<lift_points_kernel<decltype(in_lds)::value>>(grid, lds, st, probs, pid, pid_batched, V, HW, Np, ws);
+    });
 }
 
 }  // extern "C"

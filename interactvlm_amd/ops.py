@@ -139,23 +139,36 @@ class LiftPlan:
     """Vertex-major CSR of constant pixel->vertex tables (built once on the GPU)."""
 
     def __init__(self, vid: torch.Tensor, bary: torch.Tensor, num_vertices: int):
-        lib = _lib.load()
         vid = _req(vid, torch.int32, "vid")
         bary = _req(bary, torch.float32, "bary")
         assert vid.dim() == 4 and vid.shape[-1] == 3 and vid.shape == bary.shape, "tables must be [V,H,W,3]"
         V, H, W, _ = vid.shape
-        self.V, self.HW, self.hw_shape, self.num_vertices = V, H * W, (H, W), int(num_vertices)
-        dev = vid.device
-        cap = 3 * V * H * W
+        self._build("ivlm_lift_plan_build", (vid, bary), V, H, W, num_vertices, 3 * V * H * W)
+
+    @classmethod
+    def from_points(cls, pid: torch.Tensor, num_points: int):
+        """Point-major CSR of a pixel -> point map (pid i32 [V,H,W], -1 = no point): weights 1, evaluated with mode 2."""
+        pid = _req(pid, torch.int32, "pid")
+        assert pid.dim() == 3, "pid must be [V,H,W]"
+        self = cls.__new__(cls)
+        V, H, W = pid.shape
+        self._build("ivlm_lift_points_plan_build", (pid,), V, H, W, num_points, V * H * W)
+        return self
+
+    def _build(self, entry_point, tables, V, H, W, n, cap):
+        """allocate for ``cap`` entries, invert ``tables`` with ``entry_point``, read the entry count back and trim to it"""
+        lib = _lib.load()
+        self.V, self.HW, self.hw_shape, self.num_vertices = V, H * W, (H, W), int(n)
+        dev = tables[0].device
         self.row_ptr = torch.empty(V * self.num_vertices + 1, dtype=torch.int32, device=dev)
         ent_pix = torch.empty(cap, dtype=torch.int32, device=dev)
         ent_w = torch.empty(cap, dtype=torch.float32, device=dev)
         nnz = torch.zeros(1, dtype=torch.int32, device=dev)
         ws_bytes = lib.ivlm_lift_plan_workspace_bytes(V, self.HW, self.num_vertices)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(lib.ivlm_lift_plan_build(vid.data_ptr(), bary.data_ptr(), V, self.HW, self.num_vertices,
-                                       self.row_ptr.data_ptr(), ent_pix.data_ptr(), ent_w.data_ptr(), cap,
-                                       nnz.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "lift_plan_build")
+        check(getattr(lib, entry_point)(*(t.data_ptr() for t in tables), V, self.HW, self.num_vertices, self.row_ptr.data_ptr(),
+                                        ent_pix.data_ptr(), ent_w.data_ptr(), cap, nnz.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+              entry_point[len("ivlm_"):])
         self.nnz = int(nnz.item())
         # trim to the real size (one-time copy) so the plan holds 8 B per entry, no slack
         keep = max(self.nnz, 1)  # an empty plan still needs valid (never dereferenced) pointers
@@ -164,71 +177,6 @@ class LiftPlan:
 
     def bytes(self) -> int:
         return self.nnz * 8 + self.row_ptr.numel() * 4
-
-    @classmethod
-    def from_points(cls, pid: torch.Tensor, num_points: int):
-        """Point-major CSR of a pixel -> point map (pid i32 [V,H,W], -1 = no point): weights 1, evaluated with mode 2."""
-        lib = _lib.load()
-        pid = _req(pid, torch.int32, "pid")
-        assert pid.dim() == 3, "pid must be [V,H,W]"
-        self = cls.__new__(cls)
-        V, H, W = pid.shape
-        self.V, self.HW, self.hw_shape, self.num_vertices = V, H * W, (H, W), int(num_points)
-        dev = pid.device
-        cap = V * H * W
-        self.row_ptr = torch.empty(V * self.num_vertices + 1, dtype=torch.int32, device=dev)
-        ent_pix = torch.empty(cap, dtype=torch.int32, device=dev)
-        ent_w = torch.empty(cap, dtype=torch.float32, device=dev)
-        nnz = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws_bytes = lib.ivlm_lift_plan_workspace_bytes(V, self.HW, self.num_vertices)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(lib.ivlm_lift_points_plan_build(pid.data_ptr(), V, self.HW, self.num_vertices, self.row_ptr.data_ptr(),
-                                              ent_pix.data_ptr(), ent_w.data_ptr(), cap, nnz.data_ptr(), ws.data_ptr(), ws_bytes,
-                                              _stream()), "lift_points_plan_build")
-        self.nnz = int(nnz.item())
-        keep = max(self.nnz, 1)
-        self.ent_pix = ent_pix[:keep].clone()
-        self.ent_w = ent_w[:keep].clone()
-        return self
-
-
-def lift_mesh_plan(logits: torch.Tensor, plan: LiftPlan, mode: int = 0, param: float = 20.0, want_nviews=False):
-    """logits f32 [B,V,H,W] -> contacts f32 [B,Nv] (and nviews) via the CSR plan."""
-    lib = _lib.load()
-    logits = _req(logits, torch.float32, "logits")
-    B, V = logits.shape[0], logits.shape[1]
-    assert V == plan.V and logits[0, 0].numel() == plan.HW, "logit shape does not match the lift plan"
-    out = torch.empty(B, plan.num_vertices, dtype=torch.float32, device=logits.device)
-    nviews = torch.empty_like(out) if want_nviews else None
-    call = lambda: check(lib.ivlm_lift_mesh_plan(
-        logits.data_ptr(), plan.row_ptr.data_ptr(), plan.ent_pix.data_ptr(), plan.ent_w.data_ptr(), B, V, plan.HW,
-        plan.num_vertices, mode, float(param), out.data_ptr(), _p(nviews), _stream()), "lift_mesh_plan")
-    if TIMER.enabled:  # algorithmic bytes of the dense formulation (SURVEY.md §8d): 28 B/pixel + 8 B/vertex
-        TIMER.time("lift_mesh_plan", float(B) * (V * plan.HW * 28 + 2 * plan.num_vertices * 4), call)
-    else:
-        call()
-    return (out, nviews) if want_nviews else out
-
-
-def lift_mesh_plan_lowres(low, plan: LiftPlan, input_size, original_size, img_size=1024, mode=0, param=20.0,
-                          want_nviews=False):
-    """low f32|bf16 [B,V,lh,lw] -> contacts [B,Nv]: == lift_mesh_plan(postprocess_masks(low)), fused."""
-    lib = _lib.load()
-    low = _req(low, None, "low")
-    B, V, lh, lw = low.shape
-    oh, ow = int(original_size[0]), int(original_size[1])
-    assert V == plan.V and oh * ow == plan.HW, "plan was built for a different mask size"
-    out = torch.empty(B, plan.num_vertices, dtype=torch.float32, device=low.device)
-    nviews = torch.empty_like(out) if want_nviews else None
-    call = lambda: check(lib.ivlm_lift_mesh_plan_lowres(
-        low.data_ptr(), _dt(low), lh, lw, int(img_size), int(input_size[0]), int(input_size[1]), oh, ow,
-        plan.row_ptr.data_ptr(), plan.ent_pix.data_ptr(), plan.ent_w.data_ptr(), B, V, plan.num_vertices, mode,
-        float(param), out.data_ptr(), _p(nviews), _stream()), "lift_mesh_plan_lowres")
-    if TIMER.enabled:
-        TIMER.time("lift_mesh_plan", float(B) * (V * plan.HW * 28 + 2 * plan.num_vertices * 4), call)
-    else:
-        call()
-    return (out, nviews) if want_nviews else out
 
 
 _ws_cache = {}
@@ -243,6 +191,52 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return ws
 
 
+def _lift_call(name, like, B, n, want_nviews, call, timer=None):
+    """The frame of the lift wrappers: allocate out (and nviews) f32 [B,n] on the device of ``like``, run
+    ``check(call(out_ptr, nviews_ptr, stream), name)`` - as the TIMER record ``timer = (key, work)`` when one is given and TIMER is
+    on - and -> (out, nviews) or out."""
+    out = torch.empty(B, n, dtype=torch.float32, device=like.device)
+    nviews = torch.empty_like(out) if want_nviews else None
+    run = lambda: check(call(out.data_ptr(), _p(nviews), _stream()), name)
+    if timer is not None and TIMER.enabled:
+        TIMER.time(*timer, run)
+    else:
+        run()
+    return (out, nviews) if want_nviews else out
+
+
+def _plan_timer(B, V, plan):
+    """both plan gathers are one TIMER family, priced at the algorithmic bytes of the dense formulation:
+    28 B/pixel + 8 B/vertex"""
+    return "lift_mesh_plan", float(B) * (V * plan.HW * 28 + 2 * plan.num_vertices * 4)
+
+
+def lift_mesh_plan(logits: torch.Tensor, plan: LiftPlan, mode: int = 0, param: float = 20.0, want_nviews=False):
+    """logits f32 [B,V,H,W] -> contacts f32 [B,Nv] (and nviews) via the CSR plan."""
+    lib = _lib.load()
+    logits = _req(logits, torch.float32, "logits")
+    B, V = logits.shape[0], logits.shape[1]
+    assert V == plan.V and logits[0, 0].numel() == plan.HW, "logit shape does not match the lift plan"
+    return _lift_call("lift_mesh_plan", logits, B, plan.num_vertices, want_nviews, lambda out, nviews, stream: lib.ivlm_lift_mesh_plan(
+        logits.data_ptr(), plan.row_ptr.data_ptr(), plan.ent_pix.data_ptr(), plan.ent_w.data_ptr(), B, V, plan.HW,
+        plan.num_vertices, mode, float(param), out, nviews, stream), timer=_plan_timer(B, V, plan))
+
+
+def lift_mesh_plan_lowres(low, plan: LiftPlan, input_size, original_size, img_size=1024, mode=0, param=20.0,
+                          want_nviews=False):
+    """low f32|bf16 [B,V,lh,lw] -> contacts [B,Nv]: == lift_mesh_plan(postprocess_masks(low)), fused."""
+    lib = _lib.load()
+    low = _req(low, None, "low")
+    B, V, lh, lw = low.shape
+    oh, ow = int(original_size[0]), int(original_size[1])
+    assert V == plan.V and oh * ow == plan.HW, "plan was built for a different mask size"
+    return _lift_call("lift_mesh_plan_lowres", low, B, plan.num_vertices, want_nviews,
+                      lambda out, nviews, stream: lib.ivlm_lift_mesh_plan_lowres(
+                          low.data_ptr(), _dt(low), lh, lw, int(img_size), int(input_size[0]), int(input_size[1]), oh, ow,
+                          plan.row_ptr.data_ptr(), plan.ent_pix.data_ptr(), plan.ent_w.data_ptr(), B, V, plan.num_vertices, mode,
+                          float(param), out, nviews, stream), timer=_plan_timer(B, V, plan))
+
+
 def lift_mesh_dense(logits, vid, bary, num_vertices: int, mode: int = 0, param: float = 20.0, want_nviews=False):
     """Streaming (atomic) variant over dense tables: vid i32 [V,H,W,3], bary f32 [V,H,W,3]."""
     lib = _lib.load()
@@ -252,14 +246,10 @@ def lift_mesh_dense(logits, vid, bary, num_vertices: int, mode: int = 0, param: 
     B, V = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
     nv = int(num_vertices)
-    out = torch.empty(B, nv, dtype=torch.float32, device=logits.device)
-    nviews = torch.empty_like(out) if want_nviews else None
-    nbytes = lib.ivlm_lift_mesh_dense_workspace_bytes(B, V, nv)
-    ws = _workspace(nbytes, logits.device)
-    check(lib.ivlm_lift_mesh_dense(logits.data_ptr(), vid.data_ptr(), bary.data_ptr(), B, V, HW, nv, mode,
-                                   float(param), out.data_ptr(), _p(nviews), ws.data_ptr(), ws.numel(), _stream()),
-          "lift_mesh_dense")
-    return (out, nviews) if want_nviews else out
+    ws = _workspace(lib.ivlm_lift_mesh_dense_workspace_bytes(B, V, nv), logits.device)
+    return _lift_call("lift_mesh_dense", logits, B, nv, want_nviews, lambda out, nviews, stream: lib.ivlm_lift_mesh_dense(
+        logits.data_ptr(), vid.data_ptr(), bary.data_ptr(), B, V, HW, nv, mode, float(param), out, nviews, ws.data_ptr(), ws.numel(),
+        stream))
 
 
 def lift_points(probs, pid, num_points: int, want_nviews=False):
@@ -271,13 +261,9 @@ def lift_points(probs, pid, num_points: int, want_nviews=False):
     HW = probs[0, 0].numel()
     batched = 1 if pid.dim() == probs.dim() else 0
     n = int(num_points)
-    out = torch.empty(B, n, dtype=torch.float32, device=probs.device)
-    nviews = torch.empty_like(out) if want_nviews else None
-    nbytes = lib.ivlm_lift_points_workspace_bytes(B, V, n)
-    ws = _workspace(nbytes, probs.device)
-    check(lib.ivlm_lift_points(probs.data_ptr(), pid.data_ptr(), batched, B, V, HW, n, out.data_ptr(), _p(nviews),
-                               ws.data_ptr(), ws.numel(), _stream()), "lift_points")
-    return (out, nviews) if want_nviews else out
+    ws = _workspace(lib.ivlm_lift_points_workspace_bytes(B, V, n), probs.device)
+    return _lift_call("lift_points", probs, B, n, want_nviews, lambda out, nviews, stream: lib.ivlm_lift_points(
+        probs.data_ptr(), pid.data_ptr(), batched, B, V, HW, n, out, nviews, ws.data_ptr(), ws.numel(), stream))
 
 
 def lift_points_plan(probs, plan: LiftPlan, want_nviews=False):
