@@ -1126,6 +1126,43 @@ int ivlm_mesh_sdf_intrusion(const void *plan, const float *points, const float *
                             int B, int N, float *value, float *grad_rot6d, float *grad_translation, float *grad_scale,
                             void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
 
+/* The z-buffer of a posed mesh in the camera of ivlm_soft_silhouette_* and the depth-order term on it (depth_order.hip).  NOT the
+ * reference's: PHOSA's ordinal-depth loss of the object's z-buffer against a constant occluder depth image.
+ *   u = fx X / Z + px, v = fy Y / Z + py; pixel (row i, col j) has its centre q at (j + 0.5, i + 0.5).  Per face with screen vertices
+ *   a, b, c: e_a = cross(c - b, q - b), e_b = cross(a - c, q - c), e_c = cross(b - a, q - a); the face covers the pixel when the three
+ *   are all > 0 or all < 0 (strict, both windings); z = s / (e_a / Z_a + e_b / Z_b + e_c / Z_c), s = e_a + e_b + e_c - the perspective-
+ *   correct depth 1 / sum (w_i / Z_i) with the screen-space barycentrics w_i = e_i / s.  A face whose screen area is zero, or that has a
+ *   vertex with Z <= 1e-6 or an index outside [0, N), is skipped whole.
+ * ivlm_depth_image: verts f32 [B,N,3], faces i32 [F,3] (shared by the batch) -> depth_out f32 [B,H,W] = the smallest z over the covering
+ *   faces (+inf: none), face_id_out i32 [B,H,W] = the face that attains it, the lowest index among equal depths (-1: none).
+ * ivlm_depth_order_forward: occluder_depth f32 [H,W] (D_h; +inf where there is no occluder) and signed_weight f32 [H,W] (c > 0: the
+ *   mesh is in front here, c < 0: the occluder is, 0: ignored), both constant and shared by the batch, tau > 0 ->
+ *   value_out f32 [B] = (tau / n) sum |c| softplus(x), x = sign(c) (D_o - D_h) / tau over the pixels with c != 0 and D_o, D_h finite,
+ *   n = sum |c| over the whole image, softplus(x) = max(x, 0) + log1p(exp(-|x|)); an exact 0 when n == 0.  Every pixel is converted to
+ *   fp64 before it is added (rows, then the rows in a fixed order).  The workspace keeps the z-buffer, the winners, the projected faces
+ *   and (sum, n) for the backward.
+ * ivlm_depth_order_backward: the SAME verts, images, sizes, camera, tau and workspace as the forward call it follows; grad_value f32 [B];
+ *   vert_face_offsets / vert_face_list as ivlm_soft_silhouette_backward takes them -> grad_verts_out f32 [B,N,3], the gradient with the
+ *   winner of every pixel held fixed: through Z_a, Z_b, Z_c directly and through the e_i to the six screen coordinates.  Nothing flows
+ *   through the coverage edge or through D_h.  At most IVLM_DEPTH_ORDER_CHAIN fp32 additions per lane before fp64 takes over.
+ * No floating-point atomics, every sum in a fixed order, no host read, no allocation: the same bits every call, for a pose whatever the
+ * batch around it, and under graph replay.  B <= 65535, N, F <= 2^22, H, W <= 16384, camera and tau finite, tau > 0, else
+ * IVLM_ERR_UNSUPPORTED before any launch; NULL pointers IVLM_ERR_INVALID_ARG.  workspace, 16-byte aligned (the queries return 0 for
+ * sizes that are not supported), every region padded to 256 bytes: ivlm_depth_image_workspace_bytes = B (8 N + 64 F + 16);
+ * ivlm_depth_order_workspace_bytes = that + B (8 H W + 36 F + 16 H + 16). */
+#define IVLM_DEPTH_ORDER_CHAIN 32
+size_t ivlm_depth_image_workspace_bytes(int B, int N, int F, int H, int W);
+int ivlm_depth_image(const float *verts, const int32_t *faces, int B, int N, int F, int H, int W, float fx, float fy, float px, float py,
+                     float *depth_out, int32_t *face_id_out, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+size_t ivlm_depth_order_workspace_bytes(int B, int N, int F, int H, int W);
+int ivlm_depth_order_forward(const float *verts, const int32_t *faces, const float *occluder_depth, const float *signed_weight, int B,
+                             int N, int F, int H, int W, float fx, float fy, float px, float py, float tau, float *value_out,
+                             void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+int ivlm_depth_order_backward(const float *verts, const int32_t *vert_face_offsets, const int32_t *vert_face_list,
+                              const float *occluder_depth, const float *signed_weight, const float *grad_value, int B, int N, int F,
+                              int H, int W, float fx, float fy, float px, float py, float tau, float *grad_verts_out, void *workspace,
+                              size_t workspace_bytes, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

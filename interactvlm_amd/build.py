@@ -29,6 +29,8 @@ EXTRA = {
     # every fp32 operation is the one tests/_mesh_sdf_ref.py states in its fp32 mode, which is what the tests' tolerance constants
     # were measured with
     "mesh_sdf.hip": ["-ffp-contract=off"],
+    # every fp32 operation of the z-buffer and of the depth-order term is the one its header states
+    "depth_order.hip": ["-ffp-contract=off"],
 }
 
 

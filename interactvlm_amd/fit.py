@@ -2,7 +2,8 @@
 loop that composes ``contact_icp`` (the start), ``soft_silhouette`` + ``silhouette_terms`` (mask and centroid terms) and
 ``contact_distance`` (the contact term), for B starts at once.
 
-Not the reference's: no Phong render, no depth image, no logging or video.  The rigid transform is applied pose by pose with the
+Not the reference's: no Phong render, no depth image of the reference's (``occlusion=True`` renders z-buffers of its own for the
+occlusion-aware terms, see ``ObjectPoseFit``), no logging or video.  The rigid transform is applied pose by pose with the
 operations of a single-pose run, so that every start of a batch computes the bits of its own unbatched run; with
 ``fused_transform=True`` it is ``pose.pose_transform`` (csrc/pose.hip), which keeps that property in three launches per step.
 ``search_object_pose`` (many starts, one loop, the winner picked on the device) is an addition: the reference fits one start.
@@ -19,6 +20,7 @@ from . import _lib, contact_pair, silhouette
 from .contact_icp import contact_icp
 from .contact_pair import contact_distance
 from .mesh_sdf import MeshSDF, check_closed
+from .occlusion import DEFAULT_TAU, check_tau, depth_order, occluder_maps
 from .pose import check_rotations, check_start, compose_rotations, cube_rotations, pose_arguments, pose_transform
 from .silhouette import silhouette_terms, soft_silhouette
 
@@ -29,13 +31,23 @@ DEFAULT_LOSS_WEIGHTS = {
     "contact_loss": {"w": 10.0, "kick_in": 0},
 }
 # Every term of ``ObjectPoseFit``, in the order they are added up: key -> its bit of ivlm_fit_step's terms_on (a row of term_history),
-# or None for a term that the device loop's launch sequence does not run.  The two None terms are NOT the reference's and not in
-# DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh (the model needs human_faces) and, the other
-# direction, mesh_sdf's intrusion of the human vertices into the posed object (the model needs intrusion=True).
+# or None for a term that the device loop's launch sequence does not run.  The None terms are NOT the reference's and not in
+# DEFAULT_LOSS_WEIGHTS: mesh_sdf's penetration of the object vertices into the human mesh (the model needs human_faces), the other
+# direction, mesh_sdf's intrusion of the human vertices into the posed object (the model needs intrusion=True), and occlusion's depth
+# order of the object against the human's z-buffer (the model needs occlusion=True).
 TERMS = {"mask_loss": _lib.FIT_MASK, "centroid_loss": _lib.FIT_CENTROID, "contact_loss": _lib.FIT_CONTACT,
-         "penetration_loss": None, "intrusion_loss": None}
+         "penetration_loss": None, "intrusion_loss": None, "depth_order_loss": None}
 TERM_KEYS = tuple(k for k, bit in TERMS.items() if bit is not None)
-PENETRATION_KEY, INTRUSION_KEY = (k for k, bit in TERMS.items() if bit is None)
+
+
+def _host_term(key):
+    """a key of ``TERMS`` whose value is None, looked up by name"""
+    if TERMS[key] is not None:
+        raise KeyError(f"{key}: a term of the device loop")
+    return key
+
+
+PENETRATION_KEY, INTRUSION_KEY, DEPTH_ORDER_KEY = (_host_term(k) for k in ("penetration_loss", "intrusion_loss", "depth_order_loss"))
 DEFAULT_LRS = (5e-2, 1e-2, 1e-2)  # rotation, translation, scale (optim/fit.py)
 
 
@@ -108,12 +120,18 @@ class FitScene:
     target and the centre of its bounding box, the camera, sigma and blur radius, the centroid offset, with human_faces the human's
     ``MeshSDF`` and with intrusion=True the object checked closed (``mesh_sdf.check_closed``, on a host copy) and prepared as a
     ``MeshSDF`` - every host read of a fit's preparation but the silhouette's topology cache, which is keyed by the tensor object
-    ``obj_faces`` kept here and so hits after the first use.  The arguments are ``ObjectPoseFit``'s."""
+    ``obj_faces`` kept here and so hits after the first use.  With occlusion=True (it needs human_faces) the human moved by the centroid
+    offset - the silhouette's frame - is rendered once (``occlusion.occluder_maps``) into occluder_depth, signed_weight and valid.  The
+    arguments are ``ObjectPoseFit``'s (here occlusion, human_mask and depth_tau come after human_faces)."""
 
     def __init__(self, obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
-                 hum_centroid_offset=None, sigma=1e-4, blur_radius=None, intrusion=False, human_faces=None):
+                 hum_centroid_offset=None, sigma=1e-4, blur_radius=None, intrusion=False, human_faces=None, occlusion=False,
+                 human_mask=None, depth_tau=DEFAULT_TAU):
         if not isinstance(target_mask, torch.Tensor) or target_mask.dim() != 2:
             raise ValueError("target_mask: expected [H,W]")
+        if occlusion_flag(occlusion) and human_faces is None:
+            raise ValueError("occlusion=True needs human_faces: the occluder's depth image is rendered from the human's triangles")
+        self.depth_tau = check_tau(depth_tau)
         self.camera = (focal, principal)
         self.sigma, self.blur_radius = sigma, blur_radius
         self.obj_vertices = obj_vertices.detach().float()
@@ -132,10 +150,16 @@ class FitScene:
         if intrusion:
             check_closed(self.obj_vertices, self.obj_faces)
             self.object_sdf = MeshSDF(self.obj_vertices, self.obj_faces.to(torch.int32))
+        # the occlusion-aware terms' constants: the human in the silhouette's frame (the reference's off_h_verts), rendered once
+        self.occluder_depth = self.signed_weight = self.valid = None
+        if occlusion:
+            self.occluder_depth, self.signed_weight, self.valid = occluder_maps(
+                self.human_vertices + self.hum_centroid_offset, human_faces.detach(), self.target_mask, focal, principal, human_mask)
 
     BUFFERS = ("obj_vertices", "obj_faces", "human_vertices", "object_contact_probs", "human_contact_probs", "hum_centroid_offset",
                "target_mask", "target_mask_centroid")
-    _DEFAULTS = (None,) * 8 + (1e-4, None, False, None)  # of the arguments after obj_vertices
+    OCCLUSION_BUFFERS = ("occluder_depth", "signed_weight", "valid")  # tensors with occlusion=True, else None
+    _DEFAULTS = (None,) * 8 + (1e-4, None, False, None, False, None, DEFAULT_TAU)  # of the arguments after obj_vertices
 
     @classmethod
     def of(cls, first, *rest):
@@ -179,11 +203,19 @@ class ObjectPoseFit(nn.Module):
     un-offset human vertices under the B poses: the penetration term's other direction, for a coarse object none of whose vertices
     lies inside the body while a limb passes through one of its faces.  Gated and weighted like the others, not in
     ``DEFAULT_LOSS_WEIGHTS`` either; on without intrusion=True it raises.
+    occlusion=True (it needs human_faces; NOT the reference's) makes the image terms occlusion-aware: target_mask is then the object's
+    VISIBLE pixels, the human moved by ``hum_centroid_offset`` is rendered once (``occlusion.occluder_maps``; human_mask [H,W] is the
+    photo's person mask, when there is one), ``mask_loss`` and ``centroid_loss`` are taken on alpha * valid - an object pixel hidden by
+    the body is neither wanted nor penalised - and one more term is allowed: "depth_order_loss" = ``occlusion.depth_order`` of the
+    offset object against the human's z-buffer with tau = depth_tau (scene units; 0.01 is a default nobody has measured on data),
+    gated and weighted like the others, not in ``DEFAULT_LOSS_WEIGHTS``; on without occlusion=True it raises.  (occlusion, human_mask
+    and depth_tau stand before human_faces, which stays the last parameter.)
     forward(loss_weights, step=None) -> (total [B], {term: [B]})."""
 
     def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces=None, human_vertices=None,
                  obj_contact_probs=None, human_contact_probs=None, target_mask=None, focal=None, principal=None, hum_centroid_offset=None,
-                 vars=("pose",), sigma=1e-4, blur_radius=None, fused_transform=False, intrusion=False, human_faces=None):
+                 vars=("pose",), sigma=1e-4, blur_radius=None, fused_transform=False, intrusion=False, occlusion=False, human_mask=None,
+                 depth_tau=DEFAULT_TAU, human_faces=None):
         super().__init__()
         unknown = set(vars) - {"pose", "scale"}
         if unknown:
@@ -206,10 +238,12 @@ class ObjectPoseFit(nn.Module):
         self.step = 0
         self.fused_transform = bool(fused_transform)
         self.scene = scene = FitScene.of(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask,
-                                         focal, principal, hum_centroid_offset, sigma, blur_radius, intrusion, human_faces)
+                                         focal, principal, hum_centroid_offset, sigma, blur_radius, intrusion, human_faces, occlusion,
+                                         human_mask, depth_tau)
         self.camera, self.sigma, self.blur_radius = scene.camera, scene.sigma, scene.blur_radius
-        for name in FitScene.BUFFERS:  # the scene's own tensor objects
-            self.register_buffer(name, getattr(scene, name))
+        for name in FitScene.BUFFERS + FitScene.OCCLUSION_BUFFERS:  # the scene's own tensor objects (None without occlusion=True:
+            self.register_buffer(name, getattr(scene, name))         # a None buffer is in no state_dict), so .to() moves them too
+        self.depth_tau = scene.depth_tau
         self.human_sdf, self.object_sdf = scene.human_sdf, scene.object_sdf  # plain attributes: a plan belongs to its device
 
     def object_vertices(self):
@@ -226,10 +260,15 @@ class ObjectPoseFit(nn.Module):
 
         obj = self.object_vertices()
         terms = {}
+        if on(DEPTH_ORDER_KEY) and self.valid is None:
+            raise ValueError(f"{DEPTH_ORDER_KEY} is on, but the model was built without occlusion=True: the term needs the human's "
+                             "depth image")
         if on("mask_loss") or on("centroid_loss"):
             H, W = self.target_mask.shape
             alpha = soft_silhouette(obj + self.hum_centroid_offset, self.obj_faces, self.camera[0], self.camera[1], (H, W),
                                     self.sigma, self.blur_radius)
+            if self.valid is not None:  # occlusion=True: a pixel where the body hides the object is a don't-care
+                alpha = alpha * self.valid
             mask_loss, centroid = silhouette_terms(alpha, self.target_mask)
             if on("mask_loss"):
                 terms["mask_loss"] = mask_loss
@@ -248,6 +287,9 @@ class ObjectPoseFit(nn.Module):
                 raise ValueError(f"{INTRUSION_KEY} is on, but the model was built without intrusion=True: the term needs the object "
                                  "checked closed and prepared as a MeshSDF")
             terms[INTRUSION_KEY] = self.object_sdf.intrusion(self.human_vertices, self.rotation, self.translation, self.scale)
+        if on(DEPTH_ORDER_KEY):
+            terms[DEPTH_ORDER_KEY] = depth_order(obj + self.hum_centroid_offset, self.obj_faces, self.occluder_depth,
+                                                 self.signed_weight, self.camera[0], self.camera[1], self.depth_tau)
         total = torch.zeros(self.rotation.shape[0], dtype=torch.float32, device=self.rotation.device)
         for key, val in terms.items():
             total = total + val * weights[key]["w"]
@@ -260,6 +302,21 @@ def refuse_terms_the_device_loop_lacks(loss_weights):
         if bit is None and loss_weights is not None and term_configured(key, loss_weights):
             raise ValueError(f"{key}: not available with device_loop=True (the device loop's launch sequence does not run the "
                              "term; configure kick_in = -1 or use the torch loop)")
+
+
+def occlusion_flag(occlusion):
+    """-> bool; anything but a bool is refused by name.  occlusion, human_mask and depth_tau stand before human_faces in the public
+    signatures, so a tensor here is a human_faces that was passed by position."""
+    if not isinstance(occlusion, bool):
+        raise ValueError(f"occlusion: expected True or False, got {type(occlusion).__name__} (human_faces is the last parameter: pass "
+                         "it by keyword)")
+    return occlusion
+
+
+def refuse_occlusion_in_the_device_loop(occlusion):
+    if occlusion_flag(occlusion):
+        raise ValueError("occlusion=True: not available with device_loop=True (the device loop's launch sequence takes the image terms "
+                         "on alpha itself and has no depth image; use the torch loop)")
 
 
 def fit_phases(loss_weights, max_iter):
@@ -300,13 +357,14 @@ class DevicePoseFit:
     lrs = (rotation, translation, scale), betas, eps > 0.  It owns rotation [B,6], translation [B,3], scale [B], the moments, the device step
     counter, history [max_iter,B] (the total BEFORE update i), term_history [max_iter,3,B] (``TERM_KEYS``; an exact 0 for a term
     that does not count), the workspace and the topology lists (from the silhouette module's cache: the one host read, here).
+    occlusion=True, or a scene prepared with it, is refused by name: the launch sequence has no don't-care image and no depth image.
     step() runs one iteration, run(n=None) the remaining ones (or n).  rotation_grad / translation_grad / scale_grad are the last
     step's gradients."""
 
     def __init__(self, rotation_init, translation_init, scaling_init, obj_vertices, obj_faces=None, human_vertices=None,
                  obj_contact_probs=None, human_contact_probs=None, target_mask=None, focal=None, principal=None, hum_centroid_offset=None,
                  vars=("pose",), sigma=1e-4, blur_radius=None, loss_weights=None, max_iter=250, lrs=DEFAULT_LRS, betas=(0.9, 0.999),
-                 eps=1e-8):
+                 eps=1e-8, occlusion=False):
         if not isinstance(max_iter, int) or isinstance(max_iter, bool) or max_iter < 1:
             raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
         if not set(vars):
@@ -320,6 +378,7 @@ class DevicePoseFit:
         if len(lrs) != 3 or len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas) or not eps > 0.0:
             raise ValueError(f"expected three learning rates, two betas in [0, 1) and eps > 0, got {lrs}, {betas}, {eps}")
         refuse_terms_the_device_loop_lacks(loss_weights)
+        refuse_occlusion_in_the_device_loop(occlusion or (isinstance(obj_vertices, FitScene) and obj_vertices.valid is not None))
         weights = DEFAULT_LOSS_WEIGHTS if loss_weights is None else loss_weights
         self.phases = fit_phases(weights, max_iter)
         for lo, _, bits in self.phases:
@@ -422,7 +481,7 @@ _UNSET = object()  # fused_transform was not passed: False for the torch loop, i
 def fit_object_pose(obj_vertices, obj_faces=None, human_vertices=None, obj_contact_probs=None, human_contact_probs=None, target_mask=None,
                     focal=None, principal=None, init=None, hum_centroid_offset=None, vars=("pose",), loss_weights=None, max_iter=250,
                     early_stop=False, sigma=1e-4, blur_radius=None, icp_threshold=(0.3, 0.5), icp_max_iterations=10, fused_transform=_UNSET,
-                    device_loop=False, intrusion=False, human_faces=None):
+                    device_loop=False, intrusion=False, occlusion=False, human_mask=None, depth_tau=DEFAULT_TAU, human_faces=None):
     """The loop of optim/fit.py:217-290: Adam with lr 5e-2 for the rotation, 1e-2 for the translation and 1e-2 for the scale.
 
     The scene is ``ObjectPoseFit``'s (obj_vertices may be a ``FitScene``); it is prepared once, before the loop.
@@ -436,6 +495,8 @@ def fit_object_pose(obj_vertices, obj_faces=None, human_vertices=None, obj_conta
     (``ObjectPoseFit``, ``mesh_sdf``: NOT the reference's); device_loop=True refuses that term when it is configured (kick_in >= 0).
     intrusion=True is what the term "intrusion_loss" needs (``ObjectPoseFit``: the object is checked closed and prepared once, before
     the loop); device_loop=True refuses that term in the same way.
+    occlusion=True, human_mask and depth_tau are ``ObjectPoseFit``'s (the human is rendered once, before the loop; the term
+    "depth_order_loss" needs it); device_loop=True refuses occlusion=True and that term by name.
     -> dict(rotation [B,6], translation [B,3], scale [B], object_vertices [B,N,3], history [iterations,B] (device tensor))."""
     if not isinstance(max_iter, int) or max_iter < 1:
         raise ValueError(f"max_iter: expected an integer >= 1, got {max_iter!r}")
@@ -445,10 +506,12 @@ def fit_object_pose(obj_vertices, obj_faces=None, human_vertices=None, obj_conta
         if fused_transform is not _UNSET and not fused_transform:
             raise ValueError("fused_transform=False: not available with device_loop=True (the device loop runs the fused transform)")
         refuse_terms_the_device_loop_lacks(loss_weights)
+        refuse_occlusion_in_the_device_loop(occlusion)
     fused_transform = bool(device_loop) if fused_transform is _UNSET else fused_transform
     # (the device loop runs neither extra term, so a scene made here for it prepares neither mesh)
     scene = FitScene.of(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
-                        hum_centroid_offset, sigma, blur_radius, intrusion and not device_loop, None if device_loop else human_faces)
+                        hum_centroid_offset, sigma, blur_radius, intrusion and not device_loop, None if device_loop else human_faces,
+                        occlusion, human_mask, depth_tau)
     if init is None:
         o_sel = scene.obj_vertices[scene.object_contact_probs.float() > icp_threshold[0]]
         h_sel = scene.human_vertices[scene.human_contact_probs.float() > icp_threshold[1]]
@@ -504,7 +567,7 @@ _SEARCH_FIT_KWARGS = ("hum_centroid_offset", "vars", "loss_weights", "max_iter",
 
 def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                        rotations=None, init=None, icp=True, chunk=None, obj_normals=None, human_normals=None, device_loop=False,
-                       intrusion=False, human_faces=None, **fit_kwargs):
+                       intrusion=False, occlusion=False, human_mask=None, depth_tau=DEFAULT_TAU, human_faces=None, **fit_kwargs):
     """A multi-start ``fit_object_pose``: K starts around one pose, fitted in one loop with the fused transform, scored and ranked on
     the device.  NOT the reference's, which runs one start (optim/fit.py): contact patches and a silhouette leave rotational
     ambiguities that a local fit from one start does not resolve.
@@ -522,7 +585,10 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     device_loop=True runs every loop on the device (``fit_object_pose(device_loop=True)``, ``DevicePoseFit``) and adds term_history
     [iterations,3,K]; the scoring stays the forward described above.  One ``FitScene`` is prepared with human_faces and intrusion and
     serves every loop and every scoring model, so that the score holds "penetration_loss" and "intrusion_loss" whenever loss_weights
-    configures them (device_loop=True refuses that, see ``fit_object_pose``).
+    configures them (device_loop=True refuses that, see ``fit_object_pose``).  occlusion=True, human_mask and depth_tau go to that scene
+    too: every loop and every score then takes the image terms on alpha * valid, and the score holds "depth_order_loss" when it is
+    configured - a start whose object sits on the wrong side of the body ranks behind its twin on the right side (device_loop=True
+    refuses occlusion=True by name).
 
     chunk=None fits all K starts in one loop; an integer fits them in loops of at most that many starts, to bound memory.  A start
     computes the bits of its own run whatever the batch around it, so chunk does not change a single bit of the result.
@@ -536,6 +602,7 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
         raise ValueError(f"chunk: expected None or an integer >= 1, got {chunk!r}")
     if device_loop:
         refuse_terms_the_device_loop_lacks(fit_kwargs.get("loss_weights"))
+        refuse_occlusion_in_the_device_loop(occlusion)
     if "early_stop" in fit_kwargs:
         raise ValueError("early_stop: not available in search_object_pose (it would make a start's result depend on chunk)")
     unknown = sorted(set(fit_kwargs) - set(_SEARCH_FIT_KWARGS))
@@ -575,7 +642,7 @@ def search_object_pose(obj_vertices, obj_faces, human_vertices, obj_contact_prob
     every_term = max([0] + [configured[k]["kick_in"] for k in configured if term_configured(k, configured)])  # every key that is held
     scene = FitScene(obj_vertices, obj_faces, human_vertices, obj_contact_probs, human_contact_probs, target_mask, focal, principal,
                      fit_kwargs.pop("hum_centroid_offset", None), fit_kwargs.pop("sigma", 1e-4), fit_kwargs.pop("blur_radius", None),
-                     intrusion, human_faces)
+                     intrusion, human_faces, occlusion, human_mask, depth_tau)
     step = K if chunk is None else chunk
     parts, scores = [], []
     for lo in range(0, K, step):
