@@ -1163,6 +1163,67 @@ int ivlm_depth_order_backward(const float *verts, const int32_t *vert_face_offse
                               int H, int W, float fx, float fy, float px, float py, float tau, float *grad_verts_out, void *workspace,
                               size_t workspace_bytes, ivlm_stream_t stream);
 
+/* The start of the object-pose fit (fit_start.hip): what optim/data_io.py and the stage-1 block of optim/fit.py:119-135 compute before
+ * the reference's optimiser starts, without pytorch3d or trimesh.  Every sum is fp64 from the fp32 inputs in a fixed order, rounded to
+ * fp32 once; no floating-point atomics, no host read, no allocation: the same bits every call, and under graph replay.  A degenerate
+ * input gives a status word (an IVLM_START_* bit, 0 = fine) and zeros in place of the result, never a NaN.
+ * ivlm_mesh_vertex_normals: verts f32 [N,3], faces i32 [F,3], vert_face_offsets i32 [N+1] / vert_face_list i32 [3F] as
+ *   ivlm_soft_silhouette_backward takes them (per vertex the slots face * 3 + corner of its faces, ascending) -> normals_out f32 [N,3]:
+ *   the sum over the vertex's faces of cross(b - a, c - a), added in slot order from 0.0, divided by its length; (0,0,0) for a zero sum
+ *   (an unreferenced vertex, only zero-area faces).  A slot or an index out of range is skipped.
+ * ivlm_mesh_surface_centroid: -> centroid_out f32 [3] = sum_f A_f (a + b + c) / 3 / sum_f A_f, A_f = |cross(b - a, c - a)| / 2;
+ *   status_out i64 [1] = IVLM_START_NO_AREA (and a zero centroid) when no face has an area.  A face with an index outside [0, N) is
+ *   skipped.  workspace: ivlm_mesh_surface_centroid_workspace_bytes(F) = 32 ceil(F / 256) bytes padded to 256.
+ * ivlm_mask_stats: mask u8 [H,W] (a pixel is on when its byte is not 0) -> record_out i64 [IVLM_MASK_RECORD], the IVLM_MASK_* fields:
+ *   the count, the bounding box, the sums of the row and of the column indices, (row, col) of the first and of the second pixel that is
+ *   on, in row-major order (-1 for a field that no pixel defines), and IVLM_START_EMPTY_MASK in the status for count 0.  Integers only.
+ *   workspace: ivlm_mask_stats_workspace_bytes(H, W) = 72 ceil(H W / 4096) bytes padded to 256.
+ * ivlm_contact_depth: verts f32 [N,3], probs [N] of p_dtype (IVLM_F32 or IVLM_BF16), over the vertices with (float)probs > threshold
+ *   (strict) -> record_out i64 [IVLM_DEPTH_RECORD] = (their number, IVLM_START_NO_CONTACT when it is 0), z_sum_out f64 [1] the sum of
+ *   their z, z_out f32 [1] the mean rounded once (0 for none).  workspace: ivlm_contact_depth_workspace_bytes(N) = 16 ceil(N / 256)
+ *   bytes padded to 256.
+ * ivlm_start_translation: the two records and z of the calls above, camera f32 [4] = (fx, fy, px, py) and centroid_offset f32 [3] (or
+ *   NULL = 0) on the device -> translation_out f32 [3], status_out i64 [1].  mirror = 1: optim/fit.py:119-135 as written, in fp32, one
+ *   operation at a time: T = (((r2 + c2) / 2 - px) z / fx, ((r1 + c1) / 2 - py) z / fy, z) with (r1, c1) / (r2, c2) the first / second
+ *   pixel that is on; fewer than two such pixels: IVLM_START_FEW_PIXELS.  mirror = 0 (NOT the reference's): the point at depth
+ *   z + offset.z on the camera ray through (col_sum / count + 0.5, row_sum / count + 0.5), minus centroid_offset; fp64, rounded once;
+ *   count 0: IVLM_START_EMPTY_MASK.  Both: no vertex in the depth record: IVLM_START_NO_CONTACT.
+ * N, F <= 2^22, H, W <= 16384, else IVLM_ERR_UNSUPPORTED (the size queries return 0); NULL pointers and non-positive sizes
+ * IVLM_ERR_INVALID_ARG before any launch; workspaces 16-byte aligned. */
+#define IVLM_MASK_COUNT 0
+#define IVLM_MASK_ROW_MIN 1
+#define IVLM_MASK_ROW_MAX 2
+#define IVLM_MASK_COL_MIN 3
+#define IVLM_MASK_COL_MAX 4
+#define IVLM_MASK_ROW_SUM 5
+#define IVLM_MASK_COL_SUM 6
+#define IVLM_MASK_FIRST_ROW 7
+#define IVLM_MASK_FIRST_COL 8
+#define IVLM_MASK_SECOND_ROW 9
+#define IVLM_MASK_SECOND_COL 10
+#define IVLM_MASK_STATUS 11
+#define IVLM_MASK_RECORD 12
+#define IVLM_DEPTH_COUNT 0
+#define IVLM_DEPTH_STATUS 1
+#define IVLM_DEPTH_RECORD 2
+#define IVLM_START_EMPTY_MASK 1
+#define IVLM_START_FEW_PIXELS 2
+#define IVLM_START_NO_CONTACT 4
+#define IVLM_START_NO_AREA 8
+int ivlm_mesh_vertex_normals(const float *verts, const int32_t *faces, const int32_t *vert_face_offsets, const int32_t *vert_face_list,
+                             int N, int F, float *normals_out, ivlm_stream_t stream);
+size_t ivlm_mesh_surface_centroid_workspace_bytes(int F);
+int ivlm_mesh_surface_centroid(const float *verts, const int32_t *faces, int N, int F, float *centroid_out, int64_t *status_out,
+                               void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+size_t ivlm_mask_stats_workspace_bytes(int H, int W);
+int ivlm_mask_stats(const uint8_t *mask, int H, int W, int64_t *record_out, void *workspace, size_t workspace_bytes,
+                    ivlm_stream_t stream);
+size_t ivlm_contact_depth_workspace_bytes(int N);
+int ivlm_contact_depth(const float *verts, const void *probs, int p_dtype, int N, float threshold, int64_t *record_out,
+                       double *z_sum_out, float *z_out, void *workspace, size_t workspace_bytes, ivlm_stream_t stream);
+int ivlm_start_translation(const int64_t *mask_record, const int64_t *depth_record, const float *z, const float *camera,
+                           const float *centroid_offset, int mirror, float *translation_out, int64_t *status_out, ivlm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * "Render" of Render-Localize-Lift: rasterise a mesh / point cloud into the lift tables.
  * pytorch3d semantics (preprocess_data/render_mesh_utils.py:115-174, utils_obj_pc.py:28-42,88-113,

@@ -31,6 +31,8 @@ EXTRA = {
     "mesh_sdf.hip": ["-ffp-contract=off"],
     # every fp32 operation of the z-buffer and of the depth-order term is the one its header states
     "depth_order.hip": ["-ffp-contract=off"],
+    # the fp32 steps of the stage-1 translation are optim/fit.py:125-128's torch operations one by one
+    "fit_start.hip": ["-ffp-contract=off"],
 }
 
 

@@ -19,6 +19,11 @@ SAM_STD_PIXEL = (58.395, 57.12, 57.375)
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)  # utils/utils.py:14-15 (0-1 RGB)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
+# OSX camera setup of the object-pose fit (optim/constants.py:6-8; read by fit_start.osx_camera)
+OSX_FOCAL_VIRTUAL = (5000, 5000)                                        # optim/constants.py:6
+OSX_INPUT_BODY_SHAPE = (256, 192)                                       # optim/constants.py:7
+OSX_PRINCPT = (OSX_INPUT_BODY_SHAPE[1] / 2, OSX_INPUT_BODY_SHAPE[0] / 2)  # optim/constants.py:8
+
 _OBJ_CAMS = {
     "frontleft": (2.0, 45.0, 315.0, 0.0, 0.0),
     "frontright": (2.0, 45.0, 45.0, 0.0, 0.0),

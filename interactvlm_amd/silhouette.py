@@ -100,7 +100,8 @@ def topology_of(faces, n):
     _topology.pop(key, None)  # (a stale entry of this tensor: re-inserted as the newest)
     while len(_topology) >= _TOPOLOGY_MAX:
         _topology.pop(next(iter(_topology)))  # the oldest
-    _topology[key] = (weakref.ref(faces, lambda _, key=key: _topology.pop(key, None)), faces._version, n, value)
+    # (the table is bound here: a tensor that dies at interpreter exit finds the module's globals already cleared)
+    _topology[key] = (weakref.ref(faces, lambda _, key=key, table=_topology: table.pop(key, None)), faces._version, n, value)
     return value
 
 
