@@ -17,53 +17,40 @@
 //                Nothing flows through the coverage edge or through D_h.
 //
 // Launches (the caller's stream, no atomics on floats, every sum in a fixed order: the same bits every call, for a pose whatever the
-// batch around it; built with -ffp-contract=off, so every fp32 operation below is the one that is written):
-//   dep_project   per vertex (u, v); resets the pose's union box
-//   dep_faces     per face three float4 (a, b | c, 1 / Z_a, 1 / Z_b | 1 / Z_c, Z_a, Z_b, Z_c), its pixel box (no growth: an empty box for
-//                 a skipped face) and the union of the boxes (integer atomicMin / atomicMax: order-free)
-//   dep_forward   pixel-stationary, as sil_forward: one 256-thread block per 16 x 16 tile, one pixel per thread; the boxes in chunks of
-//                 256, the faces whose box meets the tile compacted into LDS in ascending face order, every lane reads the same record
-//                 and, at the pixels of the face's own box (the pixels the backward walks), keeps (z, k) under a strict <, so equal
-//                 depths stay with the lowest index
+// batch around it; built with -ffp-contract=off, so every fp32 operation below - and of screen_common.h's walk, shared with
+// silhouette.hip, as it is compiled into this file - is the one that is written):
+//   screen_project    per vertex (u, v); resets the pose's union box
+//   dep_faces         screen_face without growth; per face three float4 (a, b | c, 1 / Z_a, 1 / Z_b | 1 / Z_c, Z_a, Z_b, Z_c) and its
+//                     box; union_fold
+//   dep_forward       tile_chunk: the records of the faces that meet the tile go to LDS with their index and box, then every lane
+//                     reads the same record and, at the pixels of the face's own box (the pixels the backward walks), keeps (z, k)
+//                     under a strict <, so equal depths stay with the lowest index
 //   dord_rows / dord_final   per image row the fp64 sums (sum |c| softplus, sum |c|), every pixel converted to fp64 before it is added
-//                 (block4_sum), then the rows by wave_fold; the value and (S, n) per pose
-//   dord_backward face-stationary: one wave per face walks its box 64 pixels at a time; at the pixels it won it recomputes the e_i and
-//                 accumulates the [3, 3] record (du, dv, dZ direct per corner): IVLM_DEPTH_ORDER_CHAIN fp32 additions per lane, then
-//                 fp64, wave_sum across the lanes
-//   dord_gather   per vertex: the records of its incident faces in ascending face order (the CSR lists of the silhouette), summed in
-//                 fp64, chained through the projection to dL/d(X, Y, Z)
+//                     (block4_sum), then the rows by wave_fold; the value and (S, n) per pose
+//   dord_backward     box_walk<9>: at the pixels the face won it recomputes the e_i and adds to the [3, 3] record (du, dv, dZ direct
+//                     per corner), IVLM_DEPTH_ORDER_CHAIN fp32 additions per lane
+//   screen_gather<3>  per vertex: the records of its incident faces (the CSR lists of the silhouette), chained through the
+//                     projection to dL/d(X, Y, Z)
 #include <algorithm>
 #include <cmath>
 
-#include "fit_common.h"
+#include "screen_common.h"
 
 namespace ivlm {
 namespace {
 
-constexpr int kTile = 16;                        // pixels per tile side
-constexpr int kChunk = 256;                      // faces tested per block step = threads per block
 constexpr int kChain = IVLM_DEPTH_ORDER_CHAIN;   // fp32 additions per lane before the fp64 accumulators take over
-constexpr int kMaxN = 1 << 22;                   // vertices, faces
-constexpr int kMaxSide = 16384;                  // H, W
-constexpr float kMinZ = 1e-6f;
-
-struct DepParams {
-    float fx, fy, px, py;
-    int N, F, H, W;
-};
 
 // workspace carves, shared by the size queries and the launchers
 struct DepLayout {
-    size_t uv, tri, box, uni, depth, fid, frec, rows, sums, total;
+    ScreenLayout s;
+    size_t depth, fid, frec, rows, sums, total;
 };
 
 DepLayout dep_layout(int B, int N, int F, int H, int W, bool order) {
     DepLayout l = {};
     Carve c;
-    l.uv = c.take((size_t)B * N * 8);
-    l.tri = c.take((size_t)B * F * 48);
-    l.box = c.take((size_t)B * F * 16);
-    l.uni = c.take((size_t)B * 16);
+    l.s = screen_layout(c, B, N, F, 48);
     if (order) {
         l.depth = c.take((size_t)B * H * W * 4);
         l.fid = c.take((size_t)B * H * W * 4);
@@ -75,83 +62,20 @@ DepLayout dep_layout(int B, int N, int F, int H, int W, bool order) {
     return l;
 }
 
-bool dep_sizes_ok(int B, int N, int F, int H, int W) {
-    return B > 0 && N > 0 && F > 0 && H > 0 && W > 0 && B <= 65535 && N <= kMaxN && F <= kMaxN && H <= kMaxSide && W <= kMaxSide;
-}
-
-bool dep_camera_ok(float fx, float fy, float px, float py) {
-    return std::isfinite(fx) && std::isfinite(fy) && std::isfinite(px) && std::isfinite(py);
-}
-
-__global__ __launch_bounds__(256) void dep_project_kernel(const float* __restrict__ verts, float2* __restrict__ uv,
-                                                          int4* __restrict__ uni, DepParams p) {
-    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0) uni[b] = make_int4(p.W, p.H, -1, -1);  // empty; dep_faces (next on the stream) folds the boxes into it
-    if (n >= p.N) return;
-    const float* v = verts + ((int64_t)b * p.N + n) * 3;
-    const float z = v[2];
-    uv[(int64_t)b * p.N + n] = make_float2(fmaf(p.fx, v[0] / z, p.px), fmaf(p.fy, v[1] / z, p.py));
-}
-
-// first / last pixel whose centre can lie within [lo, hi], one pixel of slack on each side, clamped to [0, n - 1]
-__device__ __forceinline__ void pixel_range(float lo, float hi, int n, int& first, int& last) {
-    first = max((int)floorf(fminf(fmaxf(lo - 0.5f, -1.0f), (float)n)), 0);
-    last = min((int)ceilf(fminf(fmaxf(hi - 0.5f, -1.0f), (float)n)), n - 1);
-}
-
 __global__ __launch_bounds__(256) void dep_faces_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
                                                         const float2* __restrict__ uv, float4* __restrict__ tri,
-                                                        int4* __restrict__ box, int4* __restrict__ uni, DepParams p) {
+                                                        int4* __restrict__ box, int4* __restrict__ uni, ScreenParams p) {
     const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
-    int4 bx = make_int4(p.W, p.H, -1, -1);  // empty: meets no tile, holds no pixel
+    int4 bx = make_int4(p.W, p.H, -1, -1);  // empty
     if (f < p.F) {
-        const int i0 = faces[(int64_t)f * 3], i1 = faces[(int64_t)f * 3 + 1], i2 = faces[(int64_t)f * 3 + 2];
-        float2 A = make_float2(0.f, 0.f), Bv = A, C = A;
-        float za = 1.0f, zb = 1.0f, zc = 1.0f;
-        bool ok = (unsigned)i0 < (unsigned)p.N && (unsigned)i1 < (unsigned)p.N && (unsigned)i2 < (unsigned)p.N;
-        if (ok) {
-            const float* v = verts + (int64_t)b * p.N * 3;
-            za = v[(int64_t)i0 * 3 + 2];
-            zb = v[(int64_t)i1 * 3 + 2];
-            zc = v[(int64_t)i2 * 3 + 2];
-            ok = za > kMinZ && zb > kMinZ && zc > kMinZ;
-        }
-        if (ok) {
-            const float2* q = uv + (int64_t)b * p.N;
-            A = q[i0];
-            Bv = q[i1];
-            C = q[i2];
-            const float area2 = (Bv.x - A.x) * (C.y - A.y) - (Bv.y - A.y) * (C.x - A.x);
-            ok = area2 != 0.0f;
-        }
-        if (ok) {
-            int x0, x1, y0, y1;
-            pixel_range(fminf(A.x, fminf(Bv.x, C.x)), fmaxf(A.x, fmaxf(Bv.x, C.x)), p.W, x0, x1);
-            pixel_range(fminf(A.y, fminf(Bv.y, C.y)), fmaxf(A.y, fmaxf(Bv.y, C.y)), p.H, y0, y1);
-            if (x0 <= x1 && y0 <= y1) bx = make_int4(x0, y0, x1, y1);
-        } else {
-            za = zb = zc = 1.0f;
-        }
+        const ScreenFace t = screen_face(verts, faces, uv, b, f, 0.0f, p);
         const int64_t at = (int64_t)b * p.F + f;
-        tri[at * 3] = make_float4(A.x, A.y, Bv.x, Bv.y);
-        tri[at * 3 + 1] = make_float4(C.x, C.y, 1.0f / za, 1.0f / zb);
-        tri[at * 3 + 2] = make_float4(1.0f / zc, za, zb, zc);
-        box[at] = bx;
+        tri[at * 3] = make_float4(t.a.x, t.a.y, t.b.x, t.b.y);
+        tri[at * 3 + 1] = make_float4(t.c.x, t.c.y, 1.0f / t.za, 1.0f / t.zb);
+        tri[at * 3 + 2] = make_float4(1.0f / t.zc, t.za, t.zb, t.zc);
+        box[at] = bx = t.box;
     }
-    int mnx = bx.x, mny = bx.y, mxx = bx.z, mxy = bx.w;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mnx = min(mnx, __shfl_xor(mnx, o, 64));
-        mny = min(mny, __shfl_xor(mny, o, 64));
-        mxx = max(mxx, __shfl_xor(mxx, o, 64));
-        mxy = max(mxy, __shfl_xor(mxy, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0 && mxx >= 0) {  // integer min / max: the result does not depend on the order
-        atomicMin(&uni[b].x, mnx);
-        atomicMin(&uni[b].y, mny);
-        atomicMax(&uni[b].z, mxx);
-        atomicMax(&uni[b].w, mxy);
-    }
+    union_fold(bx, uni + b);
 }
 
 // the three edge functions of a face (r0 = a, b; c = (cx, cy)) at the pixel centre (qx, qy) -> covered
@@ -164,69 +88,45 @@ __device__ __forceinline__ bool edge_functions(const float4 r0, float cx, float 
 
 __global__ __launch_bounds__(kChunk) void dep_forward_kernel(const float4* __restrict__ tri, const int4* __restrict__ box,
                                                              const int4* __restrict__ uni, float* __restrict__ depth,
-                                                             int32_t* __restrict__ face_id, DepParams p) {
+                                                             int32_t* __restrict__ face_id, ScreenParams p) {
     __shared__ float4 rec[kChunk * 2];
     __shared__ float rec_izc[kChunk];
     __shared__ int rec_f[kChunk];
     __shared__ int4 rec_box[kChunk];
-    __shared__ int wcnt[kChunk / 64];
-    const int b = blockIdx.z, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-    const int tx1 = min(tx0 + kTile - 1, p.W - 1), ty1 = min(ty0 + kTile - 1, p.H - 1);
-    const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
-    const bool live = i < p.H && j < p.W;
-    const float qx = (float)j + 0.5f, qy = (float)i + 0.5f;
-    const int4 U = uni[b];
+    const int b = blockIdx.z;
+    const TilePixel t = tile_pixel(p);
     float best = INFINITY;
     int who = -1;
-    if (U.x <= tx1 && U.z >= tx0 && U.y <= ty1 && U.w >= ty0) {  // block-uniform
+    if (tile_meets(uni[b], t)) {
         const int4* bb = box + (int64_t)b * p.F;
         const float4* tb = tri + (int64_t)b * p.F * 3;
         for (int c0 = 0; c0 < p.F; c0 += kChunk) {
-            const int f = c0 + t;
-            bool hit = false;
-            int4 bx = make_int4(0, 0, -1, -1);
-            if (f < p.F) {
-                bx = bb[f];
-                hit = bx.x <= tx1 && bx.z >= tx0 && bx.y <= ty1 && bx.w >= ty0;
-            }
-            const unsigned long long m = __ballot(hit);
-            if (lane == 0) wcnt[wv] = __popcll(m);
-            __syncthreads();
-            int base = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < kChunk / 64; ++w) {
-                const int n = wcnt[w];
-                base += w < wv ? n : 0;
-                total += n;
-            }
-            if (hit) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+            const int total = tile_chunk(bb, p.F, c0, t, [&](int pos, int f, const int4& bx) {
                 rec[pos * 2] = tb[(int64_t)f * 3];
                 rec[pos * 2 + 1] = tb[(int64_t)f * 3 + 1];
                 rec_izc[pos] = tb[(int64_t)f * 3 + 2].x;
                 rec_f[pos] = f;
                 rec_box[pos] = bx;
-            }
-            __syncthreads();
-            if (live) {
+            });
+            if (t.live) {
                 for (int k = 0; k < total; ++k) {
                     // only inside the face's own box, which is all that dord_backward walks: the two kernels see the same pixels
+                    // (| and not ||: one 16-byte LDS read and one branch instead of a dependent read per comparison)
                     const int4 kb = rec_box[k];
-                    if (j < kb.x || j > kb.z || i < kb.y || i > kb.w) continue;
+                    if ((t.j < kb.x) | (t.j > kb.z) | (t.i < kb.y) | (t.i > kb.w)) continue;
                     const float4 r0 = rec[k * 2], r1 = rec[k * 2 + 1];
                     float ea, eb, ec;
-                    if (!edge_functions(r0, r1.x, r1.y, qx, qy, ea, eb, ec)) continue;
+                    if (!edge_functions(r0, r1.x, r1.y, t.qx, t.qy, ea, eb, ec)) continue;
                     const float s = (ea + eb) + ec;
                     const float tt = (ea * r1.z + eb * r1.w) + ec * rec_izc[k];
                     const float z = s / tt;
                     if (z < best) best = z, who = rec_f[k];  // ascending face order and a strict <: equal depths stay with the lowest index
                 }
-            }  // (the next chunk's records are written behind its first barrier, which every wave reaches after this loop)
+            }
         }
     }
-    if (live) {
-        const int64_t at = ((int64_t)b * p.H + i) * p.W + j;
+    if (t.live) {
+        const int64_t at = ((int64_t)b * p.H + t.i) * p.W + t.j;
         depth[at] = best;
         face_id[at] = who;
     }
@@ -283,133 +183,70 @@ __global__ __launch_bounds__(256) void dord_backward_kernel(const float4* __rest
                                                             const float* __restrict__ depth, const int32_t* __restrict__ face_id,
                                                             const float* __restrict__ occ, const float* __restrict__ cw,
                                                             const double* __restrict__ sums, const float* __restrict__ gvalue,
-                                                            float tau, float* __restrict__ frec, DepParams p) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
+                                                            float tau, float* __restrict__ frec, ScreenParams p) {
+    const int b = blockIdx.y;
     const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (f >= p.F) return;  // wave-uniform
     const int64_t at = (int64_t)b * p.F + f;
-    const int4 bx = box[at];
     const float4 r0 = tri[at * 3], r1 = tri[at * 3 + 1], r2 = tri[at * 3 + 2];
-    const int bw = bx.z - bx.x + 1, bh = bx.w - bx.y + 1;
-    const int npx = bw > 0 && bh > 0 ? bw * bh : 0;
     const float* dp = depth + (int64_t)b * p.H * p.W;
     const int32_t* fp = face_id + (int64_t)b * p.H * p.W;
     const double n = sums[(int64_t)b * 2 + 1];
     const float gn = n > 0.0 ? (float)((double)gvalue[b] / n) : 0.0f;  // dL/dD_o = gn c sigmoid(x)
     // 1 / Z_j - 1 / Z_i = (Z_i - Z_j) / (Z_i Z_j), the difference of the depths taken first
     const float dab = (r2.y - r2.z) * (r1.z * r1.w), dac = (r2.y - r2.w) * (r1.z * r2.x), dbc = (r2.z - r2.w) * (r1.w * r2.x);
-    double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int s0 = 0; s0 < npx; s0 += 64 * kChain) {  // wave-uniform bounds
-        float a[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int s1 = min(s0 + 64 * kChain, npx);
-        for (int idx = s0 + lane; idx < s1; idx += 64) {
-            const int dy = idx / bw, dx = idx - dy * bw;
-            const int i = bx.y + dy, j = bx.x + dx;
-            const int64_t px = (int64_t)i * p.W + j;
-            if (fp[px] != f) continue;
-            const float cv = cw[px];
-            float x;
-            if (!order_argument(cv, dp[px], occ[px], tau, x)) continue;
-            const float ex = expf(-fabsf(x));
-            const float sg = (x >= 0.0f ? 1.0f : ex) / (1.0f + ex);
-            const float G = (gn * cv) * sg;
-            if (G == 0.0f) continue;
-            const float qx = (float)j + 0.5f, qy = (float)i + 0.5f;
-            float ea, eb, ec;
-            edge_functions(r0, r1.x, r1.y, qx, qy, ea, eb, ec);  // (covered: the forward kernel evaluated these very operations)
-            const float s = (ea + eb) + ec;
-            const float tt = (ea * r1.z + eb * r1.w) + ec * r2.x;
-            const float z = s / tt;
-            const float h = G / (tt * tt);
-            const float ga = h * (eb * dab + ec * dac);    // G dz/de_a, n_a = e_b (1/Z_b - 1/Z_a) + e_c (1/Z_c - 1/Z_a)
-            const float gb = h * (ec * dbc - ea * dab);
-            const float gc = h * (-(ea * dac) - eb * dbc);
-            const float k = (G * z) / tt;                  // G dz/dZ_i = k e_i / Z_i^2
-            a[0] += gb * (qy - r1.y) + gc * (r0.w - qy);   // a: the end of edge c -> a (e_b), the start of a -> b (e_c)
-            a[1] += gb * (r1.x - qx) + gc * (qx - r0.z);
-            a[2] += k * (ea * (r1.z * r1.z));
-            a[3] += gc * (qy - r0.y) + ga * (r1.y - qy);   // b: the end of a -> b (e_c), the start of b -> c (e_a)
-            a[4] += gc * (r0.x - qx) + ga * (qx - r1.x);
-            a[5] += k * (eb * (r1.w * r1.w));
-            a[6] += ga * (qy - r0.w) + gb * (r0.y - qy);   // c: the end of b -> c (e_a), the start of c -> a (e_b)
-            a[7] += ga * (r0.z - qx) + gb * (qx - r0.x);
-            a[8] += k * (ec * (r2.x * r2.x));
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) acc[k] += (double)a[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) frec[at * 9 + k] = (float)acc[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void dord_gather_kernel(const float* __restrict__ verts, const float* __restrict__ frec,
-                                                          const int32_t* __restrict__ vf_off, const int32_t* __restrict__ vf_list,
-                                                          float* __restrict__ gverts, DepParams p) {
-    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= p.N) return;
-    const float* fr = frec + (int64_t)b * p.F * 9;
-    const int e0 = vf_off[n], e1 = vf_off[n + 1];
-    double gu = 0.0, gv = 0.0, gz = 0.0;
-    for (int e = e0; e < e1; ++e) {  // ascending face order: the list is sorted
-        const int slot = vf_list[e];  // face * 3 + corner
-        if ((unsigned)slot < (unsigned)p.F * 3u) {
-            gu += (double)fr[(int64_t)slot * 3];
-            gv += (double)fr[(int64_t)slot * 3 + 1];
-            gz += (double)fr[(int64_t)slot * 3 + 2];
-        }
-    }
-    const float* v = verts + ((int64_t)b * p.N + n) * 3;
-    float* g = gverts + ((int64_t)b * p.N + n) * 3;
-    const double z = (double)v[2];
-    const double iz = v[2] > kMinZ ? 1.0 / z : 0.0;  // every face of a vertex with Z <= 1e-6 is skipped: gu = gv = gz = 0
-    const double ax = gu * (double)p.fx * iz, ay = gv * (double)p.fy * iz;
-    g[0] = (float)ax;
-    g[1] = (float)ay;
-    g[2] = (float)(gz - (ax * (double)v[0] + ay * (double)v[1]) * iz);
-}
-
-DepParams dep_params(int N, int F, int H, int W, float fx, float fy, float px, float py) {
-    DepParams p;
-    p.fx = fx, p.fy = fy, p.px = px, p.py = py;
-    p.N = N, p.F = F, p.H = H, p.W = W;
-    return p;
-}
-
-// the three launches of the z-buffer, into depth / face_id
-void launch_depth(const float* verts, const int32_t* faces, int B, const DepParams& p, const DepLayout& l, void* ws, float* depth,
-                  int32_t* face_id, hipStream_t st) {
-    float2* uv = ws_at<float2>(ws, l.uv);
-    float4* tri = ws_at<float4>(ws, l.tri);
-    int4* box = ws_at<int4>(ws, l.box);
-    int4* uni = ws_at<int4>(ws, l.uni);
-    dep_project_kernel<<<dim3((p.N + 255) / 256, B), 256, 0, st>>>(verts, uv, uni, p);
-    dep_faces_kernel<<<dim3((p.F + 255) / 256, B), 256, 0, st>>>(verts, faces, uv, tri, box, uni, p);
-    dep_forward_kernel<<<dim3((p.W + kTile - 1) / kTile, (p.H + kTile - 1) / kTile, B), kChunk, 0, st>>>(tri, box, uni, depth, face_id, p);
+    box_walk<9, kChain>(box[at], p.W, [&](int i, int j, int64_t px, float (&a)[9]) {
+        if (fp[px] != f) return;
+        const float cv = cw[px];
+        float x;
+        if (!order_argument(cv, dp[px], occ[px], tau, x)) return;
+        const float ex = expf(-fabsf(x));
+        const float sg = (x >= 0.0f ? 1.0f : ex) / (1.0f + ex);
+        const float G = (gn * cv) * sg;
+        if (G == 0.0f) return;
+        const float qx = (float)j + 0.5f, qy = (float)i + 0.5f;
+        float ea, eb, ec;
+        edge_functions(r0, r1.x, r1.y, qx, qy, ea, eb, ec);  // (covered: the forward kernel evaluated these very operations)
+        const float s = (ea + eb) + ec;
+        const float tt = (ea * r1.z + eb * r1.w) + ec * r2.x;
+        const float z = s / tt;
+        const float h = G / (tt * tt);
+        const float ga = h * (eb * dab + ec * dac);    // G dz/de_a, n_a = e_b (1/Z_b - 1/Z_a) + e_c (1/Z_c - 1/Z_a)
+        const float gb = h * (ec * dbc - ea * dab);
+        const float gc = h * (-(ea * dac) - eb * dbc);
+        const float k = (G * z) / tt;                  // G dz/dZ_i = k e_i / Z_i^2
+        a[0] += gb * (qy - r1.y) + gc * (r0.w - qy);   // a: the end of edge c -> a (e_b), the start of a -> b (e_c)
+        a[1] += gb * (r1.x - qx) + gc * (qx - r0.z);
+        a[2] += k * (ea * (r1.z * r1.z));
+        a[3] += gc * (qy - r0.y) + ga * (r1.y - qy);   // b: the end of a -> b (e_c), the start of b -> c (e_a)
+        a[4] += gc * (r0.x - qx) + ga * (qx - r1.x);
+        a[5] += k * (eb * (r1.w * r1.w));
+        a[6] += ga * (qy - r0.w) + gb * (r0.y - qy);   // c: the end of b -> c (e_a), the start of c -> a (e_b)
+        a[7] += ga * (r0.z - qx) + gb * (qx - r0.x);
+        a[8] += k * (ec * (r2.x * r2.x));
+    }, frec + at * 9);
 }
 
 }  // namespace
 
 size_t depth_image_workspace_bytes(int B, int N, int F, int H, int W) {
-    if (!dep_sizes_ok(B, N, F, H, W)) return 0;
+    if (!screen_sizes_ok(B, N, F, H, W)) return 0;
     return dep_layout(B, N, F, H, W, false).total;
 }
 
 size_t depth_order_workspace_bytes(int B, int N, int F, int H, int W) {
-    if (!dep_sizes_ok(B, N, F, H, W)) return 0;
+    if (!screen_sizes_ok(B, N, F, H, W)) return 0;
     return dep_layout(B, N, F, H, W, true).total;
 }
 
 int depth_image(const float* verts, const int32_t* faces, int B, int N, int F, int H, int W, float fx, float fy, float px, float py,
                 float* depth, int32_t* face_id, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!verts || !faces || !depth || !face_id || !ws) return IVLM_ERR_INVALID_ARG;
-    if (!dep_sizes_ok(B, N, F, H, W) || !dep_camera_ok(fx, fy, px, py)) return IVLM_ERR_UNSUPPORTED;
+    if (!screen_sizes_ok(B, N, F, H, W) || !screen_camera_ok(fx, fy, px, py)) return IVLM_ERR_UNSUPPORTED;
     const DepLayout l = dep_layout(B, N, F, H, W, false);
     if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
-    launch_depth(verts, faces, B, dep_params(N, F, H, W, fx, fy, px, py), l, ws, depth, face_id, st);
+    const ScreenParams p = {fx, fy, px, py, N, F, H, W};
+    screen_forward(dep_faces_kernel, dep_forward_kernel, verts, faces, B, p, p, l.s, ws, depth, face_id, st);
     return ivlm_launch_status();
 }
 
@@ -418,12 +255,13 @@ static bool tau_ok(float tau) { return std::isfinite(tau) && tau > 0.0f; }
 int depth_order_forward(const float* verts, const int32_t* faces, const float* occ, const float* cw, int B, int N, int F, int H, int W,
                         float fx, float fy, float px, float py, float tau, float* value, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!verts || !faces || !occ || !cw || !value || !ws) return IVLM_ERR_INVALID_ARG;
-    if (!dep_sizes_ok(B, N, F, H, W) || !dep_camera_ok(fx, fy, px, py) || !tau_ok(tau)) return IVLM_ERR_UNSUPPORTED;
+    if (!screen_sizes_ok(B, N, F, H, W) || !screen_camera_ok(fx, fy, px, py) || !tau_ok(tau)) return IVLM_ERR_UNSUPPORTED;
     const DepLayout l = dep_layout(B, N, F, H, W, true);
     if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     float* depth = ws_at<float>(ws, l.depth);
     double* rows = ws_at<double>(ws, l.rows);
-    launch_depth(verts, faces, B, dep_params(N, F, H, W, fx, fy, px, py), l, ws, depth, ws_at<int32_t>(ws, l.fid), st);
+    const ScreenParams p = {fx, fy, px, py, N, F, H, W};
+    screen_forward(dep_faces_kernel, dep_forward_kernel, verts, faces, B, p, p, l.s, ws, depth, ws_at<int32_t>(ws, l.fid), st);
     dord_rows_kernel<<<dim3(H, B), 256, 0, st>>>(depth, occ, cw, tau, rows, H, W);
     dord_final_kernel<<<B, 64, 0, st>>>(rows, ws_at<double>(ws, l.sums), value, tau, H);
     return ivlm_launch_status();
@@ -433,15 +271,15 @@ int depth_order_backward(const float* verts, const int32_t* vf_off, const int32_
                          const float* gvalue, int B, int N, int F, int H, int W, float fx, float fy, float px, float py, float tau,
                          float* gverts, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!verts || !vf_off || !vf_list || !occ || !cw || !gvalue || !gverts || !ws) return IVLM_ERR_INVALID_ARG;
-    if (!dep_sizes_ok(B, N, F, H, W) || !dep_camera_ok(fx, fy, px, py) || !tau_ok(tau)) return IVLM_ERR_UNSUPPORTED;
+    if (!screen_sizes_ok(B, N, F, H, W) || !screen_camera_ok(fx, fy, px, py) || !tau_ok(tau)) return IVLM_ERR_UNSUPPORTED;
     const DepLayout l = dep_layout(B, N, F, H, W, true);
     if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
-    const DepParams p = dep_params(N, F, H, W, fx, fy, px, py);
+    const ScreenParams p = {fx, fy, px, py, N, F, H, W};
     float* frec = ws_at<float>(ws, l.frec);
-    dord_backward_kernel<<<dim3((F + 3) / 4, B), 256, 0, st>>>(ws_at<float4>(ws, l.tri), ws_at<int4>(ws, l.box), ws_at<float>(ws, l.depth),
+    dord_backward_kernel<<<dim3((F + 3) / 4, B), 256, 0, st>>>(ws_at<float4>(ws, l.s.tri), ws_at<int4>(ws, l.s.box), ws_at<float>(ws, l.depth),
                                                                ws_at<int32_t>(ws, l.fid), occ, cw, ws_at<double>(ws, l.sums), gvalue, tau,
                                                                frec, p);
-    dord_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, frec, vf_off, vf_list, gverts, p);
+    screen_gather_kernel<3><<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, frec, vf_off, vf_list, gverts, p);
     return ivlm_launch_status();
 }
 

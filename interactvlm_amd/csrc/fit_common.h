@@ -1,6 +1,7 @@
-// What the files of the object-pose fit (contact_pair.hip, contact_icp.hip, silhouette.hip, pose.hip, mesh_sdf.hip, fit_step.hip,
-// depth_order.hip) share: on the host the workspace carve, its check and the typed pointer into it; on the device the fixed-order fp64 folds and the
-// ordered compaction that "the same bits every call, for a pose whatever the batch" rests on (DESIGN 4.44 lists the orders).
+// What the files of the object-pose fit (contact_pair.hip, contact_icp.hip, pose.hip, mesh_sdf.hip, fit_step.hip, fit_start.hip, and
+// through screen_common.h silhouette.hip and depth_order.hip) share: on the host the workspace carve, its check and the typed pointer
+// into it; on the device the fixed-order fp64 folds and the ordered compaction that "the same bits every call, for a pose whatever the
+// batch" rests on (DESIGN 4.44 lists the orders).
 // Every device function is inlined into its kernel and holds only integer and fp64 additions - no fp32 multiply-add that
 // -ffp-contract could fuse - so it is the same arithmetic in the files built with -ffp-contract=off and in those built without.
 // A sum that adds in another order than these stays written out in its kernel, with a comment that says so.

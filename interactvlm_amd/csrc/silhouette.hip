@@ -14,155 +14,83 @@
 //   and through the projection.
 //
 // Launches (all on the caller's stream, no atomics on floats, every sum in a fixed order - the same bits every call, for a pose
-// whatever the batch around it):
-//   sil_project   per vertex (u, v); resets the pose's union box
-//   sil_faces     per face its three screen vertices (two float4), its pixel bounding box grown by r_px = sqrt(blur_radius / kappa)
-//                 (an empty box for a skipped face) and the union of the boxes (integer atomicMin / atomicMax: order-free)
-//   sil_forward   pixel-stationary: one 256-thread block per 16 x 16 tile, one pixel per thread.  The block walks the boxes in
-//                 chunks of 256 (one per thread), compacts the faces whose box meets the tile into LDS in ascending face order
-//                 (ballot + prefix: the list is a function of the geometry alone), then every lane reads the same record (a
-//                 broadcast ds_read_b128) and multiplies 1 + e^(-s_k / sigma) into a running fp32 product D - one rounding per
-//                 face; 1 - alpha = 1 / D.  Tiles outside the union box leave at once.  Writes alpha and keeps 1 - alpha.
-//   sil_backward  face-stationary (the two-roles-instead-of-atomics choice of contact_pair.hip): one wave per face walks the pixels
-//                 of its grown box 64 at a time, reads g_alpha (1 - alpha), recomputes p_k and the distance's derivative and
-//                 accumulates the six screen-space vertex gradients: IVLM_SILHOUETTE_CHAIN fp32 additions per lane, then fp64,
-//                 wave_sum's fp64 butterfly across the lanes, one [3, 2] fp32 record per face.  A box of very many pixels (one huge
-//                 triangle) is walked by that one wave: correct, and its latency is accepted.
-//   sil_gather    per vertex: the records of its incident faces in ascending face order (incidence lists are inputs, built once per
-//                 topology by the caller), summed in fp64, chained through the projection to dL/d(X, Y, Z).
+// whatever the batch around it).  The walk over the faces is screen_common.h's, shared with depth_order.hip; this file holds what
+// is done per (pixel, face):
+//   screen_project    per vertex (u, v); resets the pose's union box
+//   sil_faces         screen_face with the box grown by r_px = sqrt(blur_radius / kappa); per face its three screen vertices (two
+//                     float4) and its box; union_fold
+//   sil_forward       tile_chunk: the records of the faces that meet the tile go to LDS, then every lane reads the same record (a
+//                     broadcast ds_read_b128) and multiplies 1 + e^(-s_k / sigma) into a running fp32 product D - one rounding per
+//                     face; 1 - alpha = 1 / D.  Writes alpha and keeps 1 - alpha.
+//   sil_backward      box_walk<6>: at every pixel of the face's grown box it reads g_alpha (1 - alpha), recomputes p_k and the
+//                     distance's derivative and adds to the six screen-space vertex gradients, IVLM_SILHOUETTE_CHAIN fp32 additions
+//                     per lane; one [3, 2] fp32 record per face
+//   screen_gather<2>  per vertex: the records of its incident faces, chained through the projection to dL/d(X, Y, Z)
 //   terms_rows / terms_final / terms_grad   one fp64 reduction of (sum alpha, sum alpha t, sum t, sum i alpha, sum j alpha) per pose
 //                 (per row block4_sum, then the rows by wave_fold: fit_common.h), mask_loss = 1 - sum(alpha t) / (sum alpha + sum t),
 //                 centroid = (sum i alpha, sum j alpha) / sum alpha, and their analytic d / d alpha image.
 #include <algorithm>
 #include <cmath>
 
-#include "fit_common.h"
+#include "screen_common.h"
 
 namespace ivlm {
 namespace {
 
-constexpr int kTile = 16;                       // pixels per tile side
-constexpr int kChunk = 256;                     // faces tested per block step = threads per block
 constexpr int kChain = IVLM_SILHOUETTE_CHAIN;   // fp32 additions per lane before the fp64 accumulators take over
-constexpr int kMaxN = 1 << 22;                  // vertices, faces
-constexpr int kMaxSide = 16384;                 // H, W
-constexpr float kMinZ = 1e-6f;
 constexpr float kMinEdge2 = 1e-8f;
 constexpr float kMaxExp2 = 100.0f;              // e^(-s / sigma) is clamped at 2^100 and the product at 1e30: 1 - alpha >= 1e-30
 constexpr float kMaxProd = 1e30f;
 
 struct SilParams {
-    float fx, fy, px, py;
+    ScreenParams s;
     float c;      // kappa / sigma
     float c2;     // kappa / sigma * log2(e)
     float d_cut;  // blur_radius / kappa: the cut-off in pixels^2
     float r_px;   // sqrt(d_cut), rounded up
-    int N, F, H, W;
 };
 
 SilParams sil_params(int N, int F, int H, int W, float fx, float fy, float px, float py, float sigma, float blur) {
     SilParams p;
     const double side = (double)std::min(H, W);
     const double kappa = (2.0 / side) * (2.0 / side);
-    p.fx = fx;
-    p.fy = fy;
-    p.px = px;
-    p.py = py;
+    p.s = ScreenParams{fx, fy, px, py, N, F, H, W};
     p.c = (float)(kappa / (double)sigma);
     p.c2 = (float)(kappa / (double)sigma * 1.4426950408889634);
     p.d_cut = (float)((double)blur / kappa);
     p.r_px = std::nextafter((float)std::sqrt((double)blur / kappa), INFINITY);
-    p.N = N;
-    p.F = F;
-    p.H = H;
-    p.W = W;
     return p;
 }
 
 // workspace carve, shared by the size query and both launchers
 struct SilLayout {
-    size_t uv, tri, box, uni, oma, frec, total;
+    ScreenLayout s;
+    size_t oma, frec, total;
 };
 
 SilLayout sil_layout(int B, int N, int F, int H, int W) {
     SilLayout l;
     Carve c;
-    l.uv = c.take((size_t)B * N * 8);
-    l.tri = c.take((size_t)B * F * 32);
-    l.box = c.take((size_t)B * F * 16);
-    l.uni = c.take((size_t)B * 16);
+    l.s = screen_layout(c, B, N, F, 32);
     l.oma = c.take((size_t)B * H * W * 4);
     l.frec = c.take((size_t)B * F * 24);
     l.total = c.off;
     return l;
 }
 
-bool sil_sizes_ok(int B, int N, int F, int H, int W) {
-    return B > 0 && N > 0 && F > 0 && H > 0 && W > 0 && B <= 65535 && N <= kMaxN && F <= kMaxN && H <= kMaxSide && W <= kMaxSide;
-}
-
-__global__ __launch_bounds__(256) void sil_project_kernel(const float* __restrict__ verts, float2* __restrict__ uv,
-                                                          int4* __restrict__ uni, SilParams p) {
-    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0) uni[b] = make_int4(p.W, p.H, -1, -1);  // empty; sil_faces (next on the stream) folds the boxes into it
-    if (n >= p.N) return;
-    const float* v = verts + ((int64_t)b * p.N + n) * 3;
-    const float z = v[2];
-    uv[(int64_t)b * p.N + n] = make_float2(fmaf(p.fx, v[0] / z, p.px), fmaf(p.fy, v[1] / z, p.py));
-}
-
-// first / last pixel whose centre can lie within [lo, hi], one pixel of slack on each side, clamped to [0, n - 1]
-__device__ __forceinline__ void pixel_range(float lo, float hi, int n, int& first, int& last) {
-    first = max((int)floorf(fminf(fmaxf(lo - 0.5f, -1.0f), (float)n)), 0);
-    last = min((int)ceilf(fminf(fmaxf(hi - 0.5f, -1.0f), (float)n)), n - 1);
-}
-
 __global__ __launch_bounds__(256) void sil_faces_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
                                                         const float2* __restrict__ uv, float4* __restrict__ tri,
                                                         int4* __restrict__ box, int4* __restrict__ uni, SilParams p) {
     const int b = blockIdx.y, f = blockIdx.x * 256 + threadIdx.x;
-    int4 bx = make_int4(p.W, p.H, -1, -1);  // empty: meets no tile, holds no pixel
-    if (f < p.F) {
-        const int i0 = faces[(int64_t)f * 3], i1 = faces[(int64_t)f * 3 + 1], i2 = faces[(int64_t)f * 3 + 2];
-        float2 A = make_float2(0.f, 0.f), Bv = A, C = A;
-        bool ok = (unsigned)i0 < (unsigned)p.N && (unsigned)i1 < (unsigned)p.N && (unsigned)i2 < (unsigned)p.N;
-        if (ok) {
-            const float* v = verts + (int64_t)b * p.N * 3;
-            ok = v[(int64_t)i0 * 3 + 2] > kMinZ && v[(int64_t)i1 * 3 + 2] > kMinZ && v[(int64_t)i2 * 3 + 2] > kMinZ;
-        }
-        if (ok) {
-            const float2* q = uv + (int64_t)b * p.N;
-            A = q[i0];
-            Bv = q[i1];
-            C = q[i2];
-            const float area2 = (Bv.x - A.x) * (C.y - A.y) - (Bv.y - A.y) * (C.x - A.x);
-            ok = area2 != 0.0f;
-        }
-        if (ok) {
-            int x0, x1, y0, y1;
-            pixel_range(fminf(A.x, fminf(Bv.x, C.x)) - p.r_px, fmaxf(A.x, fmaxf(Bv.x, C.x)) + p.r_px, p.W, x0, x1);
-            pixel_range(fminf(A.y, fminf(Bv.y, C.y)) - p.r_px, fmaxf(A.y, fmaxf(Bv.y, C.y)) + p.r_px, p.H, y0, y1);
-            if (x0 <= x1 && y0 <= y1) bx = make_int4(x0, y0, x1, y1);
-        }
-        const int64_t at = (int64_t)b * p.F + f;
-        tri[at * 2] = make_float4(A.x, A.y, Bv.x, Bv.y);
-        tri[at * 2 + 1] = make_float4(C.x, C.y, 0.f, 0.f);
-        box[at] = bx;
+    int4 bx = make_int4(p.s.W, p.s.H, -1, -1);  // empty
+    if (f < p.s.F) {
+        const ScreenFace t = screen_face(verts, faces, uv, b, f, p.r_px, p.s);
+        const int64_t at = (int64_t)b * p.s.F + f;
+        tri[at * 2] = make_float4(t.a.x, t.a.y, t.b.x, t.b.y);
+        tri[at * 2 + 1] = make_float4(t.c.x, t.c.y, 0.f, 0.f);
+        box[at] = bx = t.box;
     }
-    int mnx = bx.x, mny = bx.y, mxx = bx.z, mxy = bx.w;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mnx = min(mnx, __shfl_xor(mnx, o, 64));
-        mny = min(mny, __shfl_xor(mny, o, 64));
-        mxx = max(mxx, __shfl_xor(mxx, o, 64));
-        mxy = max(mxy, __shfl_xor(mxy, o, 64));
-    }
-    if ((threadIdx.x & 63) == 0 && mxx >= 0) {  // integer min / max: the result does not depend on the order
-        atomicMin(&uni[b].x, mnx);
-        atomicMin(&uni[b].y, mny);
-        atomicMax(&uni[b].z, mxx);
-        atomicMax(&uni[b].w, mxy);
-    }
+    union_fold(bx, uni + b);
 }
 
 // squared distance from q to the segment a-b: d, the residual r = q - a - t (b - a), t, and the edge function cross(b - a, q - a)
@@ -204,52 +132,28 @@ __global__ __launch_bounds__(kChunk) void sil_forward_kernel(const float4* __res
                                                              const int4* __restrict__ uni, float* __restrict__ alpha,
                                                              float* __restrict__ oma, SilParams p) {
     __shared__ float4 rec[kChunk * 2];
-    __shared__ int wcnt[kChunk / 64];
-    const int b = blockIdx.z, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-    const int tx1 = min(tx0 + kTile - 1, p.W - 1), ty1 = min(ty0 + kTile - 1, p.H - 1);
-    const int j = tx0 + (t & (kTile - 1)), i = ty0 + t / kTile;
-    const bool live = i < p.H && j < p.W;
-    const float qx = (float)j + 0.5f, qy = (float)i + 0.5f;
-    const int4 U = uni[b];
+    const int b = blockIdx.z;
+    const TilePixel t = tile_pixel(p.s);
     float D = 1.0f;
-    if (U.x <= tx1 && U.z >= tx0 && U.y <= ty1 && U.w >= ty0) {  // block-uniform
-        const int4* bb = box + (int64_t)b * p.F;
-        const float4* tb = tri + (int64_t)b * p.F * 2;
-        for (int c0 = 0; c0 < p.F; c0 += kChunk) {
-            const int f = c0 + t;
-            bool hit = false;
-            if (f < p.F) {
-                const int4 bx = bb[f];
-                hit = bx.x <= tx1 && bx.z >= tx0 && bx.y <= ty1 && bx.w >= ty0;
-            }
-            const unsigned long long m = __ballot(hit);
-            if (lane == 0) wcnt[wv] = __popcll(m);
-            __syncthreads();
-            int base = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < kChunk / 64; ++w) {
-                const int n = wcnt[w];
-                base += w < wv ? n : 0;
-                total += n;
-            }
-            if (hit) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (tile_meets(uni[b], t)) {
+        const int4* bb = box + (int64_t)b * p.s.F;
+        const float4* tb = tri + (int64_t)b * p.s.F * 2;
+        for (int c0 = 0; c0 < p.s.F; c0 += kChunk) {
+            const int total = tile_chunk(bb, p.s.F, c0, t, [&](int pos, int f, const int4&) {
                 rec[pos * 2] = tb[(int64_t)f * 2];
                 rec[pos * 2 + 1] = tb[(int64_t)f * 2 + 1];
-            }
-            __syncthreads();
-            if (live) {
+            });
+            if (t.live) {
                 for (int k = 0; k < total; ++k) {
                     FaceEval o;
-                    if (face_eval(rec[k * 2], rec[k * 2 + 1], qx, qy, p, o)) D = fminf(fmaf(D, o.e, D), kMaxProd);
+                    if (face_eval(rec[k * 2], rec[k * 2 + 1], t.qx, t.qy, p, o)) D = fminf(fmaf(D, o.e, D), kMaxProd);
                 }
             }
         }
     }
-    if (live) {
+    if (t.live) {
         const float om = 1.0f / D;
-        const int64_t at = ((int64_t)b * p.H + i) * p.W + j;
+        const int64_t at = ((int64_t)b * p.s.H + t.i) * p.s.W + t.j;
         oma[at] = om;
         alpha[at] = 1.0f - om;
     }
@@ -258,76 +162,32 @@ __global__ __launch_bounds__(kChunk) void sil_forward_kernel(const float4* __res
 __global__ __launch_bounds__(256) void sil_backward_kernel(const float4* __restrict__ tri, const int4* __restrict__ box,
                                                            const float* __restrict__ oma, const float* __restrict__ galpha,
                                                            float* __restrict__ frec, SilParams p) {
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int b = blockIdx.y;
     const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (f >= p.F) return;  // wave-uniform
-    const int64_t at = (int64_t)b * p.F + f;
-    const int4 bx = box[at];
+    if (f >= p.s.F) return;  // wave-uniform
+    const int64_t at = (int64_t)b * p.s.F + f;
     const float4 r0 = tri[at * 2], r1 = tri[at * 2 + 1];
-    const int bw = bx.z - bx.x + 1, bh = bx.w - bx.y + 1;
-    const int npx = bw > 0 && bh > 0 ? bw * bh : 0;
-    const float* gp = galpha + (int64_t)b * p.H * p.W;
-    const float* op = oma + (int64_t)b * p.H * p.W;
-    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int s0 = 0; s0 < npx; s0 += 64 * kChain) {  // wave-uniform bounds
-        float a[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int s1 = min(s0 + 64 * kChain, npx);
-        for (int idx = s0 + lane; idx < s1; idx += 64) {
-            const int dy = idx / bw, dx = idx - dy * bw;
-            const int i = bx.y + dy, j = bx.x + dx;
-            const int64_t px = (int64_t)i * p.W + j;
-            const float G = gp[px] * op[px];
-            if (G == 0.0f) continue;
-            FaceEval o;
-            if (!face_eval(r0, r1, (float)j + 0.5f, (float)i + 0.5f, p, o)) continue;
-            const float pk = __fdividef(o.e, 1.0f + o.e);
-            // dL/dd = -/+ G p_k kappa / sigma (outside / inside); d d / d(edge start) = -2 (1 - t) r, d d / d(edge end) = -2 t r
-            const float h = (o.inside ? -2.0f : 2.0f) * G * pk * p.c;
-            const float hb = h * o.t, ha = h - hb;
-            const float wa = o.m == 0 ? ha : (o.m == 2 ? hb : 0.f);
-            const float wb = o.m == 1 ? ha : (o.m == 0 ? hb : 0.f);
-            const float wc = o.m == 2 ? ha : (o.m == 1 ? hb : 0.f);
-            a[0] = fmaf(wa, o.rx, a[0]);
-            a[1] = fmaf(wa, o.ry, a[1]);
-            a[2] = fmaf(wb, o.rx, a[2]);
-            a[3] = fmaf(wb, o.ry, a[3]);
-            a[4] = fmaf(wc, o.rx, a[4]);
-            a[5] = fmaf(wc, o.ry, a[5]);
-        }
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc[k] += (double)a[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) frec[at * 6 + k] = (float)acc[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void sil_gather_kernel(const float* __restrict__ verts, const float* __restrict__ frec,
-                                                         const int32_t* __restrict__ vf_off, const int32_t* __restrict__ vf_list,
-                                                         float* __restrict__ gverts, SilParams p) {
-    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= p.N) return;
-    const float* fr = frec + (int64_t)b * p.F * 6;
-    const int e0 = vf_off[n], e1 = vf_off[n + 1];
-    double gu = 0.0, gv = 0.0;
-    for (int e = e0; e < e1; ++e) {  // ascending face order: the list is sorted
-        const int slot = vf_list[e];  // face * 3 + corner
-        if ((unsigned)slot < (unsigned)p.F * 3u) {
-            gu += (double)fr[(int64_t)slot * 2];
-            gv += (double)fr[(int64_t)slot * 2 + 1];
-        }
-    }
-    const float* v = verts + ((int64_t)b * p.N + n) * 3;
-    float* g = gverts + ((int64_t)b * p.N + n) * 3;
-    const double z = (double)v[2];
-    const double iz = v[2] > kMinZ ? 1.0 / z : 0.0;  // every face of a vertex with Z <= 1e-6 is skipped: gu = gv = 0
-    const double ax = gu * (double)p.fx * iz, ay = gv * (double)p.fy * iz;
-    g[0] = (float)ax;
-    g[1] = (float)ay;
-    g[2] = (float)(-(ax * (double)v[0] + ay * (double)v[1]) * iz);
+    const float* gp = galpha + (int64_t)b * p.s.H * p.s.W;
+    const float* op = oma + (int64_t)b * p.s.H * p.s.W;
+    box_walk<6, kChain>(box[at], p.s.W, [&](int i, int j, int64_t px, float (&a)[6]) {
+        const float G = gp[px] * op[px];
+        if (G == 0.0f) return;
+        FaceEval o;
+        if (!face_eval(r0, r1, (float)j + 0.5f, (float)i + 0.5f, p, o)) return;
+        const float pk = __fdividef(o.e, 1.0f + o.e);
+        // dL/dd = -/+ G p_k kappa / sigma (outside / inside); d d / d(edge start) = -2 (1 - t) r, d d / d(edge end) = -2 t r
+        const float h = (o.inside ? -2.0f : 2.0f) * G * pk * p.c;
+        const float hb = h * o.t, ha = h - hb;
+        const float wa = o.m == 0 ? ha : (o.m == 2 ? hb : 0.f);
+        const float wb = o.m == 1 ? ha : (o.m == 0 ? hb : 0.f);
+        const float wc = o.m == 2 ? ha : (o.m == 1 ? hb : 0.f);
+        a[0] = fmaf(wa, o.rx, a[0]);
+        a[1] = fmaf(wa, o.ry, a[1]);
+        a[2] = fmaf(wb, o.rx, a[2]);
+        a[3] = fmaf(wb, o.ry, a[3]);
+        a[4] = fmaf(wc, o.rx, a[4]);
+        a[5] = fmaf(wc, o.ry, a[5]);
+    }, frec + at * 6);
 }
 
 // ---- image losses --------------------------------------------------------------------------------------------------------------
@@ -393,30 +253,22 @@ __global__ __launch_bounds__(256) void terms_grad_kernel(const float* __restrict
 }  // namespace
 
 size_t soft_silhouette_workspace_bytes(int B, int N, int F, int H, int W) {
-    if (!sil_sizes_ok(B, N, F, H, W)) return 0;
+    if (!screen_sizes_ok(B, N, F, H, W)) return 0;
     return sil_layout(B, N, F, H, W).total;
 }
 
 static bool sil_camera_ok(float fx, float fy, float px, float py, float sigma, float blur) {
-    return std::isfinite(fx) && std::isfinite(fy) && std::isfinite(px) && std::isfinite(py) && std::isfinite(sigma) && sigma > 0.0f &&
-           std::isfinite(blur) && blur >= 0.0f;
+    return screen_camera_ok(fx, fy, px, py) && std::isfinite(sigma) && sigma > 0.0f && std::isfinite(blur) && blur >= 0.0f;
 }
 
 int soft_silhouette_forward(const float* verts, const int32_t* faces, int B, int N, int F, int H, int W, float fx, float fy, float px,
                             float py, float sigma, float blur, float* alpha, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!verts || !faces || !alpha || !ws) return IVLM_ERR_INVALID_ARG;
-    if (!sil_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
+    if (!screen_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
     const SilLayout l = sil_layout(B, N, F, H, W);
     if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     const SilParams p = sil_params(N, F, H, W, fx, fy, px, py, sigma, blur);
-    float2* uv = ws_at<float2>(ws, l.uv);
-    float4* tri = ws_at<float4>(ws, l.tri);
-    int4* box = ws_at<int4>(ws, l.box);
-    int4* uni = ws_at<int4>(ws, l.uni);
-    float* oma = ws_at<float>(ws, l.oma);
-    sil_project_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, uv, uni, p);
-    sil_faces_kernel<<<dim3((F + 255) / 256, B), 256, 0, st>>>(verts, faces, uv, tri, box, uni, p);
-    sil_forward_kernel<<<dim3((W + kTile - 1) / kTile, (H + kTile - 1) / kTile, B), kChunk, 0, st>>>(tri, box, uni, alpha, oma, p);
+    screen_forward(sil_faces_kernel, sil_forward_kernel, verts, faces, B, p.s, p, l.s, ws, alpha, ws_at<float>(ws, l.oma), st);
     return ivlm_launch_status();
 }
 
@@ -424,16 +276,16 @@ int soft_silhouette_backward(const float* verts, const int32_t* vf_off, const in
                              int H, int W, float fx, float fy, float px, float py, float sigma, float blur, float* gverts, void* ws,
                              size_t ws_bytes, hipStream_t st) {
     if (!verts || !vf_off || !vf_list || !galpha || !gverts || !ws) return IVLM_ERR_INVALID_ARG;
-    if (!sil_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
+    if (!screen_sizes_ok(B, N, F, H, W) || !sil_camera_ok(fx, fy, px, py, sigma, blur)) return IVLM_ERR_UNSUPPORTED;
     const SilLayout l = sil_layout(B, N, F, H, W);
     if (!workspace_ok(ws, ws_bytes, l.total, 16)) return IVLM_ERR_WORKSPACE;
     const SilParams p = sil_params(N, F, H, W, fx, fy, px, py, sigma, blur);
-    const float4* tri = ws_at<float4>(ws, l.tri);
-    const int4* box = ws_at<int4>(ws, l.box);
+    const float4* tri = ws_at<float4>(ws, l.s.tri);
+    const int4* box = ws_at<int4>(ws, l.s.box);
     const float* oma = ws_at<float>(ws, l.oma);
     float* frec = ws_at<float>(ws, l.frec);
     sil_backward_kernel<<<dim3((F + 3) / 4, B), 256, 0, st>>>(tri, box, oma, galpha, frec, p);
-    sil_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, frec, vf_off, vf_list, gverts, p);
+    screen_gather_kernel<2><<<dim3((N + 255) / 256, B), 256, 0, st>>>(verts, frec, vf_off, vf_list, gverts, p.s);
     return ivlm_launch_status();
 }
 
