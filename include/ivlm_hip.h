@@ -339,7 +339,9 @@ int ivlm_attention_bf16_split(const void *q, const void *q_lo, const void *k, co
 /* The same operator with fp32 q / k / v / o and no operand rounding, for the SAM mask decoder's small attentions
  * (transformer.py:220-242: head dim 16 or 32; 9 tokens x 4096 image positions or the reverse) and the AttentionSplitter
  * (components.py:155-193: one head of 128 over V keys): scores = (q.k) * scale, fp32 softmax, fp32 P.V on the VALU.
- * D % 4 == 0, D <= 256 (16 / 32 take the fast kernels).  Strides as above but multiples of 4. */
+ * D % 4 == 0, D <= 256 (16 / 32 take the fast kernels), else IVLM_ERR_UNSUPPORTED.  Strides as above but multiples of 4 and the
+ * four pointers 16-byte aligned (every kernel moves float4); a NULL pointer, a size or kv_batch_div <= 0 or B % kv_batch_div != 0:
+ * IVLM_ERR_INVALID_ARG.  Every refusal comes before any launch. */
 int ivlm_attention_f32(const float *q, const float *k, const float *v, float *o, const int64_t *strides_host, int B, int H,
                        int Sq, int Sk, int D, float scale, int kv_batch_div, ivlm_stream_t stream);
 /* Benchmark/test hook: -1 (default) picks per shape; 0 forces the 4-wave / 128-query block, 1 the 8-wave ping-pong block

@@ -160,6 +160,8 @@ int attention_f32(const float* q, const float* k, const float* v, float* o, cons
     if (D <= 0 || D > 256 || (D & 3)) return IVLM_ERR_UNSUPPORTED;
     for (int i = 0; i < 12; ++i)
         if (st12[i] & 3) return IVLM_ERR_INVALID_ARG;  // 16-byte rows
+    for (const void* p : {(const void*)q, (const void*)k, (const void*)v, (const void*)o})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return IVLM_ERR_INVALID_ARG;  // every kernel moves float4
     AttnF32Args a;
     a.q = q; a.k = k; a.v = v; a.o = o;
     a.q_bs = st12[0]; a.q_hs = st12[1]; a.q_rs = st12[2];

@@ -129,7 +129,7 @@ struct AttnArgs {
 
 // softmax(scale * Q.K^T (+ rel-pos bias) (+ causal mask)) . V ; bf16 in/out, fp32 softmax. D in {16,32,64,80,128}.
 int attention_bf16(const AttnArgs& a, hipStream_t st);
-// fp32 operands end to end (SAM mask decoder): D in {16, 32}; strides[12] as the C ABI documents
+// fp32 operands end to end (SAM mask decoder, AttentionSplitter): D % 4 == 0 up to 256; strides[12] as the C ABI documents
 int attention_f32(const float* q, const float* k, const float* v, float* o, const int64_t* st12, int B, int H, int Sq, int Sk,
                   int D, float scale, int kv_div, hipStream_t st);
 // decomposed relative-position bias terms of SAM's ViT (image_encoder.py:354-392) as fp32 tables

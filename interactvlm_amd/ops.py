@@ -845,8 +845,9 @@ def relpos_bias_split(q, q_lo, tab_h, tab_w, SH, SW):
 
 
 def attention_f32(q, k, v, scale, out=None):
-    """fp32 q [B,H,Sq,D], k/v [Bk,H,Sk,D] (D in 16, 32; arbitrary strides % 4) -> o [B,H,Sq,D] fp32 as a view of a
-    [B,Sq,H,D] buffer; scores = (q.k) * scale, no operand rounding (SAM mask decoder)."""
+    """fp32 q [B,H,Sq,D], k/v [Bk,H,Sk,D] (any D % 4 == 0 up to 256: 16 and 32 take the mask decoder's kernels, every other
+    width - the AttentionSplitter's 128 - the wide one; arbitrary strides % 4, 16-byte aligned pointers) -> o [B,H,Sq,D] fp32 as
+    a view of a [B,Sq,H,D] buffer; scores = (q.k) * scale, no operand rounding."""
     import ctypes
 
     lib = _lib.load()

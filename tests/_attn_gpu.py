@@ -1,6 +1,7 @@
-"""GPU-side helpers shared by the attention tests (test_attention_edges_gpu.py, test_attention_routes_gpu.py): every tensor a kernel
-reads is a view into a larger buffer of finite poison (a neighbouring "head" of poison directly behind each head's D columns, slack
-rows behind the last row), the output goes into a sentinel-filled buffer that must be untouched outside the logical region."""
+"""GPU-side helpers shared by the attention tests (test_attention_edges_gpu.py, test_attention_routes_gpu.py,
+test_attention_f32_gpu.py): every tensor a kernel reads is a view into a larger buffer of finite poison (a neighbouring "head" of
+poison directly behind each head's D columns, slack rows behind the last row), the output goes into a sentinel-filled buffer that
+must be untouched outside the logical region."""
 import torch
 
 import _attn_ref as R
@@ -26,11 +27,12 @@ class block_shape:
         self.lib.ivlm_attention_pingpong(-1)
 
 
-def _packed(x, rt, dev, ghost=None):
-    """x [B,H,S,D] -> the same values as a [B,H,S,D] view of a poisoned [B, S + SLACK, H, 2, D] buffer on the device: a head's D
-    columns are followed by D columns of poison, the last row by SLACK rows of it (ghost [D]: the first slack row of every head)."""
+def _packed(x, rt, dev, ghost=None, pad=2):
+    """x [B,H,S,D] -> the same values as a [B,H,S,D] view of a poisoned [B, S + SLACK, H, pad, D] buffer on the device: a head's D
+    columns are followed by (pad - 1) * D columns of poison, the last row by SLACK rows of it (ghost [D]: the first slack row of every
+    head).  Head stride pad * D, row stride H * pad * D: another pad, other strides."""
     B, H, S, D = x.shape
-    buf = torch.full((B, S + SLACK, H, 2, D), POISON, dtype=rt)
+    buf = torch.full((B, S + SLACK, H, pad, D), POISON, dtype=rt)
     buf[:, 1::2] *= -1
     buf[:, :S, :, 0] = x.permute(0, 2, 1, 3).to(rt)
     if ghost is not None:
@@ -60,6 +62,27 @@ def _attend(q, k, v, rt, dev, scale, ghost=(None, None), **kw):
     buf, out = _out_buffer(B, H, Sq, D, rt, dev)
     got = ops.attention(qd, kd, vd, scale, out=out, **kw)
     assert got.data_ptr() == out.data_ptr() and got.dtype == rt
+    _assert_untouched(buf, Sq)
+    return out.cpu()
+
+
+def _attend_f32(q, k, v, dev, scale, ghost=(None, None), k_pad=2, v_pad=3, kv_batches=None):
+    """ops.attention_f32 on poisoned-buffer views of fp32 q [B,H,Sq,D], k / v [Bk,H,Sk,D] (cpu), out= a sentinel buffer; -> cpu
+    [B,H,Sq,D].  k and v sit in buffers of DIFFERENT padding: k_rs != v_rs and k_hs != v_hs (all strides stay multiples of 4 floats,
+    all bases 16-byte aligned).  kv_batches = n: the call gets the first n batches of k / v, the others lie behind them in the same
+    buffers (what a kernel with a wrong K/V batch index then reads is another batch's rows, not unmapped memory)."""
+    from interactvlm_amd import ops
+
+    F32 = torch.float32
+    B, H, Sq, D = q.shape
+    qd, kd, vd = _packed(q, F32, dev), _packed(k, F32, dev, ghost[0], pad=k_pad), _packed(v, F32, dev, ghost[1], pad=v_pad)
+    assert kd.stride(2) != vd.stride(2) and kd.stride(1) != vd.stride(1)
+    assert all(s % 4 == 0 for t in (qd, kd, vd) for s in t.stride()[:3]) and all(t.data_ptr() % 16 == 0 for t in (qd, kd, vd))
+    if kv_batches is not None:
+        kd, vd = kd[:kv_batches], vd[:kv_batches]
+    buf, out = _out_buffer(B, H, Sq, D, F32, dev)
+    got = ops.attention_f32(qd, kd, vd, scale, out=out)
+    assert got.data_ptr() == out.data_ptr() and got.dtype == F32
     _assert_untouched(buf, Sq)
     return out.cpu()
 

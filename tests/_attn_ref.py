@@ -7,6 +7,8 @@
                case of those two roundings (each at most ``u`` relative: ``u * wabs`` from p, ``u * |o|`` from the output).
 * ``probe``    exact "one key per query" inputs: which keys a kernel saw can be read off its output.
 * the case tables shared by ``test_attn_ref_cpu.py`` (separability, emulation caps, mutants) and ``test_attention_edges_gpu.py``.
+* ``probe_f32``, ``probe_verdict_f32`` and the ``F32_*`` tables: the same for the fp32 kernels (``test_attention_f32_gpu.py``), whose
+  bounds are absolute (no operand rounding to measure in units of).
 """
 import functools
 import math
@@ -162,6 +164,108 @@ def probe_verdict(got, vt, o, wabs, visible, rt, emu_stats=None, got_stats=None)
             if not within_margin(gs, emu_stats):
                 bad.append(f"hidden-target rows off the reference: ratio max / rms {gs[0]:.3g} / {gs[1]:.3g} vs emulation {emu_stats[0]:.3g} / {emu_stats[1]:.3g}")
     return bad
+
+
+# ---- fp32 operands (csrc/attention_f32.hip; tests/test_attention_f32_gpu.py) ------------------------------------------------------------
+# A visible probe target: every other key has a score 16 * hamming lower, so the target's weight falls short of 1 by at most
+# (1 + e^-16)^16 - 1 = 1.8e-6 (the sum over all 2^16 - 1 other codes, however many of them are keys).  All values lie in [0, 1], so
+# the fp64 output is within 1.8e-6 of V[target]; 2^-18 = 3.8e-6 is twice that.  The fp32 kernel adds a few units of 2^-24: the
+# scores are exact or one rounding off (probe_f32), the weights of the other keys sum to < 2e-6 and V[target] itself is exact.
+VISIBLE_TOL_F32 = 2.0 ** -18
+# the project's documented bound of this kernel against fp64 (DESIGN.md "attention_f32 ... torch fp64 | 2e-5"; the bound of
+# tests/test_dense_gpu.py::test_attention_f32_vs_torch)
+F32_TOL = 2e-5
+
+
+def probe_f32(Sq, Sk, D, target):
+    """``probe`` for fp32 operands, D % 16 == 0: -> (q, k, v, scale) with q the bare +-1 code (scale = 128 / D makes ``probe``'s q
+    multiplier exactly 1) and scale = 128 / D rounded to fp32, as a python float: the number the test hands to the kernel AND to
+    ref64.  Every dot product is then a small integer (|.| <= D, exact in fp32) and a score that integer times ONE fp32 constant:
+    128 - 16 * hamming(j, target) up to a single rounding, exact when D (hence the scale) is a power of two."""
+    assert D % 16 == 0
+    q, k, v = probe(Sq, Sk, D, target, scale=128.0 / D)
+    assert bool((q.abs() == 1.0).all())
+    return q, k, v, float(torch.tensor(128.0 / D, dtype=torch.float32))
+
+
+F32_KEY_TAIL_SKS = (1, 2, 9, 63, 64, 65, 127, 128, 129, 200, 4096)  # both sides of the 64 / 65 route boundary; Sk % 64 = 1, 63, 0, 1 past a stride
+F32_WIDE_DS = (48, 64, 80, 128, 256)  # the wide kernel with 12 ... 64 live lanes
+F32_KEY_TAIL = ([(Sk, D) for D in (16, 32) for Sk in F32_KEY_TAIL_SKS]  # (Sk, D): Sq = KEY_TAIL_SQ, targets of key_tail_targets
+                + [(Sk, D) for D in F32_WIDE_DS for Sk in (1, 4, 65, 200)])
+F32_QUERY_EDGES = (  # (B, H, Sq, Sk, D), targets of spread_targets
+    # thread per query, 256 queries per block: the block edge from both sides, a second block with 1 and with 44 live threads
+    [(1, 2, Sq, 9, 16) for Sq in (1, 255, 256, 257, 300)] + [(2, 1, Sq, 9, 32) for Sq in (1, 255, 256, 257, 300)]
+    # wave per query, 4 waves per block: B * H * Sq % 4 = 1, 2, 3 - the last block has 3, 2, 1 dead waves
+    + [(B, H, Sq, Sk, D) for Sk, D in ((70, 16), (70, 32), (4, 128)) for B, H, Sq in ((1, 1, 1), (1, 3, 2), (1, 1, 7))])
+F32_KV_ROUTES = [(9, 16), (70, 16), (4, 128)]  # (Sk, D) of the K/V broadcast probe: once per route
+F32_KV_B = 4
+
+
+def attend32(q, k, v, scale):
+    """plain fp32 torch softmax attention of fp32 operands (k / v of batch b // (B // Bk)): what a correct fp32 kernel computes up to
+    the order of its sums - the stand-in for the kernel in the CPU mutants"""
+    B = q.shape[0]
+    s = torch.einsum("bhqd,bhkd->bhqk", q, _expand_kv(k, B)) * scale
+    return torch.einsum("bhqk,bhkd->bhqd", torch.softmax(s, dim=-1), _expand_kv(v, B))
+
+
+def probe_errors_f32(got, vt, o, visible):
+    """(largest |got - V[target]| over the visible rows, smallest max-column distance from V[target] over the hidden rows, largest
+    |got - o| over the hidden rows); None where there is no such row.  got / vt / o [Sq, D] of one (b, h), visible [Sq] bool."""
+    d = (got.double() - vt).abs()
+    hid = ~visible
+    return (float(d[visible].max()) if visible.any() else None,
+            float(d[hid].amax(dim=-1).min()) if hid.any() else None,
+            float((got.double() - o)[hid].abs().max()) if hid.any() else None)
+
+
+def probe_verdict_f32(got, vt, o, visible):
+    """The probe assertions of test_attention_f32_gpu.py as one function (shared with the mutants of the CPU test): a list of failure
+    strings (empty = pass)."""
+    vis_err, sep, hid_err = probe_errors_f32(got, vt, o, visible)
+    bad = []
+    if vis_err is not None and not vis_err <= VISIBLE_TOL_F32:
+        bad.append(f"visible target missed: |got - V[target]| = {vis_err:.3g} > {VISIBLE_TOL_F32:.3g}")
+    if sep is not None and not sep >= SEPARATION:
+        bad.append(f"hidden target seen: output within {sep:.3g} of V[target]")
+    if hid_err is not None and not hid_err <= F32_TOL:
+        bad.append(f"hidden-target rows off the reference: |got - fp64| = {hid_err:.3g} > {F32_TOL:.3g}")
+    return bad
+
+
+@functools.lru_cache(maxsize=None)
+def f32_kv_case(Sk, D, roll):
+    """The K/V broadcast probe, Sq = KEY_TAIL_SQ: (q [Sq,D], k, v [F32_KV_B,1,Sk,D], scale, expected rows [F32_KV_B,Sq,D] fp64 by K/V
+    batch).  roll "v": every K/V batch holds the value rows rotated by another amount (kv_batches) under the same keys; roll "k":
+    the key rows rotated under the same values (code t sits in row (t + 5 i) % Sk of batch i, so that row's value comes back).  A call
+    with kv_div = div reads the first F32_KV_B // div batches; the others are there so that a wrong batch index is a wrong row."""
+    target = spread_targets(KEY_TAIL_SQ, Sk)
+    q, k, v, scale = probe_f32(KEY_TAIL_SQ, Sk, D, target)
+    n = F32_KV_B
+    if roll == "v":
+        ks, vs = k.expand(n, 1, Sk, D), kv_batches(v, n)
+        want = torch.stack([vs[i, 0][target] for i in range(n)])
+    else:
+        ks, vs = kv_batches(k, n), v.expand(n, 1, Sk, D)
+        want = torch.stack([v[(target + 5 * i) % Sk] for i in range(n)])
+    return q.float(), ks.float(), vs.float(), scale, want
+
+
+@functools.lru_cache(maxsize=None)
+def f32_probe_case(Sq, Sk, D, name):
+    """One fp32 probe run, computed once per process: (q, k, v [Sk rows], ghost (k, v row Sk) or (None, None), scale, V[target], fp64
+    output [Sq, D], visible [Sq]).  name: a key of key_tail_targets, or "edges" for spread_targets."""
+    if name == "edges":
+        target, vis = spread_targets(Sq, Sk), True
+    else:
+        assert Sq == KEY_TAIL_SQ
+        target, vis = key_tail_targets(Sk)[name]
+    n = max(Sk, int(target.max()) + 1)
+    q, k, v, scale = probe_f32(Sq, n, D, target)
+    q, k, v = q.float(), k.float(), v.float()
+    ghost = (k[Sk], v[Sk]) if n > Sk else (None, None)
+    o = ref64(q[None, None], k[None, None, :Sk], v[None, None, :Sk], scale)[0][0, 0]
+    return q, k[:Sk], v[:Sk], ghost, scale, v[target].double(), o, torch.full((Sq,), vis)
 
 
 # ---- random-value cases ------------------------------------------------------------------------------------------------------------

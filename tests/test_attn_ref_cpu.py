@@ -5,10 +5,14 @@
 * the emulation of the kernel's documented roundings stays under committed caps on every random-value case - the GPU thresholds are
   multiples of the emulation's ratio, so a changed seed or case cannot silently loosen them;
 * mutants of the reference (last key dropped, causal mask shifted by one, K/V batch 0 for every query batch), rounded like a
-  kernel's output, violate the GPU test's assertions."""
+  kernel's output, violate the GPU test's assertions;
+* the fp32 probes of tests/test_attention_f32_gpu.py: every table entry stays inside half the visible bound and outside the separation
+  in fp64, a plain fp32 softmax passes the verdict, and its mutants (last key dropped, ghost key seen, K/V batch b instead of
+  b // div) do not."""
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -207,3 +211,93 @@ def test_mutant_kv_batch_zero(div, rt):
         assert R.probe_verdict(good[b, 0], vt, o[b, 0], wabs[b, 0], vis, rt) == []
         assert bool(R.probe_verdict(bad[b, 0], vt, o[b, 0], wabs[b, 0], vis, rt)) == (b // div != 0)
 
+
+
+# ---- fp32 operands: the probes, tables and mutants of tests/test_attention_f32_gpu.py ---------------------------------------------------
+F32_DS = (16, 32) + R.F32_WIDE_DS
+
+
+def test_f32_probe_construction():
+    tg = [0, 1, 77, 255, 299]
+    ham = torch.tensor([[bin(j ^ t).count("1") for j in range(300)] for t in tg], dtype=torch.float64)
+    for D in F32_DS:
+        q, k, v, scale = R.probe_f32(5, 300, D, torch.tensor(tg))
+        assert scale == float(np.float32(128.0 / D))
+        for t in (q, k, v):
+            assert torch.equal(t.float().double(), t)  # exact in fp32
+        dot = q.float() @ k.float().T  # every partial sum is an integer of at most D: exact in any order
+        assert torch.equal(dot.double(), q @ k.T) and float(dot.abs().max()) <= D
+        s32 = (dot * torch.tensor(scale, dtype=torch.float32)).double()  # the kernel's score: ONE rounding
+        want = 128.0 - 16.0 * ham
+        assert float((s32 - (q @ k.T) * scale).abs().max()) <= 2.0 ** -24 * 128  # against ref64's score of the same fp32 scale
+        assert float((s32 - want).abs().max()) <= 2.0 ** -24 * 128 * 2  # (and the rounding of the scale itself)
+        if D & (D - 1) == 0:
+            assert torch.equal(s32, want)
+
+
+def test_f32_tables_cover_the_routes():
+    for D in (16, 32):  # both sides of the few-keys / many-keys boundary, lane-count classes 1, 63, 0 and 1 past a 64-key stride
+        assert {sk for sk, d in R.F32_KEY_TAIL if d == D} == set(R.F32_KEY_TAIL_SKS) and {64, 65, 63, 128, 129} <= set(R.F32_KEY_TAIL_SKS)
+    for D in R.F32_WIDE_DS:
+        assert {sk for sk, d in R.F32_KEY_TAIL if d == D} == {1, 4, 65, 200}
+    few = {c[2] for c in R.F32_QUERY_EDGES if c[3] <= 64 and c[4] in (16, 32)}
+    assert few == {1, 255, 256, 257, 300}
+    for Sk, D in ((70, 16), (70, 32), (4, 128)):  # wave per query: every count of dead waves in the last block
+        assert {c[0] * c[1] * c[2] % 4 for c in R.F32_QUERY_EDGES if c[3:] == (Sk, D)} == {1, 2, 3}
+
+
+@pytest.mark.parametrize("Sk,D", R.F32_KEY_TAIL)
+def test_f32_key_tail_probes_separable(Sk, D):
+    """The reference alone stays inside HALF the visible bound and outside the separation, and a plain fp32 softmax passes the verdict."""
+    for name in R.key_tail_targets(Sk):
+        q, k, v, ghost, scale, vt, o, vis = R.f32_probe_case(R.KEY_TAIL_SQ, Sk, D, name)
+        assert (ghost[0] is not None) == (name == "ghost")
+        vis_err, sep, _ = R.probe_errors_f32(o, vt, o, vis)
+        assert vis_err is None or vis_err <= R.VISIBLE_TOL_F32 / 2, (name, vis_err)
+        assert sep is None or sep >= R.SEPARATION, (name, sep)
+        got = R.attend32(q[None, None], k[None, None], v[None, None], scale)[0, 0]
+        assert R.probe_verdict_f32(got, vt, o, vis) == [], name
+
+
+@pytest.mark.parametrize("case", R.F32_QUERY_EDGES, ids=_id)
+def test_f32_query_edge_probes_separable(case):
+    B, H, Sq, Sk, D = case
+    q, k, v, _, scale, vt, o, vis = R.f32_probe_case(Sq, Sk, D, "edges")
+    if Sq >= Sk:
+        assert len(set(R.spread_targets(Sq, Sk).tolist())) == Sk  # spread over ALL keys
+    assert bool(vis.all()) and R.probe_errors_f32(o, vt, o, vis)[0] <= R.VISIBLE_TOL_F32 / 2
+    assert R.probe_verdict_f32(R.attend32(q[None, None], k[None, None], v[None, None], scale)[0, 0], vt, o, vis) == []
+
+
+@pytest.mark.parametrize("Sk,D", [c for c in R.F32_KEY_TAIL if c[0] > 1])
+def test_f32_mutant_last_key_dropped(Sk, D):
+    q, k, v, _, scale, vt, o, vis = R.f32_probe_case(R.KEY_TAIL_SQ, Sk, D, "last")
+    got = R.attend32(q[None, None], k[None, None, :-1], v[None, None, :-1], scale)[0, 0]
+    assert R.probe_verdict_f32(got, vt, o, vis)
+
+
+@pytest.mark.parametrize("Sk,D", R.F32_KEY_TAIL)
+def test_f32_mutant_ghost_key_seen(Sk, D):
+    q, k, v, ghost, scale, vt, o, vis = R.f32_probe_case(R.KEY_TAIL_SQ, Sk, D, "ghost")
+    kg, vg = torch.cat([k, ghost[0][None]]), torch.cat([v, ghost[1][None]])
+    got = R.attend32(q[None, None], kg[None, None], vg[None, None], scale)[0, 0]
+    assert R.probe_verdict_f32(got, vt, o, vis)
+
+
+@pytest.mark.parametrize("roll", ["v", "k"])
+@pytest.mark.parametrize("div", R.KV_DIVS)
+@pytest.mark.parametrize("Sk,D", R.F32_KV_ROUTES)
+def test_f32_mutant_kv_batch_not_divided(Sk, D, div, roll):
+    """K/V batch b instead of b // div: every query batch but the first returns another batch's row, at least 1/16 away."""
+    q, ks, vs, scale, want = R.f32_kv_case(Sk, D, roll)
+    B, n = R.F32_KV_B, R.F32_KV_B // div
+    for i in range(B):
+        for j in range(i):
+            assert float((want[i] - want[j]).abs().amax(dim=-1).min()) >= 1.0 / 16
+    qb = q[None, None].expand(B, 1, *q.shape)
+    o = R.ref64(qb, ks[:n], vs[:n], scale)[0]
+    good, bad = R.attend32(qb, ks[:n], vs[:n], scale), R.attend32(qb, ks, vs, scale)
+    vis = torch.ones(q.shape[0], dtype=torch.bool)
+    for b in range(B):
+        assert R.probe_verdict_f32(good[b, 0], want[b // div], o[b, 0], vis) == []
+        assert bool(R.probe_verdict_f32(bad[b, 0], want[b // div], o[b, 0], vis)) == (b != b // div)
