@@ -802,6 +802,27 @@ int ivlm_normalize_pad_u8(const uint8_t *src, int H, int W, int y0, int x0, int 
  * -> low f32 [B,4gh,4gw] */
 int ivlm_mask_dot(const void *up, const void *hyper, int dtype, float *low, int B, int gh, int gw, int C,
                   ivlm_stream_t stream);
+/* The same for M mask tokens in one pass over `up` (multimask output: mask_decoder.py:150-159): hyper [B,M,C] -> low f32
+ * [B,M,4gh,4gw], low[:, m] bit for bit what ivlm_mask_dot gives for hyper[:, m] (one shared contraction over ascending channels).
+ * C % 8 == 0; 1 <= M <= 4, else IVLM_ERR_UNSUPPORTED before any launch. */
+int ivlm_mask_dot_multi(const void *up, const void *hyper, int dtype, float *low, int B, int M, int gh, int gw, int C,
+                        ivlm_stream_t stream);
+/* PromptEncoder._embed_points / _embed_boxes (prompt_encoder.py:78-109) for R rows: coords f32 [R,2] = (x, y) in the padded input
+ * frame of H x W pixels, labels i32 [R], gauss f32 [2,F] (unrounded), table f32 [5,2F] = rows (negative point, positive point, box
+ * corner 0, box corner 1, not-a-point) -> out f32 [R,2F] = [sin a | cos a] + table[label], a = 2 pi ((2 (coord + 0.5) / (W, H) - 1)
+ * @ gauss) in fp32 in the reference's operation order.  label -1: the not-a-point row alone, whatever the coordinates; labels 0..3:
+ * their table row added; any other label: a row of NaN (the table is never indexed outside its rows).  F % 32 == 0 and F <= 128,
+ * else IVLM_ERR_UNSUPPORTED before any launch. */
+int ivlm_prompt_embed(const float *coords, const int32_t *labels, const float *gauss, const float *table, float *out, int64_t R,
+                      int F, int H, int W, ivlm_stream_t stream);
+/* PromptEncoder._embed_masks (prompt_encoder.py:56-64, 111-114) as one kernel: mask f32 [B,4gh,4gw] -> dense f32 [B,gh*gw,C]
+ * (channels last).  Per output cell its 4x4 patch goes through conv k2s2 (1 -> 4, w0 [4,1,2,2], b0) -> LayerNorm2d (ln1, eps) ->
+ * exact-erf GELU -> conv k2s2 (4 -> 16, w3 [16,4,2,2], b3) -> LayerNorm2d (ln2) -> GELU -> conv 1x1 (16 -> C, w6 [C,16], b6), all in
+ * fp32; every weight f32 in the checkpoint's own layout.  mask and dense 16-byte aligned.  C % 64 == 0 and C <= 256,
+ * mask_in_chans == 16, else IVLM_ERR_UNSUPPORTED before any launch. */
+int ivlm_mask_downscale(const float *mask, const float *w0, const float *b0, const float *ln1_w, const float *ln1_b, const float *w3,
+                        const float *b3, const float *ln2_w, const float *ln2_b, const float *w6, const float *b6, float *dense, int B,
+                        int gh, int gw, int C, int mask_in_chans, float eps, ivlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Right after the path

@@ -33,6 +33,8 @@ EXTRA = {
     "depth_order.hip": ["-ffp-contract=off"],
     # the fp32 steps of the stage-1 translation are optim/fit.py:125-128's torch operations one by one
     "fit_start.hip": ["-ffp-contract=off"],
+    # the point / box encoding is the reference's fp32 operations one by one, in its order
+    "sam_prompt.hip": ["-ffp-contract=off"],
 }
 
 

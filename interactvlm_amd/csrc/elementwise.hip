@@ -1,5 +1,5 @@
 // Data-movement / elementwise kernels of the contact-inference path (gfx950).  All HBM-bound: 16-byte
-// coalesced accesses, no LDS, grid-stride.
+// coalesced accesses, no LDS (mask_dot_multi apart), grid-stride.
 //   im2col_nchw        patch embedding as GEMM   (SAM image_encoder.py:404-426; HF CLIP patch_embedding)
 //   im2col3x3_nhwc     SAM neck 3x3 conv as GEMM (image_encoder.py:92-108)
 //   gather_rows        window partition / unpartition(+residual), token-embedding gather, CLS drop
@@ -9,6 +9,7 @@
 //   rope_kv            rotate-half RoPE on q,k in the fused qkv buffer + KV-cache append (HF LlamaAttention)
 //   mask_dot           masks = hyper_in @ upscaled  (mask_decoder.py:150-153) with the pixel un-shuffle of
 //                      the two k2s2 transposed convolutions
+//   mask_dot_multi     the same for up to four mask tokens in one pass over the upscaled embedding (through LDS)
 #include "kernels.h"
 
 namespace ivlm {
@@ -335,24 +336,87 @@ __global__ __launch_bounds__(kT) void rope_kv_split_kernel(bf16_t* __restrict__ 
 
 // up [B, gh, gw, 2,2, 2,2, C] (two k2s2 transposed convs, channels last)  x  hyper [B, C]
 //   -> low [B, 4gh, 4gw] fp32 at (4y + 2dy + dy2, 4x + 2dx + dx2)
+// (the contraction of mask_dot_kernel and mask_dot_multi_kernel, channel by channel in ascending order: one function, so that the two
+//  cannot drift apart - mask_dot_multi promises mask_dot's bits)
+__device__ __forceinline__ float mask_dot_acc8(float acc, const float* a, const float* h) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += a[j] * h[j];
+    return acc;
+}
+// ... and where pixel i = (b, y, x, dy, dx, dy2, dx2) of `up` lands in low [B, M, 4gh, 4gw] (token m of M)
+__device__ __forceinline__ int64_t mask_dot_pixel(int64_t i, int gh, int gw, int m, int M) {
+    const int sub = (int)(i & 15);
+    const int64_t cell = i >> 4;
+    const int xx = (int)(cell % gw), yy = (int)((cell / gw) % gh), b = (int)(cell / ((int64_t)gw * gh));
+    const int dy = sub >> 3, dx = (sub >> 2) & 1, dy2 = (sub >> 1) & 1, dx2 = sub & 1;
+    const int Y = 4 * yy + 2 * dy + dy2, X = 4 * xx + 2 * dx + dx2;
+    return (((int64_t)b * M + m) * 4 * gh + Y) * (4 * gw) + X;
+}
 __global__ __launch_bounds__(kT) void mask_dot_kernel(const void* __restrict__ up, const void* __restrict__ hyper, int kind,
                                                       float* __restrict__ low, int B, int gh, int gw, int C) {
     const int64_t total = (int64_t)B * gh * gw * 16;
     for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < total; i += (int64_t)gridDim.x * kT) {
-        const int sub = (int)(i & 15);
-        const int64_t cell = i >> 4;
-        const int xx = (int)(cell % gw), yy = (int)((cell / gw) % gh), b = (int)(cell / ((int64_t)gw * gh));
-        const int dy = sub >> 3, dx = (sub >> 2) & 1, dy2 = (sub >> 1) & 1, dx2 = sub & 1;
+        const int b = (int)((i >> 4) / ((int64_t)gw * gh));
         float acc = 0.0f;
         for (int c = 0; c < C; c += 8) {
             float a[8], h[8];
             load8(up, kind, i * C + c, a);
             load8(hyper, kind, (int64_t)b * C + c, h);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc += a[j] * h[j];
+            acc = mask_dot_acc8(acc, a, h);
         }
-        const int Y = 4 * yy + 2 * dy + dy2, X = 4 * xx + 2 * dx + dx2;
-        low[((int64_t)b * 4 * gh + Y) * (4 * gw) + X] = acc;
+        low[mask_dot_pixel(i, gh, gw, 0, 1)] = acc;
+    }
+}
+
+// The same for M <= 4 mask tokens in ONE pass over `up`: hyper [B, M, C] -> low [B, M, 4gh, 4gw], every token's value the bits
+// mask_dot gives for hyper[:, m] (mask_dot_acc8 over ascending channels).  mask_dot's thread reads its pixel's C channels as a
+// 4C-byte strip of its own, C/8 strided 32-byte requests per lane; here a block's kT pixels are one contiguous span of `up`, read
+// by consecutive lanes 32 channels at a time into an LDS tile whose rows are padded to 36 floats (144 B = 9 slots of 16 B: the
+// ds_read_b128 of consecutive rows fall on different slots), then each thread walks its own row against the M hyper rows.
+constexpr int kMdChunk = 32, kMdLd = kMdChunk + 4;
+template <int M>
+__global__ __launch_bounds__(kT) void mask_dot_multi_kernel(const void* __restrict__ up, const void* __restrict__ hyper, int kind,
+                                                            float* __restrict__ low, int B, int gh, int gw, int C) {
+    __shared__ __attribute__((aligned(16))) float tile[kT * kMdLd];
+    const int64_t total = (int64_t)B * gh * gw * 16;
+    for (int64_t base = (int64_t)blockIdx.x * kT; base < total; base += (int64_t)gridDim.x * kT) {
+        const int64_t i = base + threadIdx.x;
+        const bool live = i < total;
+        const int rows = (int)(total - base < kT ? total - base : kT);
+        const int b = live ? (int)((i >> 4) / ((int64_t)gw * gh)) : 0;
+        float acc[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[m] = 0.0f;
+        for (int c0 = 0; c0 < C; c0 += kMdChunk) {
+            const int g8 = (C - c0 < kMdChunk ? C - c0 : kMdChunk) >> 3;
+            __syncthreads();  // (the previous chunk's rows have been read)
+            for (int j = threadIdx.x; j < rows * g8; j += kT) {
+                const int r = j / g8, g = j - r * g8;
+                float f[8];
+                load8(up, kind, (base + r) * C + c0 + g * 8, f);
+                float4* d = reinterpret_cast<float4*>(tile + r * kMdLd + g * 8);
+                d[0] = make_float4(f[0], f[1], f[2], f[3]);
+                d[1] = make_float4(f[4], f[5], f[6], f[7]);
+            }
+            __syncthreads();
+            if (live) {
+                for (int g = 0; g < g8; ++g) {
+                    const float4* s = reinterpret_cast<const float4*>(tile + threadIdx.x * kMdLd + g * 8);
+                    const float4 s0 = s[0], s1 = s[1];
+                    const float a[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+#pragma unroll
+                    for (int m = 0; m < M; ++m) {
+                        float h[8];
+                        load8(hyper, kind, ((int64_t)b * M + m) * C + c0 + g * 8, h);
+                        acc[m] = mask_dot_acc8(acc[m], a, h);
+                    }
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) low[mask_dot_pixel(i, gh, gw, m, M)] = acc[m];
+        }
     }
 }
 
@@ -476,6 +540,18 @@ int mask_dot(const void* up, const void* hyper, int kind, float* low, int B, int
     mask_dot_kernel<<<grid_for((int64_t)B * gh * gw * 16), kT, 0, st>>>(up, hyper, kind, low, B, gh, gw, C);
     return ivlm_launch_status();
 }
+int mask_dot_multi(const void* up, const void* hyper, int kind, float* low, int B, int M, int gh, int gw, int C, hipStream_t st) {
+    if (!up || !hyper || !low || B <= 0 || gh <= 0 || gw <= 0 || C <= 0 || (C & 7) || (kind & ~1)) return IVLM_ERR_INVALID_ARG;
+    if (M < 1 || M > 4) return IVLM_ERR_UNSUPPORTED;
+    const int blocks = grid_for((int64_t)B * gh * gw * 16);
+    switch (M) {
+        case 1: mask_dot_multi_kernel<1><<<blocks, kT, 0, st>>>(up, hyper, kind, low, B, gh, gw, C); break;
+        case 2: mask_dot_multi_kernel<2><<<blocks, kT, 0, st>>>(up, hyper, kind, low, B, gh, gw, C); break;
+        case 3: mask_dot_multi_kernel<3><<<blocks, kT, 0, st>>>(up, hyper, kind, low, B, gh, gw, C); break;
+        default: mask_dot_multi_kernel<4><<<blocks, kT, 0, st>>>(up, hyper, kind, low, B, gh, gw, C); break;
+    }
+    return ivlm_launch_status();
+}
 
 }  // namespace ivlm
 
@@ -551,6 +627,11 @@ int ivlm_rope_table(float* cos_tab, float* sin_tab, int T, int D, float theta, i
 int ivlm_mask_dot(const void* up, const void* hyper, int dtype, float* low, int B, int gh, int gw, int C, ivlm_stream_t s) {
     ivlm_enter();
     return ivlm::mask_dot(up, hyper, dtype == IVLM_F32, low, B, gh, gw, C, ivlm_stream(s));
+}
+int ivlm_mask_dot_multi(const void* up, const void* hyper, int dtype, float* low, int B, int M, int gh, int gw, int C,
+                        ivlm_stream_t s) {
+    ivlm_enter();
+    return ivlm::mask_dot_multi(up, hyper, dtype == IVLM_F32, low, B, M, gh, gw, C, ivlm_stream(s));
 }
 int ivlm_normalize_pad_u8(const uint8_t* src, int H, int W, int y0, int x0, int ch, int cw, const float* mean3_host,
                           const float* std3_host, void* out, int out_bf16, int OH, int OW, ivlm_stream_t s) {

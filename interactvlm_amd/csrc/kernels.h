@@ -156,6 +156,7 @@ int rope_table(float* cos_tab, float* sin_tab, int T, int D, float theta, hipStr
 int normalize_pad_u8(const uint8_t* src, int H, int W, int y0, int x0, int ch, int cw, const float* mean3,
                      const float* std3, void* out, int out_bf16, int OH, int OW, hipStream_t st);
 int mask_dot(const void* up, const void* hyper, int kind, float* low, int B, int gh, int gw, int C, hipStream_t st);
+int mask_dot_multi(const void* up, const void* hyper, int kind, float* low, int B, int M, int gh, int gw, int C, hipStream_t st);
 
 // ---- metrics / SMPL-X transfer (metrics.hip) ------------------------------------------------------------
 int contact_prf(const float* gt, const float* pred, int B, int n, float thr, float* out, hipStream_t st);

@@ -1125,6 +1125,62 @@ def mask_dot(up, hyper, B, gh, gw):
     return low
 
 
+def mask_dot_multi(up, hyper, B, gh, gw, out=None):
+    """``mask_dot`` for M <= 4 mask tokens in one pass over ``up``: hyper [B,M,C] -> low fp32 [B,M,4gh,4gw], low[:, m] the bits of
+    ``mask_dot(up, hyper[:, m])``."""
+    lib = _lib.load()
+    up = _req(up, None, "up")
+    hyper = _req(hyper, up.dtype, "hyper")
+    if hyper.dim() != 3 or hyper.shape[0] != B or up.numel() != B * gh * gw * 16 * hyper.shape[-1]:
+        raise IvlmError(f"mask_dot_multi: hyper {tuple(hyper.shape)} / up {tuple(up.shape)} do not match B={B}, grid {gh}x{gw}")
+    M, C = hyper.shape[1], hyper.shape[2]
+    low = torch.empty(B, M, 4 * gh, 4 * gw, dtype=F32, device=up.device) if out is None else _req(out, F32, "out")
+    if tuple(low.shape) != (B, M, 4 * gh, 4 * gw):
+        raise IvlmError(f"mask_dot_multi: out {tuple(low.shape)}, expected {(B, M, 4 * gh, 4 * gw)}")
+    check(lib.ivlm_mask_dot_multi(up.data_ptr(), hyper.data_ptr(), _dtc(up), low.data_ptr(), B, M, gh, gw, C, _stream()), "mask_dot_multi")
+    return low
+
+
+def prompt_embed(coords, labels, gauss, table, input_size, out=None):
+    """PromptEncoder._embed_points / _embed_boxes for R rows: coords fp32 [R,2] (x, y) in the padded input frame, labels int32 [R]
+    (-1 not-a-point, 0 / 1 negative / positive point, 2 / 3 box corners; anything else gives a NaN row), gauss fp32 [2,F], table fp32
+    [5,2F], input_size (H, W) -> fp32 [R,2F]."""
+    lib = _lib.load()
+    coords, labels = _req(coords, F32, "coords"), _req(labels, torch.int32, "labels")
+    gauss, table = _req(gauss, F32, "gauss"), _req(table, F32, "table")
+    R, nf = labels.numel(), gauss.shape[-1]
+    if coords.numel() != 2 * R or gauss.numel() != 2 * nf or table.numel() != 10 * nf or R < 1:
+        raise IvlmError(f"prompt_embed: coords {tuple(coords.shape)}, labels {tuple(labels.shape)}, gauss {tuple(gauss.shape)}, "
+                        f"table {tuple(table.shape)}: expected [R,2], [R], [2,F], [5,2F]")
+    o = torch.empty(R, 2 * nf, dtype=F32, device=coords.device) if out is None else _req(out, F32, "out")
+    if o.numel() != R * 2 * nf:
+        raise IvlmError(f"prompt_embed: out {tuple(o.shape)}, expected {(R, 2 * nf)}")
+    check(lib.ivlm_prompt_embed(coords.data_ptr(), labels.data_ptr(), gauss.data_ptr(), table.data_ptr(), o.data_ptr(), R, nf,
+                                int(input_size[0]), int(input_size[1]), _stream()), "prompt_embed")
+    return o
+
+
+def mask_downscale(mask, weights, eps=1e-6, out=None):
+    """PromptEncoder._embed_masks as one kernel: mask fp32 [B,4gh,4gw], weights = the ten fp32 tensors (conv0 w, b, norm1 w, b, conv3
+    w, b, norm4 w, b, conv6 w, b) of ``mask_downscaling`` in the checkpoint's layouts -> dense fp32 [B, gh*gw, C] (channels last)."""
+    lib = _lib.load()
+    mask = _req(mask, F32, "mask")
+    ws = [_req(t, F32, "weights") for t in weights]
+    if mask.dim() != 3 or mask.shape[1] % 4 or mask.shape[2] % 4 or mask.numel() == 0 or len(ws) != 10:
+        raise IvlmError(f"mask_downscale: mask {tuple(mask.shape)}, expected [B,4gh,4gw], and ten weight tensors")
+    B, gh, gw = mask.shape[0], mask.shape[1] // 4, mask.shape[2] // 4
+    mid, C = ws[5].numel(), ws[9].numel()
+    want = (4 * (mid // 4), mid // 4, mid // 4, mid // 4, mid * mid, mid, mid, mid, C * mid, C)
+    if tuple(t.numel() for t in ws) != want:
+        raise IvlmError(f"mask_downscale: weight sizes {tuple(t.numel() for t in ws)}, expected {want}")
+    o = torch.empty(B, gh * gw, C, dtype=F32, device=mask.device) if out is None else _req(out, F32, "out")
+    if o.numel() != B * gh * gw * C:
+        raise IvlmError(f"mask_downscale: out {tuple(o.shape)}, expected {(B, gh * gw, C)}")
+    check(lib.ivlm_mask_downscale(mask.data_ptr(), *[t.data_ptr() for t in ws], o.data_ptr(), B, gh, gw, C, mid, float(eps),
+                                  _stream()), "mask_downscale")
+    return o
+
+
 # ---- the decode-attention entry points: what their argument lists share ----------------------------------------------------------
 def _pos_pair(pos):
     """(host position, device position pointer): one of the two is used"""

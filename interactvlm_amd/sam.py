@@ -1,4 +1,4 @@
-"""SAM ViT image encoder, prompt encoder (text path) and two-way mask decoder on the HIP kernels.
+"""SAM ViT image encoder, prompt encoder (text, point, box and mask prompts) and two-way mask decoder on the HIP kernels.
 
 Host-side orchestration only (buffers, views, launch order); every FLOP runs in libivlm_hip.so.
 Mirrors model/segment_anything/modeling/{image_encoder,prompt_encoder,mask_decoder,transformer,sam}.py of the
@@ -397,6 +397,17 @@ class SamMaskDecoder:
         self.c_mid, self.c_up = w0.shape[1], w1.shape[1]
         self.hyper0 = [_LinF32(w, f"{md}.output_hypernetworks_mlps.0.layers.{j}", device) for j in range(3)]
         self.iou = [_LinF32(w, f"{md}.iou_prediction_head.layers.{j}", device) for j in range(3)]
+        # the point / box / mask prompts and the multi-mask output (encode_prompts, predict_masks): all hypernetworks (hyper[0] is
+        # hyper0), the Gaussian matrix unrounded, the label table of ops.prompt_embed [negative point ; positive point ; box corner 0 ;
+        # box corner 1 ; not-a-point] and the ten tensors of mask_downscaling in the checkpoint's layouts
+        self.hyper = [self.hyper0] + [[_LinF32(w, f"{md}.output_hypernetworks_mlps.{m}.layers.{j}", device) for j in range(3)]
+                                      for m in range(1, self.n_mask)]
+        self.gauss = gauss
+        self.point_table = f32(torch.cat([w[f"{pe}.point_embeddings.{i}.weight"].reshape(1, C) for i in range(4)]
+                                         + [w[pe + ".not_a_point_embed.weight"].reshape(1, C)], 0))
+        self.mask_down = [f32(w[f"{pe}.mask_downscaling.{n}"].reshape(-1)) for n in
+                          ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight", "3.bias", "4.weight", "4.bias", "6.weight", "6.bias")]
+        self.input_size = (16 * grid, 16 * grid)  # PromptEncoder.input_image_size: 16 input pixels per grid cell (build_sam.py)
 
     def _attn(self, a, q_split, k_split, v_split, B, Sq, Sk, heads=8, kv_batch=None):
         """Attention.forward (transformer.py:220-242). *_split are [B*S, 2C] hi|lo rows -> fp32 [B*Sq, inner] (before out_proj)."""
@@ -434,8 +445,21 @@ class SamMaskDecoder:
         tokens = torch.cat([self.out_tokens, text_embeds[0].to(F32)], dim=0)  # [Nt, C]
         Nt = tokens.shape[0]
         query_pe = tokens.unsqueeze(0).expand(V, Nt, C).reshape(V * Nt, C).contiguous()
-        queries = query_pe
         keys = ops.add_rows(image_embeddings.reshape(V * HW, C).contiguous(), self.no_mask, out_kind="f32")  # src + dense
+        hs, keys = self._transformer(query_pe, keys, V, Nt, HW)
+        sp = ops.split_rows
+        iou_tok = hs[:, 0, :].contiguous()
+        mask_tok0 = hs[:, 1, :].contiguous()  # mask token 0: multimask_output=False keeps masks[:, 0:1]
+        u = self._upscale(keys)
+        h = self.hyper0[2](sp(self.hyper0[1](sp(self.hyper0[0](sp(mask_tok0), act="relu")), act="relu")))  # [V, 32]
+        low = ops.mask_dot(u, h, V, g, g)  # f32 [V, 4g, 4g]
+        iou = self.iou[2](sp(self.iou[1](sp(self.iou[0](sp(iou_tok), act="relu")), act="relu")))
+        return low.unsqueeze(1), iou[:, 0:1]
+
+    def _transformer(self, query_pe, keys, V, Nt, HW):
+        """TwoWayTransformer.forward (transformer.py:62-107) + norm_final_attn for V token sets of Nt tokens: query_pe fp32 [V*Nt, C]
+        (the tokens: they are their own positional encoding), keys fp32 [V*HW, C] (src + dense) -> (hs fp32 [V, Nt, C], keys)."""
+        queries = query_pe
         key_pe = self.key_pe  # [HW, C], broadcast over V by row modulo
         sp = ops.split_rows
         for li, L in enumerate(self.layers):
@@ -459,17 +483,138 @@ class SamMaskDecoder:
         q = ops.add_rows(queries, query_pe, out_kind="split")
         k = ops.add_rows(keys, key_pe, out_kind="split")
         fa = self._attn(self.final_attn, q, k, sp(keys), V, Nt, HW)
-        hs = self.norm_final(self.final_attn["o"](fa, residual=queries), out_f32=True).view(V, Nt, C)
-        iou_tok = hs[:, 0, :].contiguous()
-        mask_tok0 = hs[:, 1, :].contiguous()  # mask token 0: multimask_output=False keeps masks[:, 0:1]
-        # output_upscaling: ConvT(256->64) -> LayerNorm2d -> GELU -> ConvT(64->32) -> GELU, as GEMMs on pixels
+        hs = self.norm_final(self.final_attn["o"](fa, residual=queries), out_f32=True)
+        return hs.view(V, Nt, hs.shape[-1]), keys
+
+    def _upscale(self, keys):
+        """output_upscaling: ConvT(256->64) -> LayerNorm2d -> GELU -> ConvT(64->32) -> GELU, as GEMMs on pixels: keys fp32 [V*HW, C] ->
+        fp32 [V*HW*4, (dy2,dx2,32)], the layout ops.mask_dot reads"""
+        sp = ops.split_rows
         u = ops.linear(sp(keys), self.up0_w, self.up0_b, out_f32=True)  # [V*HW, (dy,dx,64)]
         u = self.up_ln(u.view(-1, self.c_mid), gelu=True, out_f32=True)  # per output pixel over 64 channels
-        u = ops.linear(sp(u), self.up1_w, self.up1_b, act="gelu", out_f32=True)  # [V*HW*4, (dy2,dx2,32)]
-        h = self.hyper0[2](sp(self.hyper0[1](sp(self.hyper0[0](sp(mask_tok0), act="relu")), act="relu")))  # [V, 32]
-        low = ops.mask_dot(u, h, V, g, g)  # f32 [V, 4g, 4g]
+        return ops.linear(sp(u), self.up1_w, self.up1_b, act="gelu", out_f32=True)  # [V*HW*4, (dy2,dx2,32)]
+
+    # ---- point / box / mask prompts, multi-mask output (prompt_encoder.py:78-114, 140-186; mask_decoder.py:75-164) --------------------
+    def encode_prompts(self, points=None, labels=None, boxes=None, mask_input=None):
+        """PromptEncoder.forward(points=(points, labels), boxes=boxes, masks=mask_input): points fp32 [B,N,2] as (x, y) in the padded
+        input frame with labels [B,N] (1 positive, 0 negative, -1 not a point), boxes fp32 [B,4] (x0, y0, x1, y1), mask_input fp32
+        [B,1,4g,4g] -> (sparse fp32 [B,N',C], dense fp32 [B,g*g,C] or None for no mask).  Token order of the reference: the points,
+        then the pad point (label -1) only when there is no box, then the two box corners."""
+        B = check_prompts(points, labels, boxes, mask_input, 4 * self.grid)
+        dev = self.device
+        coords, labs = [], []
+        if points is not None:
+            coords.append(points.to(dev, F32))
+            labs.append(labels.to(dev, torch.int32))
+            if boxes is None:
+                coords.append(torch.zeros(B, 1, 2, dtype=F32, device=dev))
+                labs.append(torch.full((B, 1), -1, dtype=torch.int32, device=dev))
+        if boxes is not None:
+            coords.append(boxes.to(dev, F32).reshape(B, 2, 2))
+            labs.append(torch.tensor([2, 3], dtype=torch.int32, device=dev).expand(B, 2))
+        if coords:
+            coords, labs = torch.cat(coords, 1).contiguous(), torch.cat(labs, 1).contiguous()
+            sparse = ops.prompt_embed(coords, labs, self.gauss, self.point_table, self.input_size).view(B, labs.shape[1], self.C)
+        else:
+            sparse = torch.empty(B, 0, self.C, dtype=F32, device=dev)
+        dense = None
+        if mask_input is not None:
+            m = mask_input.to(dev, F32).reshape(B, 4 * self.grid, 4 * self.grid).contiguous()
+            dense = ops.mask_downscale(m, self.mask_down, eps=1e-6)
+        return sparse, dense
+
+    def predict_masks(self, image_embedding, sparse, dense=None, multimask_output=True):
+        """MaskDecoder.forward for B prompt sets on ONE image: image_embedding [g*g, C] fp32 or bf16 (channels last), sparse fp32
+        [B,N,C], dense fp32 [B,g*g,C] or None (the no-mask embedding) -> (low_res fp32 [B,M,4g,4g], iou fp32 [B,M]): mask tokens 1..3
+        with multimask_output, else token 0 (mask_decoder.py:105-111) - slices of one [B,4,...] result, which is replayed as one HIP
+        graph per (B, N, dense or not) like the text path (``use_graph``; the same kernels in the same order as the eager chain)."""
+        low, iou = self._predict_all(image_embedding, sparse, dense, graph=True)
+        return (low[:, 1:], iou[:, 1:]) if multimask_output else (low[:, 0:1], iou[:, 0:1])
+
+    def _predict_all(self, image_embedding, sparse, dense, graph=False):
+        """all mask tokens: (low_res fp32 [B,n_mask,4g,4g], iou fp32 [B,n_mask]).  The image embedding and key_pe are repeated over the
+        B prompts (mask_decoder.py:137-139) by the row modulo of ops.add_rows; every prompt carries 5 + N tokens.  graph: replay
+        where graphs are enabled, else the eager chain."""
+        B, N = check_decoder_inputs(self.grid, self.C, self.n_mask, image_embedding, sparse, dense)
+        inputs = [image_embedding, sparse] + ([] if dense is None else [dense])
+        if graph and graphs.enabled(self.use_graph, *inputs):
+            key = ("prompts", B, N, dense is not None, image_embedding.dtype)
+            return self._graphs.run(key, self._predict_chain, inputs)
+        return self._predict_chain(*inputs)
+
+    def _predict_chain(self, image_embedding, sparse, dense=None):
+        g, C = self.grid, self.C
+        HW = g * g
+        B, N = sparse.shape[0], sparse.shape[1]
+        Nt = 1 + self.n_mask + N
+        tokens = torch.cat([self.out_tokens.unsqueeze(0).expand(B, -1, -1), sparse], dim=1).reshape(B * Nt, C).contiguous()
+        if dense is None:  # no_mask_embed expanded over the grid, as the reference hands it to the decoder
+            dense = self.no_mask.expand(B * HW, C)
+        keys = ops.add_rows(dense.reshape(B * HW, C).contiguous(), image_embedding.contiguous(), out_kind="f32")  # dense + src[row % HW]
+        hs, keys = self._transformer(tokens, keys, B, Nt, HW)
+        sp = ops.split_rows
+        u = self._upscale(keys)
+        hyper = torch.stack([mlp[2](sp(mlp[1](sp(mlp[0](sp(hs[:, 1 + m, :].contiguous()), act="relu")), act="relu")))
+                             for m, mlp in enumerate(self.hyper)], dim=1).contiguous()  # [B, n_mask, 32]
+        low = ops.mask_dot_multi(u, hyper, B, g, g)  # f32 [B, n_mask, 4g, 4g]
+        iou_tok = hs[:, 0, :].contiguous()
         iou = self.iou[2](sp(self.iou[1](sp(self.iou[0](sp(iou_tok), act="relu")), act="relu")))
-        return low.unsqueeze(1), iou[:, 0:1]
+        return low, iou
+
+
+def check_decoder_inputs(grid, C, n_mask, image_embedding, sparse, dense):
+    """The argument checks of SamMaskDecoder.predict_masks, before the library loads -> (B, N)"""
+    HW = grid * grid
+    if not isinstance(sparse, torch.Tensor) or sparse.dim() != 3 or sparse.shape[-1] != C or sparse.shape[0] < 1 or sparse.dtype != F32:
+        raise ValueError(f"sparse: expected float32 [B,N,{C}], got {_describe(sparse)}")
+    B, N = sparse.shape[0], sparse.shape[1]
+    if not isinstance(image_embedding, torch.Tensor) or tuple(image_embedding.shape) != (HW, C) or image_embedding.dtype not in (F32, BF16):
+        raise ValueError(f"image_embedding: expected ONE image's float32 or bfloat16 [{HW},{C}], got {_describe(image_embedding)}")
+    if dense is not None and (not isinstance(dense, torch.Tensor) or tuple(dense.shape) != (B, HW, C) or dense.dtype != F32):
+        raise ValueError(f"dense: expected float32 [{B},{HW},{C}] or None, got {_describe(dense)}")
+    if n_mask > 4:
+        raise ValueError(f"{n_mask} mask tokens: mask_dot_multi takes up to 4")
+    return B, N
+
+
+def _describe(t):
+    return f"{t.dtype} {tuple(t.shape)}".replace("torch.", "") if isinstance(t, torch.Tensor) else type(t).__name__
+
+
+def check_prompts(points, labels, boxes, mask_input, mask_side, batch=True):
+    """The argument checks of a prompt set (SamMaskDecoder.encode_prompts, SamPredictor), all before the library loads -> B.
+    batch: [B,N,2] / [B,N] / [B,4] / [B,1,S,S]; else one prompt set, [N,2] / [N] / [4] / [1,S,S]."""
+    r = 1 if batch else 0
+    lead = "[B," if batch else "["
+    for t, name in ((points, "point_coords"), (labels, "point_labels"), (boxes, "boxes" if batch else "box"), (mask_input, "mask_input")):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if points is None and boxes is None and mask_input is None:
+        if labels is not None:
+            raise ValueError("point_labels given without point_coords")
+        raise ValueError("no prompt: give point_coords with point_labels, a box or a mask_input")
+    if (points is None) != (labels is None):
+        raise ValueError("point_labels given without point_coords" if points is None else "point_coords given without point_labels")
+    sizes = []
+    if points is not None:
+        if points.dim() != r + 2 or points.shape[-1] != 2 or points.shape[-2] < 1 or not points.is_floating_point():
+            raise ValueError(f"point_coords: expected floating-point {lead}N,2] with N >= 1, got {_describe(points)}")
+        if tuple(labels.shape) != tuple(points.shape[:-1]) or labels.is_floating_point() or labels.dtype == torch.bool:
+            raise ValueError(f"point_labels: expected integer {lead}N] = {tuple(points.shape[:-1])}, got {_describe(labels)}")
+        sizes.append((points.shape[0] if batch else 1, "point_coords"))
+    if boxes is not None:
+        if boxes.dim() != r + 1 or boxes.shape[-1] != 4 or not boxes.is_floating_point():
+            raise ValueError(f"{'boxes' if batch else 'box'}: expected floating-point {lead}4], got {_describe(boxes)}")
+        sizes.append((boxes.shape[0] if batch else 1, "boxes"))
+    if mask_input is not None:
+        if mask_input.dim() != r + 3 or tuple(mask_input.shape[r:]) != (1, mask_side, mask_side) or not mask_input.is_floating_point():
+            raise ValueError(f"mask_input: expected floating-point {lead}1,{mask_side},{mask_side}], got {_describe(mask_input)}")
+        sizes.append((mask_input.shape[0] if batch else 1, "mask_input"))
+    B = sizes[0][0]
+    for b, name in sizes:
+        if b != B or b < 1:
+            raise ValueError(f"{name}: {b} prompt sets, {sizes[0][1]} has {B}")
+    return B
 
 
 def postprocess_masks(low_res, input_size, original_size, img_size=1024, apply_sigmoid=False, sigmoid_gt=None, ignore_label=-1.0):
