@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import re
 
+import torch  # (before the library is loaded: libivlm_hip.so must bind to torch's HIP runtime instance)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (IVLM_LIB_PATH: load another build of the same library - kernel experiments; the default is the in-tree build)
 LIB_PATH = os.environ.get("IVLM_LIB_PATH") or os.path.join(_HERE, "libivlm_hip.so")
@@ -90,7 +92,6 @@ def load():
         raise IvlmError(
             f"{LIB_PATH} not found: the HIP extension is required (no CPU fallback). "
             "Build it with `python -m interactvlm_amd.build` (hipcc --offload-arch=gfx950).")
-    import torch  # noqa: F401  -- first: libivlm_hip.so must bind to torch's HIP runtime instance
     lib = C.CDLL(LIB_PATH)
     for name, (ret, args) in header_prototypes().items():
         try:
@@ -112,8 +113,6 @@ def load():
 
 def stream():
     """the handle of torch's current stream, as an ``ivlm_stream_t``"""
-    import torch
-
     return torch.cuda.current_stream().cuda_stream
 
 
@@ -129,6 +128,17 @@ def require_gpu(named):
             raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
 
 
+def require(t, dtype, name):
+    """-> t, a contiguous GPU tensor of ``dtype`` (None: any); what every wrapper asks of an operand it hands over by address"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if dtype is not None and t.dtype != dtype:
+        raise IvlmError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise IvlmError(f"{name}: tensor must be contiguous")
+    return t
+
+
 def workspace(size_fn, what, device, **sizes):
     """Ask ``size_fn(*sizes.values())`` (an ``ivlm_*_bytes`` query) and -> (uint8 tensor of that size on ``device``, nbytes); sizes the
     library refuses (the query returns 0) raise.  device None: only the check, -> (None, nbytes)."""
@@ -137,8 +147,6 @@ def workspace(size_fn, what, device, **sizes):
         raise IvlmError(f"{what}: sizes {', '.join(f'{k}={v}' for k, v in sizes.items())} are not supported")
     if device is None:
         return None, nbytes
-    import torch
-
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 

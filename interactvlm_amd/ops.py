@@ -5,6 +5,7 @@ requires CUDA(HIP) tensors and raises if the extension is missing — there is n
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import os
 
@@ -12,12 +13,11 @@ import torch
 
 from . import _lib
 from ._lib import IvlmError, check
+from ._lib import header_constant as _abi
 
-IVLM_F32, IVLM_BF16 = 0, 1
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+BF16, F16, F32, U8 = torch.bfloat16, torch.float16, torch.float32, torch.uint8
+IVLM_F32, IVLM_BF16, IVLM_FP8 = _abi("IVLM_F32"), _abi("IVLM_BF16"), _abi("IVLM_FP8")
+_req, _p, _stream = _lib.require, _lib.ptr, _lib.stream  # one helper set: the operand check, the address (0 for None), torch's stream
 
 
 class KernelTimer:
@@ -34,14 +34,11 @@ class KernelTimer:
 
     def _rt(self):
         if self._hip is None:
-            import ctypes
-            import os
             self._hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
             self._hip.hipEventElapsedTime.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_void_p]
         return self._hip
 
     def _event(self):
-        import ctypes
         ev = ctypes.c_void_p()
         rc = self._rt().hipEventCreate(ctypes.byref(ev))
         if rc != 0:
@@ -49,7 +46,6 @@ class KernelTimer:
         return ev
 
     def _elapsed_ms(self, a, b):
-        import ctypes
         ms = ctypes.c_float()
         rc = self._rt().hipEventElapsedTime(ctypes.byref(ms), a, b)
         if rc != 0:
@@ -110,26 +106,44 @@ class KernelTimer:
 TIMER = KernelTimer()
 
 
-def _req(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise IvlmError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
-    if dtype is not None and t.dtype != dtype:
-        raise IvlmError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
-        raise IvlmError(f"{name}: tensor must be contiguous")
-    return t
+def _run(what, fn, *args, timer=None):
+    """The launch frame of every wrapper: the ``ivlm_*`` entry point ``fn`` on torch's current stream, its status through ``check``
+    under the wrapper's name ``what``; timer = (family, work, tag): the launch is a TIMER record (when TIMER is on)."""
+    if timer is None or not TIMER.enabled:
+        check(fn(*args, _stream()), what)
+    else:
+        TIMER.time(timer[0], timer[1], lambda: check(fn(*args, _stream()), what), tag=timer[2])
+
+
+# An operand / output kind: name -> (torch dtype, row width in units of the logical columns, ABI code).  The split kinds are rows
+# [hi(cols) | lo(cols)] with x = hi + lo.  A new kind is one line here (and the keyword that selects it in ``_kind``).
+_KINDS = {"f32": (F32, 1, IVLM_F32), "bf16": (BF16, 1, IVLM_BF16), "f16": (F16, 1, _abi("IVLM_F16")),
+          "split": (BF16, 2, _abi("IVLM_BF16_SPLIT")), "split_f16": (F16, 2, _abi("IVLM_F16_SPLIT")), "fp8": (U8, 1, IVLM_FP8)}
+_KIND_OF = {dtype: kind for kind, (dtype, width, _) in _KINDS.items() if width == 1}
+
+
+def _kind(out_f32=False, out_split=False, out_f16=False, fp8_scale=None):
+    """the public keywords of the wrappers -> the name of the output kind they ask for"""
+    if fp8_scale is not None:
+        return "fp8"
+    if out_split:
+        return "split_f16" if out_f16 else "split"
+    return "f16" if out_f16 else ("f32" if out_f32 else "bf16")
+
+
+def _out_of(kind, lead, cols, device):
+    """a new output of ``kind``: ``lead`` rows of ``cols`` logical columns"""
+    dtype, width, _ = _KINDS[kind]
+    return torch.empty((*lead, width * cols), dtype=dtype, device=device)
 
 
 def _dt(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
+    """the ABI code of an fp32 or bf16 operand (the kernels that take fp16 are told so by their callers, by name)"""
+    if t.dtype == F32:
         return IVLM_F32
-    if t.dtype == torch.bfloat16:
+    if t.dtype == BF16:
         return IVLM_BF16
     raise IvlmError(f"unsupported dtype {t.dtype}")
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
 
 
 # --------------------------------------------------------------------------------------------
@@ -166,9 +180,8 @@ class LiftPlan:
         nnz = torch.zeros(1, dtype=torch.int32, device=dev)
         ws_bytes = lib.ivlm_lift_plan_workspace_bytes(V, self.HW, self.num_vertices)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        check(getattr(lib, entry_point)(*(t.data_ptr() for t in tables), V, self.HW, self.num_vertices, self.row_ptr.data_ptr(),
-                                        ent_pix.data_ptr(), ent_w.data_ptr(), cap, nnz.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
-              entry_point[len("ivlm_"):])
+        _run(entry_point[len("ivlm_"):], getattr(lib, entry_point), *(t.data_ptr() for t in tables), V, self.HW, self.num_vertices,
+             self.row_ptr.data_ptr(), ent_pix.data_ptr(), ent_w.data_ptr(), cap, nnz.data_ptr(), ws.data_ptr(), ws_bytes)
         self.nnz = int(nnz.item())
         # trim to the real size (one-time copy) so the plan holds 8 B per entry, no slack
         keep = max(self.nnz, 1)  # an empty plan still needs valid (never dereferenced) pointers
@@ -193,22 +206,18 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 
 def _lift_call(name, like, B, n, want_nviews, call, timer=None):
     """The frame of the lift wrappers: allocate out (and nviews) f32 [B,n] on the device of ``like``, run
-    ``check(call(out_ptr, nviews_ptr, stream), name)`` - as the TIMER record ``timer = (key, work)`` when one is given and TIMER is
-    on - and -> (out, nviews) or out."""
+    ``call(out_ptr, nviews_ptr, stream)`` through the launch frame ``_run`` - as the TIMER record ``timer = (key, work, tag)`` when
+    one is given - and -> (out, nviews) or out."""
     out = torch.empty(B, n, dtype=torch.float32, device=like.device)
     nviews = torch.empty_like(out) if want_nviews else None
-    run = lambda: check(call(out.data_ptr(), _p(nviews), _stream()), name)
-    if timer is not None and TIMER.enabled:
-        TIMER.time(*timer, run)
-    else:
-        run()
+    _run(name, lambda stream: call(out.data_ptr(), _p(nviews), stream), timer=timer)
     return (out, nviews) if want_nviews else out
 
 
 def _plan_timer(B, V, plan):
     """both plan gathers are one TIMER family, priced at the algorithmic bytes of the dense formulation:
     28 B/pixel + 8 B/vertex"""
-    return "lift_mesh_plan", float(B) * (V * plan.HW * 28 + 2 * plan.num_vertices * 4)
+    return "lift_mesh_plan", float(B) * (V * plan.HW * 28 + 2 * plan.num_vertices * 4), None
 
 
 def lift_mesh_plan(logits: torch.Tensor, plan: LiftPlan, mode: int = 0, param: float = 20.0, want_nviews=False):
@@ -288,13 +297,11 @@ def postprocess_masks(low_res, input_size, original_size, img_size: int = 1024, 
     if sigmoid_gt is not None:
         gt = _req(sigmoid_gt, torch.float32, "sigmoid_gt")
         assert gt.numel() == out.numel()
-        check(lib.ivlm_postprocess_masks_valid(low_res.data_ptr(), _dt(low_res), n, h, w, int(img_size), int(input_size[0]),
-                                               int(input_size[1]), oh, ow, gt.data_ptr(), float(ignore_label), out.data_ptr(),
-                                               _stream()), "postprocess_masks_valid")
+        _run("postprocess_masks_valid", lib.ivlm_postprocess_masks_valid, low_res.data_ptr(), _dt(low_res), n, h, w, int(img_size),
+             int(input_size[0]), int(input_size[1]), oh, ow, gt.data_ptr(), float(ignore_label), out.data_ptr())
         return out
-    check(lib.ivlm_postprocess_masks(low_res.data_ptr(), _dt(low_res), n, h, w, int(img_size), int(input_size[0]),
-                                     int(input_size[1]), oh, ow, 1 if apply_sigmoid else 0, out.data_ptr(),
-                                     _stream()), "postprocess_masks")
+    _run("postprocess_masks", lib.ivlm_postprocess_masks, low_res.data_ptr(), _dt(low_res), n, h, w, int(img_size), int(input_size[0]),
+         int(input_size[1]), oh, ow, 1 if apply_sigmoid else 0, out.data_ptr())
     return out
 
 
@@ -302,7 +309,6 @@ def postprocess_masks(low_res, input_size, original_size, img_size: int = 1024, 
 # dense building blocks
 # --------------------------------------------------------------------------------------------
 ACT = {"none": 0, "gelu": 1, "quick_gelu": 2, "relu": 3, "silu": 4, "swiglu": 5, "sigmoid": 6}
-BF16 = torch.bfloat16
 
 
 SPLITK = os.environ.get("IVLM_SPLITK", "1") != "0"  # small-M GEMMs (prefill, CLIP): cut K so that >= ~3 tiles per CU are in flight
@@ -329,7 +335,7 @@ def _splitk_counters(device):
     key = (device.index, _stream())
     c = cnts.get(key)
     if c is None:
-        c = cnts[key] = torch.zeros(4096, dtype=torch.int32, device=device)
+        c = cnts[key] = torch.zeros(_abi("IVLM_SPLITK_COUNTERS"), dtype=torch.int32, device=device)
     return c
 
 
@@ -346,7 +352,8 @@ def _splitk_rule(M, N, K, act, has_rms):
     return _lib.load().ivlm_gemm_splitk_choice(M, N, K, act, has_rms)
 
 
-GEMM_A_F32, GEMM_RES_F32, GEMM_A_SPLIT, GEMM_OUT_SPLIT, GEMM_F16, GEMM_OUT_F16, GEMM_W_PANEL = 1, 2, 4, 8, 16, 32, 64
+GEMM_A_F32, GEMM_RES_F32, GEMM_A_SPLIT, GEMM_OUT_SPLIT, GEMM_F16, GEMM_OUT_F16, GEMM_W_PANEL = (
+    _abi("IVLM_GEMM_" + f) for f in ("A_F32", "RES_F32", "A_SPLIT", "OUT_SPLIT", "F16", "OUT_F16", "W_PANEL"))
 
 
 def panel_weight(w):
@@ -355,8 +362,28 @@ def panel_weight(w):
     N, K = w.shape
     assert K % 64 == 0
     return w.view(N, K // 64, 64).permute(1, 0, 2).contiguous()
-F16 = torch.float16
-F32 = torch.float32
+
+
+def _epilogue(N, act, bias, residual, res_shape, rms, out_f32):
+    """What the linears' argument lists share, with the checks that go with it -> (n_out, the residual's flag bits, (bias, residual,
+    ldr), (act code, out_f32), (rms weight, eps)).  res_shape None: the residual is [..., N] rows of one stride (ldr); a tuple: it
+    is contiguous and of that shape; an int: contiguous with that many elements."""
+    r2, ldr, flags = None, 0, 0
+    if residual is not None:
+        if res_shape is None:
+            r2 = residual.reshape(-1, N)
+            assert r2.stride(-1) == 1
+            ldr = r2.stride(0)
+        else:
+            r2, ldr = residual, N
+            assert r2.is_contiguous() and (r2.numel() == res_shape if isinstance(res_shape, int) else tuple(r2.shape) == res_shape)
+        assert r2.dtype in (BF16, F32)
+        if r2.dtype == F32:
+            flags = GEMM_RES_F32
+    if bias is not None:
+        assert bias.dtype == BF16 and bias.is_contiguous()
+    return (N // 2 if act == "swiglu" else N, flags, (_p(bias), _p(r2), ldr), (ACT[act], 1 if out_f32 else 0),
+            (_p(rms[0]), float(rms[1])) if rms else (0, 0.0))
 
 
 def linear(x, weight, bias=None, act="none", residual=None, res_mod=0, out=None, out_f32=False, rms=None, out_rows=None,
@@ -399,61 +426,35 @@ def linear(x, weight, bias=None, act="none", residual=None, res_mod=0, out=None,
         if M <= 16 or out_rows is not None or a_split or out_split:
             raise IvlmError("linear: K-panel weights serve the plain tile GEMMs (M > 16) only")
         flags |= GEMM_W_PANEL
-    n_out = N // 2 if act == "swiglu" else N
+    kind = _kind(out_f32, out_split, out_f16)
+    n_out, res_flags, bias_res, act_out, rms_args = _epilogue(
+        N, act, bias, residual, None, rms, out.dtype == F32 if out is not None else kind == "f32")
+    flags |= res_flags
     if out_split:
         flags |= GEMM_OUT_SPLIT
-    n_cols = 2 * n_out if out_split else n_out
     if out is None:
-        lead = x.shape[:-1] if a_rows is None else (M,)
-        out = torch.empty(tuple(lead) + (n_cols,), dtype=F32 if (out_f32 and not out_split) else (F16 if out_f16 else BF16),
-                          device=x.device)
-    assert not out_split or out.dtype == (F16 if out_f16 else BF16)
-    o2 = out.reshape(-1, n_cols)
+        out = _out_of(kind, x.shape[:-1] if a_rows is None else (M,), n_out, x.device)
+    assert not out_split or out.dtype == _KINDS[kind][0]
+    o2 = out.reshape(-1, _KINDS[kind][1] * n_out)
     assert o2.stride(-1) == 1 and weight.stride(-1) == 1
-    ldw = 64 if w_panel else weight.stride(0)
-    r2, ldr = None, 0
-    if residual is not None:
-        r2 = residual.reshape(-1, N)
-        assert r2.dtype in (BF16, F32) and r2.stride(-1) == 1
-        ldr = r2.stride(0)
-        if r2.dtype == F32:
-            flags |= GEMM_RES_F32
-    if bias is not None:
-        assert bias.dtype == BF16 and bias.is_contiguous()
-    call = lambda: check(lib.ivlm_gemm_bf16(
-        x2.data_ptr(), x2.stride(0), weight.data_ptr(), ldw, o2.data_ptr(), o2.stride(0), _p(bias),
-        _p(r2), ldr, int(res_mod), M, N, K, ACT[act], 1 if out.dtype == F32 else 0, 1, 0, 0, 0, 0,
-        _p(rms[0]) if rms else 0, float(rms[1]) if rms else 0.0, flags, _p(out_rows), _p(a_rows), _stream()), "gemm_bf16")
+    # what the three entry points take alike: A, W, C with their row strides, the epilogue operands, the sizes
+    head = (x2.data_ptr(), x2.stride(0), weight.data_ptr(), 64 if w_panel else weight.stride(0), o2.data_ptr(), o2.stride(0),
+            *bias_res, int(res_mod), M, N, K, *act_out)
+    # work = algorithmic FLOPs (MFMA path; a split A operand doubles the MFMA work of the same algorithmic product: counted once)
+    # or weight bytes (GEMV path)
+    timer = (("gemm_bf16_mfma", 2.0 * M * N * K, (M, N, K, act, "split" if a_split else "")) if M > 16
+             else ("gemv_bf16", 2.0 * N * K, (M, N, K, act)))
     splits = _splitk_choice(M, N, K, act, rms) if (x.dtype in (BF16, F16) and out_rows is None and a_rows is None) else 1
     if splits > 1 and o2.stride(0) % 4 == 0:
         ws = torch.empty(splits * M * N, dtype=F32, device=x.device)  # caching allocator: stream-safe
         if SPLITK_FUSED:  # reduction inside the GEMM launch (the tile's last block sums its slices): same values, one launch
-            cnt = _splitk_counters(x.device)
-            call = lambda: check(lib.ivlm_gemm_bf16_splitk_fused(
-                x2.data_ptr(), x2.stride(0), weight.data_ptr(), ldw, o2.data_ptr(), o2.stride(0), _p(bias),
-                _p(r2), ldr, int(res_mod), M, N, K, ACT[act], 1 if out.dtype == F32 else 0, splits, ws.data_ptr(),
-                ws.numel() * 4, cnt.data_ptr(), flags, _stream()), "gemm_bf16_splitk_fused")
+            _run("gemm_bf16_splitk_fused", lib.ivlm_gemm_bf16_splitk_fused, *head, splits, ws.data_ptr(), ws.numel() * 4,
+                 _splitk_counters(x.device).data_ptr(), flags, timer=timer)
         else:
-            call = lambda: check(lib.ivlm_gemm_bf16_splitk(
-                x2.data_ptr(), x2.stride(0), weight.data_ptr(), ldw, o2.data_ptr(), o2.stride(0), _p(bias),
-                _p(r2), ldr, int(res_mod), M, N, K, ACT[act], 1 if out.dtype == F32 else 0, splits, ws.data_ptr(),
-                ws.numel() * 4, flags, _stream()), "gemm_bf16_splitk")
-    if TIMER.enabled:  # work = algorithmic FLOPs (MFMA path) or weight bytes (GEMV path)
-        if M > 16:  # (a split A operand doubles the MFMA work of the same algorithmic product: counted once)
-            TIMER.time("gemm_bf16_mfma", 2.0 * M * N * K, call, tag=(M, N, K, act, "split" if a_split else ""))
-        else:
-            TIMER.time("gemv_bf16", 2.0 * N * K, call, tag=(M, N, K, act))
+            _run("gemm_bf16_splitk", lib.ivlm_gemm_bf16_splitk, *head, splits, ws.data_ptr(), ws.numel() * 4, flags, timer=timer)
     else:
-        call()
+        _run("gemm_bf16", lib.ivlm_gemm_bf16, *head, 1, 0, 0, 0, 0, *rms_args, flags, _p(out_rows), _p(a_rows), timer=timer)
     return out
-
-
-def _dtc(t):
-    return IVLM_F32 if t.dtype == F32 else IVLM_BF16
-
-
-IVLM_FP8 = 3
-U8 = torch.uint8
 
 
 def layernorm(x, weight, bias, eps=1e-5, gelu=False, out=None, out_f32=False, out_rows=None, fp8_scale=None, out_split=False,
@@ -464,19 +465,15 @@ def layernorm(x, weight, bias, eps=1e-5, gelu=False, out=None, out_f32=False, ou
     lib = _lib.load()
     x = _req(x, None, "x")
     cols = x.shape[-1]
+    kind = _kind(out_f32, out_split, out_f16, fp8_scale)
+    ydt = _KINDS[kind][2]
     if out is None:
-        if out_split:
-            out = torch.empty(x.shape[:-1] + (2 * cols,), dtype=F16 if out_f16 else BF16, device=x.device)
-        elif out_f16:
-            out = torch.empty(x.shape, dtype=F16, device=x.device)
-        else:
-            out = torch.empty(x.shape, dtype=U8 if fp8_scale is not None else (F32 if out_f32 else BF16), device=x.device)
-    y = out
-    ydt = IVLM_FP8 if fp8_scale is not None else ((5 if out_f16 else 2) if out_split else (4 if out_f16 else _dtc(y)))
-    check(lib.ivlm_layernorm(x.data_ptr(), _dtc(x), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), ydt,
-                             x.numel() // cols, cols, float(eps), 1 if gelu else 0, _p(out_rows), _p(fp8_scale), _stream()),
-          "layernorm")
-    return y
+        out = _out_of(kind, x.shape[:-1], cols, x.device)
+    elif kind in ("bf16", "f32"):  # (a given output that no keyword describes is written as what it is)
+        ydt = _dt(out)
+    _run("layernorm", lib.ivlm_layernorm, x.data_ptr(), _dt(x), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), ydt,
+         x.numel() // cols, cols, float(eps), 1 if gelu else 0, _p(out_rows), _p(fp8_scale))
+    return out
 
 
 def amax(x, out=None):
@@ -486,7 +483,7 @@ def amax(x, out=None):
     assert x.numel() % 8 == 0
     if out is None:
         out = torch.zeros(1, dtype=F32, device=x.device)
-    check(lib.ivlm_amax(x.data_ptr(), _dtc(x), x.numel(), out.data_ptr(), _stream()), "amax")
+    _run("amax", lib.ivlm_amax, x.data_ptr(), _dt(x), x.numel(), out.data_ptr())
     return out
 
 
@@ -500,6 +497,10 @@ def quantize_fp8(x, scale=None):
     return q, scale
 
 
+# ivlm_gemm_fp8 numbers its e4m3 output itself: include/ivlm_hip.h gives the number in the entry point's comment and no name for it
+_GEMM_FP8_OUT_E4M3 = 2
+
+
 def linear_fp8(xq, wq, scale_a, scale_w, bias=None, act="none", residual=None, out=None, out_kind="bf16", scale_out=None,
                out_rows=None, a_rows=None):
     """act((xq . wq^T) * scale_a * scale_w + bias) + residual with e4m3 operands (uint8 tensors [M,K] / [N,K]) on the MX
@@ -510,28 +511,17 @@ def linear_fp8(xq, wq, scale_a, scale_w, bias=None, act="none", residual=None, o
     assert xq.dtype == U8 and wq.dtype == U8 and wq.shape[1] == K
     x2 = xq.reshape(-1, K)
     M = x2.shape[0] if a_rows is None else a_rows.numel()
-    n_out = N // 2 if act == "swiglu" else N
+    n_out, flags, bias_res, act_out, _ = _epilogue(N, act, bias, residual, None, None, False)
+    if out is not None:
+        out_kind = _KIND_OF[out.dtype]
+    assert out_kind in ("bf16", "f32", "fp8")
     if out is None:
-        dt = {"bf16": BF16, "f32": F32, "fp8": U8}[out_kind]
-        out = torch.empty((M, n_out), dtype=dt, device=xq.device)
-    else:
-        out_kind = {BF16: "bf16", F32: "f32", U8: "fp8"}[out.dtype]
+        out = _out_of(out_kind, (M,), n_out, xq.device)
     o2 = out.reshape(-1, n_out)
-    r2, ldr, flags = None, 0, 0
-    if residual is not None:
-        r2 = residual.reshape(-1, N)
-        ldr = r2.stride(0)
-        if r2.dtype == F32:
-            flags |= GEMM_RES_F32
-    kind = {"bf16": IVLM_BF16, "f32": IVLM_F32, "fp8": 2}[out_kind]
-    call = lambda: check(lib.ivlm_gemm_fp8(
-        x2.data_ptr(), x2.stride(0), wq.data_ptr(), wq.stride(0), o2.data_ptr(), o2.stride(0), _p(bias), _p(r2), ldr, M, N, K,
-        ACT[act], kind, scale_a.data_ptr(), scale_w.data_ptr(), _p(scale_out), flags, _p(out_rows), _p(a_rows), _stream()),
-        "gemm_fp8")
-    if TIMER.enabled:
-        TIMER.time("gemm_fp8_mfma", 2.0 * M * N * K, call, tag=(M, N, K, act))
-    else:
-        call()
+    code = _GEMM_FP8_OUT_E4M3 if out_kind == "fp8" else _KINDS[out_kind][2]
+    _run("gemm_fp8", lib.ivlm_gemm_fp8, x2.data_ptr(), x2.stride(0), wq.data_ptr(), wq.stride(0), o2.data_ptr(), o2.stride(0),
+         *bias_res, M, N, K, act_out[0], code, scale_a.data_ptr(), scale_w.data_ptr(), _p(scale_out), flags, _p(out_rows),
+         _p(a_rows), timer=("gemm_fp8_mfma", 2.0 * M * N * K, (M, N, K, act)))
     return out
 
 
@@ -542,20 +532,10 @@ def linear_fp8w(x, wq, scale_w, bias=None, act="none", residual=None, out_f32=Tr
     x = _req(x, F32, "x")
     N, K = wq.shape
     assert x.numel() == K and wq.dtype == U8 and wq.stride(1) == 1
-    n_out = N // 2 if act == "swiglu" else N
-    out = torch.empty(1, n_out, dtype=F32 if out_f32 else BF16, device=x.device)
-    flags = 0
-    if residual is not None:
-        assert residual.is_contiguous() and residual.numel() == N
-        if residual.dtype == F32:
-            flags |= GEMM_RES_F32
-    call = lambda: check(lib.ivlm_gemv_fp8w(x.data_ptr(), wq.data_ptr(), wq.stride(0), scale_w.data_ptr(), out.data_ptr(), _p(bias),
-                                            _p(residual), N, K, ACT[act], 1 if out_f32 else 0, _p(rms[0]) if rms else 0,
-                                            float(rms[1]) if rms else 0.0, flags, _stream()), "gemv_fp8w")
-    if TIMER.enabled:
-        TIMER.time("gemv_fp8w", 1.0 * N * K, call, tag=(1, N, K, act))  # work = weight BYTES
-    else:
-        call()
+    n_out, flags, (b, r, _), act_out, rms_args = _epilogue(N, act, bias, residual, N, rms, out_f32)
+    out = _out_of(_kind(out_f32), (1,), n_out, x.device)
+    _run("gemv_fp8w", lib.ivlm_gemv_fp8w, x.data_ptr(), wq.data_ptr(), wq.stride(0), scale_w.data_ptr(), out.data_ptr(), b, r, N, K,
+         *act_out, *rms_args, flags, timer=("gemv_fp8w", 1.0 * N * K, (1, N, K, act)))  # work = weight BYTES
     return out
 
 
@@ -582,16 +562,15 @@ class PackedBf12:
             lib, w, K = _lib.load(), w.contiguous(), w.shape[1]
             self.ebase = torch.empty(n_rows, dtype=torch.int32, device=w.device)
             self.patch_ptr = torch.empty(n_rows + 1, dtype=torch.int32, device=w.device)
-            check(lib.ivlm_pack_bf12m_count(w.data_ptr(), self.rows, n_rows, K, self.ebase.data_ptr(), self.patch_ptr.data_ptr(),
-                                            _stream()), "pack_bf12m_count")
+            _run("pack_bf12m_count", lib.ivlm_pack_bf12m_count, w.data_ptr(), self.rows, n_rows, K, self.ebase.data_ptr(),
+                 self.patch_ptr.data_ptr())
             self.n_patches = int(self.patch_ptr[-1])
             self.patch_col = torch.zeros(max(1, self.n_patches), dtype=torch.int32, device=w.device)
             self.patch_val = torch.zeros(max(1, self.n_patches), dtype=BF16, device=w.device)
             self.P = torch.empty(n_rows // 16, K // 64, 4, 16, 2, 8, dtype=torch.uint8, device=w.device)
             self.E = torch.empty(n_rows // 16, K // 64, 4, 16, 2, 4, dtype=torch.uint8, device=w.device)
-            check(lib.ivlm_pack_bf12m_fill(w.data_ptr(), self.rows, n_rows, K, self.ebase.data_ptr(), self.patch_ptr.data_ptr(),
-                                           self.P.data_ptr(), self.E.data_ptr(), self.patch_col.data_ptr(), self.patch_val.data_ptr(),
-                                           _stream()), "pack_bf12m_fill")
+            _run("pack_bf12m_fill", lib.ivlm_pack_bf12m_fill, w.data_ptr(), self.rows, n_rows, K, self.ebase.data_ptr(),
+                 self.patch_ptr.data_ptr(), self.P.data_ptr(), self.E.data_ptr(), self.patch_col.data_ptr(), self.patch_val.data_ptr())
             self.shape, self.frag = (n_rows, K), True
             return
         if pad_rows and w.shape[0] % 16:
@@ -646,7 +625,7 @@ class PackedBf12:
     def unpack(self):
         """-> bf16 [rows, K], bit-identical to the matrix that was packed."""
         out = torch.empty(self.shape, dtype=BF16, device=self.P.device)
-        check(_lib.load().ivlm_unpack_bf12(*self._args(), self.shape[0], self.shape[1], out.data_ptr(), _stream()), "unpack_bf12")
+        _run("unpack_bf12", _lib.load().ivlm_unpack_bf12, *self._args(), self.shape[0], self.shape[1], out.data_ptr())
         self._keep = None
         return out[: self.rows]
 
@@ -663,43 +642,24 @@ def linear_bf12(x, wp: PackedBf12, bias=None, act="none", residual=None, out_f32
     else:
         assert x.dtype == F32 and x.is_contiguous() and x.dim() == 2 and x.shape[1] == K and 1 <= x.shape[0] <= 16
         dev = x.device
-    n_out = N // 2 if act == "swiglu" else N
     M = 1 if parts is not None else x.shape[0]
-    out = torch.empty(M, n_out, dtype=F32 if out_f32 else BF16, device=dev)
+    n_out, flags, (b, r, _), act_out, rms_args = _epilogue(N, act, bias, residual, (M, N) if M > 1 else N, rms, out_f32)
+    out = _out_of(_kind(out_f32), (M,), n_out, dev)
+    timer = ("gemv_bf16", 2.0 * N * K, (M, N, K, act, "bf12"))  # work = the ALGORITHMIC bytes (the bf16 matrix), like the other decode linears
     if M > 1:  # the batched decode step: M activation rows meet every rebuilt weight fragment (fragment layout only)
         assert wp.frag and wp.rows == N
-        flags = 0
-        if residual is not None:
-            assert residual.dtype in (BF16, F32) and residual.is_contiguous() and tuple(residual.shape) == (M, N)
-            flags = GEMM_RES_F32 if residual.dtype == F32 else 0
-        call = lambda: check(lib.ivlm_gemv16_bf12m(x.data_ptr(), K, M, *wp._args_frag(), out.data_ptr(), n_out, _p(bias), _p(residual), N,
-                                                   N, K, ACT[act], 1 if out_f32 else 0, _p(rms[0]) if rms else 0,
-                                                   float(rms[1]) if rms else 0.0, flags, _stream()), "gemv16_bf12m")
-        if TIMER.enabled:
-            TIMER.time("gemv_bf16", 2.0 * N * K, call, tag=(M, N, K, act, "bf12"))
-        else:
-            call()
+        _run("gemv16_bf12m", lib.ivlm_gemv16_bf12m, x.data_ptr(), K, M, *wp._args_frag(), out.data_ptr(), n_out, b, r, N, N, K, *act_out,
+             *rms_args, flags, timer=timer)
         return out
-    flags = 0
-    if residual is not None:
-        assert residual.dtype in (BF16, F32) and residual.is_contiguous() and residual.numel() == N
-        if residual.dtype == F32:
-            flags |= GEMM_RES_F32
     if parts is not None:
-        call = lambda: check(lib.ivlm_gemv1_bf12m_parts(pt.data_ptr(), pD, *wp._args_frag(), out.data_ptr(), _p(bias), _p(residual), N, K,
-                                                        ACT[act], 1 if out_f32 else 0, flags, _stream()), "gemv1_bf12m_parts")
+        _run("gemv1_bf12m_parts", lib.ivlm_gemv1_bf12m_parts, pt.data_ptr(), pD, *wp._args_frag(), out.data_ptr(), b, r, N, K, *act_out,
+             flags, timer=timer)
     elif wp.frag:  # MFMA kernel on the fragment layout
-        call = lambda: check(lib.ivlm_gemv1_bf12m(x.data_ptr(), *wp._args_frag(), out.data_ptr(), _p(bias), _p(residual), N, K,
-                                                  ACT[act], 1 if out_f32 else 0, _p(rms[0]) if rms else 0,
-                                                  float(rms[1]) if rms else 0.0, flags, _stream()), "gemv1_bf12m")
+        _run("gemv1_bf12m", lib.ivlm_gemv1_bf12m, x.data_ptr(), *wp._args_frag(), out.data_ptr(), b, r, N, K, *act_out, *rms_args, flags,
+             timer=timer)
     else:
-        call = lambda: check(lib.ivlm_gemv1_bf12(x.data_ptr(), *wp._args(), out.data_ptr(), _p(bias), _p(residual), N, K, ACT[act],
-                                                 1 if out_f32 else 0, _p(rms[0]) if rms else 0, float(rms[1]) if rms else 0.0,
-                                                 flags, _stream()), "gemv1_bf12")
-    if TIMER.enabled:  # work = the ALGORITHMIC bytes (the bf16 matrix), like the other decode linears
-        TIMER.time("gemv_bf16", 2.0 * N * K, call, tag=(1, N, K, act, "bf12"))
-    else:
-        call()
+        _run("gemv1_bf12", lib.ivlm_gemv1_bf12, x.data_ptr(), *wp._args(), out.data_ptr(), b, r, N, K, *act_out, *rms_args, flags,
+             timer=timer)
     return out if wp.rows == N or act == "swiglu" else out[:, : wp.rows]
 
 
@@ -707,17 +667,14 @@ def rmsnorm(x, weight, eps=1e-5, out_f32=False, out_split=False, fp8_scale=None,
     lib = _lib.load()
     x = _req(x, None, "x")
     cols = x.shape[-1]
-    if fp8_scale is not None:  # e4m3 bytes of the normalised row / scale: the operand of linear_fp8
-        y = torch.empty(x.shape, dtype=U8, device=x.device)
-        check(lib.ivlm_rmsnorm_fp8(x.data_ptr(), _dtc(x), weight.data_ptr(), y.data_ptr(), x.numel() // cols, cols, float(eps),
-                                   fp8_scale.data_ptr(), _stream()), "rmsnorm_fp8")
-        return y
-    if out_split:
-        y = torch.empty(x.shape[:-1] + (2 * cols,), dtype=BF16, device=x.device)
+    kind = _kind(out_f32, out_split, out_f16 and not out_split, fp8_scale)  # (its split rows are bf16 whatever out_f16 says)
+    y = _out_of(kind, x.shape[:-1], cols, x.device)
+    if kind == "fp8":  # e4m3 bytes of the normalised row / scale: the operand of linear_fp8
+        _run("rmsnorm_fp8", lib.ivlm_rmsnorm_fp8, x.data_ptr(), _dt(x), weight.data_ptr(), y.data_ptr(), x.numel() // cols, cols,
+             float(eps), fp8_scale.data_ptr())
     else:
-        y = torch.empty(x.shape, dtype=F16 if out_f16 else (F32 if out_f32 else BF16), device=x.device)
-    check(lib.ivlm_rmsnorm(x.data_ptr(), _dtc(x), weight.data_ptr(), y.data_ptr(), 2 if out_split else (4 if out_f16 else _dtc(y)),
-                           x.numel() // cols, cols, float(eps), _stream()), "rmsnorm")
+        _run("rmsnorm", lib.ivlm_rmsnorm, x.data_ptr(), _dt(x), weight.data_ptr(), y.data_ptr(), _KINDS[kind][2], x.numel() // cols,
+             cols, float(eps))
     return y
 
 
@@ -726,7 +683,7 @@ def bf16_to_f16(w):
     w = w.contiguous()
     assert w.dtype == torch.bfloat16
     out = torch.empty(w.shape, dtype=torch.float16, device=w.device)
-    check(_lib.load().ivlm_bf16_to_f16(w.data_ptr(), out.data_ptr(), w.numel(), _stream()), "bf16_to_f16")
+    _run("bf16_to_f16", _lib.load().ivlm_bf16_to_f16, w.data_ptr(), out.data_ptr(), w.numel())
     return out
 
 
@@ -751,11 +708,14 @@ def relpos_table64(tab_h, tab_w):
     return t
 
 
+def _strides12(q, k, v, o):
+    """the attention entry points' stride argument: the three leading strides of q, k, v and o as one int64[12]"""
+    return ctypes.cast((ctypes.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, o) for i in range(3))), ctypes.c_void_p)
+
+
 def _attn_operands(q, k, v, o, rel, rel_tab, prescale_q, grid_table):
     """What ``attention`` and ``attention_split`` pass alike: the stride array, the rel_h / rel_w pointers, kh, kw, the prescale flag."""
-    import ctypes
-
-    st = (ctypes.c_int64 * 12)(*(t.stride(i) for t in (q, k, v, o) for i in range(3)))
+    st = _strides12(q, k, v, o)
     rel_h = rel_w = None
     kh = kw = 0
     if rel is not None:
@@ -780,8 +740,6 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, rel=None, out=None, presca
     b // (B//Bk)) -> o [B,H,Sq,D] as a view of a [B,Sq,H,D] buffer (so o.transpose(1,2) is contiguous).
     rel = (rel_h f32 [B*H,Sq,KH], rel_w f32 [B*H,Sq,KW]) adds SAM's decomposed rel-pos bias; rel_tab = (relpos_table64(...), side)
     lets the kernel compute those terms itself (14 x 14 windows)."""
-    import ctypes
-
     lib = _lib.load()
     B, H, Sq, D = q.shape
     Bk, Sk = k.shape[0], k.shape[2]
@@ -794,14 +752,11 @@ def attention(q, k, v, scale, causal=False, q_pos0=0, rel=None, out=None, presca
     st, rel_h, rel_w, kh, kw, pre = _attn_operands(q, k, v, out, rel, rel_tab, prescale_q, grid_table=True)
     if q_lo is not None:  # fp16 "exact q": q = q + q_lo as IEEE halves (SAM shapes; the strides of q)
         assert dt == F16 and q_lo.dtype == F16 and q_lo.stride() == q.stride() and q_lo.shape == q.shape and not causal and B == Bk
-        check(lib.ivlm_attention_f16_qsplit(q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                            ctypes.cast(st, ctypes.c_void_p), B, H, Sq, Sk, D, float(scale), rel_h, rel_w,
-                                            kh, kw, int(q_lo_level), _stream()), "attention_f16_qsplit")
+        _run("attention_f16_qsplit", lib.ivlm_attention_f16_qsplit, q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), v.data_ptr(),
+             out.data_ptr(), st, B, H, Sq, Sk, D, float(scale), rel_h, rel_w, kh, kw, int(q_lo_level))
         return out
-    fn = lib.ivlm_attention_f16 if dt == F16 else lib.ivlm_attention_bf16
-    check(fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-             ctypes.cast(st, ctypes.c_void_p), B, H, Sq, Sk, D, float(scale), 1 if causal else 0,
-             int(q_pos0), rel_h, rel_w, kh, kw, B // Bk, pre, _stream()), "attention")
+    _run("attention", lib.ivlm_attention_f16 if dt == F16 else lib.ivlm_attention_bf16, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+         out.data_ptr(), st, B, H, Sq, Sk, D, float(scale), 1 if causal else 0, int(q_pos0), rel_h, rel_w, kh, kw, B // Bk, pre)
     return out
 
 
@@ -809,8 +764,6 @@ def attention_split(q, q_lo, k, k_lo, v, v_lo, scale, causal=False, q_pos0=0, re
     """"Parity" precision of ``attention``: every operand as hi + lo bf16 planes (the *_lo tensors have the shapes and strides of
     the hi ones), fp32-operand arithmetic on the bf16 matrix cores.  out: bf16 [B, Sq, 2, H, D] buffer (default: allocated), the
     rows [hi(H*D) | lo(H*D)] of the next GEMM's a_split operand; returned as [B*Sq, 2*H*D]."""
-    import ctypes
-
     lib = _lib.load()
     B, H, Sq, D = q.shape
     Bk, Sk = k.shape[0], k.shape[2]
@@ -822,10 +775,9 @@ def attention_split(q, q_lo, k, k_lo, v, v_lo, scale, causal=False, q_pos0=0, re
     assert out.shape == (B, Sq, 2, H, D) and out.stride(4) == 1
     oh, ol = out[:, :, 0].permute(0, 2, 1, 3), out[:, :, 1].permute(0, 2, 1, 3)  # [B,H,Sq,D] views
     st, rel_h, rel_w, kh, kw, pre = _attn_operands(q, k, v, oh, rel, rel_tab, prescale_q, grid_table=False)
-    check(lib.ivlm_attention_bf16_split(q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), k_lo.data_ptr(), v.data_ptr(),
-                                        v_lo.data_ptr(), oh.data_ptr(), ol.data_ptr(), ctypes.cast(st, ctypes.c_void_p), B, H,
-                                        Sq, Sk, D, float(scale), 1 if causal else 0, int(q_pos0), rel_h, rel_w, kh, kw,
-                                        B // Bk, pre, _stream()), "attention_split")
+    _run("attention_split", lib.ivlm_attention_bf16_split, q.data_ptr(), q_lo.data_ptr(), k.data_ptr(), k_lo.data_ptr(), v.data_ptr(),
+         v_lo.data_ptr(), oh.data_ptr(), ol.data_ptr(), st, B, H, Sq, Sk, D, float(scale), 1 if causal else 0, int(q_pos0), rel_h,
+         rel_w, kh, kw, B // Bk, pre)
     return out.view(B * Sq, 2 * H * D)
 
 
@@ -838,9 +790,8 @@ def relpos_bias_split(q, q_lo, tab_h, tab_w, SH, SW):
     assert S == SH * SW and q.stride(3) == 1 and q.stride() == q_lo.stride() and tab_h.is_contiguous() and tab_w.is_contiguous()
     rel_h = torch.empty(B * H, S, SH, dtype=torch.float32, device=q.device)
     rel_w = torch.empty(B * H, S, SW, dtype=torch.float32, device=q.device)
-    check(lib.ivlm_relpos_bias_split(q.data_ptr(), q_lo.data_ptr(), q.stride(0), q.stride(1), q.stride(2), tab_h.data_ptr(),
-                                     tab_w.data_ptr(), B, H, SH, SW, D, rel_h.data_ptr(), rel_w.data_ptr(), _stream()),
-          "relpos_bias_split")
+    _run("relpos_bias_split", lib.ivlm_relpos_bias_split, q.data_ptr(), q_lo.data_ptr(), q.stride(0), q.stride(1), q.stride(2),
+         tab_h.data_ptr(), tab_w.data_ptr(), B, H, SH, SW, D, rel_h.data_ptr(), rel_w.data_ptr())
     return rel_h, rel_w
 
 
@@ -848,8 +799,6 @@ def attention_f32(q, k, v, scale, out=None):
     """fp32 q [B,H,Sq,D], k/v [Bk,H,Sk,D] (any D % 4 == 0 up to 256: 16 and 32 take the mask decoder's kernels, every other
     width - the AttentionSplitter's 128 - the wide one; arbitrary strides % 4, 16-byte aligned pointers) -> o [B,H,Sq,D] fp32 as
     a view of a [B,Sq,H,D] buffer; scores = (q.k) * scale, no operand rounding."""
-    import ctypes
-
     lib = _lib.load()
     B, H, Sq, D = q.shape
     Bk, Sk = k.shape[0], k.shape[2]
@@ -857,10 +806,8 @@ def attention_f32(q, k, v, scale, out=None):
     assert q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     if out is None:
         out = torch.empty(B, Sq, H, D, dtype=F32, device=q.device).permute(0, 2, 1, 3)
-    st = (ctypes.c_int64 * 12)(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-                               v.stride(0), v.stride(1), v.stride(2), out.stride(0), out.stride(1), out.stride(2))
-    check(lib.ivlm_attention_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ctypes.cast(st, ctypes.c_void_p),
-                                 B, H, Sq, Sk, D, float(scale), B // Bk, _stream()), "attention_f32")
+    _run("attention_f32", lib.ivlm_attention_f32, q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _strides12(q, k, v, out),
+         B, H, Sq, Sk, D, float(scale), B // Bk)
     return out
 
 
@@ -893,30 +840,21 @@ def relpos_bias(q, tab_h, tab_w, SH, SW, cat=None, q_lo=None):
         npad, M = cat.shape[0], B * S
         assert q_lo is None or (q_lo.dtype == F16 and q_lo.stride() == q.stride())
         G = torch.empty(H, M, npad, dtype=F32, device=q.device)
-        call = lambda: check(lib.ivlm_relpos_bias_f16(q.data_ptr(), _p(q_lo), q.stride(0), q.stride(1), q.stride(2), cat.data_ptr(), npad,
-                                                      B, H, SH, SW, D, G.data_ptr(), G.numel() * 4, rel_h.data_ptr(), rel_w.data_ptr(),
-                                                      _stream()), "relpos_bias_f16")
-        if TIMER.enabled:
-            TIMER.time("gemm_bf16_mfma", 2.0 * H * M * npad * D, call, tag=("relpos", M, npad, D))
-        else:
-            call()
+        _run("relpos_bias_f16", lib.ivlm_relpos_bias_f16, q.data_ptr(), _p(q_lo), q.stride(0), q.stride(1), q.stride(2), cat.data_ptr(),
+             npad, B, H, SH, SW, D, G.data_ptr(), G.numel() * 4, rel_h.data_ptr(), rel_w.data_ptr(),
+             timer=("gemm_bf16_mfma", 2.0 * H * M * npad * D, ("relpos", M, npad, D)))
         return rel_h, rel_w
     if (RELPOS_GEMM and cat is not None and min(SH, SW) >= 32 and q.dtype == cat.dtype and q.stride(0) == S * q.stride(2) and q.stride(2) % 8 == 0
             and q.stride(1) % 8 == 0 and D % 8 == 0 and q.data_ptr() % 16 == 0):
         npad, M = cat.shape[0], B * S
         G = torch.empty(H, M, npad, dtype=BF16, device=q.device)
-        call = lambda: check(lib.ivlm_gemm_bf16(q.data_ptr(), q.stride(2), cat.data_ptr(), D, G.data_ptr(), npad, 0, 0, 0, 0,
-                                                M, npad, D, 0, 0, H, q.stride(1), 0, M * npad, 0, 0, 0.0, 0, 0, 0, _stream()),
-                             "relpos gemm")
-        if TIMER.enabled:
-            TIMER.time("gemm_bf16_mfma", 2.0 * H * M * npad * D, call, tag=("relpos", M, npad, D))
-        else:
-            call()
-        check(lib.ivlm_relpos_gather(G.data_ptr(), M * npad, npad, B, H, SH, SW, rel_h.data_ptr(), rel_w.data_ptr(), _stream()),
-              "relpos_gather")
+        _run("relpos gemm", lib.ivlm_gemm_bf16, q.data_ptr(), q.stride(2), cat.data_ptr(), D, G.data_ptr(), npad, 0, 0, 0, 0,
+             M, npad, D, ACT["none"], 0, H, q.stride(1), 0, M * npad, 0, 0, 0.0, 0, 0, 0,
+             timer=("gemm_bf16_mfma", 2.0 * H * M * npad * D, ("relpos", M, npad, D)))
+        _run("relpos_gather", lib.ivlm_relpos_gather, G.data_ptr(), M * npad, npad, B, H, SH, SW, rel_h.data_ptr(), rel_w.data_ptr())
         return rel_h, rel_w
-    check(lib.ivlm_relpos_bias(q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), tab_h.data_ptr(), tab_w.data_ptr(),
-                               B, H, SH, SW, D, rel_h.data_ptr(), rel_w.data_ptr(), _stream()), "relpos_bias")
+    _run("relpos_bias", lib.ivlm_relpos_bias, q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), tab_h.data_ptr(), tab_w.data_ptr(),
+         B, H, SH, SW, D, rel_h.data_ptr(), rel_w.data_ptr())
     return rel_h, rel_w
 
 
@@ -928,9 +866,9 @@ def argmax(logits, bump=None):
     out = torch.empty(rows, dtype=torch.int32, device=logits.device)
     if bump is not None:
         assert bump.dtype == torch.int32 and bump.is_cuda and bump.numel() == rows and bump.is_contiguous()
-        check(lib.ivlm_argmax_f32_bump(logits.data_ptr(), rows, cols, out.data_ptr(), bump.data_ptr(), _stream()), "argmax_bump")
+        _run("argmax_bump", lib.ivlm_argmax_f32_bump, logits.data_ptr(), rows, cols, out.data_ptr(), bump.data_ptr())
         return out
-    check(lib.ivlm_argmax_f32(logits.data_ptr(), rows, cols, out.data_ptr(), _stream()), "argmax")
+    _run("argmax", lib.ivlm_argmax_f32, logits.data_ptr(), rows, cols, out.data_ptr())
     return out
 
 
@@ -945,7 +883,7 @@ def im2col_nchw(x, ks, stride, kpad=None):
     kpad = kpad or ((K + 63) // 64) * 64
     gh, gw = (H - ks) // stride + 1, (W - ks) // stride + 1
     out = torch.empty(B * gh * gw, kpad, dtype=BF16, device=x.device)
-    check(lib.ivlm_im2col_nchw(x.data_ptr(), out.data_ptr(), B, C, H, W, ks, stride, kpad, _stream()), "im2col_nchw")
+    _run("im2col_nchw", lib.ivlm_im2col_nchw, x.data_ptr(), out.data_ptr(), B, C, H, W, ks, stride, kpad)
     return out
 
 
@@ -954,7 +892,7 @@ def im2col3x3_nhwc(x):
     x = _req(x, BF16, "x")
     B, H, W, C = x.shape
     out = torch.empty(B * H * W, 9 * C, dtype=BF16, device=x.device)
-    check(lib.ivlm_im2col3x3_nhwc(x.data_ptr(), out.data_ptr(), B, H, W, C, _stream()), "im2col3x3")
+    _run("im2col3x3", lib.ivlm_im2col3x3_nhwc, x.data_ptr(), out.data_ptr(), B, H, W, C)
     return out
 
 
@@ -965,12 +903,9 @@ def im2col3x3_nhwc_split(x_split, B, H, W, C):
     assert x_split.shape == (B * H * W, 2 * C)
     out = torch.empty(B * H * W, 18 * C, dtype=BF16, device=x_split.device)
     for half in range(2):
-        check(lib.ivlm_im2col3x3_nhwc_strided(x_split.data_ptr() + half * C * 2, 2 * C, out.data_ptr() + half * 9 * C * 2,
-                                              18 * C, B, H, W, C, _stream()), "im2col3x3_strided")
+        _run("im2col3x3_strided", lib.ivlm_im2col3x3_nhwc_strided, x_split.data_ptr() + half * C * 2, 2 * C, out.data_ptr() + half * 9 *
+             C * 2, 18 * C, B, H, W, C)
     return out
-
-
-_KIND = {"bf16": IVLM_BF16, "f32": IVLM_F32, "split": 2, "fp8": 3}
 
 
 def gather_rows(src, idx=None, add=None, out=None, out_kind=None, scale=None):
@@ -989,18 +924,17 @@ def gather_rows(src, idx=None, add=None, out=None, out_kind=None, scale=None):
     if out_kind is None:
         ref = out if out is not None else (add if add is not None else src)
         out_kind = "f32" if ref.dtype == F32 else "bf16"
+    assert out_kind in ("bf16", "f32", "split", "fp8")
     if out is None:
-        out = (torch.empty(rows, 2 * cols, dtype=BF16, device=src.device) if out_kind == "split"
-               else torch.empty(rows, cols, dtype={"f32": F32, "fp8": torch.uint8}.get(out_kind, BF16), device=src.device))
-    assert out.stride(-1) == 1 and out.dtype == {"f32": F32, "fp8": torch.uint8}.get(out_kind, BF16)
+        out = _out_of(out_kind, (rows,), cols, src.device)
+    assert out.stride(-1) == 1 and out.dtype == _KINDS[out_kind][0]
     assert (out_kind == "fp8") == (scale is not None)
     lda = 0
     if add is not None:
         assert add.dtype in (BF16, F32) and add.stride(-1) == 1
         lda = add.stride(0)
-    check(lib.ivlm_gather_rows(out.data_ptr(), _KIND[out_kind], out.stride(0), src.data_ptr(), _dtc(src), src.stride(0),
-                               _p(idx), _p(add), _dtc(add) if add is not None else 0, lda, rows, cols, _p(scale), _stream()),
-          "gather_rows")
+    _run("gather_rows", lib.ivlm_gather_rows, out.data_ptr(), _KINDS[out_kind][2], out.stride(0), src.data_ptr(), _dt(src), src.stride(0),
+         _p(idx), _p(add), _dt(add) if add is not None else 0, lda, rows, cols, _p(scale))
     return out
 
 
@@ -1009,8 +943,7 @@ def fill_rows(dst, idx, row):
     lib = _lib.load()
     assert dst.dtype in (BF16, F16) and row.dtype == dst.dtype and dst.stride(-1) == 1 and row.is_contiguous()  # (a 16-bit copy)
     assert idx.dtype == torch.int32 and idx.is_contiguous() and row.numel() == dst.shape[-1]
-    check(lib.ivlm_fill_rows(dst.data_ptr(), dst.stride(0), idx.data_ptr(), idx.numel(), row.data_ptr(), dst.shape[-1],
-                             _stream()), "fill_rows")
+    _run("fill_rows", lib.ivlm_fill_rows, dst.data_ptr(), dst.stride(0), idx.data_ptr(), idx.numel(), row.data_ptr(), dst.shape[-1])
     return dst
 
 
@@ -1029,11 +962,11 @@ def add_rows(a, b, out=None, op="add", out_kind=None):
     cols = a.shape[-1]
     if out_kind is None:
         out_kind = "f32" if (out if out is not None else a).dtype == F32 else "bf16"
+    assert out_kind in ("bf16", "f32", "split")
     if out is None:
-        out = (torch.empty(a.shape[:-1] + (2 * cols,), dtype=BF16, device=a.device) if out_kind == "split"
-               else torch.empty(a.shape, dtype=F32 if out_kind == "f32" else BF16, device=a.device))
-    check(lib.ivlm_add_rows(out.data_ptr(), _KIND[out_kind], a.data_ptr(), _dtc(a), b.data_ptr(), _dtc(b),
-                            a.numel() // cols, cols, b.numel() // cols, 1 if op == "mul" else 0, _stream()), "add_rows")
+        out = _out_of(out_kind, a.shape[:-1], cols, a.device)
+    _run("add_rows", lib.ivlm_add_rows, out.data_ptr(), _KINDS[out_kind][2], a.data_ptr(), _dt(a), b.data_ptr(), _dt(b),
+         a.numel() // cols, cols, b.numel() // cols, 1 if op == "mul" else 0)
     return out
 
 
@@ -1044,8 +977,7 @@ def uncertainty_mlp(emb, w1, b1, w2, b2, w3, b3):
     assert emb.shape[-1] == 256 and tuple(w1.shape) == (64, 256) and tuple(w2.shape) == (16, 64) and w3.numel() == 16
     ws = [_req(t, BF16, "w") for t in (w1, b1, w2, b2, w3, b3)]
     out = torch.empty(emb.shape[:-1], dtype=F32, device=emb.device)
-    check(_lib.load().ivlm_uncertainty_mlp(emb.data_ptr(), out.numel(), *[t.data_ptr() for t in ws], out.data_ptr(), _stream()),
-          "uncertainty_mlp")
+    _run("uncertainty_mlp", _lib.load().ivlm_uncertainty_mlp, emb.data_ptr(), out.numel(), *[t.data_ptr() for t in ws], out.data_ptr())
     return out
 
 
@@ -1056,7 +988,7 @@ def resize_bilinear(src, size, dtype=torch.float32):
     oh, ow = int(size[0]), int(size[1])
     out = torch.empty(src.shape[:-2] + (oh, ow), dtype=dtype, device=src.device)
     n = src.numel() // (h * w)
-    check(_lib.load().ivlm_resize_bilinear(src.data_ptr(), n, h, w, out.data_ptr(), _dtc(out), oh, ow, _stream()), "resize_bilinear")
+    _run("resize_bilinear", _lib.load().ivlm_resize_bilinear, src.data_ptr(), n, h, w, out.data_ptr(), _dt(out), oh, ow)
     return out
 
 
@@ -1065,7 +997,7 @@ def dense_pe(gauss, h, w, dtype=torch.float32):
     gauss = _req(gauss, torch.float32, "gauss")
     nf = gauss.shape[1]
     pe = torch.empty(h * w, 2 * nf, dtype=dtype, device=gauss.device)
-    check(lib.ivlm_dense_pe(gauss.data_ptr(), pe.data_ptr(), _dtc(pe), h, w, nf, _stream()), "dense_pe")
+    _run("dense_pe", lib.ivlm_dense_pe, gauss.data_ptr(), pe.data_ptr(), _dt(pe), h, w, nf)
     return pe
 
 
@@ -1089,8 +1021,8 @@ def rope_kv(qkv, H, D, pos0, theta, kcache=None, vcache=None, table=None):
     assert qkv.dtype in (BF16, F16) and qkv.stride(-1) == 1 and (kcache is None or (kcache.dtype == qkv.dtype == vcache.dtype))
     _rope_extents(qkv, 3 * H * D, H, D, pos0, table, (kcache, vcache))
     T = qkv.shape[0]
-    check((lib.ivlm_rope_kv_f16 if qkv.dtype == F16 else lib.ivlm_rope_kv)(qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0), float(theta), _p(kcache), _p(vcache),
-                                                                           _p(table[0]) if table else 0, _p(table[1]) if table else 0, _stream()), "rope_kv")
+    _run("rope_kv", (lib.ivlm_rope_kv_f16 if qkv.dtype == F16 else lib.ivlm_rope_kv), qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0),
+         float(theta), _p(kcache), _p(vcache), _p(table[0]) if table else 0, _p(table[1]) if table else 0)
     return qkv
 
 
@@ -1102,8 +1034,8 @@ def rope_kv_split(qkv, H, D, pos0, caches, table):
     T = qkv.shape[0]
     kc = caches if caches is not None else (None,) * 4
     _rope_extents(qkv, 6 * H * D, H, D, pos0, table, kc)
-    check(lib.ivlm_rope_kv_split(qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0), _p(kc[0]), _p(kc[1]), _p(kc[2]), _p(kc[3]),
-                                 table[0].data_ptr(), table[1].data_ptr(), _stream()), "rope_kv_split")
+    _run("rope_kv_split", lib.ivlm_rope_kv_split, qkv.data_ptr(), qkv.stride(0), T, H, D, int(pos0), _p(kc[0]), _p(kc[1]), _p(kc[2]),
+         _p(kc[3]), table[0].data_ptr(), table[1].data_ptr())
     return qkv
 
 
@@ -1111,7 +1043,7 @@ def rope_table(T, D, theta, device):
     lib = _lib.load()
     c = torch.empty(T, D // 2, dtype=torch.float32, device=device)
     s = torch.empty_like(c)
-    check(lib.ivlm_rope_table(c.data_ptr(), s.data_ptr(), T, D, float(theta), _stream()), "rope_table")
+    _run("rope_table", lib.ivlm_rope_table, c.data_ptr(), s.data_ptr(), T, D, float(theta))
     return c, s
 
 
@@ -1121,7 +1053,7 @@ def mask_dot(up, hyper, B, gh, gw):
     hyper = _req(hyper, up.dtype, "hyper")
     C = hyper.shape[-1]
     low = torch.empty(B, 4 * gh, 4 * gw, dtype=F32, device=up.device)
-    check(lib.ivlm_mask_dot(up.data_ptr(), hyper.data_ptr(), _dtc(up), low.data_ptr(), B, gh, gw, C, _stream()), "mask_dot")
+    _run("mask_dot", lib.ivlm_mask_dot, up.data_ptr(), hyper.data_ptr(), _dt(up), low.data_ptr(), B, gh, gw, C)
     return low
 
 
@@ -1137,7 +1069,7 @@ def mask_dot_multi(up, hyper, B, gh, gw, out=None):
     low = torch.empty(B, M, 4 * gh, 4 * gw, dtype=F32, device=up.device) if out is None else _req(out, F32, "out")
     if tuple(low.shape) != (B, M, 4 * gh, 4 * gw):
         raise IvlmError(f"mask_dot_multi: out {tuple(low.shape)}, expected {(B, M, 4 * gh, 4 * gw)}")
-    check(lib.ivlm_mask_dot_multi(up.data_ptr(), hyper.data_ptr(), _dtc(up), low.data_ptr(), B, M, gh, gw, C, _stream()), "mask_dot_multi")
+    _run("mask_dot_multi", lib.ivlm_mask_dot_multi, up.data_ptr(), hyper.data_ptr(), _dt(up), low.data_ptr(), B, M, gh, gw, C)
     return low
 
 
@@ -1155,8 +1087,8 @@ def prompt_embed(coords, labels, gauss, table, input_size, out=None):
     o = torch.empty(R, 2 * nf, dtype=F32, device=coords.device) if out is None else _req(out, F32, "out")
     if o.numel() != R * 2 * nf:
         raise IvlmError(f"prompt_embed: out {tuple(o.shape)}, expected {(R, 2 * nf)}")
-    check(lib.ivlm_prompt_embed(coords.data_ptr(), labels.data_ptr(), gauss.data_ptr(), table.data_ptr(), o.data_ptr(), R, nf,
-                                int(input_size[0]), int(input_size[1]), _stream()), "prompt_embed")
+    _run("prompt_embed", lib.ivlm_prompt_embed, coords.data_ptr(), labels.data_ptr(), gauss.data_ptr(), table.data_ptr(), o.data_ptr(),
+         R, nf, int(input_size[0]), int(input_size[1]))
     return o
 
 
@@ -1176,8 +1108,8 @@ def mask_downscale(mask, weights, eps=1e-6, out=None):
     o = torch.empty(B, gh * gw, C, dtype=F32, device=mask.device) if out is None else _req(out, F32, "out")
     if o.numel() != B * gh * gw * C:
         raise IvlmError(f"mask_downscale: out {tuple(o.shape)}, expected {(B, gh * gw, C)}")
-    check(lib.ivlm_mask_downscale(mask.data_ptr(), *[t.data_ptr() for t in ws], o.data_ptr(), B, gh, gw, C, mid, float(eps),
-                                  _stream()), "mask_downscale")
+    _run("mask_downscale", lib.ivlm_mask_downscale, mask.data_ptr(), *[t.data_ptr() for t in ws], o.data_ptr(), B, gh, gw, C, mid,
+         float(eps))
     return o
 
 
@@ -1192,18 +1124,32 @@ def _rope_tail(theta, scale, table):
 
 
 def _cache_code(kcache):
-    return 4 if kcache.dtype == F16 else IVLM_BF16
+    return _KINDS[_KIND_OF[kcache.dtype]][2]
+
+
+def _decode_checks(kcache, vcache, pos, n_pos=None, slabs=False, table=None, D=0):
+    """What the kernels cannot see, before the launch.  The cache pair: 16-bit planes of one dtype, contiguous [Tmax, H, D] (slabs:
+    [B, Tmax, H, D], every slab contiguous, one slab stride).  A device position: int32 (n_pos: exactly that many, contiguous).
+    table (the batch-prefix and verify forms hand theirs over): a cos / sin row for every position below Tmax."""
+    assert kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
+    if slabs:
+        assert kcache.dim() == 4 and kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
+    else:
+        assert kcache.is_contiguous() and vcache.is_contiguous()
+    if isinstance(pos, torch.Tensor):
+        assert pos.dtype == torch.int32 and pos.is_cuda and (pos.numel() >= 1 if n_pos is None else pos.numel() == n_pos and pos.is_contiguous())
+    if table is not None:
+        assert table[0].shape[0] >= kcache.shape[1 if slabs else 0] and table[0].shape[1] == D // 2
 
 
 def llama_decode_attn_parts(qkv, kcache, vcache, H, D, pos, theta, scale, parts, table=None):
     """Split-KV decode attention WITHOUT the merge: RoPE + cache append + four key ranges per head -> parts fp32 [H, 4, D + 4] (o
     unnormalised | max | sum | pad) for ``linear_bf12(..., parts=)`` (the o_proj merges them while it stages its activation row)."""
     lib = _lib.load()
-    assert qkv.dtype == F32 and qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
-    assert parts.dtype == F32 and parts.is_contiguous() and parts.numel() >= H * 4 * (D + 4) and kcache.dtype in (BF16, F16)
-    check(lib.ivlm_llama_decode_attn_parts(qkv.data_ptr(), _cache_code(kcache), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0],
-                                           parts.data_ptr(), H, D, *_pos_pair(pos), *_rope_tail(theta, scale, table), _stream()),
-          "llama_decode_attn_parts")
+    _decode_checks(kcache, vcache, pos)
+    assert qkv.dtype == F32 and qkv.is_contiguous() and parts.dtype == F32 and parts.is_contiguous() and parts.numel() >= H * 4 * (D + 4)
+    _run("llama_decode_attn_parts", lib.ivlm_llama_decode_attn_parts, qkv.data_ptr(), _cache_code(kcache), kcache.data_ptr(),
+         vcache.data_ptr(), kcache.shape[0], parts.data_ptr(), H, D, *_pos_pair(pos), *_rope_tail(theta, scale, table))
     return parts
 
 
@@ -1218,26 +1164,23 @@ def llama_decode_attn(qkv, kcache, vcache, H, D, pos, theta, scale, out=None, ta
     pos: python int, or an int32 device tensor [1] (read by the kernel: HIP-graph friendly).  kcache [Tmax, H, D].
     lo = (kcache_lo, vcache_lo): "parity" precision, K / V cached as hi + lo planes (fp32 qkv only).
     scratch (decode_attn_scratch; fp32 qkv, no lo planes): the split-KV kernel - H x S blocks instead of H."""
-    assert qkv.dtype in (BF16, F32) and qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
+    _decode_checks(kcache, vcache, pos)
+    assert qkv.dtype in (BF16, F32) and qkv.is_contiguous()
     if out is None:
         out = torch.empty(1, H * D, dtype=qkv.dtype, device=qkv.device)
-    dev_pos = isinstance(pos, torch.Tensor)
-    if dev_pos:
-        assert pos.dtype == torch.int32 and pos.is_cuda
     lib, q, k, v = _lib.load(), qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
     rest = (kcache.shape[0], out.data_ptr(), H, D, *_pos_pair(pos), *_rope_tail(theta, scale, table))
     if scratch is not None and lo is None and qkv.dtype == F32:
-        assert kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
-        check(lib.ivlm_llama_decode_attn_splitkv(q, _cache_code(kcache), k, v, *rest, scratch.data_ptr(), scratch.numel(), _stream()),
-              "llama_decode_attn_splitkv")
+        _run("llama_decode_attn_splitkv", lib.ivlm_llama_decode_attn_splitkv, q, _cache_code(kcache), k, v, *rest, scratch.data_ptr(),
+             scratch.numel())
     elif lo is not None:
         assert qkv.dtype == F32 and lo[0].is_contiguous() and lo[1].is_contiguous() and lo[0].shape == kcache.shape
-        check(lib.ivlm_llama_decode_attn_split(q, k, lo[0].data_ptr(), v, lo[1].data_ptr(), *rest, _stream()), "llama_decode_attn_split")
+        _run("llama_decode_attn_split", lib.ivlm_llama_decode_attn_split, q, k, lo[0].data_ptr(), v, lo[1].data_ptr(), *rest)
     elif kcache.dtype == F16:  # fp16 cache (the fp16-operand prefill): fp32 qkv / o
-        assert qkv.dtype == F32 and vcache.dtype == F16
-        check(lib.ivlm_llama_decode_attn_f16(q, k, v, *rest, _stream()), "llama_decode_attn_f16")
+        assert qkv.dtype == F32
+        _run("llama_decode_attn_f16", lib.ivlm_llama_decode_attn_f16, q, k, v, *rest)
     else:
-        check(lib.ivlm_llama_decode_attn(q, _dtc(qkv), k, v, *rest, _stream()), "llama_decode_attn")
+        _run("llama_decode_attn", lib.ivlm_llama_decode_attn, q, _dt(qkv), k, v, *rest)
     return out
 
 
@@ -1246,22 +1189,21 @@ def llama_decode_attn_batch(qkv, kcache, vcache, H, D, pos_dev, theta, scale, ta
     sequence), pos_dev int32 [B] on the device -> o [B, H*D].  A sequence whose position has reached Tmax is skipped: its
     output row is zero (written by the kernel)."""
     B = qkv.shape[0]
-    assert qkv.dtype in (BF16, F32) and qkv.stride(1) == 1 and kcache.dim() == 4 and kcache.shape[0] == B
-    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
-    assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() == B and pos_dev.is_contiguous()
+    _decode_checks(kcache, vcache, pos_dev, n_pos=B, slabs=True)
+    assert qkv.dtype in (BF16, F32) and qkv.stride(1) == 1 and kcache.shape[0] == B
     if out is None:
         out = torch.empty(B, H * D, dtype=qkv.dtype, device=qkv.device)
     lib, q, k, v = _lib.load(), (qkv.data_ptr(), qkv.stride(0)), kcache.data_ptr(), vcache.data_ptr()
     rest = (kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D, pos_dev.data_ptr(), *_rope_tail(theta, scale, table))
     if lo is not None:  # "parity" precision: hi + lo cache planes
         assert qkv.dtype == F32 and lo[0].stride() == kcache.stride() and lo[1].stride() == vcache.stride()
-        check(lib.ivlm_llama_decode_attn_batch_split(*q, k, lo[0].data_ptr(), v, lo[1].data_ptr(), *rest, _stream()),
-              "llama_decode_attn_batch_split")
+        _run("llama_decode_attn_batch_split", lib.ivlm_llama_decode_attn_batch_split, *q, k, lo[0].data_ptr(), v, lo[1].data_ptr(),
+             *rest)
     elif kcache.dtype == F16:
-        assert qkv.dtype == F32 and vcache.dtype == F16
-        check(lib.ivlm_llama_decode_attn_batch_f16(*q, k, v, *rest, _stream()), "llama_decode_attn_batch_f16")
+        assert qkv.dtype == F32
+        _run("llama_decode_attn_batch_f16", lib.ivlm_llama_decode_attn_batch_f16, *q, k, v, *rest)
     else:
-        check(lib.ivlm_llama_decode_attn_batch(q[0], _dtc(qkv), q[1], k, v, *rest, _stream()), "llama_decode_attn_batch")
+        _run("llama_decode_attn_batch", lib.ivlm_llama_decode_attn_batch, q[0], _dt(qkv), q[1], k, v, *rest)
     return out
 
 
@@ -1282,23 +1224,19 @@ def llama_decode_attn_batch_prefix(qkv, kcache, vcache, H, D, pos_dev, prefix_de
     B = qkv.shape[0]
     if host_check is not None:
         assert all(int(p) >= int(host_check[1]) for p in host_check[0]), "a sequence sits inside the shared prefix"
-    assert qkv.dtype == F32 and qkv.stride(1) == 1 and kcache.dim() == 4 and kcache.shape[0] == B
-    assert kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
-    assert kcache[0].is_contiguous() and vcache[0].is_contiguous() and kcache.stride(0) == vcache.stride(0)
-    assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() == B and pos_dev.is_contiguous()
+    _decode_checks(kcache, vcache, pos_dev, n_pos=B, slabs=True, table=table, D=D)
+    assert qkv.dtype == F32 and qkv.stride(1) == 1 and kcache.shape[0] == B
     assert prefix_dev.dtype == torch.int32 and prefix_dev.is_cuda and prefix_dev.numel() >= 1
-    if table is not None:  # (the kernels read the cos / sin row of every position below Tmax)
-        assert table[0].shape[0] >= kcache.shape[1] and table[0].shape[1] == D // 2
     if out is None:
         out = torch.empty(B, H * D, dtype=F32, device=qkv.device)
     if scratch is None:
         scratch = decode_attn_prefix_scratch(B, H, D, qkv.device)
     args = (kcache.data_ptr(), vcache.data_ptr(), kcache.stride(0), kcache.shape[1], out.data_ptr(), out.stride(0), B, H, D,
-            pos_dev.data_ptr(), prefix_dev.data_ptr(), *_rope_tail(theta, scale, table), scratch.data_ptr(), scratch.numel(), _stream())
+            pos_dev.data_ptr(), prefix_dev.data_ptr(), *_rope_tail(theta, scale, table), scratch.data_ptr(), scratch.numel())
     if kcache.dtype == F16:
-        check(lib.ivlm_llama_decode_attn_batch_prefix_f16(qkv.data_ptr(), qkv.stride(0), *args), "llama_decode_attn_batch_prefix_f16")
+        _run("llama_decode_attn_batch_prefix_f16", lib.ivlm_llama_decode_attn_batch_prefix_f16, qkv.data_ptr(), qkv.stride(0), *args)
     else:
-        check(lib.ivlm_llama_decode_attn_batch_prefix(qkv.data_ptr(), IVLM_F32, qkv.stride(0), *args), "llama_decode_attn_batch_prefix")
+        _run("llama_decode_attn_batch_prefix", lib.ivlm_llama_decode_attn_batch_prefix, qkv.data_ptr(), IVLM_F32, qkv.stride(0), *args)
     return out
 
 
@@ -1308,17 +1246,14 @@ def llama_verify_attn(qkv, kcache, vcache, H, D, pos_dev, theta, scale, table=No
     attention in one launch.  Rows whose position reaches Tmax are not appended; their output rows are zero."""
     lib = _lib.load()
     k = qkv.shape[0]
+    _decode_checks(kcache, vcache, pos_dev, table=table, D=D)
     assert qkv.dtype == F32 and qkv.is_contiguous() and qkv.shape[1] == 3 * H * D and 1 <= k <= 16
-    assert kcache.is_contiguous() and vcache.is_contiguous() and kcache.dtype in (BF16, F16) and vcache.dtype == kcache.dtype
     assert kcache.shape == vcache.shape and tuple(kcache.shape[1:]) == (H, D)
-    assert pos_dev.dtype == torch.int32 and pos_dev.is_cuda and pos_dev.numel() >= 1
-    if table is not None:  # (the kernel reads the cos / sin rows of every position it appends)
-        assert table[0].shape[0] >= kcache.shape[0] and table[0].shape[1] == D // 2
     if out is None:
         out = torch.empty(k, H * D, dtype=F32, device=qkv.device)
     fn = lib.ivlm_llama_verify_attn_f16 if kcache.dtype == F16 else lib.ivlm_llama_verify_attn
-    check(fn(qkv.data_ptr(), k, kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(), H, D, pos_dev.data_ptr(),
-             *_rope_tail(theta, scale, table), _stream()), "llama_verify_attn")
+    _run("llama_verify_attn", fn, qkv.data_ptr(), k, kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], out.data_ptr(), H, D,
+         pos_dev.data_ptr(), *_rope_tail(theta, scale, table))
     return out
 
 
@@ -1331,8 +1266,8 @@ def spec_accept(amax, fed, n_draft, n_acc, tok, pos):
     for t in (amax, fed, n_draft, n_acc, tok, pos):
         assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
     assert fed.numel() == k
-    check(lib.ivlm_spec_accept(amax.data_ptr(), fed.data_ptr(), n_draft.data_ptr(), k, n_acc.data_ptr(), tok.data_ptr(), pos.data_ptr(),
-                               _stream()), "spec_accept")
+    _run("spec_accept", lib.ivlm_spec_accept, amax.data_ptr(), fed.data_ptr(), n_draft.data_ptr(), k, n_acc.data_ptr(), tok.data_ptr(),
+         pos.data_ptr())
 
 
 def llama_attn_oproj(qkv, kcache, vcache, wo, x, H, D, pos_dev, step_dev, counter, status, theta, scale, table, scratch):
@@ -1340,10 +1275,9 @@ def llama_attn_oproj(qkv, kcache, vcache, wo, x, H, D, pos_dev, step_dev, counte
     lib = _lib.load()
     assert qkv.dtype == F32 and x.dtype == F32 and scratch.dtype == F32
     out = torch.empty(1, H * D, dtype=F32, device=qkv.device)
-    check(lib.ivlm_llama_attn_oproj(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0], scratch.data_ptr(),
-                                    wo.data_ptr(), x.data_ptr(), out.data_ptr(), H, D, float(theta), float(scale),
-                                    table[0].data_ptr(), table[1].data_ptr(), pos_dev.data_ptr(), step_dev.data_ptr(),
-                                    counter.data_ptr(), status.data_ptr(), _stream()), "llama_attn_oproj")
+    _run("llama_attn_oproj", lib.ivlm_llama_attn_oproj, qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), kcache.shape[0],
+         scratch.data_ptr(), wo.data_ptr(), x.data_ptr(), out.data_ptr(), H, D, float(theta), float(scale), table[0].data_ptr(),
+         table[1].data_ptr(), pos_dev.data_ptr(), step_dev.data_ptr(), counter.data_ptr(), status.data_ptr())
     return out
 
 
@@ -1357,23 +1291,22 @@ def contact_prf(gt, pred, threshold=0.5):
     pred = _req(pred, torch.float32, "pred")
     B, n = pred.shape
     out = torch.empty(B, 3, dtype=torch.float32, device=pred.device)
-    check(lib.ivlm_contact_prf(gt.data_ptr(), pred.data_ptr(), B, n, float(threshold), out.data_ptr(), _stream()),
-          "contact_prf")
+    _run("contact_prf", lib.ivlm_contact_prf, gt.data_ptr(), pred.data_ptr(), B, n, float(threshold), out.data_ptr())
     return out
 
 
 o_contact_prf = contact_prf  # get_o_contact_metrics (utils/eval_utils.py:96-125): the same arithmetic under the object name
 
 
-_BAND_THRESHOLDS = {}
+@functools.lru_cache(maxsize=None)
+def _device_constant(values, device):
+    """fp32 numbers (a tuple) as a device tensor, uploaded once per (values, device)"""
+    return torch.tensor(values, dtype=torch.float32).to(device)
 
 
 def band_thresholds(thresholds, device):
     """The thresholds of a band census as an fp32 device tensor, uploaded once per (values, device)."""
-    key = (tuple(float(t) for t in thresholds), str(device))
-    if key not in _BAND_THRESHOLDS:
-        _BAND_THRESHOLDS[key] = torch.tensor(key[0], dtype=torch.float32).to(device)
-    return _BAND_THRESHOLDS[key]
+    return _device_constant(tuple(float(t) for t in thresholds), str(device))
 
 
 def contact_band_census(p, thresholds, margin):
@@ -1402,8 +1335,8 @@ def contact_band_census(p, thresholds, margin):
         raise IvlmError(f"margin must be >= 0, got {margin}")
     counts = torch.empty(B, J + 1, dtype=torch.int32, device=p.device)
     mindist = torch.empty(B, J, dtype=torch.float32, device=p.device)
-    check(lib.ivlm_contact_band_census(p.data_ptr(), ld, B, nv, thr.data_ptr(), J, float(margin), counts.data_ptr(),
-                                       mindist.data_ptr(), _stream()), "contact_band_census")
+    _run("contact_band_census", lib.ivlm_contact_band_census, p.data_ptr(), ld, B, nv, thr.data_ptr(), J, float(margin),
+         counts.data_ptr(), mindist.data_ptr())
     return counts, mindist
 
 
@@ -1427,14 +1360,13 @@ def mask_band_census(logits, plan: LiftPlan, threshold=0.3, margin=1e-3):
         return counts
     nbytes = lib.ivlm_mask_band_census_workspace_bytes()
     ws = _workspace(nbytes, logits.device)
-    check(lib.ivlm_mask_band_census(logits.data_ptr(), plan.V, plan.HW, plan.ent_pix.data_ptr(), plan.row_ptr.data_ptr(),
-                                    plan.V * plan.num_vertices, float(threshold), float(margin), counts.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), _stream()), "mask_band_census")
+    _run("mask_band_census", lib.ivlm_mask_band_census, logits.data_ptr(), plan.V, plan.HW, plan.ent_pix.data_ptr(),
+         plan.row_ptr.data_ptr(), plan.V * plan.num_vertices, float(threshold), float(margin), counts.data_ptr(), ws.data_ptr(),
+         ws.numel())
     return counts
 
 
-_SEG_GT_CODE = {torch.uint8: 0, torch.int32: 1, torch.float32: 2}  # IVLM_SEG_GT_*
-_AFFORD_THRESHOLDS = {}
+_SEG_GT_CODE = {torch.uint8: _abi("IVLM_SEG_GT_U8"), torch.int32: _abi("IVLM_SEG_GT_I32"), torch.float32: _abi("IVLM_SEG_GT_F32")}
 
 
 def seg_iou_counts(pred, gt, ignore_label=255):
@@ -1452,8 +1384,8 @@ def seg_iou_counts(pred, gt, ignore_label=255):
     nbytes = lib.ivlm_seg_iou_workspace_bytes(V)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     out = torch.empty(V, 3, 2, dtype=torch.int32, device=pred.device)
-    check(lib.ivlm_seg_iou_counts(pred.data_ptr(), gt.data_ptr(), _SEG_GT_CODE[gt.dtype], V, H, W, int(ignore_label),
-                                  out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "seg_iou_counts")
+    _run("seg_iou_counts", lib.ivlm_seg_iou_counts, pred.data_ptr(), gt.data_ptr(), _SEG_GT_CODE[gt.dtype], V, H, W, int(ignore_label),
+         out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
@@ -1462,10 +1394,7 @@ def afford_thresholds(device):
     a scalar in fp32) and kept on the device: uploaded once per device."""
     import numpy as np
 
-    key = str(device)
-    if key not in _AFFORD_THRESHOLDS:
-        _AFFORD_THRESHOLDS[key] = torch.from_numpy(np.linspace(0, 1, 20).astype(np.float32)).to(device)
-    return _AFFORD_THRESHOLDS[key]
+    return _device_constant(tuple(float(t) for t in np.linspace(0, 1, 20).astype(np.float32)), str(device))
 
 
 def affordance_metrics(gt, pred, thresholds=None):
@@ -1480,8 +1409,8 @@ def affordance_metrics(gt, pred, thresholds=None):
     B, n = pred.shape
     out = torch.empty(B, 4, dtype=torch.float32, device=pred.device)
     valid = torch.empty(B, dtype=torch.int32, device=pred.device)
-    check(lib.ivlm_afford_metrics(gt.data_ptr(), pred.data_ptr(), B, n, thr.data_ptr(), thr.numel(), 2048.0, out.data_ptr(),
-                                  valid.data_ptr(), _stream()), "afford_metrics")
+    _run("afford_metrics", lib.ivlm_afford_metrics, gt.data_ptr(), pred.data_ptr(), B, n, thr.data_ptr(), thr.numel(), 2048.0,
+         out.data_ptr(), valid.data_ptr())
     return out, valid
 
 
@@ -1497,8 +1426,8 @@ def h_geo_metric_per_sample(pred, gt, dist):
     nbytes = lib.ivlm_h_geo_workspace_bytes(n)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     out = torch.empty(B, 2, dtype=torch.float32, device=pred.device)
-    check(lib.ivlm_h_geo_metric(dist.data_ptr(), pred.data_ptr(), gt.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(), nbytes,
-                                _stream()), "h_geo_metric")
+    _run("h_geo_metric", lib.ivlm_h_geo_metric, dist.data_ptr(), pred.data_ptr(), gt.data_ptr(), B, n, out.data_ptr(), ws.data_ptr(),
+         nbytes)
     return out
 
 
@@ -1527,6 +1456,6 @@ class SparseRows:
         lib = _lib.load()
         x = _req(x, torch.float32, "x")
         y = torch.empty(x.shape[0], self.rows, dtype=torch.float32, device=x.device)
-        check(lib.ivlm_spmv_csr(self.row_ptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(), x.data_ptr(),
-                                x.shape[0], self.rows, self.cols, y.data_ptr(), _stream()), "spmv_csr")
+        _run("spmv_csr", lib.ivlm_spmv_csr, self.row_ptr.data_ptr(), self.col.data_ptr(), self.val.data_ptr(), x.data_ptr(), x.shape[0],
+             self.rows, self.cols, y.data_ptr())
         return y

@@ -42,9 +42,6 @@ class LlamaStages:
         lib = _lib.load()
         self._dws = torch.zeros(lib.ivlm_llama_decode_workspace_bytes(C.byref(self.cfg)), dtype=torch.uint8, device=llm.device)
 
-    def _stream(self):
-        return torch.cuda.current_stream().cuda_stream
-
     def prefill(self, x, pos0=0):
         """x fp32 [T, hidden] -> final-norm hidden fp32 [T, hidden]; appends to the instance's KV cache."""
         lib = _lib.load()
@@ -56,7 +53,7 @@ class LlamaStages:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         check(lib.ivlm_llama_prefill(C.byref(self.cfg), self.layers, llm.norm.data_ptr(), llm.kcache.data_ptr(),
                                      llm.vcache.data_ptr(), llm.rope[0].data_ptr(), llm.rope[1].data_ptr(), x.data_ptr(), T,
-                                     int(pos0), out.data_ptr(), ws.data_ptr(), nbytes, self._stream()), "llama_prefill")
+                                     int(pos0), out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "llama_prefill")
         return out
 
     def _layers16(self):
@@ -80,7 +77,7 @@ class LlamaStages:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         check(lib.ivlm_llama_prefill_f16(C.byref(self.cfg), self._layers16(), llm.norm.data_ptr(), llm.kcache.data_ptr(),
                                          llm.vcache.data_ptr(), llm.rope[0].data_ptr(), llm.rope[1].data_ptr(), x.data_ptr(), T,
-                                         int(pos0), out.data_ptr(), ws.data_ptr(), nbytes, self._stream()), "llama_prefill_f16")
+                                         int(pos0), out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "llama_prefill_f16")
         return out
 
     def decode_step_f16kv(self, x, pos_dev, advance=True):
@@ -91,7 +88,7 @@ class LlamaStages:
         check(lib.ivlm_llama_decode_step_f16kv(C.byref(self.cfg), self.layers, llm.norm.data_ptr(), llm.kcache.data_ptr(),
                                                llm.vcache.data_ptr(), llm.rope[0].data_ptr(), llm.rope[1].data_ptr(), x.data_ptr(),
                                                pos_dev.data_ptr(), 1 if advance else 0, out.data_ptr(), self._dws.data_ptr(),
-                                               self._dws.numel(), self._stream()), "llama_decode_step_f16kv")
+                                               self._dws.numel(), _lib.stream()), "llama_decode_step_f16kv")
         return out
 
     def _layers_bf12(self):
@@ -120,11 +117,11 @@ class LlamaStages:
         lib = _lib.load()
         llm = self.llm
         out = torch.empty_like(x)
-        cache_dt = 4 if llm.precision == "f16" else 1  # IVLM_F16 | IVLM_BF16
+        cache_dt = _lib.header_constant("IVLM_F16" if llm.precision == "f16" else "IVLM_BF16")
         check(lib.ivlm_llama_decode_step_bf12(C.byref(self.cfg), self._layers_bf12(), llm.norm.data_ptr(), llm.kcache.data_ptr(),
                                               llm.vcache.data_ptr(), cache_dt, llm.rope[0].data_ptr(), llm.rope[1].data_ptr(),
                                               x.data_ptr(), pos_dev.data_ptr(), 1 if advance else 0, out.data_ptr(),
-                                              self._dws.data_ptr(), self._dws.numel(), self._stream()), "llama_decode_step_bf12")
+                                              self._dws.data_ptr(), self._dws.numel(), _lib.stream()), "llama_decode_step_bf12")
         return out
 
     def start_generation(self):
@@ -138,7 +135,7 @@ class LlamaStages:
         check(lib.ivlm_llama_decode_step(C.byref(self.cfg), self.layers, llm.norm.data_ptr(), llm.kcache.data_ptr(),
                                          llm.vcache.data_ptr(), llm.rope[0].data_ptr(), llm.rope[1].data_ptr(), x.data_ptr(),
                                          pos_dev.data_ptr(), 1 if advance else 0, out.data_ptr(), self._dws.data_ptr(),
-                                         self._dws.numel(), self._stream()), "llama_decode_step")
+                                         self._dws.numel(), _lib.stream()), "llama_decode_step")
         return out
 
 
@@ -187,10 +184,10 @@ class ClipStages:
                     ClipLayerC(p(L["ln1"].w), p(L["ln1"].b), p(L["qkv_h"]), p(L["qkv_b"]), p(L["out_h"]), p(L["out"].b), p(L["ln2"].w),
                                p(L["ln2"].b), p(L["fc1_h"]), p(L["fc1"].b), p(L["fc2_h"]), p(L["fc2"].b)) for L in Ls])
             check(lib.ivlm_clip_encode_f16(C.byref(self.cfg), C.byref(self.head), self.layers16, images.data_ptr(), B, out.data_ptr(),
-                                           ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "clip_encode_f16")
+                                           ws.data_ptr(), nbytes, _lib.stream()), "clip_encode_f16")
             return out
         check(lib.ivlm_clip_encode(C.byref(self.cfg), C.byref(self.head), self.layers, images.data_ptr(), B, out.data_ptr(),
-                                   ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "clip_encode")
+                                   ws.data_ptr(), nbytes, _lib.stream()), "clip_encode")
         return out
 
 
@@ -261,7 +258,7 @@ class SamEncodeStages:
         nbytes = size_fn(C.byref(self.cfg), V)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
         check(fn(C.byref(self.cfg), C.byref(self.head), self.blocks, *extra, images.data_ptr(), V, out.data_ptr(), ws.data_ptr(),
-                 nbytes, torch.cuda.current_stream().cuda_stream), "sam_encode (" + precision + ")")
+                 nbytes, _lib.stream()), "sam_encode (" + precision + ")")
         return out
 
 
@@ -324,5 +321,5 @@ class SamDecodeStages:
         nbytes = lib.ivlm_sam_decode_workspace_bytes(V, g, Cc, txt.shape[0], self.mlp_dim)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=emb.device)
         check(lib.ivlm_sam_decode(C.byref(self.w), V, g, txt.shape[0], emb.data_ptr(), txt.data_ptr(), low.data_ptr(),
-                                  iou.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "sam_decode")
+                                  iou.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "sam_decode")
         return low.unsqueeze(1), iou[:, 0:1]

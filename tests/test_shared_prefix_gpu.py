@@ -125,6 +125,23 @@ def test_prefix_kernel_rejects_what_it_does_not_support(hip_lib, cuda):
         kc = torch.zeros(2, TMAX, H, D, dtype=torch.bfloat16, device=cuda)
         ops.llama_decode_attn_batch_prefix(q, kc, kc.clone(), H, D, torch.tensor([30, 19], dtype=torch.int32, device=cuda), pre, 10000.0,
                                            D ** -0.5, table=tab, host_check=([30, 19], 20))
+    # what the decode-attention wrappers check alike before they launch, one input per check: a position tensor that is not int32, K and
+    # V caches of different dtypes, a RoPE table shorter than the cache
+    q = torch.zeros(2, 3 * H * D, device=cuda)
+    kc = torch.zeros(2, TMAX, H, D, dtype=torch.bfloat16, device=cuda)
+    pos = torch.tensor([30, 40], dtype=torch.int32, device=cuda)
+    short = tuple(t[: TMAX - 1] for t in tab)
+    rest = (10000.0, D ** -0.5)
+    for bad in (lambda: ops.llama_decode_attn_batch_prefix(q, kc, kc.clone(), H, D, pos.long(), pre, *rest, table=tab),
+                lambda: ops.llama_decode_attn_batch_prefix(q, kc, kc.half(), H, D, pos, pre, *rest, table=tab),
+                lambda: ops.llama_decode_attn_batch_prefix(q, kc, kc.clone(), H, D, pos, pre, *rest, table=short),
+                lambda: ops.llama_decode_attn_batch(q, kc, kc.clone(), H, D, pos.long(), *rest, table=tab),
+                lambda: ops.llama_decode_attn(q[:1], kc[0], kc[1], H, D, pos[:1].long(), *rest, table=tab),
+                lambda: ops.llama_verify_attn(q, kc[0], kc[1].half(), H, D, pos[:1], *rest, table=tab),
+                lambda: ops.llama_verify_attn(q, kc[0], kc[1], H, D, pos[:1], *rest, table=short)):
+        with pytest.raises(AssertionError):
+            bad()
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("precision", ["default", "f16"])
