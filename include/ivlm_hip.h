@@ -823,6 +823,23 @@ int ivlm_prompt_embed(const float *coords, const int32_t *labels, const float *g
 int ivlm_mask_downscale(const float *mask, const float *w0, const float *b0, const float *ln1_w, const float *ln1_b, const float *w3,
                         const float *b3, const float *ln2_w, const float *ln2_b, const float *w6, const float *b6, float *dense, int B,
                         int gh, int gw, int C, int mask_in_chans, float eps, ivlm_stream_t stream);
+/* The filter stage of the automatic mask generator (automatic_mask_generator.py:290-307) without the full-resolution logits.
+ * low f32 [n,h,w] and the geometry of ivlm_postprocess_masks -> out i32 [n,8] per candidate: #(v > t_hi), #(v > t_mid), #(v > t_lo),
+ * then x0, y0, x1, y1 of {v > t_mid} as inclusive pixel indices (0, 0, 0, 0 for an empty set: batched_mask_to_box), then 0.  v is
+ * bit for bit the value ivlm_postprocess_masks stores at that pixel; it is never written.  active i32 [n] or NULL: a row with
+ * active[i] == 0 is written as zeros and samples nothing.  The call initialises out itself (three launches, no host read, no
+ * allocation: capturable).  n <= 65535 and oh * ow < 2^31, else IVLM_ERR_UNSUPPORTED before any launch. */
+int ivlm_mask_census(const float *low, int n, int h, int w, int img, int in_h, int in_w, int oh, int ow, float t_hi, float t_mid,
+                     float t_lo, const int32_t *active, int32_t *out, ivlm_stream_t stream);
+/* torchvision's box NMS for boxes ALREADY IN SCORE ORDER: boxes f32 [n,4] XYXY (16-byte aligned), valid i32 [n] or NULL -> keep i32
+ * [n] of 0 / 1.  Row j is dropped when a KEPT row i < j has IoU(i, j) > iou_threshold, in fp32 and in torchvision's order: area =
+ * (x2 - x1) (y2 - y1), inter = max(0, min x2 - max x1) max(0, min y2 - max y1), iou = inter / (area_i + area_j - inter); 0 / 0
+ * suppresses nothing.  A row with valid[i] == 0 is neither kept nor suppresses.  Two launches: the n x ceil(n / 64) bit matrix of
+ * 64-bit words in the workspace (ivlm_box_nms_workspace_bytes(n) bytes, 8-byte aligned; 0 for sizes that are not supported), then
+ * one wave that walks the rows in order.  n <= 16384 (33.5 MB), else IVLM_ERR_UNSUPPORTED before any launch. */
+size_t ivlm_box_nms_workspace_bytes(int n);
+int ivlm_box_nms(const float *boxes, const int32_t *valid, int n, float iou_threshold, int32_t *keep, void *workspace,
+                 size_t workspace_bytes, ivlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Right after the path

@@ -305,6 +305,41 @@ def postprocess_masks(low_res, input_size, original_size, img_size: int = 1024, 
     return out
 
 
+def mask_census(low_res, input_size, original_size, img_size=1024, thresholds=(1.0, 0.0, -1.0), active=None, out=None):
+    """low_res f32 [n,h,w] -> int32 [n,8] per candidate, of the values ``postprocess_masks`` would store (never written): the counts
+    above thresholds = (hi, mid, lo), the box x0, y0, x1, y1 of {v > mid} in inclusive pixel indices (zeros when empty), 0.  active
+    int32 [n]: rows with 0 come out as zeros and sample nothing."""
+    lib = _lib.load()
+    low_res = _req(low_res, F32, "low_res")
+    if low_res.dim() != 3 or low_res.numel() == 0:
+        raise IvlmError(f"mask_census: low_res {tuple(low_res.shape)}, expected [n,h,w]")
+    n, h, w = low_res.shape
+    if active is not None and _req(active, torch.int32, "active").numel() != n:
+        raise IvlmError(f"mask_census: active {tuple(active.shape)}, expected [{n}]")
+    o = torch.empty(n, 8, dtype=torch.int32, device=low_res.device) if out is None else _req(out, torch.int32, "out")
+    if o.numel() != 8 * n:
+        raise IvlmError(f"mask_census: out {tuple(o.shape)}, expected {(n, 8)}")
+    _run("mask_census", lib.ivlm_mask_census, low_res.data_ptr(), n, h, w, int(img_size), int(input_size[0]), int(input_size[1]),
+         int(original_size[0]), int(original_size[1]), *[float(t) for t in thresholds], _p(active), o.data_ptr())
+    return o
+
+
+def box_nms(boxes, iou_threshold, valid=None):
+    """boxes f32 [n,4] XYXY ALREADY IN SCORE ORDER, valid int32 [n] or None -> keep int32 [n] of 0 / 1: torchvision's NMS (a row is
+    dropped when a kept row before it has IoU > iou_threshold); rows with valid == 0 neither keep nor suppress."""
+    lib = _lib.load()
+    boxes = _req(boxes, F32, "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.shape[0] < 1:
+        raise IvlmError(f"box_nms: boxes {tuple(boxes.shape)}, expected [n,4] with n >= 1")
+    n = boxes.shape[0]
+    if valid is not None and _req(valid, torch.int32, "valid").numel() != n:
+        raise IvlmError(f"box_nms: valid {tuple(valid.shape)}, expected [{n}]")
+    ws, nbytes = _lib.workspace(lib.ivlm_box_nms_workspace_bytes, "box_nms", boxes.device, n=n)
+    keep = torch.empty(n, dtype=torch.int32, device=boxes.device)
+    _run("box_nms", lib.ivlm_box_nms, boxes.data_ptr(), _p(valid), n, float(iou_threshold), keep.data_ptr(), ws.data_ptr(), nbytes)
+    return keep
+
+
 # --------------------------------------------------------------------------------------------
 # dense building blocks
 # --------------------------------------------------------------------------------------------
